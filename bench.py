@@ -8,7 +8,9 @@ on one synthetic rollout that is already resident in HBM: GAE over env_num x T t
 steps (forward, PPO loss, backward, global-norm clip, Adam).  value = env-frames/s = 4 (frame-skip) x env-steps
 consumed / wall time, whole job over all ranks.
 
-The same JSON line also carries (rank 0, one GPU):
+A plain run (``python bench.py --gpus 1 --steps K --warmup W``) sets up, warms up, times K updates, writes the last
+update's outputs when ``--dump-outputs DIR`` is given, and prints the headline line.  With ``--full`` the same JSON line
+also carries (rank 0, one GPU):
   roofline      dominant kernel of an SGD step, timed live with HIP events on the launch stream
   e2e           SURVEY 8(d)'s metric through the PLUGIN classes: alg.prepare_data x env_num (host numpy ->
                 pinned staging -> async H2D) + alg.train() + alg.get_weights() (D2H), env_num 32 and the YAML's 10
@@ -23,7 +25,7 @@ The same JSON line also carries (rank 0, one GPU):
 
 N > 1: ``python bench.py --gpus N`` spawns N ranks itself (torch.distributed.run, one process per GPU, RCCL) when it
 is not already running under a launcher, and FAILS if it cannot.  Two data-parallel modes are measured in the same
-run: ``value`` = weak scaling (every rank owns env_num=32 trajectories and a 320-row local minibatch, one all-reduce
+``--full`` run: ``value`` = weak scaling (every rank owns env_num=32 trajectories and a 320-row local minibatch, one all-reduce
 of the flat fp32 gradient per SGD step, grad_scale 1/N); ``strict`` = the reference's global minibatch of 320 rows
 split into N shards (40 rows per GPU at N=8), shared permutation, means over the global minibatch.
 """
@@ -226,6 +228,19 @@ def emit_result(out):
             log("could not write", pth, repr(exc))
     log("detail:", json.dumps(out))
     _emit(compact_line(out))
+
+
+def dump_outputs(dirname, keep):
+    """What the last timed update handed back to its caller, as <dirname>/<name>.npy (float32 / float64 as computed):
+    the updated flat parameters, the loss accumulator and the GAE outputs the update trained on (about 3.5 MB)."""
+    os.makedirs(dirname, exist_ok=True)
+    torch.cuda.synchronize()
+    net = keep["net"]
+    for name, t in (("params", net.params), ("loss_acc", net.loss_acc), ("gae_adv", keep["d_adv"]),
+                    ("gae_target", keep["d_tgt"]), ("gae_old_value", keep["d_oldv"])):
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+    log("outputs of the last timed update written to", dirname)
 
 
 _T0 = time.perf_counter()
@@ -609,7 +624,7 @@ def in_graph_kernel_stats(workload, timeout=240):
         return None, "rocprofv3 not on PATH"
     tmp = tempfile.mkdtemp(prefix="xt_ig_")
     cmd = [exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable, os.path.abspath(__file__),
-           "--workload", workload, "--steps", "6", "--warmup", "2", "--quick", "--no-cpu-baseline", "--no-in-graph-stats"]
+           "--workload", workload, "--steps", "6", "--warmup", "2", "--full", "--quick", "--no-cpu-baseline", "--no-in-graph-stats"]
     try:
         subprocess.run(cmd, cwd=tmp, env=dict(os.environ, TMPDIR=tmp), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
                        timeout=timeout, check=True)
@@ -1297,7 +1312,7 @@ def main():
     ap.add_argument("--detail-file", default=None, help="where the full result goes (default: bench_detail.json next to bench.py)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the IMPALA workloads and the plugin-path (e2e) runs")
-    ap.add_argument("--quick", action="store_true", help="headline + roofline only (profiling runs)")
+    ap.add_argument("--quick", action="store_true", help="with --full: headline + roofline only (profiling runs)")
     ap.add_argument("--force-dp-path", action="store_true",
                     help="run the N>1 code path (step-wise fwd/bwd -> all-reduce -> clip+Adam) even with one rank")
     ap.add_argument("--dp-variants", default="all",
@@ -1317,9 +1332,20 @@ def main():
                     help="print ONLY the modelled 2/4/8-GPU block (measured 1-GPU step time at 40/80/160/320 rows + a modelled "
                          "all-reduce), labelled as modelled")
     ap.add_argument("--workload", default="ppo", choices=["ppo"] + sorted(IMPALA),
-                    help="ppo = BASELINE configs[1] (the headline metric, default; its JSON line carries the IMPALA "
-                         "workloads as `secondary`); the IMPALA names print that workload's own line (profiling)")
+                    help="ppo = BASELINE configs[1] (the headline metric, default; with --full its JSON line carries the "
+                         "IMPALA workloads as `secondary`); the IMPALA names print that workload's own line (profiling)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the line can carry (roofline, sustained, e2e, "
+                         "secondary workloads, cpu_baseline, ...; N > 1: strict sharding, IMPALA data parallel).  Without it "
+                         "a run sets up, warms up, times --steps updates and prints the headline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed update handed back (parameters, loss, GAE "
+                         "outputs) as DIR/<name>.npy; the inputs are seeded, so runs with the same arguments are comparable")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.workload != "ppo" or args.section or args.model_scaling):
+        ap.error("--dump-outputs applies to the headline workload (--workload ppo)")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -1513,7 +1539,7 @@ def main():
             dist.all_reduce(hi, op=dist.ReduceOp.MAX)
             assert float(lo) == float(hi), "data-parallel replicas diverged"
         keep = dict(net=net, obs=obs, action=action, logp=logp, value=value, reward=reward, done=done, d_obs=d_obs,
-                    d_perm=d_perm, one_update=one_update, rccl=rccl, graph=graph)
+                    d_perm=d_perm, d_adv=d_adv, d_tgt=d_tgt, d_oldv=d_oldv, one_update=one_update, rccl=rccl, graph=graph)
         return elapsed, n, keep
 
     elapsed, n, keep = run_mode("weak")
@@ -1611,7 +1637,15 @@ def main():
         if dist is not None:
             out["config"]["ranks_in_group"] = dist.get_world_size()
     out["update_tflops"] = PPO_MFLOP_PER_SAMPLE_PASS * 1e6 * n * CFG["NUM_SGD_ITER"] * world * args.steps / elapsed / 1e12
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, keep)     # before anything below runs more updates on the same network
 
+    if world > 1 and not args.full:
+        if rank == 0:
+            emit_result(out)
+        dist.barrier()
+        dist.destroy_process_group()
+        return
     if world > 1:
         # ---- strict data parallelism: the reference's global minibatch of 320 rows sharded over the ranks
         keep_weak = keep
@@ -1684,6 +1718,11 @@ def main():
         return
 
     # ------------------------------------------------------------------ single GPU: the rest of the line (rank 0)
+    if not args.full:
+        emit_result(out)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     net, d_obs, d_perm = keep["net"], keep["d_obs"], keep["d_perm"]
     idx = d_perm[0, :bsz].contiguous()
     kern = layer_rooflines(net, spec, bsz, d_obs, idx, x6=True)

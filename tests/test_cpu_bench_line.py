@@ -64,3 +64,14 @@ def test_compact_line_of_a_multi_gpu_result():
     assert line["dp_variants"]["direct"] == 1.5e7 and line["dp_variants"]["hook"].startswith("invalid")
     assert line["strict"]["rows_per_gpu"] == 40
     assert line["secondary"]["pong_impala_speedup"] == {"weak": 1e8, "strict": 2e7}
+
+
+def test_bench_refuses_meaningless_step_counts_and_dumps_of_other_workloads():
+    """--steps sets the number of timed updates (ms_per_step divides by it): zero is refused before any work, as is
+    --dump-outputs for anything but the headline workload."""
+    import subprocess
+    import sys
+    for extra in (["--steps", "0"], ["--warmup", "-1"], ["--workload", "breakout_impala", "--dump-outputs", "x"]):
+        proc = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py")] + extra,
+                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+        assert proc.returncode == 2 and b"error" in proc.stderr, extra

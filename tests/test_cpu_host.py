@@ -390,58 +390,59 @@ def test_linear_cosine_decay_known_answers():
     assert all(a > b for a, b in zip(vals, vals[1:]))                                   # monotone decreasing
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/zeus/common/util/register.py"),
-                    reason="the reference checkout only exists in the authoring container")
-def test_reference_registry_accepts_the_hip_plugins_as_integration_md_says():
-    """INTEGRATION.md section 1 against the reference's REAL registry: zeus/common/util/register.py is loaded
-    unmodified (its two imports that need uninstalled packages are stubbed: `absl.logging` -> stdlib logging and
-    `zeus.set_backend`, which would import TensorFlow, -> no-op) and the drop-in subclasses are
-    registered and resolved by class __name__, which is how alg_para.alg_name / model_name select plugins
-    (register.py:58-69)."""
-    import importlib.util
-    import logging as pylogging
-    import types
-    absl = types.ModuleType("absl")
-    absl.logging = pylogging
-    zeus = types.ModuleType("zeus")
-    zeus.set_backend = lambda **kw: None
-    saved = {k: sys.modules.get(k) for k in ("absl", "absl.logging", "zeus")}
-    sys.modules["absl"], sys.modules["absl.logging"], sys.modules["zeus"] = absl, pylogging, zeus
-    try:
-        spec = importlib.util.spec_from_file_location("_ref_register", "/root/reference/zeus/common/util/register.py")
-        ref = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(ref)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
+def test_reference_registry_accepts_the_hip_plugins_as_integration_md_says(golden_dir):
+    """INTEGRATION.md section 1 against the reference's REAL registry: zeus/common/util/register.py, executed unmodified
+    by oracle/gen_golden_registry.py with the drop-in subclasses registered through its decorators, resolved them by
+    class __name__, which is how alg_para.alg_name / model_name select plugins (register.py:58-69).  The recorded
+    resolution (tests/golden/registry.json) must still describe today's plugin classes, and this package's registry
+    must resolve them, and treat misuse, as the reference's did."""
+    import inspect
+    import json
     from xingtian_amd.algorithm.impala.impala_opt import IMPALAOpt as _IMPALAOpt
     from xingtian_amd.algorithm.ppo.ppo import PPO as _PPO
     from xingtian_amd.model.impala.impala_cnn_opt import ImpalaCnnOpt as _ImpalaCnnOpt
     from xingtian_amd.model.ppo.ppo_cnn import PpoCnn as _PpoCnn
+    from xingtian_amd.register import Registers, Registry
 
-    @ref.Registers.model
+    with open(os.path.join(golden_dir, "registry.json")) as f:
+        rec = json.load(f)
+    regs = {k: Registry(k) for k in rec["keys"]}
+
+    @regs["model"]
     class PpoCnnHip(_PpoCnn):
         pass
 
-    @ref.Registers.model
+    @regs["model"]
     class ImpalaCnnOptHip(_ImpalaCnnOpt):
         pass
 
-    @ref.Registers.algorithm
+    @regs["algorithm"]
     class PPOHip(_PPO):
         pass
 
-    @ref.Registers.algorithm
+    @regs["algorithm"]
     class IMPALAOptHip(_IMPALAOpt):
         pass
 
-    assert ref.Registers.model["PpoCnnHip"] is PpoCnnHip and ref.Registers.model["ImpalaCnnOptHip"] is ImpalaCnnOptHip
-    assert ref.Registers.algorithm["PPOHip"] is PPOHip and ref.Registers.algorithm["IMPALAOptHip"] is IMPALAOptHip
+    assert regs["model"]["PpoCnnHip"] is PpoCnnHip and regs["model"]["ImpalaCnnOptHip"] is ImpalaCnnOptHip
+    assert regs["algorithm"]["PPOHip"] is PPOHip and regs["algorithm"]["IMPALAOptHip"] is IMPALAOptHip
+    for kind, keys in rec["keys"].items():
+        assert sorted(regs[kind].keys()) == keys, kind
+        for name, want in rec["registered"][kind].items():
+            cls = regs[kind][name]
+            assert {"name": cls.__name__, "bases": ["{}.{}".format(b.__module__, b.__name__) for b in cls.__bases__]} == want
+    # misuse is met as the reference's registry met it
+    probe = Registry("probe")
+    first, second = type("Twice", (object,), {}), type("Twice", (object,), {})
+    probe(first)
+    probe(second)
+    assert (probe["Twice"] is second) == rec["second_registration_wins"]
+    for call, err in ((lambda: probe(42), "non_callable_error"), (lambda: probe["NoSuchPlugin"], "unknown_name_error"),
+                      (Registers, "instancing_error")):
+        with pytest.raises(Exception) as info:
+            call()
+        assert type(info.value).__name__ == rec[err], err
     # same constructor contract as the reference's plugin classes: Algorithm(model_info, alg_config, **kw), Model(model_info)
-    import inspect
     assert list(inspect.signature(PPOHip.__init__).parameters)[:3] == ["self", "model_info", "alg_config"]
     assert list(inspect.signature(PpoCnnHip.__init__).parameters)[:2] == ["self", "model_info"]
 

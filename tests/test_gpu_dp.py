@@ -115,14 +115,14 @@ def test_impala_sum_loss_two_ranks_whole_trajectory_shards(tmp_path):
 
 
 def test_bench_self_spawns_two_ranks_and_reports_weak_strict_and_impala():
-    """``python bench.py --gpus 2`` outside a launcher must start the two ranks itself and print ONE JSON line with
+    """``python bench.py --gpus 2 --full`` outside a launcher must start the two ranks itself and print ONE JSON line with
     ``n_gpus: 2``, the weak-scaling headline, the strict-sharding result and the IMPALA data-parallel secondaries
     (here with the diagnostic gloo transport, the two ranks sharing the one GPU)."""
     import json
     import tempfile
     detail = os.path.join(tempfile.mkdtemp(prefix="xt_bench_"), "detail.json")     # (not the tree's bench_detail.json)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--test-backend", "gloo", "--steps", "2", "--warmup", "1",
-           "--detail-file", detail]
+           "--full", "--detail-file", detail]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     proc = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=420)

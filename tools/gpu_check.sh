@@ -1,16 +1,17 @@
 #!/bin/bash
-# One GPU-box call: the -m gpu suite, the default bench line, and in-graph kernel averages of the three workloads.
+# One GPU-box call: the -m gpu suite, the full bench line, and in-graph kernel averages of the three workloads.
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+OUT=${OUT:-$R/out}
 TAG=${1:-r04}
-mkdir -p $R/gpurun_out
+mkdir -p $OUT
 cd $R
-timeout 600 python -m pytest tests -m "not gpu" -x -q > gpurun_out/${TAG}_pytest_cpu.log 2>&1; tail -2 gpurun_out/${TAG}_pytest_cpu.log
-timeout 1500 python -m pytest tests -m gpu -x -q > gpurun_out/${TAG}_pytest.log 2>&1; tail -4 gpurun_out/${TAG}_pytest.log
-timeout 600 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err; tail -3 gpurun_out/${TAG}_bench.err
+timeout 600 python -m pytest tests -m "not gpu" -x -q > $OUT/${TAG}_pytest_cpu.log 2>&1; tail -2 $OUT/${TAG}_pytest_cpu.log
+timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/${TAG}_pytest.log 2>&1; tail -4 $OUT/${TAG}_pytest.log
+timeout 600 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; tail -3 $OUT/${TAG}_bench.err
 python - <<P
 import json
 try:
-    d = json.loads(open("gpurun_out/${TAG}_bench.json").read().strip().splitlines()[-1])
+    d = json.loads(open("$OUT/${TAG}_bench.json").read().strip().splitlines()[-1])
     print("PPO value", d["value"], "ms", d["ms_per_step"], "frac", d["roofline"]["frac"], d["roofline"]["kernel"])
     print("kernels", d["roofline"]["kernels_us_isolated"])
     print("sustained", d.get("sustained"))
@@ -28,9 +29,9 @@ except Exception as e:
 P
 cd /tmp && export TMPDIR=/tmp
 for W in ppo breakout_impala pong_impala_speedup; do
-  rm -rf /tmp/qs; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/qs -- python $R/bench.py --workload $W --steps 6 --warmup 2 --no-cpu-baseline --quick > /tmp/qs.log 2>&1
+  rm -rf /tmp/qs; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/qs -- python $R/bench.py --workload $W --steps 6 --warmup 2 --no-cpu-baseline --full --quick > /tmp/qs.log 2>&1
   f=$(find /tmp/qs -name "*kernel_stats.csv" | head -1)
-  cp $f $R/gpurun_out/${TAG}_kernel_stats_$W.csv
+  cp $f $OUT/${TAG}_kernel_stats_$W.csv
   python - <<P
 import csv
 print("---- $W")

@@ -1,17 +1,18 @@
 #!/bin/bash
-# One GPU-box call: the -m gpu suite + the default bench line (no profiling).  usage: tools/gpu_quick.sh <tag> [pytest -k expr]
+# One GPU-box call: the -m gpu suite + the full bench line (no profiling).  usage: tools/gpu_quick.sh <tag> [pytest -k expr]
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+OUT=${OUT:-$R/out}
 TAG=${1:-r04}
-mkdir -p $R/gpurun_out
+mkdir -p $OUT
 cd $R
 if [ -n "$2" ]; then K=(-k "$2"); else K=(); fi
-timeout 600 python -m pytest tests -m "not gpu" -x -q > gpurun_out/${TAG}_pytest_cpu.log 2>&1; tail -2 gpurun_out/${TAG}_pytest_cpu.log
-timeout 1500 python -m pytest tests -m gpu -x -q "${K[@]}" > gpurun_out/${TAG}_pytest.log 2>&1; tail -15 gpurun_out/${TAG}_pytest.log
-timeout 600 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err; tail -3 gpurun_out/${TAG}_bench.err
+timeout 600 python -m pytest tests -m "not gpu" -x -q > $OUT/${TAG}_pytest_cpu.log 2>&1; tail -2 $OUT/${TAG}_pytest_cpu.log
+timeout 1500 python -m pytest tests -m gpu -x -q "${K[@]}" > $OUT/${TAG}_pytest.log 2>&1; tail -15 $OUT/${TAG}_pytest.log
+timeout 600 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; tail -3 $OUT/${TAG}_bench.err
 python - <<P
 import json
 try:
-    d = json.loads(open("gpurun_out/${TAG}_bench.json").read().strip().splitlines()[-1])
+    d = json.loads(open("$OUT/${TAG}_bench.json").read().strip().splitlines()[-1])
     print("PPO value", d["value"], "ms", d["ms_per_step"], "frac", d["roofline"]["frac"], d["roofline"]["kernel"])
     print("kernels", d["roofline"]["kernels_us_isolated"])
     print("sustained", d.get("sustained"))

@@ -2,7 +2,7 @@
 # In-graph per-kernel averages of a short headline run (rocprofv3 --kernel-trace --stats) + the bench value; GPU box.
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/qs; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/qs -- python $R/bench.py --steps 8 --warmup 2 --quick --no-cpu-baseline > /tmp/qs.log 2>&1
+rm -rf /tmp/qs; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/qs -- python $R/bench.py --steps 8 --warmup 2 --full --quick --no-cpu-baseline > /tmp/qs.log 2>&1
 python - <<'P'
 import csv,glob
 f=glob.glob("/tmp/qs/**/*kernel_stats.csv",recursive=True)[0]
