@@ -239,6 +239,34 @@ int xt_layer_wgrad(const xt_conv_geom* g, const xt_input_xform* xf, int32_t B,
 int xt_layer_dgrad(const xt_conv_geom* g, int32_t B, const float* dy, const float* w,
                    const float* x, int32_t act_prev, float* dx, void* stream);
 
+/* The fused backward launch of one non-first trunk layer as the update runs it (weight + bias gradient and input
+ * gradient in ONE launch), stand-alone for tests: no head weight-gradient blocks, no norm partials.
+ *   x      [B,H,W,C] f32: the producer's output (the weight gradient's operand)
+ *   x_pre  NULL, or the producer's pre-activation when act_prev needs it (swish, gelu: see XT_ACT_SWISH)
+ *   relu_mask NULL, or the producer's relu sign mask (bit c of word p = x[p,c] > 0; read where C = 32)
+ *   dx     [B,H,W,C] = act_prev'(.) * col2im(dY . W^T);  dwb [(K+1)*N] = [dW | db] (final, as xt_layer_wgrad)
+ *   slabs  [slab_cap, (K+1)*N] (may be NULL with msplit <= 1 -- the per-sample forms then stay off)
+ * *path_out (may be NULL) receives the branch taken: XT_BWD_PATH_* | dg mode << XT_BWD_DG_SHIFT | XT_ARITH_* <<
+ * XT_BWD_ARITH_SHIFT, where the dg mode is the input gradient's form (0 LDS-tiled, 1 register-direct, 2 all
+ * parity classes per block, 3 register-direct 64-row tiles, 4 ... with the dY halo in LDS, 5 sample per workgroup). */
+#define XT_BWD_PATH_S2FUSED 1        /* 4x4/2 16->32, B >= 512: input + weight gradient per sample, one slab each   */
+#define XT_BWD_PATH_S2C16 2          /* 4x4/2 16->32: sample-per-workgroup bf16x6 input gradient, tiled weight grad */
+#define XT_BWD_PATH_HALO 3           /* stride-1 halo input gradient in its own instance (bf16x6 or fp32)           */
+#define XT_BWD_PATH_CLASSES_PF4 4    /* all-classes stride-2 input gradient, four taps in flight, launch cut to 512 */
+#define XT_BWD_PATH_CLASSES_WROWS 5  /* ... next to the staged-rows weight gradient (wgrad_rows 1 / 2)             */
+#define XT_BWD_PATH_CLASSES 6        /* ... plain form                                                              */
+#define XT_BWD_PATH_PF_GENERIC 7     /* Dense deep-prefetch instance (1x1, stride 1)                                */
+#define XT_BWD_PATH_PAIR_SS 8        /* generic tile pair: 128x32 weight gradient, 128x32 input gradient            */
+#define XT_BWD_PATH_PAIR_SL 9        /* ... 128x32 weight gradient, 64x64 input gradient                            */
+#define XT_BWD_PATH_PAIR_LS 10       /* ... 64x64 weight gradient, 128x32 input gradient                            */
+#define XT_BWD_PATH_PAIR_LL 11       /* ... 64x64 weight gradient, 64x64 input gradient                             */
+#define XT_BWD_PATH_PAIR_LL_WX6 12   /* ... 64x64 pair with the bf16x6 weight gradient (dense_wgrad_x6)             */
+#define XT_BWD_DG_SHIFT 8
+#define XT_BWD_ARITH_SHIFT 12
+int xt_layer_bwd(const xt_conv_geom* g, int32_t B, const float* x, const float* x_pre, const float* dy,
+                 const float* w, int32_t act_prev, const uint32_t* relu_mask, float* dx, float* dwb, float* slabs,
+                 int32_t slab_cap, int32_t msplit, void* stream, int32_t* path_out);
+
 /* --------------------------------------------------------------- heads */
 /* logits[B,A] = f_pi.Wpi + bpi ; value[B] = f_v.Wv + bv.   (pi_latent / output_value
  * Dense layers, xt/model/model_utils.py:64-65; 1x1 Conv2D policy + dense baseline,

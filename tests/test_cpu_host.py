@@ -1330,3 +1330,17 @@ def test_inline_prefetcher_stages_on_the_learner_thread_one_train_ahead():
         pf2.close()
     finally:
         ring.close()
+
+
+@pytest.mark.parametrize("build", ["mlp_50_30", "cnn42_50"])
+def test_netspec_refuses_hidden_widths_outside_4z(build):
+    """Every layer kernel reads and writes 4-channel groups (and the entry points refuse other widths, see REFUSED in
+    tests/test_gpu_kernels.py): a hidden width that is not a multiple of 4 (a YAML's hidden_sizes: [50]) is refused
+    when the network is described, naming the layer, instead of reaching a kernel."""
+    from xingtian_amd.model import netspec
+    with pytest.raises(ValueError, match=r"hidden_mlp_0: channel counts must be multiples of 4 .*N=50"):
+        if build == "mlp_50_30":
+            netspec.ppo_mlp((4,), 2, (50, 30), "tanh", False)
+        else:
+            netspec.ppo_cnn((42, 42, 4), 4, (50,), "relu", True)
+    netspec.ppo_mlp((4,), 2, (52, 32), "tanh", False)          # (the neighbouring widths in 4Z are taken)

@@ -130,7 +130,46 @@ LAYER_CASES = [
     # not monotonic: the input-gradient epilogue is given the producer's PRE-activation
     ("conv3_swish", "conv", (9, 9), 32, 64, 3, 1, "valid", "swish", 9, False),
     ("fc_gelu", "dense", (1, 1), 64, 64, 1, 1, "valid", "gelu", 130, False),
+    # channel counts that are not multiples of 4 (a YAML's hidden_sizes: [50]): every layer kernel reads and writes
+    # 4-channel groups, so each entry refuses them before any launch (REFUSED) -- the float4 tails of the split-K
+    # finish and the slab reduction never see an N or a (K+1)*N outside 4Z
+    ("fc_3136_50", "dense", (1, 1), 3136, 50, 1, 1, "valid", "relu", 37, False),
+    ("fc_52_6", "dense", (1, 1), 52, 6, 1, 1, "valid", "tanh", 130, False),
+    ("conv3_s1_12_7", "conv", (11, 11), 12, 7, 3, 1, "valid", "relu", 5, False),
+    ("conv5_s2_same_6_5", "conv", (11, 11), 6, 5, 5, 2, "same", "tanh", 3, False),
 ]
+# case -> the error its refusal must carry
+REFUSED = {"fc_3136_50": "output channels N=50 must be a multiple of 4",
+           "fc_52_6": "output channels N=6 must be a multiple of 4",
+           "conv3_s1_12_7": "output channels N=7 must be a multiple of 4",
+           "conv5_s2_same_6_5": "input channels C=6 must be a multiple of 4"}
+SENTINEL = -1.2345e37
+TAIL = 64
+
+
+def with_tail(n, fill):
+    """a device buffer of n floats prefilled with `fill` and followed by TAIL sentinel floats (canary: a store past
+    the end of the output shows up as a changed sentinel)"""
+    t = torch.full((n + TAIL,), fill, dtype=torch.float32, device="cuda")
+    t[n:] = SENTINEL
+    return t
+
+
+def tail_intact(t, n):
+    return bool((t[n:] == SENTINEL).all())
+
+
+def refused(L, case, rc, *outs):
+    """True when `case` is one of REFUSED and the entry refused it with its error and wrote nothing (outs are
+    (buffer, fill) pairs); False for every other case"""
+    if case[0] not in REFUSED:
+        return False
+    assert rc != 0, case[0]
+    assert REFUSED[case[0]] in L.load().xt_last_error().decode(), case[0]
+    torch.cuda.synchronize()
+    for t, fill in outs:
+        assert (torch.isnan(t).all() if fill != fill else (t == fill).all()), case[0]
+    return True
 
 
 def _layer_data(case, seed=0):
@@ -162,12 +201,17 @@ def test_layer_fwd(L, case, ksplit):
     xf = L.InputXform(1 if u8 else 0, 0.0, 255.0 if u8 else 1.0)
     lib = L.load()
     m = b * lay.out_h * lay.out_w
-    y = torch.full((m, lay.cout), float("nan"), device="cuda")
-    partial = torch.zeros((8, m, lay.cout), device="cuda")
-    L.check(lib.xt_layer_fwd(ctypes.byref(g), ctypes.byref(xf), b, L.ptr(dev(x_raw)), None, L.ptr(dev(w)),
-                             L.ptr(dev(bias)), L.ptr(y), L.ptr(partial), ksplit, None), "fwd")
+    mn = m * lay.cout
+    y = with_tail(mn, float("nan"))
+    partial = with_tail(8 * mn, 0.0)
+    rc = lib.xt_layer_fwd(ctypes.byref(g), ctypes.byref(xf), b, L.ptr(dev(x_raw)), None, L.ptr(dev(w)),
+                          L.ptr(dev(bias)), L.ptr(y), L.ptr(partial), ksplit, None)
+    if refused(L, case, rc, (y[:mn], float("nan")), (partial[:8 * mn], 0.0)):
+        return
+    L.check(rc, "fwd")
     torch.cuda.synchronize()
-    got = y.cpu().numpy()
+    assert tail_intact(y, mn) and tail_intact(partial, 8 * mn), case[0]
+    got = y[:mn].cpu().numpy().reshape(m, lay.cout)
     assert np.isfinite(got).all()
     assert rel_err(got, ref) < 2e-6, case[0]
     assert max_err_scaled(got, ref) < 1e-5
@@ -202,11 +246,17 @@ def test_layer_wgrad(L, case, msplit):
     u8 = x_raw.dtype == np.uint8
     xf = L.InputXform(1 if u8 else 0, 0.0, 255.0 if u8 else 1.0)
     kk = cols.shape[1]
-    out = torch.full(((kk + 1) * lay.cout,), float("nan"), device="cuda")
-    slabs = torch.zeros((16 * (kk + 1) * lay.cout,), device="cuda")
-    L.check(L.load().xt_layer_wgrad(ctypes.byref(g), ctypes.byref(xf), b, L.ptr(dev(x_raw)), None, L.ptr(dev(dy)),
-                                    L.ptr(out), L.ptr(slabs), msplit, None), "wgrad")
-    got = out.cpu().numpy()
+    nw = (kk + 1) * lay.cout
+    out = with_tail(nw, float("nan"))
+    slabs = with_tail(16 * nw, 0.0)
+    rc = L.load().xt_layer_wgrad(ctypes.byref(g), ctypes.byref(xf), b, L.ptr(dev(x_raw)), None, L.ptr(dev(dy)),
+                                 L.ptr(out), L.ptr(slabs), msplit, None)
+    if refused(L, case, rc, (out[:nw], float("nan")), (slabs[:16 * nw], 0.0)):
+        return
+    L.check(rc, "wgrad")
+    torch.cuda.synchronize()
+    assert tail_intact(out, nw) and tail_intact(slabs, 16 * nw), case[0]
+    got = out[:nw].cpu().numpy()
     assert np.isfinite(got).all()
     assert rel_err(got[:kk * lay.cout].reshape(kk, lay.cout), ref_w) < 3e-6, case[0]
     assert rel_err(got[kk * lay.cout:], ref_b) < 3e-6
@@ -232,8 +282,11 @@ def test_layer_dgrad(L, case):
             ref = nets.act_bwd(dx.reshape(xp.shape), xp.astype(np.float64), act_prev)
         g = geom_of(L, lay)
         out = torch.full(xp.shape, float("nan"), device="cuda")
-        L.check(L.load().xt_layer_dgrad(ctypes.byref(g), b, L.ptr(dev(dy)), L.ptr(dev(w)), L.ptr(dev(xp)),
-                                        L.ACT[act_prev], L.ptr(out), None), "dgrad")
+        rc = L.load().xt_layer_dgrad(ctypes.byref(g), b, L.ptr(dev(dy)), L.ptr(dev(w)), L.ptr(dev(xp)),
+                                     L.ACT[act_prev], L.ptr(out), None)
+        if refused(L, case, rc, (out, float("nan"))):
+            continue
+        L.check(rc, "dgrad")
         got = out.cpu().numpy()
         assert np.isfinite(got).all(), case[0]
         # (softplus / softsign: the fp32 output carries the pre-activation only to ~1e-7 relative near saturation)

@@ -1922,7 +1922,7 @@ int launch_dgrad(const xt_conv_geom* cg, int B, const float* dy, const float* w,
 int launch_bwd_layer(const xt_conv_geom* cg, int B, const float* x_in, const float* dy, const float* w,
                      int act_prev, float* dx, float* dwb, float* slabs, int msplit, const HeadWgArgs* hw,
                      int* msplit_out, hipStream_t st, const uint32_t* xmask, int slab_cap, const float* x_grad,
-                     float* sq_partials, int* npre_out) {
+                     float* sq_partials, int* npre_out, int* path_out) {
   if (!x_grad) x_grad = x_in;
   if (npre_out) *npre_out = 0;
   BwdLayerArgs a;
@@ -2046,7 +2046,7 @@ int launch_bwd_layer(const xt_conv_geom* cg, int B, const float* x_in, const flo
       a.wg.mchunk = per;                  // samples per group
       a.wg.d_rowq = make_fastdiv((uint32_t)(g.W * kWrC / 4));
       a.wg.msplit = groups;
-      a.wg.out = slabs;
+      a.wg.out = groups == 1 ? dwb : slabs;     // (one group: its slab is the final gradient, as msplit_out = 1 says)
       a.wg_gx = g.KH; a.wg_gy = 1; a.wg_gz = groups;
       a.n_wg = g.KH * groups;
       if (msplit_out) *msplit_out = groups;
@@ -2115,18 +2115,25 @@ int launch_bwd_layer(const xt_conv_geom* cg, int B, const float* x_in, const flo
   } while (0)
   last_arith() = XT_ARITH_FP32;          // (register-direct input gradients and the x6 = 0 forms)
   if (dx6 || (tuning().bf16x6 && a.dg_direct == 2)) last_arith() = XT_ARITH_FP32_BF16X6;
+  // which branch runs (xt_layer_bwd's path_out; recorded in front of the launch, changes nothing)
+  auto taken = [&](int path) {
+    if (path_out) *path_out = path | (a.dg_direct << XT_BWD_DG_SHIFT) | (last_arith() << XT_BWD_ARITH_SHIFT);
+  };
   if (s2fused) {
     last_arith() = XT_ARITH_BF16X6;
+    taken(XT_BWD_PATH_S2FUSED);
     if (pad) hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, true, 128, 32, 4, 1, 0, 5>), dim3(total), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 0, 5>), dim3(total), dim3(256), 0, st, a);
   } else if (s2c16) {
     last_arith() = XT_ARITH_FP32_BF16X6;
+    taken(XT_BWD_PATH_S2C16);
     if (pad) hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, true, 128, 32, 4, 1, 0, 3>), dim3(total), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 0, 3>), dim3(total), dim3(256), 0, st, a);
   } else if (halo_inst) {
     const int hx6 = tuning().bf16x6;     // 0: fp32 MFMA (A/B)
     const int nsamp = 63 / (g.H * g.W) + 2;
     if (hx6 && (size_t)3 * (nsamp * g.OHOW + 1) * (g.N * 2 + 16) <= 44 * 1024) last_arith() = XT_ARITH_FP32_BF16X6;
+    taken(XT_BWD_PATH_HALO);
     if (hx6 && (size_t)3 * (nsamp * g.OHOW + 1) * (g.N * 2 + 16) <= 44 * 1024) {
       if (tuning().dense_wgrad_x6 == 2)      // EXPERIMENT (off by default): conv3's weight gradient bf16x6 with one LDS stage
         hipLaunchKernelGGL((igemm_bwd_layer_kernel<64, 64, 2, 2, false, 128, 32, 4, 1, 0, 2, false, 0, 2>), dim3(total), dim3(256), 0, st, a);
@@ -2138,12 +2145,14 @@ int launch_bwd_layer(const xt_conv_geom* cg, int B, const float* x_in, const flo
   } else if (a.dg_direct == 2 && pf4_only) {
     // WROWS = 3: the LDS-tiled im2col weight gradient next to the all-taps-in-flight input gradient (250 VGPRs: two
     // workgroups per CU, the launch cut to 512 co-resident workgroups)
+    taken(XT_BWD_PATH_CLASSES_PF4);
     hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 2, 0, false, 3>), dim3(total), dim3(256), 0, st, a);
   } else if (a.dg_direct == 2 && wrows) {
     // (KH/S) * (KW/S) * (N/32) == 4 reduction steps: the input-gradient blocks keep all four taps' operands in flight
 #ifdef XT_TL_EXPERIMENT
     if (exp_alone) a.dg_direct = 99;
 #endif
+    taken(XT_BWD_PATH_CLASSES_WROWS);
     if ((g.KH / g.S) * (g.KW / g.S) * (g.N >> 5) == 4 && tuning().wgrad_rows != 2)
       hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 2, 0, false, 2>), dim3(total), dim3(256), 0, st, a);
     else
@@ -2151,24 +2160,37 @@ int launch_bwd_layer(const xt_conv_geom* cg, int B, const float* x_in, const flo
   } else if (a.dg_direct == 2) {
     XT_REQUIRE(wsmall && dsmall && !pad, "bwd_layer: the all-classes input gradient needs the small-tile configuration");
     const int x6 = tuning().bf16x6;      // 0: fp32 MFMA in the all-classes input gradient (A/B)
+    taken(XT_BWD_PATH_CLASSES);
     if (x6) hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 2>), dim3(total), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 1>), dim3(total), dim3(256), 0, st, a);
   } else if (pf_generic) {
     if (tuning().dense_wgrad_x6) {        // (round 5) the Dense weight gradient on the bf16 matrix cores as well
       last_arith() = XT_ARITH_BF16X6;
+      taken(XT_BWD_PATH_PF_GENERIC);
       hipLaunchKernelGGL((igemm_bwd_layer_kernel<64, 64, 2, 2, false, 64, 64, 2, 2, 0, 0, true, 3, 1>), dim3(total2), dim3(256), 0, st, a);
     } else {
+      taken(XT_BWD_PATH_PF_GENERIC);
       hipLaunchKernelGGL((igemm_bwd_layer_kernel<64, 64, 2, 2, false, 64, 64, 2, 2, 0, 0, true, 3>), dim3(total2), dim3(256), 0, st, a);
     }
-  } else if (wsmall && dsmall) XT_BWD(128, 32, 4, 1, 128, 32, 4, 1);
-  else if (wsmall) XT_BWD(128, 32, 4, 1, 64, 64, 2, 2);
-  else if (dsmall) XT_BWD(64, 64, 2, 2, 128, 32, 4, 1);
-  else if (tuning().dense_wgrad_x6 && dx6 && !pad) {
+  } else if (wsmall && dsmall) {
+    taken(XT_BWD_PATH_PAIR_SS);
+    XT_BWD(128, 32, 4, 1, 128, 32, 4, 1);
+  } else if (wsmall) {
+    taken(XT_BWD_PATH_PAIR_SL);
+    XT_BWD(128, 32, 4, 1, 64, 64, 2, 2);
+  } else if (dsmall) {
+    taken(XT_BWD_PATH_PAIR_LS);
+    XT_BWD(64, 64, 2, 2, 128, 32, 4, 1);
+  } else if (tuning().dense_wgrad_x6 && dx6 && !pad) {
     // the generic 64x64 pair (ImpalaCnnOpt's 11x11 "dense" conv) with the one-LDS-stage bf16x6 weight gradient (three
     // workgroups per CU as before): pong_impala_speedup 214.6 -> 212.3 us per 1000-frame train, breakout_impala unchanged
     last_arith() = XT_ARITH_BF16X6;
+    taken(XT_BWD_PATH_PAIR_LL_WX6);
     hipLaunchKernelGGL((igemm_bwd_layer_kernel<64, 64, 2, 2, false, 64, 64, 2, 2, 0, 0, true, 0, 2>), dim3(total), dim3(256), 0, st, a);
-  } else XT_BWD(64, 64, 2, 2, 64, 64, 2, 2);
+  } else {
+    taken(XT_BWD_PATH_PAIR_LL);
+    XT_BWD(64, 64, 2, 2, 64, 64, 2, 2);
+  }
 #undef XT_BWD
 #undef XT_BWD2
   XT_LAUNCH_CHECK();
@@ -2192,6 +2214,26 @@ int xt_layer_wgrad(const xt_conv_geom* g, const xt_input_xform* xf, int32_t B, c
 int xt_layer_dgrad(const xt_conv_geom* g, int32_t B, const float* dy, const float* w, const float* x,
                    int32_t act_prev, float* dx, void* stream) {
   return xt::launch_dgrad(g, B, dy, w, x, act_prev, dx, xt::as_stream(stream));
+}
+
+int xt_layer_bwd(const xt_conv_geom* g, int32_t B, const float* x, const float* x_pre, const float* dy,
+                 const float* w, int32_t act_prev, const uint32_t* relu_mask, float* dx, float* dwb, float* slabs,
+                 int32_t slab_cap, int32_t msplit, void* stream, int32_t* path_out) {
+  if (path_out) *path_out = 0;
+  // (the launch only ever LOWERS the split it is asked for, or sizes its per-sample forms by slab_cap)
+  XT_REQUIRE(g && (msplit <= 1 || (slabs != nullptr && msplit <= slab_cap)),
+             "xt_layer_bwd: msplit %d needs a slab buffer of at least that many slabs (capacity %d)", msplit, slab_cap);
+  const hipStream_t st = xt::as_stream(stream);
+  int nslab = 1;
+  if (int rc = xt::launch_bwd_layer(g, B, x, dy, w, act_prev, dx, dwb, slabs, msplit, nullptr, &nslab, st, relu_mask,
+                                    slabs ? slab_cap : 0, x_pre, nullptr, nullptr, path_out))
+    return rc;
+  if (nslab > 1) {
+    const int count = (g->KH * g->KW * g->C + 1) * g->N;
+    hipLaunchKernelGGL(xt::reduce_slabs_kernel, dim3((count / 4 + 255) / 256), dim3(256), 0, st, slabs, dwb, count, nslab);
+    XT_LAUNCH_CHECK();
+  }
+  return 0;
 }
 
 }  // extern "C"

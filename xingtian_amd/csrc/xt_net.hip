@@ -41,7 +41,8 @@ int launch_fwd(const xt_conv_geom*, const xt_input_xform*, int, const void*, con
                uint32_t* relu_mask = nullptr, int* mask_written = nullptr);
 int launch_bwd_layer(const xt_conv_geom*, int, const float*, const float*, const float*, int, float*, float*, float*,
                      int, const HeadWgArgs*, int*, hipStream_t, const uint32_t* xmask = nullptr, int slab_cap = 0,
-                     const float* x_grad = nullptr, float* sq_partials = nullptr, int* npre_out = nullptr);
+                     const float* x_grad = nullptr, float* sq_partials = nullptr, int* npre_out = nullptr,
+                     int* path_out = nullptr);
 int launch_act_apply(const float* z, float* y, long long count, int act, hipStream_t st);
 int launch_conv12_same_fwd(const xt_conv_geom*, const xt_input_xform*, const xt_conv_geom*, int, const void*, const int32_t*,
                            const float*, const float*, float*, const float*, const float*, float*, hipStream_t);
