@@ -86,7 +86,7 @@ def main():
     import torch
     from xingtian_amd import lib as L
     L.LIB_PATH = os.environ.get("XT_TL_LIB") or os.path.join(ROOT, "xingtian_amd", "libxt_mi355x_tl.so")
-    if os.environ.get("XT_TL_KNOBS"):          # e.g. XT_TL_KNOBS='{"wgrad_rows": 3}' (experiment builds)
+    if os.environ.get("XT_TL_KNOBS"):          # tuning knobs for this run, e.g. XT_TL_KNOBS='{"wgrad_rows": 1}'
         import json
         L.set_tuning(**json.loads(os.environ["XT_TL_KNOBS"]))
     from xingtian_amd.model import netspec

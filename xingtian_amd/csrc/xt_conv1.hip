@@ -14,6 +14,7 @@
 // 16-byte loads (the minibatch row gather idx[b] is fused here) and produces all of its OH*OW x 32 outputs.
 #include "xt_common.h"
 #include "xt_conv1_dev.h"
+#include "xt_launch.h"
 
 namespace xt {
 

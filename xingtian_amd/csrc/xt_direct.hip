@@ -30,6 +30,7 @@
 #include "xt_common.h"
 #include "xt_igemm.h"
 #include "xt_direct_dev.h"
+#include "xt_launch.h"
 
 namespace xt {
 
@@ -260,8 +261,9 @@ int launch_fwd_direct(const xt_conv_geom* cg, const xt_input_xform* xf, int B, c
 
 // Plan for the fused per-layer backward launch (256-thread blocks -> NW = 4, one 32x32 tile per block): only the
 // shapes where the direct kernel measured faster (single-column tiles, long reduction, not too many tiles).
-bool plan_dgrad_direct_fused(const Geom& g, DDgradArgs* a, int* nblocks) {
-  if (!use_direct() || !tuning().direct_dgrad || g.N % 32 != 0 || g.C % 32 != 0) return false;
+// t: the caller's snapshot of the tuning knobs (one consistent view per planned launch)
+bool plan_dgrad_direct_fused(const xt_tuning& t, const Geom& g, DDgradArgs* a, int* nblocks) {
+  if (!t.direct || !t.direct_dgrad || g.N % 32 != 0 || g.C % 32 != 0) return false;
   if (g.C % 64 == 0) return false;                       // TJ = 2 shapes stay on the LDS-tiled kernel
   const int hc = (g.H + g.S - 1) / g.S, wc = (g.W + g.S - 1) / g.S;
   const int mc = g.B * hc * wc;
@@ -269,7 +271,7 @@ bool plan_dgrad_direct_fused(const Geom& g, DDgradArgs* a, int* nblocks) {
   const int jmax = ((g.KH + g.S - 1) / g.S) * ((g.KW + g.S - 1) / g.S);
   const int nsteps = jmax * (g.N / 32);
   const int tiles = ((mc + 31) / 32) * (g.C / 32) * nclass;
-  if (!direct_all() && (nsteps < 8 || tiles >= tuning().direct_tile64_tiles)) return false;
+  if (!t.direct_all && (nsteps < 8 || tiles >= t.direct_tile64_tiles)) return false;
   a->g = g;
   a->mt = (mc + 31) / 32;
   a->ct = g.C / 32;

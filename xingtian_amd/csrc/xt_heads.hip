@@ -2,6 +2,7 @@
 // All HBM/latency-bound; wave64 shuffles for the reductions, no atomics (deterministic).
 #include "xt_common.h"
 #include "xt_heads_dev.h"
+#include "xt_launch.h"
 
 namespace xt {
 

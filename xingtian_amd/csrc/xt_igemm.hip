@@ -22,6 +22,7 @@
 #include "xt_heads_dev.h"
 #include "xt_direct_dev.h"
 #include "xt_conv1_dev.h"
+#include "xt_launch.h"
 
 namespace xt {
 
@@ -1535,9 +1536,6 @@ __device__ __forceinline__ void wgrad_rows_body(const WgradArgs& p, const int gr
     __syncthreads();
     if (s == s_beg) XT_TL(2);
     if (s + 2 < s_end) { if (even) fetch_s(RA, s + 2); else fetch_s(RB, s + 2); }
-#ifdef XT_TL_EXPERIMENT
-    if (s == s_beg) XT_TL(3);
-#endif
     // four position pairs per step, two register sets (no copies): the eight operand reads of step i+1 are ISSUED
     // before the four MFMAs of step i and the offset quad of step i+2 before that (clamped, unconditional).  The
     // sched_barriers pin that order: left alone, the scheduler sinks every read next to its MFMA and the wave -- the
@@ -1584,16 +1582,11 @@ __device__ __forceinline__ void wgrad_rows_body(const WgradArgs& p, const int gr
     }
     if (nst & 1) mma4(a0, b0);
 #undef XT_WR_INTERLEAVE
-#ifdef XT_TL_EXPERIMENT
-    if (s == s_beg) XT_TL(4);
-#endif
     if (do_bias) {
       for (int m = bg; m < g.OHOW; m += 8) bsum += ds[m * kWrN + bn];
     }
   }
-#ifndef XT_TL_EXPERIMENT
   XT_TL(3);
-#endif
   float* out = p.out + (size_t)group * ((size_t)(g.K + 1) * kWrN);
   const int k0 = (ky * kWrKW + kx) * kWrC;
 #pragma unroll
@@ -1612,9 +1605,7 @@ __device__ __forceinline__ void wgrad_rows_body(const WgradArgs& p, const int gr
       out[(size_t)g.K * kWrN + t] = sum;
     }
   }
-#ifndef XT_TL_EXPERIMENT
   XT_TL(4);
-#endif
   XT_TL_DRAIN(5);
 }
 
@@ -1646,9 +1637,6 @@ __global__ __launch_bounds__(256, WROWS ? 2 : 3) void igemm_bwd_layer_kernel(con
   constexpr int SM = (D4 && dgrad4_smem_floats<D4 == 2>() > SM0) ? dgrad4_smem_floats<D4 == 2>() : SM0;
   __shared__ __attribute__((aligned(16))) float smem[SM];
   int b = blockIdx.x;
-#ifdef XT_TL_EXPERIMENT
-  if (b < p.n_dg && p.dg_direct == 99) return;      // experiment: weight-gradient blocks alone
-#endif
   if (b < p.n_dg) {                       // dgrad first: it is on the critical path of the next layer
     if constexpr (D4 != 0) {              // stride-2 conv: the four parity classes of a position tile in one block
       igemm_dgrad4_body<D4 == 2, (WROWS >= 2)>(p.dg, b, smem);
@@ -1711,19 +1699,6 @@ static inline int pick_ksplit_chunk(int K, int split, int* chunk) {
   *chunk = per * 32;
   return (steps + per - 1) / per;   // effective split count
 }
-
-int launch_conv1_fwd_bf16x3(const xt_conv_geom*, const xt_input_xform*, int, const void*, const int32_t*, const float*,
-                            const float*, float*, hipStream_t, uint32_t*, int*);
-int launch_conv1_wgrad_bf16x3(const xt_conv_geom*, const xt_input_xform*, int, const void*, const int32_t*,
-                              const float*, float*, float*, int, int*, hipStream_t);
-int launch_conv1_same_fwd(const xt_conv_geom*, const xt_input_xform*, int, const void*, const int32_t*, const float*,
-                          const float*, float*, hipStream_t);
-int launch_conv1_same_wgrad(const xt_conv_geom*, const xt_input_xform*, int, const void*, const int32_t*, const float*,
-                            float*, float*, int, int*, hipStream_t);
-bool plan_dgrad_direct_fused(const Geom&, DDgradArgs*, int*);
-int launch_dgrad_direct(const xt_conv_geom*, int, const float*, const float*, const float*, int, float*, hipStream_t);
-int launch_fwd_direct(const xt_conv_geom*, const xt_input_xform*, int, const void*, const int32_t*, const float*,
-                      const float*, float*, float*, int, hipStream_t, int*);
 
 static bool use_kg2() { return tuning().fwd_two_groups != 0; }
 static bool use_bf16x3() { return tuning().conv1_bf16x3 != 0; }
@@ -1916,283 +1891,229 @@ int launch_dgrad(const xt_conv_geom* cg, int B, const float* dy, const float* w,
   return 0;
 }
 
-// wgrad (fp32 input) + dgrad (+ head wgrad) of one non-first layer in ONE launch.
-// x_grad (may be null = x_in): what the input gradient's activation-derivative epilogue reads -- the producer's
-// PRE-activation when its activation is not monotonic (act_needs_preact), else its output x_in
-int launch_bwd_layer(const xt_conv_geom* cg, int B, const float* x_in, const float* dy, const float* w,
-                     int act_prev, float* dx, float* dwb, float* slabs, int msplit, const HeadWgArgs* hw,
-                     int* msplit_out, hipStream_t st, const uint32_t* xmask, int slab_cap, const float* x_grad,
-                     float* sq_partials, int* npre_out, int* path_out) {
-  if (!x_grad) x_grad = x_in;
-  if (npre_out) *npre_out = 0;
-  BwdLayerArgs a;
-  if (int rc = make_geom(cg, nullptr, B, &a.wg.g)) return rc;
-  a.dg.g = a.wg.g;
-  const Geom& g = a.wg.g;
+// ------------------------------------------------------------------ fused backward of one layer: plan, then launch
+// wgrad (fp32 input) + dgrad (+ head wgrad) of one non-first layer in ONE launch.  plan_bwd_layer decides everything
+// (no HIP call, no tensor pointer); launch_bwd_layer fills the pointers in and launches the instance the plan names.
+
+// One enumerator per igemm_bwd_layer_kernel instance that can be launched.  Pair<W><D>: the generic LDS-tiled pairs by
+// weight-gradient / input-gradient tile (S = 128x32, L = 64x64), each also padded and / or with the bf16x6 input gradient.
+#define XT_BWD_PAIR4(P) kBwdPair##P, kBwdPair##P##Pad, kBwdPair##P##X6, kBwdPair##P##PadX6
+enum BwdInst {
+  kBwdS2Fused, kBwdS2FusedPad, kBwdS2c16, kBwdS2c16Pad, kBwdHalo, kBwdHaloX6, kBwdHaloX6Wx6,
+  kBwdClassesPf4, kBwdClassesWrows2, kBwdClassesWrows1, kBwdClassesX6, kBwdClasses, kBwdDense, kBwdDenseWx6, kBwdPairLLWx6,
+  XT_BWD_PAIR4(SS), XT_BWD_PAIR4(SL), XT_BWD_PAIR4(LS), XT_BWD_PAIR4(LL)
+};
+#undef XT_BWD_PAIR4
+
+// What the plan decides besides the non-pointer fields of BwdLayerArgs, which it fills directly.  There, wg.msplit is THE
+// number of slabs the weight gradient is written as, whatever its form: 1 = final in dwb, else that many in `slabs`.
+struct BwdPlan {
+  BwdInst inst;
+  int path;       // XT_BWD_PATH_*
+  int arith;      // XT_ARITH_*
+  int npre;       // squared-norm partials the weight-gradient blocks leave (0: none)
+};
+
+// LDS-tiled weight gradient: the reduction over M in (at most) `split` slabs, one grid layer each
+static void cut_wgrad(int split, BwdLayerArgs* a) {
+  a->wg.msplit = a->wg_gz = pick_ksplit_chunk(a->wg.g.M, split > 1 ? split : 1, &a->wg.mchunk);
+  a->n_wg = a->wg_gx * a->wg_gy * a->wg_gz;
+}
+// ... re-cut so that its blocks fit the `room` workgroup slots which the other blocks of the launch leave
+static void fit_wgrad(int room, BwdLayerArgs* a) {
+  if (a->n_wg > room) cut_wgrad(room / (a->wg_gx * a->wg_gy), a);
+}
+
+// g.B samples; msplit: requested weight-gradient split; slab_cap: slabs the slab buffer holds (have_slabs: there is one);
+// n_hw: head weight-gradient blocks riding along (0: none); want_npre: the caller can take squared-norm partials.
+// The branches in order of precedence, one early return each.
+static int plan_bwd_layer(const Geom& g, int msplit, bool have_slabs, int slab_cap, int n_hw, bool want_npre,
+                          BwdLayerArgs* a, BwdPlan* p) {
+  const xt_tuning t = tuning();      // ONE snapshot: a knob changed on another thread mid-call cannot give a mixed view
+  const int B = g.B;
   // (the buffer loads of the backward kernels address their tensors with 32-bit byte offsets, 2^31 = "out of range")
   XT_REQUIRE((long long)g.M * g.N * 4 < (1ll << 31) && (long long)g.B * g.HWC * 4 < (1ll << 31),
              "bwd_layer: activation / gradient tensors of 2 GiB or more are not supported (batch %d)", B);
-  // ---- wgrad part
-  a.wg.in = x_in; a.wg.idx = nullptr; a.wg.dy = dy;
-  a.wg.sq_out = nullptr; a.wg.sq_gx = 0;
-  if (msplit < 1) msplit = 1;
-  int chunk;
-  msplit = pick_ksplit_chunk(g.M, msplit, &chunk);
-  XT_REQUIRE(msplit == 1 || slabs != nullptr, "bwd_layer: msplit>1 needs a slab buffer");
-  a.wg.msplit = msplit; a.wg.mchunk = chunk;
-  a.wg.out = msplit == 1 ? dwb : slabs;
-  if (msplit_out) *msplit_out = msplit;
-  const bool wsmall = g.N <= 32;
-  a.wg_gx = wsmall ? (g.K + 127) / 128 : (g.K + 63) / 64;
-  a.wg_gy = wsmall ? (g.N + 31) / 32 : (g.N + 63) / 64;
-  a.wg_gz = msplit;
-  a.n_wg = a.wg_gx * a.wg_gy * a.wg_gz;
-  // ---- dgrad part
-  a.dg.dy = dy; a.dg.w = w; a.dg.x = x_grad; a.dg.dx = dx; a.dg.act_prev = act_prev; a.dg.xmask = nullptr;
-  if (int rc = fill_class_divs(g, &a.dg)) return rc;
-  const int hc = (g.H + g.S - 1) / g.S, wc = (g.W + g.S - 1) / g.S;
-  const int mc = B * hc * wc;
-  const bool dsmall = g.C <= 32;
-  a.dg_gx = dsmall ? (mc + 127) / 128 : (mc + 63) / 64;
-  a.dg_gy = dsmall ? (g.C + 31) / 32 : (g.C + 63) / 64;
-  a.dg_gz = g.S * g.S;
-  a.n_dg = a.dg_gx * a.dg_gy * a.dg_gz;
-  a.dg_direct = 0;
-  a.dg_xcd = tuning().fwd_xcd_chunk != 0 ? 1 : 0;
-  {
-    const int no_d4 = tuning().dgrad_all_classes ? 0 : 1;
-    if (!no_d4 && g.S == 2 && g.KH % 2 == 0 && g.KW % 2 == 0 && g.H % 2 == 0 && g.W % 2 == 0 && g.PT == 0 &&
-        g.PL == 0 && g.C == 32 && g.N == 32 && (g.OH - 1) * g.S + g.KH <= g.H && (g.OW - 1) * g.S + g.KW <= g.W) {
-      a.dg_direct = 2;
-      a.n_dg = (B * (g.H / 2) * (g.W / 2) + 127) / 128;
-      if (act_prev == XT_ACT_RELU) a.dg.xmask = xmask;       // (C == 32: one mask word per pixel)
+  const bool x6 = t.bf16x6 != 0, pad = is_padded(g), wsmall = g.N <= 32, dsmall = g.C <= 32;
+  const auto take = [&](BwdInst inst, int path, int arith) { p->inst = inst; p->path = path; p->arith = arith; return 0; };
+  p->npre = 0;
+  a->wg.g = a->dg.g = g;
+  a->n_hw = n_hw;
+  // ---- the generic forms: LDS-tiled weight gradient ...
+  a->wg_gx = wsmall ? (g.K + 127) / 128 : (g.K + 63) / 64;
+  a->wg_gy = wsmall ? (g.N + 31) / 32 : (g.N + 63) / 64;
+  const int tiles = a->wg_gx * a->wg_gy;
+  cut_wgrad(msplit, a);
+  XT_REQUIRE(a->wg.msplit == 1 || have_slabs, "bwd_layer: msplit>1 needs a slab buffer");
+  // ... and LDS-tiled input gradient, one grid layer per stride-parity class
+  if (int rc = fill_class_divs(g, &a->dg)) return rc;
+  const int mc = B * ((g.H + g.S - 1) / g.S) * ((g.W + g.S - 1) / g.S);
+  a->dg_gx = dsmall ? (mc + 127) / 128 : (mc + 63) / 64;
+  a->dg_gy = dsmall ? (g.C + 31) / 32 : (g.C + 63) / 64;
+  a->dg_gz = g.S * g.S;
+  a->n_dg = a->dg_gx * a->dg_gy * a->dg_gz;
+  a->dg_xcd = t.fwd_xcd_chunk != 0 ? 1 : 0;
+
+  // ---- stride-2 4x4 with 16 input channels (ImpalaCnnOpt conv2): sample-per-workgroup bf16x6 input gradient
+  // (C == 16: neither the all-classes nor a register-direct input gradient takes the shape)
+  const size_t s2_dy_bytes = (size_t)3 * (g.OHOW + 1) * 80, s2_x_bytes = (size_t)3 * (g.H * g.W + 1) * 32;
+  if (x6 && g.S == 2 && g.KH == 4 && g.KW == 4 && g.C == 16 && g.N == 32 && s2_dy_bytes <= 8 * 1024 * 4) {
+    a->ddg.g = g;
+    a->dg_direct = 5;
+    a->n_dg = B;
+    if (t.bwd_deep_prefetch && 2 * B <= 256) { a->ddg.ct = 2; a->n_dg = 2 * B; }     // two workgroups per sample (four: no further gain)
+    // ... and, for large batches, the weight gradient in the same workgroups: 512 of them (two per CU), one slab each
+    if (B >= 512 && have_slabs && slab_cap >= 512 && s2_dy_bytes + s2_x_bytes <= 18 * 1024 * 4) {
+      a->n_dg = 512;                                   // each walks samples bid, bid + 512, ...
+      a->n_wg = 0;
+      a->wg.msplit = a->n_dg;
+      return take(pad ? kBwdS2FusedPad : kBwdS2Fused, XT_BWD_PATH_S2FUSED, XT_ARITH_BF16X6);
+    }
+    return take(pad ? kBwdS2c16Pad : kBwdS2c16, XT_BWD_PATH_S2C16, XT_ARITH_FP32_BF16X6);
+  }
+
+  // ---- which input gradient: all stride-2 parity classes of a position tile in one block, register-direct, or LDS-tiled
+  const int halo_nsamp = 63 / (g.H * g.W) + 2;      // samples that the 64 rows of a halo tile can touch
+  if (t.dgrad_all_classes && g.S == 2 && g.KH % 2 == 0 && g.KW % 2 == 0 && g.H % 2 == 0 && g.W % 2 == 0 && g.PT == 0 &&
+      g.PL == 0 && g.C == 32 && g.N == 32 && (g.OH - 1) * g.S + g.KH <= g.H && (g.OW - 1) * g.S + g.KW <= g.W) {
+    a->dg_direct = 2;
+    a->n_dg = (B * (g.H / 2) * (g.W / 2) + 127) / 128;
+  } else if (plan_dgrad_direct_fused(t, g, &a->ddg, &a->n_dg)) {
+    a->dg_direct = 1;
+    a->ddg.deep = t.bwd_deep_prefetch != 0 ? 1 : 0;
+    // dgrad_tile64 = 0: 32-row tiles (A/B; measured 30.4 vs 27.7 us for conv3 at B=320)
+    if (t.dgrad_tile64 && g.S == 1 && a->n_dg > 512) {   // 64-row tiles: half the blocks, the weight operand shared by two row tiles
+      a->ddg.mt = (B * g.H * g.W + 63) / 64;
+      a->n_dg = a->ddg.mt * a->ddg.ct;
+      // dgrad_halo = 0: register-direct dY gather instead of the LDS halo (A/B)
+      const bool halo = t.dgrad_halo && (size_t)(halo_nsamp * g.OHOW + 1) * (g.N + 4) * 4 <= 36 * 1024 && g.N + 4 <= 256;
+      a->dg_direct = halo ? 4 : 3;
     }
   }
-  if (a.dg_direct == 0) {
-    int nblk = 0;
-    a.ddg.deep = 0;
-    if (plan_dgrad_direct_fused(g, &a.ddg, &nblk)) {
-      a.ddg.deep = tuning().bwd_deep_prefetch != 0 ? 1 : 0;
-      a.ddg.dy = dy; a.ddg.w = w; a.ddg.x = x_grad; a.ddg.dx = dx; a.ddg.act_prev = act_prev;
-      a.dg_direct = 1;
-      a.n_dg = nblk;
-      const int ti2 = tuning().dgrad_tile64;   // 0: 32-row tiles (A/B; measured 30.4 vs 27.7 us for conv3 at B=320)
-      if (ti2 && g.S == 1 && nblk > 512) { // 64-row tiles: half the blocks, the weight operand shared by two row tiles
-        const int mc = B * g.H * g.W;
-        a.ddg.mt = (mc + 63) / 64;
-        a.n_dg = a.ddg.mt * a.ddg.ct;
-        a.dg_direct = 3;
-        const int halo = tuning().dgrad_halo;   // 0: register-direct dY gather instead of the LDS halo (A/B)
-        const int nsamp = 63 / (g.H * g.W) + 2;
-        if (halo && (size_t)(nsamp * g.OHOW + 1) * (g.N + 4) * 4 <= 36 * 1024 && g.N + 4 <= 256) a.dg_direct = 4;
-      }
-    }
-  }
-  // ---- head wgrad part
-  a.n_hw = 0;
-  if (hw) { a.hw = *hw; a.n_hw = hw->gx * hw->nchunk; }
-  else { a.hw.gx = 1; a.hw.nchunk = 0; }
-  // The halo input gradient has its own kernel instance (tuning.bwd_own_instance = 0: the generic one): three workgroups per CU
-  // instead of two.  With it, a launch that is only a little larger than the 768 co-resident workgroups is cut to
+
+  // ---- The halo input gradient has its own kernel instance (tuning.bwd_own_instance = 0: the generic one): three workgroups per
+  // CU instead of two.  With it, a launch that is only a little larger than the 768 co-resident workgroups is cut to
   // one round (tuning.bwd_fit_slots, 0 = off): the surplus weight-gradient blocks otherwise start when the first
   // input-gradient blocks END and the launch takes two block lifetimes.  Measured for conv3 at B=320: generic 26.3,
   // own instance 24.4, own instance + one round 22.6 us (with the register-direct dY gather both made it SLOWER:
   // a third co-resident workgroup thrashed the L1 that gather depends on).
-  const int spec = tuning().bwd_own_instance, fit = tuning().bwd_fit_slots;
-  const bool halo_inst = a.dg_direct == 4 && spec && !wsmall && !is_padded(g);
-  if (halo_inst) {
-    const int tiles = a.wg_gx * a.wg_gy;
-    const int room = fit - a.n_dg - a.n_hw;
-    if (fit > 0 && a.n_wg + a.n_dg + a.n_hw > fit && room >= tiles * 8 && a.n_wg <= 2 * room) {
-      msplit = pick_ksplit_chunk(g.M, room / tiles, &chunk);      // effective split <= room / tiles
-      a.wg.msplit = msplit; a.wg.mchunk = chunk;
-      a.wg.out = msplit == 1 ? dwb : slabs;
-      if (msplit_out) *msplit_out = msplit;
-      a.wg_gz = msplit;
-      a.n_wg = tiles * msplit;
-    }
+  if (a->dg_direct == 4 && t.bwd_own_instance && !wsmall && !pad) {
+    const int room = t.bwd_fit_slots - a->n_dg - n_hw;
+    if (t.bwd_fit_slots > 0 && room >= tiles * 8 && a->n_wg <= 2 * room) fit_wgrad(room, a);
+    // (bf16x6 = 0, or a halo that does not fit the LDS as bf16 planes: fp32 MFMA)
+    if (!x6 || (size_t)3 * (halo_nsamp * g.OHOW + 1) * (g.N * 2 + 16) > 44 * 1024)
+      return take(kBwdHalo, XT_BWD_PATH_HALO, XT_ARITH_FP32);
+    // dense_wgrad_x6 = 2: EXPERIMENT (off by default): conv3's weight gradient bf16x6 with one LDS stage
+    return take(t.dense_wgrad_x6 == 2 ? kBwdHaloX6Wx6 : kBwdHaloX6, XT_BWD_PATH_HALO, XT_ARITH_FP32_BF16X6);
   }
-  // stride-2 4x4 with 16 input channels (ImpalaCnnOpt conv2): sample-per-workgroup bf16x6 input gradient
-  const bool s2c16 = tuning().bf16x6 && a.dg_direct == 0 && g.S == 2 && g.KH == 4 && g.KW == 4 && g.C == 16 && g.N == 32 &&
-                     wsmall && (size_t)3 * (g.OHOW + 1) * 80 <= 8 * 1024 * 4;
-  if (s2c16) {
-    a.ddg.g = g; a.ddg.dy = dy; a.ddg.w = w; a.ddg.x = x_grad; a.ddg.dx = dx; a.ddg.act_prev = act_prev;
-    a.ddg.mt = 0; a.ddg.ct = 0; a.ddg.deep = 0;
-    a.dg_direct = 5;
-    a.n_dg = B;
-    if (tuning().bwd_deep_prefetch && 2 * B <= 256) { a.ddg.ct = 2; a.n_dg = 2 * B; }     // two workgroups per sample (four: no further gain)
-  }
-  // ... and, for large batches, the weight gradient in the same workgroups: 512 of them (two per CU), one slab each
-  const bool s2fused = s2c16 && B >= 512 && slabs != nullptr && slab_cap >= 512 &&
-                       (size_t)3 * (g.OHOW + 1) * 80 + (size_t)3 * (g.H * g.W + 1) * 32 <= 18 * 1024 * 4;
-  if (s2fused) {
-    a.n_dg = 512;                                    // each walks samples bid, bid + 512, ...
-    a.n_wg = 0;
-    a.wg.out = slabs;
-    a.wg.msplit = a.n_dg;
-    if (msplit_out) *msplit_out = a.n_dg;
-  }
-  const bool pad = is_padded(g);
-  // staged-rows weight gradient (wgrad_rows_body) next to the all-classes input gradient: workgroup = (sample group,
-  // kernel row), ceil(B / 64) samples per group so that KH * groups ~ one workgroup per CU, one slab per group
-  bool wrows = false;
-  if ((tuning().wgrad_rows == 1 || tuning().wgrad_rows == 2 || tuning().wgrad_rows == 3) && tuning().bf16x6 &&
-      a.dg_direct == 2 && !pad && g.C == kWrC && g.N == kWrN && g.KW == kWrKW &&
-      slabs != nullptr && wrows_smem_floats(g.OH, g.OW, g.W) <= kWrMaxSmemFloats &&
-      g.OH * (g.W * kWrC / 4) <= kWrXQ * 256 && g.OHOW * (kWrN / 4) <= kWrDQ * 256) {
-    const int per = (B + 63) / 64, groups = (B + per - 1) / per;
-    if (groups <= slab_cap) {
-      wrows = true;
-      a.wg.mchunk = per;                  // samples per group
-      a.wg.d_rowq = make_fastdiv((uint32_t)(g.W * kWrC / 4));
-      a.wg.msplit = groups;
-      a.wg.out = groups == 1 ? dwb : slabs;     // (one group: its slab is the final gradient, as msplit_out = 1 says)
-      a.wg_gx = g.KH; a.wg_gy = 1; a.wg_gz = groups;
-      a.n_wg = g.KH * groups;
-      if (msplit_out) *msplit_out = groups;
-    }
-  }
-  bool pf4_only = false;
-  if (!wrows && tuning().wgrad_rows == 4 && tuning().bf16x6 && a.dg_direct == 2 && !pad &&
-      (g.KH / g.S) * (g.KW / g.S) * (g.N >> 5) == 4) {
-    const int tiles = a.wg_gx * a.wg_gy, room = 512 - a.n_dg - a.n_hw;
-    if (room >= tiles * 8) {
-      pf4_only = true;
-      if (a.n_wg > room) {
-        msplit = pick_ksplit_chunk(g.M, room / tiles, &chunk);
-        a.wg.msplit = msplit; a.wg.mchunk = chunk;
-        a.wg.out = msplit == 1 ? dwb : slabs;
-        if (msplit_out) *msplit_out = msplit;
-        a.wg_gz = msplit;
-        a.n_wg = tiles * msplit;
+
+  // ---- the all-classes input gradient (bf16x6 = 0: fp32 MFMA in it, A/B)
+  if (a->dg_direct == 2) {
+    XT_REQUIRE(wsmall && dsmall && !pad, "bwd_layer: the all-classes input gradient needs the small-tile configuration");
+    const int arith = x6 ? XT_ARITH_FP32_BF16X6 : XT_ARITH_FP32;
+    // (KH/S) * (KW/S) * (N/32) == 4 reduction steps: the input-gradient blocks keep all four taps' operands in flight
+    const bool taps4 = (g.KH / g.S) * (g.KW / g.S) * (g.N >> 5) == 4;
+    // staged-rows weight gradient (wgrad_rows_body) next to it: workgroup = (sample group, kernel row), ceil(B / 64)
+    // samples per group so that KH * groups ~ one workgroup per CU, one slab per group
+    if ((t.wgrad_rows == 1 || t.wgrad_rows == 2 || t.wgrad_rows == 3) && x6 && g.C == kWrC && g.N == kWrN &&
+        g.KW == kWrKW && have_slabs && wrows_smem_floats(g.OH, g.OW, g.W) <= kWrMaxSmemFloats &&
+        g.OH * (g.W * kWrC / 4) <= kWrXQ * 256 && g.OHOW * (kWrN / 4) <= kWrDQ * 256) {
+      const int per = (B + 63) / 64, groups = (B + per - 1) / per;
+      if (groups <= slab_cap) {
+        a->wg.mchunk = per;                 // samples per group
+        a->wg.d_rowq = make_fastdiv((uint32_t)(g.W * kWrC / 4));
+        a->wg.msplit = groups;              // (one group: its slab is the final gradient)
+        a->wg_gx = g.KH; a->wg_gy = 1; a->wg_gz = groups;
+        a->n_wg = g.KH * groups;
+        return take(taps4 && t.wgrad_rows != 2 ? kBwdClassesWrows2 : kBwdClassesWrows1, XT_BWD_PATH_CLASSES_WROWS, arith);
       }
     }
+    // WROWS = 3: the LDS-tiled im2col weight gradient next to the all-taps-in-flight input gradient (250 VGPRs: two
+    // workgroups per CU, the launch cut to 512 co-resident workgroups)
+    const int room = 512 - a->n_dg - n_hw;
+    if (t.wgrad_rows == 4 && x6 && taps4 && room >= tiles * 8) {
+      fit_wgrad(room, a);
+      return take(kBwdClassesPf4, XT_BWD_PATH_CLASSES_PF4, arith);
+    }
+    return take(x6 ? kBwdClassesX6 : kBwdClasses, XT_BWD_PATH_CLASSES, arith);
   }
-  const int total = a.n_wg + a.n_dg + a.n_hw;
-#ifdef XT_TL_EXPERIMENT
-  const bool exp_alone = wrows && tuning().wgrad_rows == 3;
-#endif
-  const bool dx6 = tuning().bf16x6 != 0 && a.dg_direct == 0;     // LDS-tiled input gradient on the bf16 matrix cores
+
+  // ---- the generic LDS-tiled weight gradient next to a register-direct or LDS-tiled input gradient
+  const bool dx6 = x6 && a->dg_direct == 0;     // LDS-tiled input gradient on the bf16 matrix cores
   // Deep-prefetch instance of the generic LDS-tiled pair (Dense layers: S = 1, 1x1): every class reduction has at most 8
   // steps -> all input-gradient operands in flight, four register stages in the weight gradient, two workgroups per CU;
   // the weight-gradient split is cut so that the launch stays within 512 co-resident workgroups
-  bool pf_generic = false;
-  if (tuning().bwd_deep_prefetch && dx6 && !pad && !wsmall && !dsmall && g.S == 1 && g.KH == 1 && g.KW == 1 && g.N <= 256 &&
-      a.dg_direct == 0) {
-    // (the head weight-gradient blocks come last in block order and are short: they may spill into a second round)
-    const int tiles = a.wg_gx * a.wg_gy, room = 512 - a.n_dg - a.n_hw;
-    if (512 - a.n_dg >= tiles) {
-      pf_generic = true;
-      if (a.n_wg > room) {
-        msplit = pick_ksplit_chunk(g.M, room / tiles > 1 ? room / tiles : 1, &chunk);
-        a.wg.msplit = msplit; a.wg.mchunk = chunk;
-        a.wg.out = msplit == 1 ? dwb : slabs;
-        if (msplit_out) *msplit_out = msplit;
-        a.wg_gz = msplit;
-        a.n_wg = tiles * msplit;
-      }
-    }
-  }
-  const int total2 = a.n_wg + a.n_dg + a.n_hw;
+  // (the head weight-gradient blocks come last in block order and are short: they may spill into a second round)
+  const bool dense = t.bwd_deep_prefetch && dx6 && !pad && !wsmall && !dsmall && g.S == 1 && g.KH == 1 && g.KW == 1 &&
+                     g.N <= 256 && 512 - a->n_dg >= tiles;
+  if (dense) fit_wgrad(512 - a->n_dg - n_hw, a);
   // a weight gradient written by ONE slab per tile is final: its blocks also leave their share of the squared global
   // norm, which saves the reduction launch a read of the whole tensor (PpoCnn's Dense layer: 6.4 of its 29 MB)
-  const bool generic_wg = !wrows && !s2fused && !s2c16 && !halo_inst && a.dg_direct != 2;
-  if (sq_partials && npre_out && generic_wg && a.wg.msplit == 1 && a.wg_gz == 1) {
-    a.wg.sq_out = sq_partials; a.wg.sq_gx = a.wg_gx;
-    *npre_out = a.wg_gx * a.wg_gy;
+  if (want_npre && a->wg.msplit == 1) { a->wg.sq_gx = a->wg_gx; p->npre = tiles; }
+  if (dense)      // dense_wgrad_x6: (round 5) the Dense weight gradient on the bf16 matrix cores as well
+    return t.dense_wgrad_x6 ? take(kBwdDenseWx6, XT_BWD_PATH_PF_GENERIC, XT_ARITH_BF16X6)
+                            : take(kBwdDense, XT_BWD_PATH_PF_GENERIC, XT_ARITH_FP32_BF16X6);
+  // the generic 64x64 pair (ImpalaCnnOpt's 11x11 "dense" conv) with the one-LDS-stage bf16x6 weight gradient (three
+  // workgroups per CU as before): pong_impala_speedup 214.6 -> 212.3 us per 1000-frame train, breakout_impala unchanged
+  if (!wsmall && !dsmall && t.dense_wgrad_x6 && dx6 && !pad) return take(kBwdPairLLWx6, XT_BWD_PATH_PAIR_LL_WX6, XT_ARITH_BF16X6);
+  const int pair = (wsmall ? 0 : 2) + (dsmall ? 0 : 1);      // SS, SL, LS, LL: the order of BwdInst and of XT_BWD_PATH_PAIR_*
+  return take(BwdInst(kBwdPairSS + 4 * pair + (pad ? 1 : 0) + (dx6 ? 2 : 0)), XT_BWD_PATH_PAIR_SS + pair,
+              dx6 ? XT_ARITH_FP32_BF16X6 : XT_ARITH_FP32);      // (fp32: register-direct input gradients and the x6 = 0 forms)
+}
+
+int launch_bwd_layer(const BwdLayerCall& c) {
+  Geom g;
+  if (int rc = make_geom(c.g, nullptr, c.B, &g)) return rc;
+  BwdLayerArgs a{};
+  BwdPlan p;
+  if (int rc = plan_bwd_layer(g, c.msplit, c.slabs != nullptr, c.slab_cap, c.hw ? c.hw->gx * c.hw->nchunk : 0,
+                              c.sq_partials && c.npre_out, &a, &p))
+    return rc;
+  const float* x_grad = c.x_grad ? c.x_grad : c.x;
+  a.wg.in = c.x; a.wg.dy = c.dy;
+  a.wg.out = a.wg.msplit == 1 ? c.dwb : c.slabs;
+  if (c.nslab_out) *c.nslab_out = a.wg.msplit;
+  if (p.npre) a.wg.sq_out = c.sq_partials;
+  if (c.npre_out) *c.npre_out = p.npre;
+  a.dg.dy = c.dy; a.dg.w = c.w; a.dg.x = x_grad; a.dg.dx = c.dx; a.dg.act_prev = c.act_prev;
+  if (a.dg_direct == 2 && c.act_prev == XT_ACT_RELU) a.dg.xmask = c.xmask;       // (C == 32: one mask word per pixel)
+  a.ddg.dy = c.dy; a.ddg.w = c.w; a.ddg.x = x_grad; a.ddg.dx = c.dx; a.ddg.act_prev = c.act_prev;
+  if (c.hw) a.hw = *c.hw;
+  else a.hw.gx = 1;
+  last_arith() = p.arith;
+  if (c.path_out) *c.path_out = p.path | (a.dg_direct << XT_BWD_DG_SHIFT) | (p.arith << XT_BWD_ARITH_SHIFT);
+  const dim3 grid(a.n_wg + a.n_dg + a.n_hw);
+#define XT_BWD_GO(...) hipLaunchKernelGGL((igemm_bwd_layer_kernel<__VA_ARGS__>), grid, dim3(256), 0, c.st, a)
+#define XT_BWD_PAIR(P, WBI, WBJ, WWI, WWJ, DBI, DBJ, DWI, DWJ)                                                   \
+  case kBwdPair##P##PadX6: XT_BWD_GO(WBI, WBJ, WWI, WWJ, true, DBI, DBJ, DWI, DWJ, 0, 0, true); break;            \
+  case kBwdPair##P##X6:    XT_BWD_GO(WBI, WBJ, WWI, WWJ, false, DBI, DBJ, DWI, DWJ, 0, 0, true); break;           \
+  case kBwdPair##P##Pad:   XT_BWD_GO(WBI, WBJ, WWI, WWJ, true, DBI, DBJ, DWI, DWJ, 0, 0, false); break;           \
+  case kBwdPair##P:        XT_BWD_GO(WBI, WBJ, WWI, WWJ, false, DBI, DBJ, DWI, DWJ, 0, 0, false); break;
+  // (the compiler emits the instances in the order of their first use, i.e. of these cases: moving one moves its code in
+  // the library's code object)
+  switch (p.inst) {
+    case kBwdS2FusedPad:    XT_BWD_GO(128, 32, 4, 1, true, 128, 32, 4, 1, 0, 5); break;
+    case kBwdS2Fused:       XT_BWD_GO(128, 32, 4, 1, false, 128, 32, 4, 1, 0, 5); break;
+    case kBwdS2c16Pad:      XT_BWD_GO(128, 32, 4, 1, true, 128, 32, 4, 1, 0, 3); break;
+    case kBwdS2c16:         XT_BWD_GO(128, 32, 4, 1, false, 128, 32, 4, 1, 0, 3); break;
+    case kBwdHaloX6Wx6:     XT_BWD_GO(64, 64, 2, 2, false, 128, 32, 4, 1, 0, 2, false, 0, 2); break;
+    case kBwdHaloX6:        XT_BWD_GO(64, 64, 2, 2, false, 128, 32, 4, 1, 0, 2); break;
+    case kBwdHalo:          XT_BWD_GO(64, 64, 2, 2, false, 128, 32, 4, 1, 0, 1); break;
+    case kBwdClassesPf4:    XT_BWD_GO(128, 32, 4, 1, false, 128, 32, 4, 1, 2, 0, false, 3); break;
+    case kBwdClassesWrows2: XT_BWD_GO(128, 32, 4, 1, false, 128, 32, 4, 1, 2, 0, false, 2); break;
+    case kBwdClassesWrows1: XT_BWD_GO(128, 32, 4, 1, false, 128, 32, 4, 1, 2, 0, false, 1); break;
+    case kBwdClassesX6:     XT_BWD_GO(128, 32, 4, 1, false, 128, 32, 4, 1, 2); break;
+    case kBwdClasses:       XT_BWD_GO(128, 32, 4, 1, false, 128, 32, 4, 1, 1); break;
+    case kBwdDenseWx6:      XT_BWD_GO(64, 64, 2, 2, false, 64, 64, 2, 2, 0, 0, true, 3, 1); break;
+    case kBwdDense:         XT_BWD_GO(64, 64, 2, 2, false, 64, 64, 2, 2, 0, 0, true, 3); break;
+    XT_BWD_PAIR(SS, 128, 32, 4, 1, 128, 32, 4, 1)
+    XT_BWD_PAIR(SL, 128, 32, 4, 1, 64, 64, 2, 2)
+    XT_BWD_PAIR(LS, 64, 64, 2, 2, 128, 32, 4, 1)
+    case kBwdPairLLWx6:     XT_BWD_GO(64, 64, 2, 2, false, 64, 64, 2, 2, 0, 0, true, 0, 2); break;
+    XT_BWD_PAIR(LL, 64, 64, 2, 2, 64, 64, 2, 2)
   }
-#define XT_BWD2(WBI, WBJ, WWI, WWJ, DBI, DBJ, DWI, DWJ, X6V)                                                    \
-  do {                                                                                                          \
-    if (pad) hipLaunchKernelGGL((igemm_bwd_layer_kernel<WBI, WBJ, WWI, WWJ, true, DBI, DBJ, DWI, DWJ, 0, 0, X6V>), \
-                                dim3(total), dim3(256), 0, st, a);                                              \
-    else hipLaunchKernelGGL((igemm_bwd_layer_kernel<WBI, WBJ, WWI, WWJ, false, DBI, DBJ, DWI, DWJ, 0, 0, X6V>),  \
-                            dim3(total), dim3(256), 0, st, a);                                                  \
-  } while (0)
-#define XT_BWD(WBI, WBJ, WWI, WWJ, DBI, DBJ, DWI, DWJ)                                                          \
-  do {                                                                                                          \
-    if (dx6) XT_BWD2(WBI, WBJ, WWI, WWJ, DBI, DBJ, DWI, DWJ, true);                                             \
-    else XT_BWD2(WBI, WBJ, WWI, WWJ, DBI, DBJ, DWI, DWJ, false);                                                \
-  } while (0)
-  last_arith() = XT_ARITH_FP32;          // (register-direct input gradients and the x6 = 0 forms)
-  if (dx6 || (tuning().bf16x6 && a.dg_direct == 2)) last_arith() = XT_ARITH_FP32_BF16X6;
-  // which branch runs (xt_layer_bwd's path_out; recorded in front of the launch, changes nothing)
-  auto taken = [&](int path) {
-    if (path_out) *path_out = path | (a.dg_direct << XT_BWD_DG_SHIFT) | (last_arith() << XT_BWD_ARITH_SHIFT);
-  };
-  if (s2fused) {
-    last_arith() = XT_ARITH_BF16X6;
-    taken(XT_BWD_PATH_S2FUSED);
-    if (pad) hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, true, 128, 32, 4, 1, 0, 5>), dim3(total), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 0, 5>), dim3(total), dim3(256), 0, st, a);
-  } else if (s2c16) {
-    last_arith() = XT_ARITH_FP32_BF16X6;
-    taken(XT_BWD_PATH_S2C16);
-    if (pad) hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, true, 128, 32, 4, 1, 0, 3>), dim3(total), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 0, 3>), dim3(total), dim3(256), 0, st, a);
-  } else if (halo_inst) {
-    const int hx6 = tuning().bf16x6;     // 0: fp32 MFMA (A/B)
-    const int nsamp = 63 / (g.H * g.W) + 2;
-    if (hx6 && (size_t)3 * (nsamp * g.OHOW + 1) * (g.N * 2 + 16) <= 44 * 1024) last_arith() = XT_ARITH_FP32_BF16X6;
-    taken(XT_BWD_PATH_HALO);
-    if (hx6 && (size_t)3 * (nsamp * g.OHOW + 1) * (g.N * 2 + 16) <= 44 * 1024) {
-      if (tuning().dense_wgrad_x6 == 2)      // EXPERIMENT (off by default): conv3's weight gradient bf16x6 with one LDS stage
-        hipLaunchKernelGGL((igemm_bwd_layer_kernel<64, 64, 2, 2, false, 128, 32, 4, 1, 0, 2, false, 0, 2>), dim3(total), dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((igemm_bwd_layer_kernel<64, 64, 2, 2, false, 128, 32, 4, 1, 0, 2>), dim3(total), dim3(256), 0, st, a);
-    }
-    else
-      hipLaunchKernelGGL((igemm_bwd_layer_kernel<64, 64, 2, 2, false, 128, 32, 4, 1, 0, 1>), dim3(total), dim3(256), 0, st, a);
-  } else if (a.dg_direct == 2 && pf4_only) {
-    // WROWS = 3: the LDS-tiled im2col weight gradient next to the all-taps-in-flight input gradient (250 VGPRs: two
-    // workgroups per CU, the launch cut to 512 co-resident workgroups)
-    taken(XT_BWD_PATH_CLASSES_PF4);
-    hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 2, 0, false, 3>), dim3(total), dim3(256), 0, st, a);
-  } else if (a.dg_direct == 2 && wrows) {
-    // (KH/S) * (KW/S) * (N/32) == 4 reduction steps: the input-gradient blocks keep all four taps' operands in flight
-#ifdef XT_TL_EXPERIMENT
-    if (exp_alone) a.dg_direct = 99;
-#endif
-    taken(XT_BWD_PATH_CLASSES_WROWS);
-    if ((g.KH / g.S) * (g.KW / g.S) * (g.N >> 5) == 4 && tuning().wgrad_rows != 2)
-      hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 2, 0, false, 2>), dim3(total), dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 2, 0, false, 1>), dim3(total), dim3(256), 0, st, a);
-  } else if (a.dg_direct == 2) {
-    XT_REQUIRE(wsmall && dsmall && !pad, "bwd_layer: the all-classes input gradient needs the small-tile configuration");
-    const int x6 = tuning().bf16x6;      // 0: fp32 MFMA in the all-classes input gradient (A/B)
-    taken(XT_BWD_PATH_CLASSES);
-    if (x6) hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 2>), dim3(total), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 1>), dim3(total), dim3(256), 0, st, a);
-  } else if (pf_generic) {
-    if (tuning().dense_wgrad_x6) {        // (round 5) the Dense weight gradient on the bf16 matrix cores as well
-      last_arith() = XT_ARITH_BF16X6;
-      taken(XT_BWD_PATH_PF_GENERIC);
-      hipLaunchKernelGGL((igemm_bwd_layer_kernel<64, 64, 2, 2, false, 64, 64, 2, 2, 0, 0, true, 3, 1>), dim3(total2), dim3(256), 0, st, a);
-    } else {
-      taken(XT_BWD_PATH_PF_GENERIC);
-      hipLaunchKernelGGL((igemm_bwd_layer_kernel<64, 64, 2, 2, false, 64, 64, 2, 2, 0, 0, true, 3>), dim3(total2), dim3(256), 0, st, a);
-    }
-  } else if (wsmall && dsmall) {
-    taken(XT_BWD_PATH_PAIR_SS);
-    XT_BWD(128, 32, 4, 1, 128, 32, 4, 1);
-  } else if (wsmall) {
-    taken(XT_BWD_PATH_PAIR_SL);
-    XT_BWD(128, 32, 4, 1, 64, 64, 2, 2);
-  } else if (dsmall) {
-    taken(XT_BWD_PATH_PAIR_LS);
-    XT_BWD(64, 64, 2, 2, 128, 32, 4, 1);
-  } else if (tuning().dense_wgrad_x6 && dx6 && !pad) {
-    // the generic 64x64 pair (ImpalaCnnOpt's 11x11 "dense" conv) with the one-LDS-stage bf16x6 weight gradient (three
-    // workgroups per CU as before): pong_impala_speedup 214.6 -> 212.3 us per 1000-frame train, breakout_impala unchanged
-    last_arith() = XT_ARITH_BF16X6;
-    taken(XT_BWD_PATH_PAIR_LL_WX6);
-    hipLaunchKernelGGL((igemm_bwd_layer_kernel<64, 64, 2, 2, false, 64, 64, 2, 2, 0, 0, true, 0, 2>), dim3(total), dim3(256), 0, st, a);
-  } else {
-    taken(XT_BWD_PATH_PAIR_LL);
-    XT_BWD(64, 64, 2, 2, 64, 64, 2, 2);
-  }
-#undef XT_BWD
-#undef XT_BWD2
+#undef XT_BWD_PAIR
+#undef XT_BWD_GO
   XT_LAUNCH_CHECK();
   return 0;
 }
@@ -2225,9 +2146,11 @@ int xt_layer_bwd(const xt_conv_geom* g, int32_t B, const float* x, const float* 
              "xt_layer_bwd: msplit %d needs a slab buffer of at least that many slabs (capacity %d)", msplit, slab_cap);
   const hipStream_t st = xt::as_stream(stream);
   int nslab = 1;
-  if (int rc = xt::launch_bwd_layer(g, B, x, dy, w, act_prev, dx, dwb, slabs, msplit, nullptr, &nslab, st, relu_mask,
-                                    slabs ? slab_cap : 0, x_pre, nullptr, nullptr, path_out))
-    return rc;
+  xt::BwdLayerCall c;
+  c.g = g; c.B = B; c.x = x; c.x_grad = x_pre; c.dy = dy; c.w = w; c.act_prev = act_prev; c.xmask = relu_mask;
+  c.dx = dx; c.dwb = dwb; c.slabs = slabs; c.slab_cap = slabs ? slab_cap : 0; c.msplit = msplit;
+  c.st = st; c.nslab_out = &nslab; c.path_out = path_out;
+  if (int rc = xt::launch_bwd_layer(c)) return rc;
   if (nslab > 1) {
     const int count = (g->KH * g->KW * g->C + 1) * g->N;
     hipLaunchKernelGGL(xt::reduce_slabs_kernel, dim3((count / 4 + 255) / 256), dim3(256), 0, st, slabs, dwb, count, nslab);

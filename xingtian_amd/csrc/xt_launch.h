@@ -1,0 +1,120 @@
+// Host launchers and planners that are called across translation units, declared once (with their default arguments).
+// Included by the file that defines each of them and by the files that call it.
+#pragma once
+#include "xt_common.h"
+#include "xt_igemm.h"
+#include "xt_heads_dev.h"
+
+namespace xt {
+
+struct DDgradArgs;      // xt_direct_dev.h
+
+// ------------------------------------------------------------------ xt_igemm.hip: trunk layers
+// deferred_ksplit (may be null): the split-K partials are left for the caller to sum and *deferred_ksplit says how many
+int launch_fwd(const xt_conv_geom* cg, const xt_input_xform* xf, int B, const void* in, const int32_t* idx,
+               const float* w, const float* bias, float* y, float* partial, int ksplit, hipStream_t st,
+               int* deferred_ksplit = nullptr, uint32_t* relu_mask = nullptr, int* mask_written = nullptr);
+int launch_wgrad(const xt_conv_geom* cg, const xt_input_xform* xf, int B, const void* in, const int32_t* idx,
+                 const float* dy, float* dwb, float* slabs, int msplit, hipStream_t st, int reduce_now = 1,
+                 int* msplit_out = nullptr, int slab_cap = 0);
+int launch_dgrad(const xt_conv_geom* cg, int B, const float* dy, const float* w, const float* x, int act_prev,
+                 float* dx, hipStream_t st);
+
+// One fused backward launch of a non-first layer: weight gradient + input gradient (+ the head weight gradients).
+struct BwdLayerCall {
+  const xt_conv_geom* g = nullptr;
+  int B = 0;
+  const float* x = nullptr;            // the layer's input = its producer's output [B,H,W,C]
+  const float* x_grad = nullptr;       // what the input gradient's activation-derivative epilogue reads: the producer's
+                                       // PRE-activation when its activation is not monotonic (act_needs_preact); null = x
+  const float* dy = nullptr;           // d(pre-activation) of this layer
+  const float* w = nullptr;
+  int act_prev = 0;                    // the producer's activation
+  const uint32_t* xmask = nullptr;     // the producer's relu sign mask (may be null)
+  float* dx = nullptr;                 // d(pre-activation) of the producer
+  float* dwb = nullptr;                // the weight + bias gradient, when it is written as a single slab
+  float* slabs = nullptr;              // ... else `*nslab_out` slabs for the caller to sum (may be null: msplit 1)
+  int slab_cap = 0;                    // slabs that `slabs` can hold
+  int msplit = 1;                      // requested weight-gradient split (the launch may lower it)
+  const HeadWgArgs* hw = nullptr;      // head weight-gradient blocks riding along (may be null)
+  float* sq_partials = nullptr;        // with npre_out: where a single-slab weight gradient leaves squared-norm partials
+  hipStream_t st = nullptr;
+  int* nslab_out = nullptr;            // slabs written: 1 = the gradient is final in dwb
+  int* npre_out = nullptr;             // squared-norm partials written (0: none)
+  int* path_out = nullptr;             // the branch taken, as xt_layer_bwd reports it
+};
+int launch_bwd_layer(const BwdLayerCall& c);
+
+// ------------------------------------------------------------------ xt_direct.hip: register-direct family (< 0: not taken)
+int launch_fwd_direct(const xt_conv_geom* cg, const xt_input_xform* xf, int B, const void* in, const int32_t* idx,
+                      const float* w, const float* bias, float* y, float* partial, int ksplit_max, hipStream_t st,
+                      int* ksplit_out);
+int launch_dgrad_direct(const xt_conv_geom* cg, int B, const float* dy, const float* w, const float* x, int act_prev,
+                        float* dx, hipStream_t st);
+bool plan_dgrad_direct_fused(const xt_tuning& t, const Geom& g, DDgradArgs* a, int* nblocks);
+
+// ------------------------------------------------------------------ xt_conv1.hip: uint8 first layers (< 0: not taken)
+int launch_conv1_fwd_bf16x3(const xt_conv_geom* g, const xt_input_xform* xf, int B, const void* in, const int32_t* idx,
+                            const float* w, const float* bias, float* y, hipStream_t st, uint32_t* relu_mask,
+                            int* mask_written);
+int launch_conv1_wgrad_bf16x3(const xt_conv_geom* g, const xt_input_xform* xf, int B, const void* in,
+                              const int32_t* idx, const float* dy, float* dwb, float* slabs, int max_slabs,
+                              int* msplit_out, hipStream_t st);
+int launch_conv1_same_fwd(const xt_conv_geom* g, const xt_input_xform* xf, int B, const void* in, const int32_t* idx,
+                          const float* w, const float* bias, float* y, hipStream_t st);
+int launch_conv1_same_wgrad(const xt_conv_geom* g, const xt_input_xform* xf, int B, const void* in, const int32_t* idx,
+                            const float* dy, float* dwb, float* slabs, int max_slabs, int* msplit_out, hipStream_t st);
+int launch_conv12_same_fwd(const xt_conv_geom* g, const xt_input_xform* xf, const xt_conv_geom* g2, int B,
+                           const void* in, const int32_t* idx, const float* w, const float* bias, float* y,
+                           const float* w2, const float* b2, float* y2, hipStream_t st);
+
+// ------------------------------------------------------------------ xt_heads.hip: heads and losses
+int launch_act_apply(const float* z, float* y, long long count, int act, hipStream_t st);
+int launch_ppo_heads_fused(const PpoHeadArgs& a, hipStream_t st);
+int launch_impala_heads_fwd(const ImpalaHeadArgs& a, hipStream_t st);
+int launch_impala_vtrace_bwd(const ImpalaLossArgs& a, int n_traj, hipStream_t st);
+int launch_impala_loss_reduce(const float* traj_loss, int n, float* out, float* acc, hipStream_t st);
+int launch_ppo_loss_gauss(const float* mean, const float* log_std, const float* value, int B, int A, const int32_t* idx,
+                          const float* action, const float* old_logp, const double* adv, const float* old_v,
+                          const double* target_v, float clip_ratio, float ent_coef, float vf_clip, float critic_coef,
+                          float inv_b, float* dmean, float* dvalue, float* dls_rows, int ldls, float* terms,
+                          hipStream_t st);
+int launch_heads_dfeat(const float* f_pi, const float* f_v, int B, int F, int A, const float* wpi, const float* wv,
+                       const float* dlogits, const float* dvalue, int act_prev, float* df_pi, float* df_v,
+                       hipStream_t st);
+int launch_heads_wgrad_partial(const float* f_pi, const float* f_v, int B, int F, int A, const float* dlogits,
+                               const float* dvalue, float* slab_pi, long long stride_pi, float* slab_v,
+                               long long stride_v, int* nchunk_out, hipStream_t st);
+
+// ------------------------------------------------------------------ xt_optim.hip: gradient reduction, norm, optimisers
+int launch_global_norm(const float* grad, long long count, float clip_norm, float grad_scale, float lr, float beta1,
+                       float beta2, int advance, float* state, float* scratch, hipStream_t st,
+                       const float* lr_dev = nullptr, int* nblocks_out = nullptr);
+int launch_sqnorm_partial(const float* grad, long long count, float* scratch, int* nblocks_out, hipStream_t st);
+int launch_norm_finalize(const float* partial, int nblocks, float clip_norm, float grad_scale, float lr, float beta1,
+                         float beta2, int advance, float* state, const LossArgs* la, hipStream_t st,
+                         const float* lr_dev = nullptr);
+int launch_grads_finish(GradTable* tab, float* partial, int max_partials, int* nblocks_out, const FinalizeArgs* fin,
+                        hipStream_t st, unsigned select = 0, unsigned early = 0, const DpFinish* dpf = nullptr);
+int grads_finish_resident_blocks();
+int grads_finish_fused_grid(const GradTable* tab);
+int launch_adam(float* param, const float* grad, float* m, float* v, long long count, float beta1, float beta2,
+                float eps, const float* state, hipStream_t st);
+int launch_adam_clip(float* param, const float* grad, float* m, float* v, long long count, float beta1, float beta2,
+                     float eps, float* state, const float* partial, int nblocks, float clip_norm, float grad_scale,
+                     hipStream_t st, const DpStep* dp = nullptr, int block_cap = 0, const IoFold* io = nullptr);
+int launch_rmsprop_clip(float* param, const float* grad, float* mg, float* ms, long long count, float lr, float decay,
+                        float eps, float* state, const float* partial, int nblocks, float clip_norm, float grad_scale,
+                        hipStream_t st, const float* lr_dev = nullptr, const DpStep* dp = nullptr, int block_cap = 0);
+int launch_dp_tail_write(float* tail, int rank, float rows, const float* loss, float* state, float lr,
+                         const float* lr_dev, float beta1, float beta2, int advance, hipStream_t st);
+int launch_dp_tail_consume(const DpStep* dp, hipStream_t st);
+int launch_dp_reduce_wait(const DpStep* dp, hipStream_t st);
+
+// ------------------------------------------------------------------ xt_xgmi.hip: the direct exchange fused into the step
+int direct_fill_finish(xt_direct_comm* c, int64_t count, DpFinish* f);
+int direct_launch_scatter(xt_direct_comm* c, const float* buf, int64_t count, hipStream_t st);
+int direct_fill_step(xt_direct_comm* c, int64_t count, int64_t count_grad, DpStep* s, const float** result,
+                     const float** partial, int* npartial, int* block_cap);
+
+}  // namespace xt

@@ -13,6 +13,7 @@
 
 #include "xt_common.h"
 #include "xt_heads_dev.h"
+#include "xt_launch.h"
 
 namespace xt {
 
@@ -35,53 +36,6 @@ xt_tuning& tuning() {
                         /*tail_overlap*/ 0, /*tail_fused*/ 0, /*dense_wgrad_x6*/ 1, /*fwd_fuse12*/ 0};
   return t;
 }
-
-int launch_fwd(const xt_conv_geom*, const xt_input_xform*, int, const void*, const int32_t*, const float*,
-               const float*, float*, float*, int, hipStream_t, int* deferred_ksplit = nullptr,
-               uint32_t* relu_mask = nullptr, int* mask_written = nullptr);
-int launch_bwd_layer(const xt_conv_geom*, int, const float*, const float*, const float*, int, float*, float*, float*,
-                     int, const HeadWgArgs*, int*, hipStream_t, const uint32_t* xmask = nullptr, int slab_cap = 0,
-                     const float* x_grad = nullptr, float* sq_partials = nullptr, int* npre_out = nullptr,
-                     int* path_out = nullptr);
-int launch_act_apply(const float* z, float* y, long long count, int act, hipStream_t st);
-int launch_conv12_same_fwd(const xt_conv_geom*, const xt_input_xform*, const xt_conv_geom*, int, const void*, const int32_t*,
-                           const float*, const float*, float*, const float*, const float*, float*, hipStream_t);
-int launch_wgrad(const xt_conv_geom*, const xt_input_xform*, int, const void*, const int32_t*, const float*,
-                 float*, float*, int, hipStream_t, int reduce_now = 1, int* msplit_out = nullptr, int slab_cap = 0);
-int launch_dgrad(const xt_conv_geom*, int, const float*, const float*, const float*, int, float*, hipStream_t);
-int launch_global_norm(const float*, long long, float, float, float, float, float, int, float*, float*, hipStream_t,
-                       const float* lr_dev = nullptr, int* nblocks_out = nullptr);
-int launch_grads_finish(GradTable*, float*, int, int*, const FinalizeArgs*, hipStream_t, unsigned select = 0,
-                        unsigned early = 0, const DpFinish* dpf = nullptr);
-int launch_dp_tail_write(float*, int, float, const float*, float*, float, const float*, float, float, int, hipStream_t);
-int launch_dp_tail_consume(const DpStep*, hipStream_t);
-int launch_dp_reduce_wait(const DpStep*, hipStream_t);
-// the direct exchange fused into the step (xt_xgmi.hip)
-int direct_fill_finish(xt_direct_comm*, int64_t, DpFinish*);
-int direct_launch_scatter(xt_direct_comm*, const float*, int64_t, hipStream_t);
-int direct_fill_step(xt_direct_comm*, int64_t, int64_t, DpStep*, const float**, const float**, int*, int*);
-int grads_finish_resident_blocks();
-int grads_finish_fused_grid(const GradTable*);
-int launch_sqnorm_partial(const float*, long long, float*, int*, hipStream_t);
-int launch_norm_finalize(const float*, int, float, float, float, float, float, int, float*, const LossArgs*, hipStream_t,
-                         const float* lr_dev = nullptr);
-int launch_ppo_heads_fused(const PpoHeadArgs&, hipStream_t);
-int launch_adam_clip(float*, const float*, float*, float*, long long, float, float, float, float*, const float*, int,
-                     float, float, hipStream_t, const DpStep* dp = nullptr, int block_cap = 0, const IoFold* io = nullptr);
-int launch_rmsprop_clip(float*, const float*, float*, float*, long long, float, float, float, float*, const float*, int,
-                        float, float, hipStream_t, const float* lr_dev = nullptr, const DpStep* dp = nullptr,
-                        int block_cap = 0);
-int launch_impala_heads_fwd(const ImpalaHeadArgs&, hipStream_t);
-int launch_impala_vtrace_bwd(const ImpalaLossArgs&, int, hipStream_t);
-int launch_impala_loss_reduce(const float*, int, float*, float*, hipStream_t);
-int launch_ppo_loss_gauss(const float*, const float*, const float*, int, int, const int32_t*, const float*, const float*,
-                          const double*, const float*, const double*, float, float, float, float, float, float*, float*,
-                          float*, int, float*, hipStream_t);
-int launch_heads_dfeat(const float*, const float*, int, int, int, const float*, const float*, const float*,
-                       const float*, int, float*, float*, hipStream_t);
-int launch_heads_wgrad_partial(const float*, const float*, int, int, int, const float*, const float*, float*,
-                               long long, float*, long long, int*, hipStream_t);
-int launch_adam(float*, const float*, float*, float*, long long, float, float, float, const float*, hipStream_t);
 
 struct Layer {
   xt_conv_geom g;
@@ -306,6 +260,27 @@ static int heads_wgrad(xt_net* n, int B, hipStream_t st) {
                                     n->ws + n->off_hslab_v, n->hstride_v, &n->head_chunks, st);
 }
 
+// The fused backward launch of non-first layer l as the update runs it (trunk_backward adds what rides on single launches
+// of the step: the head weight-gradient blocks and the squared-norm partials)
+static BwdLayerCall bwd_layer_call(xt_net* n, int l, int B, hipStream_t st) {
+  Layer& L = n->layers[l];
+  const Layer& Lprev = n->layers[l - 1];
+  BwdLayerCall c;
+  c.g = &L.g; c.B = B; c.st = st;
+  c.x = n->ws + Lprev.act_off;
+  if (Lprev.z_off >= 0) c.x_grad = n->ws + Lprev.z_off;
+  c.dy = n->ws + L.dact_off;
+  c.w = n->params + L.poff;
+  c.act_prev = Lprev.g.act;
+  if (Lprev.mask_valid) c.xmask = reinterpret_cast<const uint32_t*>(n->ws + Lprev.mask_off);
+  c.dx = n->ws + Lprev.dact_off;
+  c.dwb = n->grads + L.poff;
+  c.slabs = n->ws + L.slab_off; c.slab_cap = L.slab_cap;
+  c.msplit = wgrad_split(L, B);
+  c.nslab_out = &L.last_msplit;
+  return c;
+}
+
 // Backward through the trunks once d(features) sits in the last layer's dact: one launch per non-first layer
 // (input gradient + weight gradient [+ the head weight gradients with the very first one]), then the first layer's
 // weight gradient.  (Forking the weight-gradient kernels onto side streams inside the hipGraph measured SLOWER
@@ -327,9 +302,8 @@ static int trunk_backward(xt_net* n, const void* obs, const int32_t* idx, int B,
         if (int rc = layer_wgrad(n, l, true, obs, idx, B, st)) return rc;
         continue;
       }
-      Layer& Lprev = n->layers[l - 1];
+      BwdLayerCall c = bwd_layer_call(n, l, B, st);
       HeadWgArgs hw;
-      const HeadWgArgs* hwp = nullptr;
       if (!heads_done) {
         Layer& Lp = n->layers[n->t_end[0] - 1];
         Layer& Lv = n->layers[n->t_end[n->n_trunks - 1] - 1];
@@ -339,17 +313,13 @@ static int trunk_backward(xt_net* n, const void* obs, const int32_t* idx, int B,
         hw.stride_pi = n->hstride_pi; hw.stride_v = n->hstride_v;
         hw.B = B; hw.F = n->feat; hw.A = n->A; hw.gx = (n->feat + 63) / 64; hw.nchunk = (B + 7) / 8;
         n->head_chunks = hw.nchunk;
-        hwp = &hw;
+        c.hw = &hw;
         heads_done = true;
       }
-      if (int rc = launch_bwd_layer(&L.g, B, n->ws + Lprev.act_off, n->ws + L.dact_off, n->params + L.poff,
-                                    Lprev.g.act, n->ws + Lprev.dact_off, n->grads + L.poff, n->ws + L.slab_off,
-                                    wgrad_split(L, B), hwp, &L.last_msplit, st,
-                                    Lprev.mask_valid ? reinterpret_cast<const uint32_t*>(n->ws + Lprev.mask_off) : nullptr,
-                                    L.slab_cap, Lprev.z_off >= 0 ? n->ws + Lprev.z_off : nullptr,
-                                    // (the last layer's entry owns the FIRST partial slots: see grads_finish)
-                                    pre_ok && l == (int)n->layers.size() - 1 ? n->ws + n->off_norm : nullptr, &L.last_npre))
-        return rc;
+      // (the last layer's entry owns the FIRST partial slots: see grads_finish)
+      if (pre_ok && l == (int)n->layers.size() - 1) c.sq_partials = n->ws + n->off_norm;
+      c.npre_out = &L.last_npre;
+      if (int rc = launch_bwd_layer(c)) return rc;
       if (!first_done && after_first) { if (int rc = after_first->fn(after_first->arg)) return rc; }
       first_done = true;
     }
@@ -1713,10 +1683,7 @@ int xt_net_time_layer(xt_net* n, int32_t layer, int32_t which, const void* obs, 
                               L.slab_cap);
     xt::Layer& Lp = n->layers[layer - 1];
     if (which == 3)   // the fused per-layer backward launch (dgrad + wgrad) used by the update loop
-      return xt::launch_bwd_layer(&L.g, B, n->ws + Lp.act_off, n->ws + L.dact_off, n->params + L.poff, Lp.g.act,
-                                  n->ws + Lp.dact_off, n->grads + L.poff, n->ws + L.slab_off, xt::wgrad_split(L, B),
-                                  nullptr, &L.last_msplit, st,
-                                  Lp.mask_valid ? reinterpret_cast<const uint32_t*>(n->ws + Lp.mask_off) : nullptr, L.slab_cap);
+      return xt::launch_bwd_layer(xt::bwd_layer_call(n, layer, B, st));
     return xt::launch_dgrad(&L.g, B, n->ws + L.dact_off, n->params + L.poff, n->ws + Lp.act_off, Lp.g.act,
                             n->ws + Lp.dact_off, st);
   };

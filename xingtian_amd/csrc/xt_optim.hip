@@ -6,6 +6,7 @@
 #include <string.h>
 #include "xt_common.h"
 #include "xt_xgmi_dev.h"
+#include "xt_launch.h"
 #include <atomic>
 
 namespace xt {
@@ -1016,7 +1017,7 @@ int launch_adam_keras(float* param, const float* grad, float* m, float* v, int n
 
 int launch_norm_finalize(const float* partial, int nblocks, float clip_norm, float grad_scale, float lr, float beta1,
                          float beta2, int advance, float* state, const LossArgs* la, hipStream_t st,
-                         const float* lr_dev = nullptr) {
+                         const float* lr_dev) {
   LossArgs l{};
   if (la) l = *la;
   hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(256), 0, st, partial, nblocks, clip_norm, grad_scale, lr, beta1,

@@ -28,6 +28,7 @@
 #include <string.h>
 
 #include "xt_xgmi_dev.h"
+#include "xt_launch.h"
 
 namespace xt {
 
@@ -267,8 +268,6 @@ int direct_fill_finish(xt_direct_comm* c, int64_t count, DpFinish* f) {
   f->scatter = 1; f->rank = c->rank; f->world = c->world; f->nvec = count / 4; f->peers = c->peers; f->ctl = c->ctl;
   return 0;
 }
-
-int direct_launch_scatter(xt_direct_comm* c, const float* buf, int64_t count, hipStream_t st);
 
 // what the optimiser kernel of a fused step needs: the inbox to reduce (its first `red_blocks` workgroups sum this rank's
 // slice in rank order and push it, with its squared-norm partials, to every peer), the flags to wait for, the reduced buffer
