@@ -128,6 +128,20 @@ typedef struct xt_tuning {
                                * frames.  DEFAULT 0 (two launches): built, parity-green and MEASURED SLOWER -- 87.6 vs 83.7 us
                                * per 128-frame train, same box: 128 workgroups leave half the CUs idle and conv2 from LDS on fp32
                                * MFMA is 64 MFMAs x 64 cycles per wave, two waves per SIMD = 3.4 us */
+  int32_t bwd_fuse21;         /* (appended under ABI 12) a one-trunk network whose first two layers are PpoCnn's pair (uint8 8x8 VALID
+                               * 4 -> 32 relu, then 4x4/2 VALID 32 -> 32): the input-gradient blocks of conv2's fused backward launch
+                               * keep their 512 pixels of d(act1) in registers -- accumulator x relu' from conv1's sign mask, split
+                               * into bf16 planes -- and run conv1's weight-gradient loop on them (xt_igemm.hip: Fuse21Args).  d(act1)
+                               * is never written and conv1's own weight-gradient launch disappears.
+                               * 0: off (two launches); 1: where the flattened first-layer weight gradient would run (>= 200
+                               * workgroups, i.e. B >= 255 at 84x84); 2: at every batch size (tests).  Other nets are unaffected.
+                               * Measured FASTER than the two launches on one box, alternating: 6.65 vs 6.95 ms per 4096-sample update
+                               * (-4.3 %, every run below every run of the other arm); 27.3 us in one launch instead of 19.1 + 13.8 us,
+                               * 16 MB less written and 16 MB less read per step (profiles/bwd_fuse21_ab.md).
+                               * DEFAULT 0 all the same: it changes conv1's gradient at fp32 summation-order level (2e-7 relative per
+                               * step, every other gradient bitwise equal), and 52 sign-like Adam steps amplify that to 19 % of an
+                               * update's parameter delta -- the default update would no longer be the one the full-update parity test
+                               * and recorded benchmark outputs pin.  Opt in with bwd_fuse21 = 1 */
 } xt_tuning;
 int xt_tuning_get(xt_tuning* out);
 int xt_tuning_set(const xt_tuning* in);

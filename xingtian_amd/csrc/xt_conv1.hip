@@ -628,11 +628,6 @@ __global__ __launch_bounds__(128 * NKQ, NKQ) void conv_u8c4k8_wgrad_bf16x3_kerne
 //    (semantics measured on the GPU, tools/tr_probe.hip) -- the transposition the byte gather did by hand;
 //  * only the input rows the position range needs are staged, packed back to back (<= 44 KB instead of 3 x 28 KB),
 //    which is what makes room for the 96 KB of dY planes.
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ i32x2 lds_read_tr8(const uint8_t* p) {
-  return __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) i32x2*)(p));
-}
-
 __global__ __launch_bounds__(512, 2) void conv_u8c4k8_wgrad_flat_kernel(const C1WgArgs p) {
   constexpr int NKQ = 4, NT = 512, RQ = 2, PB = 512, NIMG = 3, NSTEP = PB / 16, NITEM = NSTEP * 64 / NT;
   extern __shared__ __attribute__((aligned(16))) uint8_t lsm[];

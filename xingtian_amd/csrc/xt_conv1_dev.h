@@ -69,6 +69,13 @@ __device__ __forceinline__ f32x16 mfma_bf16x6(const bf16x8 (&a)[3], const bf16x8
   return acc;
 }
 
+// ds_read_b64_tr_b8: in every 16-lane group lanes 2j, 2j+1 supply the address of bytes [0..7], [8..15] of row j and
+// lane c receives column c of the eight rows (see conv_u8c4k8_wgrad_flat_kernel)
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ i32x2 lds_read_tr8(const uint8_t* p) {
+  return __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) i32x2*)(p));
+}
+
 // global -> LDS copy of one frame stack: 8 x 16-byte loads per thread are issued back to back (one memory
 // latency for the whole image instead of one per loop iteration), then written to LDS
 template <int NT = 256>

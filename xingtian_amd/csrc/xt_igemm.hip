@@ -1180,8 +1180,34 @@ constexpr int dgrad4_smem_floats() {
   return SPLIT ? (12 * kD4SlotA + kD4Classes * 12 * kD4SlotB) / 4 + 128 : 32 * 129 + kD4Classes * 32 * 33 + 128;
 }
 
-template <bool SPLIT, bool PF4 = false>
-__device__ __forceinline__ void igemm_dgrad4_body(const DgradArgs& p, const int bx, float* smem) {
+// F21 (tuning.bwd_fuse21): the producer is the uint8 C = 4 8x8 first layer (PpoCnn conv1), which has no input gradient, so
+// the only reader of this block's 512 pixels of dX would be that layer's weight gradient -- a sum over positions that
+// does not care which positions a block owns.  The block therefore keeps dX: its accumulators, times relu' from the
+// producer's sign mask, ARE the B operand of the first layer's weight gradient -- lane (h, n) of a 32x32 accumulator
+// holds rows 4h + (r & 3) + 8 (r >> 2) of column n, i.e. registers 8j .. 8j+7 of a class are the eight reduction entries
+// 8h + e of one 16-position step of conv_u8c4k8_wgrad_flat_kernel's loop, for the position order
+//   step (wave, class, j), entry kk  ->  tile row 32 wave + 8 (2j + ((kk & 7) >> 2)) + 4 (kk >> 3) + (kk & 3).
+// Each wave runs that loop (ds_read_b64_tr_b8 A operand from the staged uint8 input rows, v_mfma_f32_32x32x16_bf16 x 3)
+// over its own 8 steps for all 8 kernel rows; the four waves' partial tiles are summed through LDS in a fixed order and
+// the block writes one slab of layer 0.  dX never goes to memory and no block reads what another block wrote.
+// The input rows are requested into registers under the input-gradient loop (the operand sets it has already consumed
+// free the registers) and go to LDS, over the dead operand stage, after its last barrier.
+struct Fuse21Args {
+  const uint8_t* in;     // uint8 observations [*, H0, W0, 4]
+  const int32_t* idx;    // minibatch row gather (may be null)
+  float* out;            // layer 0's slabs [(KH0 * 32 + 1) * 32] each, one per input-gradient block
+  int HWC, Wrow;         // bytes per frame stack / per input row
+  int S, KH;             // first layer's stride and kernel height
+  float xs, xb;          // input transform x * xs + xb
+  int img_cap;           // LDS bytes reserved for the packed input rows (multiple of 16, <= kF21RowUnits * 4096)
+};
+constexpr int kF21RowUnits = 11;                          // 16-byte units of input rows per thread
+constexpr int kF21SmemFloats = 2 * 256 * 36 + 4 * 32;     // the combine buffer (two parked copies of the tile) + bias partials
+
+template <bool SPLIT, bool PF4 = false, bool F21 = false>
+__device__ __forceinline__ void igemm_dgrad4_body(const DgradArgs& p, const int bx, float* smem,
+                                                  const Fuse21Args* f = nullptr) {
+  static_assert(!F21 || (SPLIT && PF4), "the fused first-layer weight gradient rides on the bf16x6 all-taps form");
   constexpr int BI = 128, SA = BI + 1, SB = 33, NA = 4;
   float* As = smem;
   float* Bs = smem + 32 * SA;                       // [class][32 k][SB]
@@ -1286,6 +1312,62 @@ __device__ __forceinline__ void igemm_dgrad4_body(const DgradArgs& p, const int 
   // under load: the loop then runs at the memory latency (timeline: 3 us per step).  PF4 (nsteps == 4, two workgroups
   // per CU = 256 VGPRs): the operands of ALL four taps are requested up front, the loop only splits, syncs and multiplies.
   Regs R0, R1, R2, R3;
+  // ---- F21: what the first layer's weight gradient needs besides the accumulators
+  int f_cum1 = 0, f_cum2 = 0, f_ntot = 0, f_po[2];      // packed 16-byte units: stack 1 / 2 start at f_cum1 / f_cum2
+  long long f_go0 = 0, f_go1 = 0, f_go2 = 0;           // global byte of packed unit u of stack i: f_go<i> + 16 u
+  uint32_t f_mpix[2], f_mw[2];
+  xt_u32x4 f_rows[kF21RowUnits];                             // (raw 16-byte units)
+  if constexpr (F21) {
+    const int CPS = HC * WC, c1 = min(Mc, i0 + BI);
+    const int s0 = i0 / CPS, slast = (c1 - 1) / CPS;      // a 128-position tile touches at most three samples (host-checked)
+    int sh0 = 0, sh1 = 0, sh2 = 0;                         // LDS byte of stack i's byte o: sh<i> + o
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int sidx = s0 + i, sc = min(sidx, g.B - 1);
+      const int srow = f->idx ? f->idx[sc] : sc;
+      int un = 0;
+      long long go = 0;
+      int sh = 0;
+      if (sidx <= slast) {
+        const int lo = max(i0, sidx * CPS) - sidx * CPS, hi = min(c1, (sidx + 1) * CPS) - 1 - sidx * CPS;
+        const int ylo = g.S * (int)fdiv((uint32_t)lo, dw), yhi = g.S * (int)fdiv((uint32_t)hi, dw) + g.S - 1;   // producer rows
+        const int blo = f->S * ylo * f->Wrow, bhi = (f->S * yhi + f->KH) * f->Wrow;
+        const int ul = blo >> 4;
+        un = ((bhi + 15) >> 4) - ul;
+        go = (long long)srow * (long long)f->HWC + ((long long)ul - f_ntot) * 16;
+        sh = (f_ntot - ul) * 16;
+      }
+      if (i == 0) { f_go0 = go; sh0 = sh; }
+      if (i == 1) { f_go1 = go; sh1 = sh; f_cum1 = f_ntot; }
+      if (i == 2) { f_go2 = go; sh2 = sh; f_cum2 = f_ntot; }
+      f_ntot += un;
+    }
+    // entry e = class * 128 + tile row: packed-row byte of the pixel's window origin, and its word of the sign mask
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int e = t + 256 * k, cls = e >> 7;
+      const int mc = min(i0 + (e & 127), c1 - 1);            // rows past the end carry zero accumulators
+      const int b = (int)fdiv((uint32_t)mc, dhw), rem = mc - b * CPS;
+      const int ty = (int)fdiv((uint32_t)rem, dw), tx = rem - ty * WC;
+      const int y = g.S * ty + (cls >> 1), x = g.S * tx + (cls & 1), di = b - s0;
+      f_mpix[k] = (uint32_t)((b * g.H + y) * g.W + x);
+      f_po[k] = (di == 0 ? sh0 : di == 1 ? sh1 : sh2) + f->S * (y * f->Wrow + x * 4);
+    }
+  }
+  // all input-row loads of the block + the mask words, back to back (stacks 1 / 2 absent: their start is f_ntot or beyond)
+#define XT_F21_REQUEST()                                                                          \
+  {                                                                                               \
+    _Pragma("unroll") for (int q = 0; q < kF21RowUnits; ++q) {                                    \
+      int u = t + 256 * q;                                                                        \
+      u = u < f_ntot ? u : 0;                                                                     \
+      long long go = f_go0;                                                                       \
+      go = u >= f_cum1 ? f_go1 : go;                                                              \
+      go = u >= f_cum2 ? f_go2 : go;                                                              \
+      f_rows[q] = *reinterpret_cast<const xt_u32x4*>(f->in + go + (long long)u * 16);              \
+    }                                                                                             \
+    f_mw[0] = p.xmask[f_mpix[0]];                                                                 \
+    f_mw[1] = p.xmask[f_mpix[1]];                                                                 \
+  }
   fetch(0, R0);
   if constexpr (PF4) { fetch(1, R1); fetch(2, R2); fetch(3, R3); }
   XT_TL(1);
@@ -1319,7 +1401,10 @@ __device__ __forceinline__ void igemm_dgrad4_body(const DgradArgs& p, const int 
   };
   if constexpr (PF4) {
     stash(R0); __syncthreads(); XT_TL(2); mma(); __syncthreads();
-    stash(R1); __syncthreads(); mma(); __syncthreads();
+    stash(R1);
+    if constexpr (F21) XT_F21_REQUEST()    // (two operand sets are consumed: their registers take the rows)
+#undef XT_F21_REQUEST
+    __syncthreads(); mma(); __syncthreads();
     stash(R2); __syncthreads(); mma(); __syncthreads();
     stash(R3); __syncthreads(); mma(); __syncthreads();
   } else {
@@ -1333,6 +1418,108 @@ __device__ __forceinline__ void igemm_dgrad4_body(const DgradArgs& p, const int 
     }
   }
   XT_TL(3);
+  if constexpr (F21) {
+    uint8_t* limg = reinterpret_cast<uint8_t*>(smem);                       // the operand stage is dead
+    int* pixoff = reinterpret_cast<int*>(limg + f->img_cap);                // [4 classes][128 tile rows]
+    uint32_t* maskw = reinterpret_cast<uint32_t*>(pixoff + 512);            // same order
+#pragma unroll
+    for (int q = 0; q < kF21RowUnits; ++q) {      // (unconditional: a guarded write makes hipcc sink each load into its branch)
+      int u = t + 256 * q;
+      u = u < f_ntot ? u : 0;
+      *reinterpret_cast<xt_u32x4*>(limg + u * 16) = f_rows[q];
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) { pixoff[t + 256 * k] = f_po[k]; maskw[t + 256 * k] = f_mw[k]; }
+    __syncthreads();
+    // A-operand role of this lane inside its 16-lane group: position entry kk = prow, byte half c16 & 1
+    const int c16 = lane & 15, grp = lane >> 4;
+    const int prow = 8 * (grp >> 1) + (c16 >> 1);
+    const int prow_t = wave * 32 + 8 * ((prow & 7) >> 2) + 4 * (prow >> 3) + (prow & 3);     // + 16 j: its tile row
+    const uint8_t* abase = limg + (grp & 1) * 16 + (c16 & 1) * 8;
+    const int Wrow = f->Wrow;
+    f32x16 wacc[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) wacc[q][r] = 0.f;
+    float bsum = 0.f;
+    i32x2 xr[2][8];
+    auto read_x = [&](int st, i32x2 (&x8)[8]) {
+      const int po = pixoff[(st >> 1) * 128 + prow_t + 16 * (st & 1)];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) x8[q] = lds_read_tr8(abase + po + q * Wrow);
+    };
+    read_x(0, xr[0]);
+#pragma unroll
+    for (int st = 0; st < 8; ++st) {              // step = (class, j)
+      const int cls = st >> 1, j = st & 1, cur = st & 1;
+      const uint4 m0 = *reinterpret_cast<const uint4*>(maskw + cls * 128 + wave * 32 + 16 * j + 4 * kl);
+      const uint4 m1 = *reinterpret_cast<const uint4*>(maskw + cls * 128 + wave * 32 + 16 * j + 8 + 4 * kl);
+      const uint32_t mk[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        v[e] = ((mk[e] >> il) & 1u) ? acc[cls][8 * j + e] : 0.f;
+        bsum += v[e];
+      }
+      bf16x8 bp[3];
+      split3_regs(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), bp);
+      if (st + 1 < 8) read_x(st + 1, xr[cur ^ 1]);
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {      // plane-major over four kernel rows: consecutive MFMAs hit different tiles
+        bf16x8 av[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) av[q] = bytes_to_bf16x8((uint32_t)xr[cur][4 * half + q].x, (uint32_t)xr[cur][4 * half + q].y);
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            wacc[4 * half + q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[q], bp[pl], wacc[4 * half + q], 0, 0, 0);
+      }
+    }
+    bsum += __shfl_xor(bsum, 32, 64);
+    XT_TL(4);
+    __syncthreads();                              // rows, tables: dead.  The combine buffer aliases them.
+    // waves 2, 3 park their tiles; waves 0, 1 add theirs on top; then all threads add the two copies and store 16 bytes
+    // each (fixed order: (w0 + w2) + (w1 + w3))
+    float* T = smem;
+    float* bred = smem + 2 * 256 * 36;
+    if (lane < 32) bred[wave * 32 + il] = bsum;
+    auto park = [&](bool add) {
+      float* Tw = T + (wave & 1) * 256 * 36;
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float* d = Tw + (q * 32 + (r & 3) + 8 * (r >> 2) + 4 * kl) * 36 + il;
+          *d = add ? wacc[q][r] + *d : wacc[q][r];
+        }
+    };
+    if (wave >= 2) park(false);
+    __syncthreads();
+    if (wave < 2) park(true);
+    __syncthreads();
+    {
+      float* slab = f->out + (size_t)bx * ((size_t)(f->KH * 32 + 1) * 32);
+      const int c4 = (t & 7) * 4;
+      float db[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) db[c] = (bred[c4 + c] + bred[64 + c4 + c]) + (bred[32 + c4 + c] + bred[96 + c4 + c]);
+#pragma unroll
+      for (int jj = 0; jj < 8; ++jj) {
+        const int krow = (t >> 3) + 32 * jj;
+        const float4 u0 = *reinterpret_cast<const float4*>(&T[krow * 36 + c4]);
+        const float4 u1 = *reinterpret_cast<const float4*>(&T[(256 + krow) * 36 + c4]);
+        float4 v;                                // d/dW of (x*xs + xb): xb * sum_p dY
+        v.x = fmaf(u0.x + u1.x, f->xs, f->xb * db[0]); v.y = fmaf(u0.y + u1.y, f->xs, f->xb * db[1]);
+        v.z = fmaf(u0.z + u1.z, f->xs, f->xb * db[2]); v.w = fmaf(u0.w + u1.w, f->xs, f->xb * db[3]);
+        *reinterpret_cast<float4*>(slab + (size_t)krow * 32 + c4) = v;
+      }
+      if (t < 8) *reinterpret_cast<float4*>(slab + (size_t)f->KH * 32 * 32 + c4) = make_float4(db[0], db[1], db[2], db[3]);
+    }
+    XT_TL_DRAIN(5);
+    return;
+  }
   // epilogue: class (ry, rx) of position row i writes pixel rowOut[i] + (ry*W + rx)*C.  A pixel is one contiguous
   // 128-byte row of C = 32 channels, but the accumulator layout has lanes = channels (dword accesses, 2 rows per
   // instruction: 64 loads of the producer activation + 64 stores per lane, 6.5 us of the block's 25).  Each class
@@ -1620,6 +1807,7 @@ struct BwdLayerArgs {
   int dg_direct;
   int dg_xcd;                // LDS-tiled input-gradient blocks in XCD-contiguous order
   HeadWgArgs hw;
+  Fuse21Args f21;            // the producer's (first layer's) weight gradient inside the input-gradient blocks (F21 instances)
   int wg_gx, wg_gy, wg_gz;   // wgrad grid
   int dg_gx, dg_gy, dg_gz;   // dgrad grid
   int n_wg, n_dg, n_hw;      // block counts (n_hw may be 0)
@@ -1629,17 +1817,24 @@ struct BwdLayerArgs {
 // a kernel is the maximum over all of its paths: the generic form needs 144 VGPR (LDS-tiled dgrad) + 32 AGPR
 // (register-direct dgrad) = two workgroups per CU, this one three.
 template <int WBI, int WBJ, int WWI, int WWJ, bool WPAD, int DBI, int DBJ, int DWI, int DWJ, int D4 = 0, int HALO = 0,
-          bool DX6 = false, int WROWS = 0, int WX6 = 0>
+          bool DX6 = false, int WROWS = 0, int WX6 = 0, bool F21 = false>
 __global__ __launch_bounds__(256, WROWS ? 2 : 3) void igemm_bwd_layer_kernel(const BwdLayerArgs p) {
   constexpr int SMD = HALO == 5 ? 18 * 1024 : HALO == 3 ? 8 * 1024 : HALO == 2 ? 11 * 1024 : HALO == 1 ? 9 * 1024 : dgrad_smem_floats<DBI, DBJ, DX6>();
   constexpr int SMW = (WROWS == 1 || WROWS == 2) ? kWrMaxSmemFloats : wgrad_smem_floats<WBI, WBJ, WPAD, WX6>();
   constexpr int SM0 = SMW > SMD ? SMW : SMD;
   constexpr int SM = (D4 && dgrad4_smem_floats<D4 == 2>() > SM0) ? dgrad4_smem_floats<D4 == 2>() : SM0;
-  __shared__ __attribute__((aligned(16))) float smem[SM];
+  // F21: dynamic LDS (kF21SmemFloats, above the 64 KB a static array may have), sized by the launch
+  static_assert(!F21 || (SM <= kF21SmemFloats && D4 == 2 && WROWS >= 2), "F21 rides on the bf16x6 all-taps input gradient");
+  __shared__ __attribute__((aligned(16))) float smem_static[F21 ? 4 : SM];
+  float* smem = smem_static;
+  if constexpr (F21) {
+    extern __shared__ __attribute__((aligned(16))) float smem_dynamic[];
+    smem = smem_dynamic;
+  }
   int b = blockIdx.x;
   if (b < p.n_dg) {                       // dgrad first: it is on the critical path of the next layer
     if constexpr (D4 != 0) {              // stride-2 conv: the four parity classes of a position tile in one block
-      igemm_dgrad4_body<D4 == 2, (WROWS >= 2)>(p.dg, b, smem);
+      igemm_dgrad4_body<D4 == 2, (WROWS >= 2), F21>(p.dg, b, smem, &p.f21);
       return;
     }
     if constexpr (HALO == 5) {            // ... input AND weight gradient per sample (the launch has no weight-gradient blocks)
@@ -1900,7 +2095,7 @@ int launch_dgrad(const xt_conv_geom* cg, int B, const float* dy, const float* w,
 #define XT_BWD_PAIR4(P) kBwdPair##P, kBwdPair##P##Pad, kBwdPair##P##X6, kBwdPair##P##PadX6
 enum BwdInst {
   kBwdS2Fused, kBwdS2FusedPad, kBwdS2c16, kBwdS2c16Pad, kBwdHalo, kBwdHaloX6, kBwdHaloX6Wx6,
-  kBwdClassesPf4, kBwdClassesWrows2, kBwdClassesWrows1, kBwdClassesX6, kBwdClasses, kBwdDense, kBwdDenseWx6, kBwdPairLLWx6,
+  kBwdClassesPf4, kBwdClassesPf4F21, kBwdClassesWrows2, kBwdClassesWrows1, kBwdClassesX6, kBwdClasses, kBwdDense, kBwdDenseWx6, kBwdPairLLWx6,
   XT_BWD_PAIR4(SS), XT_BWD_PAIR4(SL), XT_BWD_PAIR4(LS), XT_BWD_PAIR4(LL)
 };
 #undef XT_BWD_PAIR4
@@ -1912,6 +2107,7 @@ struct BwdPlan {
   int path;       // XT_BWD_PATH_*
   int arith;      // XT_ARITH_*
   int npre;       // squared-norm partials the weight-gradient blocks leave (0: none)
+  int fuse21;     // 1: the input-gradient blocks keep dX and write the producer's weight-gradient slabs (kBwdClassesPf4F21)
 };
 
 // LDS-tiled weight gradient: the reduction over M in (at most) `split` slabs, one grid layer each
@@ -1927,8 +2123,31 @@ static void fit_wgrad(int room, BwdLayerArgs* a) {
 // g.B samples; msplit: requested weight-gradient split; slab_cap: slabs the slab buffer holds (have_slabs: there is one);
 // n_hw: head weight-gradient blocks riding along (0: none); want_npre: the caller can take squared-norm partials.
 // The branches in order of precedence, one early return each.
+// Bytes of packed first-layer input rows that the largest 128-patch tile of the launch stages (the device side is the F21
+// part of igemm_dgrad4_body); -1: a tile touches more than three samples.  g: the consumer (its input = the first layer's output).
+static int f21_packed_cap(const Geom& g, const xt_conv_geom& g0) {
+  const int HC = g.H / g.S, WC = g.W / g.S, CPS = HC * WC, total = g.B * CPS, Wrow = g0.W * 4;
+  int cap = 0;
+  for (int c0 = 0; c0 < total; c0 += 128) {
+    const int c1 = total < c0 + 128 ? total : c0 + 128;
+    if ((c1 - 1) / CPS - c0 / CPS > 2) return -1;
+    int units = 0;
+    for (int sidx = c0 / CPS; sidx <= (c1 - 1) / CPS; ++sidx) {
+      const int lo = (c0 > sidx * CPS ? c0 : sidx * CPS) - sidx * CPS;
+      const int hi = (c1 < (sidx + 1) * CPS ? c1 : (sidx + 1) * CPS) - 1 - sidx * CPS;
+      const int ylo = g.S * (lo / WC), yhi = g.S * (hi / WC) + g.S - 1;
+      const int blo = g0.S * ylo * Wrow, bhi = (g0.S * yhi + g0.KH) * Wrow;
+      units += ((bhi + 15) >> 4) - (blo >> 4);
+    }
+    if (units * 16 > cap) cap = units * 16;
+  }
+  return cap;
+}
+
+// f21 (may be null): the caller offers the producer's weight gradient to the input-gradient blocks; p->fuse21 says whether
+// the plan took it (then the launch has one slab of the producer per input-gradient block and writes no dX).
 static int plan_bwd_layer(const Geom& g, int msplit, bool have_slabs, int slab_cap, int n_hw, bool want_npre,
-                          BwdLayerArgs* a, BwdPlan* p) {
+                          BwdLayerArgs* a, BwdPlan* p, const Fuse21Call* f21 = nullptr, bool have_mask = false) {
   const xt_tuning t = tuning();      // ONE snapshot: a knob changed on another thread mid-call cannot give a mixed view
   const int B = g.B;
   // (the buffer loads of the backward kernels address their tensors with 32-bit byte offsets, 2^31 = "out of range")
@@ -1937,6 +2156,7 @@ static int plan_bwd_layer(const Geom& g, int msplit, bool have_slabs, int slab_c
   const bool x6 = t.bf16x6 != 0, pad = is_padded(g), wsmall = g.N <= 32, dsmall = g.C <= 32;
   const auto take = [&](BwdInst inst, int path, int arith) { p->inst = inst; p->path = path; p->arith = arith; return 0; };
   p->npre = 0;
+  p->fuse21 = 0;
   a->wg.g = a->dg.g = g;
   a->n_hw = n_hw;
   // ---- the generic forms: LDS-tiled weight gradient ...
@@ -2033,6 +2253,27 @@ static int plan_bwd_layer(const Geom& g, int msplit, bool have_slabs, int slab_c
     const int room = 512 - a->n_dg - n_hw;
     if (t.wgrad_rows == 4 && x6 && taps4 && room >= tiles * 8) {
       fit_wgrad(room, a);
+      // bwd_fuse21: the first layer's weight gradient inside the input-gradient blocks (see Fuse21Args).  1: where the
+      // flattened first-layer weight gradient would run (its >= 200-workgroup rule: same block count), 2: any batch
+      if (t.bwd_fuse21 && f21 && have_mask && t.conv1_bf16x3 && (t.bwd_fuse21 == 2 || a->n_dg >= 200)) {
+        const xt_conv_geom& g0 = *f21->g0;
+        const xt_input_xform* xf = f21->xf;
+        const int HWC0 = g0.H * g0.W * 4;
+        const bool geom0 = xf && xf->is_u8 && g0.C == 4 && g0.KW == 8 && g0.KH == 8 && g0.N == 32 && g0.PT == 0 && g0.PL == 0 &&
+                           (g0.OH - 1) * g0.S + g0.KH <= g0.H && (g0.OW - 1) * g0.S + g0.KW <= g0.W && g0.OH == g.H &&
+                           g0.OW == g.W && g0.act == XT_ACT_RELU && HWC0 % 16 == 0 && HWC0 <= 64 * 1024 &&
+                           (g0.W * 4) % 8 == 0 && (g0.S * 4) % 16 == 0 && g.S == 2 &&
+                           (long long)g.B * HWC0 < (1ll << 31);
+        const int cap = geom0 ? f21_packed_cap(g, g0) : -1;
+        if (cap > 0 && cap <= kF21RowUnits * 4096 && cap + 4096 <= kF21SmemFloats * 4 && a->n_dg <= f21->slab_cap) {
+          Fuse21Args& fa = a->f21;
+          fa.HWC = HWC0; fa.Wrow = g0.W * 4; fa.S = g0.S; fa.KH = g0.KH; fa.img_cap = cap;
+          const float mean = fabsf(xf->mean) >= 1e-4f ? xf->mean : 0.f;
+          fa.xs = 1.f / xf->std; fa.xb = -mean * fa.xs;
+          p->fuse21 = 1;
+          return take(kBwdClassesPf4F21, XT_BWD_PATH_CLASSES_PF4, arith);
+        }
+      }
       return take(kBwdClassesPf4, XT_BWD_PATH_CLASSES_PF4, arith);
     }
     return take(x6 ? kBwdClassesX6 : kBwdClasses, XT_BWD_PATH_CLASSES, arith);
@@ -2067,8 +2308,15 @@ int launch_bwd_layer(const BwdLayerCall& c) {
   BwdLayerArgs a{};
   BwdPlan p;
   if (int rc = plan_bwd_layer(g, c.msplit, c.slabs != nullptr, c.slab_cap, c.hw ? c.hw->gx * c.hw->nchunk : 0,
-                              c.sq_partials && c.npre_out, &a, &p))
+                              c.sq_partials && c.npre_out, &a, &p, c.f21,
+                              c.xmask != nullptr && c.act_prev == XT_ACT_RELU))
     return rc;
+  if (c.f21 && c.f21->fused_out) *c.f21->fused_out = p.fuse21;
+  if (p.fuse21) {
+    a.f21.in = static_cast<const uint8_t*>(c.f21->in); a.f21.idx = c.f21->idx;
+    a.f21.out = a.n_dg == 1 ? c.f21->dwb : c.f21->slabs;      // (one block: its slab is the final gradient)
+    if (c.f21->nslab_out) *c.f21->nslab_out = a.n_dg;
+  }
   const float* x_grad = c.x_grad ? c.x_grad : c.x;
   a.wg.in = c.x; a.wg.dy = c.dy;
   a.wg.out = a.wg.msplit == 1 ? c.dwb : c.slabs;
@@ -2100,6 +2348,26 @@ int launch_bwd_layer(const BwdLayerCall& c) {
     case kBwdHaloX6:        XT_BWD_GO(64, 64, 2, 2, false, 128, 32, 4, 1, 0, 2); break;
     case kBwdHalo:          XT_BWD_GO(64, 64, 2, 2, false, 128, 32, 4, 1, 0, 1); break;
     case kBwdClassesPf4:    XT_BWD_GO(128, 32, 4, 1, false, 128, 32, 4, 1, 2, 0, false, 3); break;
+    case kBwdClassesPf4F21: {
+      const auto kern = igemm_bwd_layer_kernel<128, 32, 4, 1, false, 128, 32, 4, 1, 2, 0, false, 3, 0, true>;
+      static PerDeviceOnce attr_once;
+      attr_once.run([kern] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  kF21SmemFloats * 4);
+        (void)hipGetLastError();
+      });
+#ifdef XT_EXP_F21_TWO_LAUNCHES      // A/B form (b): the fused blocks alone, then conv2's weight-gradient blocks as a launch of their own
+      {
+        BwdLayerArgs a1 = a, a2 = a;
+        a1.n_wg = 0; a1.n_hw = 0; a2.n_dg = 0;
+        hipLaunchKernelGGL(kern, dim3(a.n_dg), dim3(256), kF21SmemFloats * 4, c.st, a1);
+        hipLaunchKernelGGL(kern, dim3(a.n_wg + a.n_hw), dim3(256), kF21SmemFloats * 4, c.st, a2);
+        break;
+      }
+#endif
+      hipLaunchKernelGGL(kern, grid, dim3(256), kF21SmemFloats * 4, c.st, a);
+      break;
+    }
     case kBwdClassesWrows2: XT_BWD_GO(128, 32, 4, 1, false, 128, 32, 4, 1, 2, 0, false, 2); break;
     case kBwdClassesWrows1: XT_BWD_GO(128, 32, 4, 1, false, 128, 32, 4, 1, 2, 0, false, 1); break;
     case kBwdClassesX6:     XT_BWD_GO(128, 32, 4, 1, false, 128, 32, 4, 1, 2); break;

@@ -20,6 +20,21 @@ int launch_wgrad(const xt_conv_geom* cg, const xt_input_xform* xf, int B, const 
 int launch_dgrad(const xt_conv_geom* cg, int B, const float* dy, const float* w, const float* x, int act_prev,
                  float* dx, hipStream_t st);
 
+// The producer's weight gradient offered to a fused backward launch (tuning.bwd_fuse21): the producer is a uint8 first
+// layer, which has no input gradient, so the launch's input-gradient blocks may keep dX and write the producer's
+// weight-gradient slabs instead (xt_igemm.hip: Fuse21Args).  *fused_out tells whether the launch did.
+struct Fuse21Call {
+  const xt_conv_geom* g0 = nullptr;    // the producer (first layer)
+  const xt_input_xform* xf = nullptr;
+  const void* in = nullptr;            // its uint8 input
+  const int32_t* idx = nullptr;        // minibatch row gather (may be null)
+  float* dwb = nullptr;                // its weight + bias gradient, when a single slab is written
+  float* slabs = nullptr;              // ... else `*nslab_out` slabs
+  int slab_cap = 0;
+  int* nslab_out = nullptr;
+  int* fused_out = nullptr;
+};
+
 // One fused backward launch of a non-first layer: weight gradient + input gradient (+ the head weight gradients).
 struct BwdLayerCall {
   const xt_conv_geom* g = nullptr;
@@ -42,6 +57,7 @@ struct BwdLayerCall {
   int* nslab_out = nullptr;            // slabs written: 1 = the gradient is final in dwb
   int* npre_out = nullptr;             // squared-norm partials written (0: none)
   int* path_out = nullptr;             // the branch taken, as xt_layer_bwd reports it
+  const Fuse21Call* f21 = nullptr;     // the producer's weight gradient may ride along (may be null)
 };
 int launch_bwd_layer(const BwdLayerCall& c);
 

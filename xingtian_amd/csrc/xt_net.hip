@@ -33,7 +33,7 @@ xt_tuning& tuning() {
                         /*direct_waves*/ 1536, /*direct_max_waves*/ 8, /*direct_tile64_tiles*/ 3072,
                         /*fwd_split_target*/ 256, /*wgrad_split_target*/ 512, /*reduce_z_lanes*/ 8,
                         /*defer_splitk*/ 1, /*finalize_ticket*/ 0, /*fwd_tiled_valid*/ 1, /*wgrad_rows*/ 4, /*fwd_prefetch_all*/ 0, /*bwd_deep_prefetch*/ 1, /*fwd_four_groups*/ 1, /*reduce_deep_lanes*/ 128, /*fwd_xcd_chunk*/ 1,
-                        /*tail_overlap*/ 0, /*tail_fused*/ 0, /*dense_wgrad_x6*/ 1, /*fwd_fuse12*/ 0};
+                        /*tail_overlap*/ 0, /*tail_fused*/ 0, /*dense_wgrad_x6*/ 1, /*fwd_fuse12*/ 0, /*bwd_fuse21*/ 0};
   return t;
 }
 
@@ -291,6 +291,7 @@ static int trunk_backward(xt_net* n, const void* obs, const int32_t* idx, int B,
                           const AfterFirstBwd* after_first = nullptr) {
   bool heads_done = false;
   bool first_done = false;
+  int fused21 = 0;      // the launch of a trunk's second layer also wrote its first layer's weight-gradient slabs
   const bool pre_ok = tuning().finalize_ticket == 0;      // (the last-block finalize form reads one partial per block)
   for (auto& L : n->layers) L.last_npre = 0;
   for (int tr = 0; tr < n->n_trunks; ++tr)
@@ -299,10 +300,22 @@ static int trunk_backward(xt_net* n, const void* obs, const int32_t* idx, int B,
       Layer& L = n->layers[l];
       if (first) {
         if (!heads_done) { if (int rc = heads_wgrad(n, B, st)) return rc; heads_done = true; }
-        if (int rc = layer_wgrad(n, l, true, obs, idx, B, st)) return rc;
+        if (!fused21)
+          if (int rc = layer_wgrad(n, l, true, obs, idx, B, st)) return rc;
         continue;
       }
       BwdLayerCall c = bwd_layer_call(n, l, B, st);
+      // bwd_fuse21: offer the first layer's weight gradient to the second layer's launch (one-trunk nets; the launch
+      // takes it for PpoCnn's relu conv1 / conv2 pair only, see plan_bwd_layer)
+      Fuse21Call f21;
+      fused21 = 0;
+      if (l - 1 == n->t_begin[tr] && n->n_trunks == 1 && tuning().bwd_fuse21 != 0) {
+        Layer& L0 = n->layers[l - 1];
+        f21.g0 = &L0.g; f21.xf = &n->xf; f21.in = obs; f21.idx = idx;
+        f21.dwb = n->grads + L0.poff; f21.slabs = n->ws + L0.slab_off; f21.slab_cap = L0.slab_cap;
+        f21.nslab_out = &L0.last_msplit; f21.fused_out = &fused21;
+        c.f21 = &f21;
+      }
       HeadWgArgs hw;
       if (!heads_done) {
         Layer& Lp = n->layers[n->t_end[0] - 1];
@@ -806,6 +819,7 @@ int xt_tuning_set(const xt_tuning* in) {
              "xt_tuning_set: reduce_z_lanes must be a power of two <= 32");
   XT_REQUIRE(in->fwd_split_target >= 1 && in->wgrad_split_target >= 1 && in->direct_waves >= 1 && in->bwd_fit_slots >= 0,
              "xt_tuning_set: block-count targets must be positive");
+  XT_REQUIRE(in->bwd_fuse21 >= 0 && in->bwd_fuse21 <= 2, "xt_tuning_set: bwd_fuse21 must be 0, 1 or 2");
   std::lock_guard<std::mutex> lk(g_tuning_mu);
   xt::tuning() = *in;
   return 0;
