@@ -748,6 +748,57 @@ int xt_net_time_layer(xt_net* net, int32_t layer, int32_t which /* 0 fwd, 1 wgra
  * running it at the same time on one device give the kernel-side cost of the exchange per rank (tools/direct_probe.py). */
 int xt_net_time_tail(xt_net* net, float lr, float clip_norm, int32_t reps, float* ms_out, void* stream);
 
+/* xt_layer_fwd that reports the branch its dispatcher took, stand-alone for tests (appended; the ABI version stays).
+ *   relu_mask    NULL, or [B*OH*OW] words for the first layer's relu sign mask (bit n of word p = y[p,n] > 0); only the
+ *                flattened first-layer forward writes it, and only when the activation is relu
+ *   mask_written NULL, or receives 1 when the mask was written, else 0
+ * *path_out (may be NULL) receives XT_FWD_PATH_* | tile << XT_FWD_TILE_SHIFT | nst << XT_FWD_NST_SHIFT |
+ * xcd << XT_FWD_XCD_SHIFT | XT_ARITH_* << XT_FWD_ARITH_SHIFT | units << XT_FWD_UNITS_SHIFT | ksplit << XT_FWD_KSPLIT_SHIFT:
+ *   tile    XT_FWD_TILE_* (0 for the first-layer kernels)
+ *   nst     steps per wave group the all-loads-up-front instance holds in flight (4 / 5 / 8), else 0
+ *   xcd     1 when the blocks run in the XCD-chunked order (LDS-tiled forms only)
+ *   units   LDS-tiled: wave groups per block (1 / 2 / 4); first-layer per frame stack: waves per block (4 / 8);
+ *           first-layer flattened and SAME: output positions per workgroup (256 / 512); register-direct: waves per block
+ *   ksplit  the EFFECTIVE split-K count the launch ran with (1 = none; reported up to 127) */
+#define XT_FWD_PATH_C1_FLAT 1        /* uint8 first layer, VALID 8-wide kernel, 32 filters: positions flattened over the batch */
+#define XT_FWD_PATH_C1_STACK 2       /* ... one frame stack per workgroup                                            */
+#define XT_FWD_PATH_C1_SAME 3        /* uint8 first layer, SAME 8x8/4 or 4x4/2, 16 filters                           */
+#define XT_FWD_PATH_DIRECT 4         /* register-direct forward (no LDS operand tiles)                               */
+#define XT_FWD_PATH_TILED_FP32 5     /* LDS-tiled, fp32 MFMA (also every uint8 layer the first-layer kernels refuse) */
+#define XT_FWD_PATH_TILED_X6 6       /* LDS-tiled, bf16x6                                                            */
+#define XT_FWD_PATH_TILED_X6_ALL 7   /* LDS-tiled, bf16x6, two wave groups with all loads up front (fwd_prefetch_all) */
+#define XT_FWD_TILE_128X32 1
+#define XT_FWD_TILE_64X64 2
+#define XT_FWD_TILE_DIRECT_TJ1 3     /* register-direct, one 32-column tile per wave                                 */
+#define XT_FWD_TILE_DIRECT_TJ2 4     /* ... two                                                                      */
+#define XT_FWD_TILE_SHIFT 4          /* 3 bits  */
+#define XT_FWD_NST_SHIFT 7           /* 4 bits  */
+#define XT_FWD_XCD_SHIFT 11          /* 1 bit   */
+#define XT_FWD_ARITH_SHIFT 12        /* 2 bits  */
+#define XT_FWD_UNITS_SHIFT 14        /* 10 bits */
+#define XT_FWD_KSPLIT_SHIFT 24       /* 7 bits  */
+int xt_layer_fwd_ex(const xt_conv_geom* g, const xt_input_xform* xf, int32_t B, const void* in, const int32_t* idx,
+                    const float* w, const float* bias, float* y, float* partial, int32_t ksplit, void* stream,
+                    uint32_t* relu_mask, int32_t* mask_written, int32_t* path_out);
+
+/* xt_layer_wgrad the way a network's update runs it (appended; the ABI version stays): the gradient is left in slabs
+ * (no reduction inside the launcher) and the slab buffer has `slab_cap` slabs, which is what lets the uint8 first-layer
+ * kernels in; more than one slab is then summed into dwb by the slab-reduction kernel, as xt_layer_bwd does.
+ * msplit > slab_cap is refused.
+ * *path_out (may be NULL) receives XT_WG1_PATH_* | XT_ARITH_* << XT_WG1_ARITH_SHIFT | units << XT_WG1_UNITS_SHIFT |
+ * slabs << XT_WG1_SLABS_SHIFT: units = waves per block (per frame stack: 4 / 8) or positions per workgroup (flattened
+ * and SAME: 256 / 512), 0 for the generic kernel; slabs = the number of slabs written (1: dwb was written directly) */
+#define XT_WG1_PATH_C1_FLAT 1        /* uint8 first layer, VALID 8x8, 32 filters: 512 positions per workgroup        */
+#define XT_WG1_PATH_C1_STACK 2       /* ... one frame stack per workgroup                                            */
+#define XT_WG1_PATH_C1_SAME 3        /* uint8 first layer, SAME 8x8/4 or 4x4/2, 16 filters                           */
+#define XT_WG1_PATH_GENERIC 4        /* LDS-tiled fp32 weight gradient                                               */
+#define XT_WG1_ARITH_SHIFT 4         /* 2 bits  */
+#define XT_WG1_UNITS_SHIFT 6         /* 10 bits */
+#define XT_WG1_SLABS_SHIFT 16        /* 15 bits */
+int xt_layer_wgrad_slabs(const xt_conv_geom* g, const xt_input_xform* xf, int32_t B, const void* in, const int32_t* idx,
+                         const float* dy, float* dwb, float* slabs, int32_t slab_cap, int32_t msplit, void* stream,
+                         int32_t* path_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -235,6 +235,9 @@ def test_layer_fwd_with_row_gather_and_mean_std(L):
 @pytest.mark.parametrize("case", LAYER_CASES, ids=[c[0] for c in LAYER_CASES])
 @pytest.mark.parametrize("msplit", [1, 5])
 def test_layer_wgrad(L, case, msplit):
+    # (xt_layer_wgrad reduces at once and offers no slab capacity, so the uint8 rows all run the generic fp32
+    # igemm_wgrad_kernel<..., U8 = true, ...>: this is its only cover.  The first-layer kernels an update runs for those
+    # geometries are tested through xt_layer_wgrad_slabs in tests/test_gpu_fwd_layer.py, WG1_CASES)
     lay, x_raw, x, w, bias, rng = _layer_data(case, seed=1)
     b = x.shape[0]
     cols = nets.im2col(x, lay) if lay.kind == "conv" else x.reshape(b, -1)

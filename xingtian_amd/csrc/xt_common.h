@@ -13,6 +13,16 @@ namespace xt {
 void set_error(const char* fmt, ...);
 xt_tuning& tuning();
 int& last_arith();             // XT_ARITH_* of the most recent layer launch (diagnostic)      // process-wide kernel-selection knobs (xt_tuning_get / xt_tuning_set); defined in xt_net.hip
+// The branch launch_fwd / launch_wgrad took most recently on the calling thread, written by the dispatcher next to the
+// launch it describes (diagnostic: xt_layer_fwd_ex / xt_layer_wgrad_slabs add last_arith() and hand it out)
+int& last_path();
+static inline int fwd_path_bits(int family, int tile, int units, int nst = 0, int ksplit = 1, int xcd = 0) {
+  return family | (tile << XT_FWD_TILE_SHIFT) | (nst << XT_FWD_NST_SHIFT) | (xcd << XT_FWD_XCD_SHIFT) |
+         (units << XT_FWD_UNITS_SHIFT) | ((ksplit > 127 ? 127 : ksplit) << XT_FWD_KSPLIT_SHIFT);
+}
+static inline int wg1_path_bits(int family, int units, int slabs) {
+  return family | (units << XT_WG1_UNITS_SHIFT) | (slabs << XT_WG1_SLABS_SHIFT);
+}
 
 #define XT_CHECK_HIP(expr)                                                                  \
   do {                                                                                      \

@@ -451,6 +451,7 @@ int launch_conv1_fwd_bf16x3(const xt_conv_geom* g, const xt_input_xform* xf, int
         if (two) hipLaunchKernelGGL(conv_u8c4k8_fwd_flat_kernel<2>, dim3((total + pb - 1) / pb), dim3(512), fl, st, a);
         else hipLaunchKernelGGL(conv_u8c4k8_fwd_flat_kernel<1>, dim3((total + pb - 1) / pb), dim3(512), fl, st, a);
         XT_LAUNCH_CHECK();
+        last_path() = fwd_path_bits(XT_FWD_PATH_C1_FLAT, 0, pb);
         if (mask_written && a.mask) *mask_written = 1;
         return 0;
       }
@@ -459,6 +460,7 @@ int launch_conv1_fwd_bf16x3(const xt_conv_geom* g, const xt_input_xform* xf, int
   if (nw == 8) hipLaunchKernelGGL(conv_u8c4k8_fwd_bf16x3_kernel<8>, dim3(B), dim3(512), lds, st, a);
   else hipLaunchKernelGGL(conv_u8c4k8_fwd_bf16x3_kernel<4>, dim3(B), dim3(256), lds, st, a);
   XT_LAUNCH_CHECK();
+  last_path() = fwd_path_bits(XT_FWD_PATH_C1_STACK, 0, nw);
   return 0;
 }
 
@@ -1406,6 +1408,7 @@ int launch_conv1_same_fwd(const xt_conv_geom* g, const xt_input_xform* xf, int B
     else hipLaunchKernelGGL((conv_u8c4_same_fwd_kernel<1, 4, 16>), grid, blk, fl, st, a);
   }
   XT_LAUNCH_CHECK();
+  last_path() = fwd_path_bits(XT_FWD_PATH_C1_SAME, 0, pb);
   return 0;
 }
 
@@ -1474,6 +1477,7 @@ int launch_conv1_same_wgrad(const xt_conv_geom* g, const xt_input_xform* xf, int
     else hipLaunchKernelGGL((conv_u8c4_same_wgrad_kernel<256, 4, 16>), grid, blk, fl, st, a);
   }
   XT_LAUNCH_CHECK();
+  last_path() = wg1_path_bits(XT_WG1_PATH_C1_SAME, pb, nblk);
   if (msplit_out) *msplit_out = nblk;
   return 0;
 }
@@ -1516,6 +1520,7 @@ int launch_conv1_wgrad_bf16x3(const xt_conv_geom* g, const xt_input_xform* xf, i
       });
       hipLaunchKernelGGL(conv_u8c4k8_wgrad_flat_kernel, dim3(nblk), dim3(512), fl, st, a);
       XT_LAUNCH_CHECK();
+      last_path() = wg1_path_bits(XT_WG1_PATH_C1_FLAT, 512, nblk);
       if (msplit_out) *msplit_out = nblk;
       return 0;
     }
@@ -1523,6 +1528,7 @@ int launch_conv1_wgrad_bf16x3(const xt_conv_geom* g, const xt_input_xform* xf, i
   if (c1_waves() == 8) hipLaunchKernelGGL(conv_u8c4k8_wgrad_bf16x3_kernel<4>, dim3(B), dim3(512), lds, st, a);
   else hipLaunchKernelGGL(conv_u8c4k8_wgrad_bf16x3_kernel<2>, dim3(B), dim3(256), lds, st, a);
   XT_LAUNCH_CHECK();
+  last_path() = wg1_path_bits(XT_WG1_PATH_C1_STACK, c1_waves(), B);
   if (msplit_out) *msplit_out = B;
   return 0;
 }

@@ -255,6 +255,7 @@ int launch_fwd_direct(const xt_conv_geom* cg, const xt_input_xform* xf, int B, c
   if (TJ == 2) XT_DF(2); else XT_DF(1);
 #undef XT_DF
   XT_LAUNCH_CHECK();
+  last_path() = fwd_path_bits(XT_FWD_PATH_DIRECT, TJ == 2 ? XT_FWD_TILE_DIRECT_TJ2 : XT_FWD_TILE_DIRECT_TJ1, nw, 0, ks);
   *ksplit_out = ks;
   return 0;
 }

@@ -1983,19 +1983,25 @@ int launch_fwd(const xt_conv_geom* cg, const xt_input_xform* xf, int B, const vo
   hipLaunchKernelGGL((igemm_fwd_kernel<BI, BJ, WI, WJ, false, false, 2, true, NSTV>),                       \
                      dim3((M + BI - 1) / BI, (N + BJ - 1) / BJ, ksplit), dim3(512), 0, st, a)
   const bool all = x6 && kg2 && !pad && tuning().fwd_prefetch_all != 0;
-  if (all && N > 32 && nst2 <= 4) XT_FWD6N(64, 64, 2, 2, 4);
-  else if (all && N > 32 && nst2 == 5) XT_FWD6N(64, 64, 2, 2, 5);
-  else if (all && N > 32 && nst2 <= 8) XT_FWD6N(64, 64, 2, 2, 8);
-  else if (all && N <= 32 && nst2 <= 4) XT_FWD6N(128, 32, 4, 1, 4);
-  else if (all && N <= 32 && nst2 <= 8) XT_FWD6N(128, 32, 4, 1, 8);
+  // (what each launch below is, for last_path(): family, wave groups, steps in flight of the all-loads-up-front form)
+  int fam = x6 ? XT_FWD_PATH_TILED_X6 : XT_FWD_PATH_TILED_FP32, groups = kg2 ? 2 : 1, nst = 0;
+#define XT_FWD_IS(FAM, GROUPS, NSTV) (fam = (FAM), groups = (GROUPS), nst = (NSTV))
+  if (all && N > 32 && nst2 <= 4) { XT_FWD6N(64, 64, 2, 2, 4); XT_FWD_IS(XT_FWD_PATH_TILED_X6_ALL, 2, 4); }
+  else if (all && N > 32 && nst2 == 5) { XT_FWD6N(64, 64, 2, 2, 5); XT_FWD_IS(XT_FWD_PATH_TILED_X6_ALL, 2, 5); }
+  else if (all && N > 32 && nst2 <= 8) { XT_FWD6N(64, 64, 2, 2, 8); XT_FWD_IS(XT_FWD_PATH_TILED_X6_ALL, 2, 8); }
+  else if (all && N <= 32 && nst2 <= 4) { XT_FWD6N(128, 32, 4, 1, 4); XT_FWD_IS(XT_FWD_PATH_TILED_X6_ALL, 2, 4); }
+  else if (all && N <= 32 && nst2 <= 8) { XT_FWD6N(128, 32, 4, 1, 8); XT_FWD_IS(XT_FWD_PATH_TILED_X6_ALL, 2, 8); }
   else
 #undef XT_FWD6N
   if (x6 && kg2 && tuning().fwd_four_groups && nblk <= 256 && chunk >= 16 * 32) {      // <= one block per CU, >= 4 steps per group (shorter chains: no gain)
     if (N > 32) XT_FWD6(64, 64, 2, 2, 4); else XT_FWD6(128, 32, 4, 1, 4);
+    XT_FWD_IS(XT_FWD_PATH_TILED_X6, 4, 0);
   } else
   if (x6 && N > 32) { if (kg2) XT_FWD6(64, 64, 2, 2, 2); else XT_FWD6(64, 64, 2, 2, 1); }
   else if (x6) { if (kg2) XT_FWD6(128, 32, 4, 1, 2); else XT_FWD6(128, 32, 4, 1, 1); }
   else if (N <= 32) XT_FWD(128, 32, 4, 1); else XT_FWD(64, 64, 2, 2);
+#undef XT_FWD_IS
+  last_path() = fwd_path_bits(fam, N <= 32 ? XT_FWD_TILE_128X32 : XT_FWD_TILE_64X64, groups, nst, ksplit, a.xcd_chunked);
 #undef XT_FWD6
 #undef XT_FWD
 #undef XT_FWD2
@@ -2048,6 +2054,7 @@ int launch_wgrad(const xt_conv_geom* cg, const xt_input_xform* xf, int B, const 
   if (N <= 32) XT_WG(128, 32, 4, 1); else XT_WG(64, 64, 2, 2);
 #undef XT_WG
   XT_LAUNCH_CHECK();
+  last_path() = wg1_path_bits(XT_WG1_PATH_GENERIC, 0, msplit);
   if (msplit_out) *msplit_out = msplit;
   if (msplit > 1 && reduce_now) {
     const int count = (K + 1) * N;
@@ -2398,6 +2405,39 @@ int xt_layer_fwd(const xt_conv_geom* g, const xt_input_xform* xf, int32_t B, con
 int xt_layer_wgrad(const xt_conv_geom* g, const xt_input_xform* xf, int32_t B, const void* in, const int32_t* idx,
                    const float* dy, float* dwb, float* slabs, int32_t msplit, void* stream) {
   return xt::launch_wgrad(g, xf, B, in, idx, dy, dwb, slabs, msplit, xt::as_stream(stream), 1, nullptr, 0);
+}
+
+int xt_layer_fwd_ex(const xt_conv_geom* g, const xt_input_xform* xf, int32_t B, const void* in, const int32_t* idx,
+                    const float* w, const float* bias, float* y, float* partial, int32_t ksplit, void* stream,
+                    uint32_t* relu_mask, int32_t* mask_written, int32_t* path_out) {
+  if (path_out) *path_out = 0;
+  xt::last_path() = 0;
+  int written = 0;
+  const int rc = xt::launch_fwd(g, xf, B, in, idx, w, bias, y, partial, ksplit, xt::as_stream(stream), nullptr, relu_mask,
+                                &written);
+  if (mask_written) *mask_written = written;
+  if (rc == 0 && path_out) *path_out = xt::last_path() | (xt::last_arith() << XT_FWD_ARITH_SHIFT);
+  return rc;
+}
+
+int xt_layer_wgrad_slabs(const xt_conv_geom* g, const xt_input_xform* xf, int32_t B, const void* in, const int32_t* idx,
+                         const float* dy, float* dwb, float* slabs, int32_t slab_cap, int32_t msplit, void* stream,
+                         int32_t* path_out) {
+  if (path_out) *path_out = 0;
+  // (the launch only ever LOWERS the split it is asked for, or sizes its first-layer forms by slab_cap)
+  XT_REQUIRE(g && (msplit <= 1 || (slabs != nullptr && msplit <= slab_cap)),
+             "xt_layer_wgrad_slabs: msplit %d needs a slab buffer of at least that many slabs (capacity %d)", msplit, slab_cap);
+  const hipStream_t st = xt::as_stream(stream);
+  xt::last_path() = 0;
+  int nslab = 1;
+  if (int rc = xt::launch_wgrad(g, xf, B, in, idx, dy, dwb, slabs, msplit, st, 0, &nslab, slabs ? slab_cap : 0)) return rc;
+  if (nslab > 1) {
+    const int count = (g->KH * g->KW * g->C + 1) * g->N;
+    hipLaunchKernelGGL(xt::reduce_slabs_kernel, dim3((count / 4 + 255) / 256), dim3(256), 0, st, slabs, dwb, count, nslab);
+    XT_LAUNCH_CHECK();
+  }
+  if (path_out) *path_out = xt::last_path() | (xt::last_arith() << XT_WG1_ARITH_SHIFT);
+  return 0;
 }
 
 int xt_layer_dgrad(const xt_conv_geom* g, int32_t B, const float* dy, const float* w, const float* x,

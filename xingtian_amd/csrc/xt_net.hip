@@ -26,6 +26,7 @@ void set_error(const char* fmt, ...) {
 }
 
 int& last_arith() { static thread_local int a = 0; return a; }      // per calling thread (one learner thread per GPU)
+int& last_path() { static thread_local int p = 0; return p; }
 xt_tuning& tuning() {
   static xt_tuning t = {/*bf16x6*/ 1, /*dgrad_all_classes*/ 1, /*dgrad_tile64*/ 1, /*dgrad_halo*/ 1, /*bwd_own_instance*/ 1,
                         /*bwd_fit_slots*/ 768, /*conv1_bf16x3*/ 1, /*conv1_flat*/ 1, /*conv1_waves*/ 8,

@@ -104,6 +104,10 @@ SIGNATURES = {
     "xt_layer_dgrad": (c_int32, [POINTER(ConvGeom), c_int32, _P, _P, _P, c_int32, _P, _P]),
     "xt_layer_bwd": (c_int32, [POINTER(ConvGeom), c_int32, _P, _P, _P, _P, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P,
                                POINTER(c_int32)]),
+    "xt_layer_fwd_ex": (c_int32, [POINTER(ConvGeom), POINTER(InputXform), c_int32, _P, _P, _P, _P, _P, _P, c_int32, _P, _P,
+                                  POINTER(c_int32), POINTER(c_int32)]),
+    "xt_layer_wgrad_slabs": (c_int32, [POINTER(ConvGeom), POINTER(InputXform), c_int32, _P, _P, _P, _P, _P, c_int32,
+                                       c_int32, _P, POINTER(c_int32)]),
     "xt_heads_fwd": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "xt_ppo_loss": (c_int32, [_P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float, c_float,
                               c_float, _P, _P, _P, _P]),
