@@ -186,6 +186,26 @@ int xt_gae_f64_ragged(const float* value_rows, const float* boot, const double* 
                       const int32_t* offsets, double* adv, double* target_value, int32_t n_traj, double gamma,
                       double lam, void* stream);
 
+/* v-trace of the non-opt IMPALA from action probabilities (xt/algorithm/impala/impala.py:139-167; appended under
+ * ABI 12), float64, one workgroup per fragment.  ROW layout: a fragment holds T + 1 observation rows and T
+ * transitions; every array here is indexed by observation row r = f*(T+1) + t, slot t = T of each fragment carries no
+ * transition (its inputs are not read), so that xt_keras_impala_loss gathers labels and observations through one idx.
+ *   policy    [n_frag*(T+1), A] f32   policy_is_logits 1: the forward's logits (float64 softmax taken here, max
+ *                                     subtracted); 0: probabilities, used as they are
+ *   value     [n_frag*(T+1)]    f32   V(s) of every row (slot T bootstraps the fragment)
+ *   onehot, behaviour [n_frag*(T+1), A] f32   taken action / behaviour policy's probabilities
+ *   reward    [n_frag*(T+1)]    f64   done [n_frag*(T+1)] u8
+ *     disc = done ? 0 : gamma;  rho = min(1, exp(log(pt + 1e-10) - log(pb + 1e-10))), pt/pb = sum_a p_a * onehot_a
+ *     acc_t = rho_t ((r_t + disc_t V_{t+1}) - V_t);  acc_j += (acc_{j+1} disc_{j+1}) rho_{j+1};  target_t = V_t + acc_t
+ *     pg_t = rho_t ((r_t + disc_t target_{t+1}) - V_t),  target_T := V_T
+ *   pg_adv, target [n_frag*(T+1)] f32: the float64 results rounded once; slot T: pg_adv = 0, target = V_T
+ *   debug (may be NULL) [3, n_frag*(T+1)] f64: rho, pg_adv, target before the rounding; slot T: 0, 0, V_T
+ * Everything after rho is rounded step by step in numpy's association: bit-for-bit numpy on the same rho.
+ * 1 <= T <= 1024, 1 <= A <= 64. */
+int xt_vtrace_probs_f64(const float* policy, int32_t policy_is_logits, const float* value, const float* onehot,
+                        const float* behaviour, const double* reward, const uint8_t* done, int32_t n_frag, int32_t T,
+                        int32_t A, double gamma, float* pg_adv, float* target, double* debug, void* stream);
+
 /* Zero-pad the innermost axis: src [rows, c_src] -> dst [rows, c_dst], elements of elem_bytes = 1 (uint8) or 4
  * (float32) bytes (ABI >= 9).  The reference's get_cnn_backbone (xt/model/model_utils.py:49-80) takes any channel
  * count (examples/ant_ppo.yaml:20: [84, 84, 3]); the layer kernels read 4-channel groups, so such observations enter
@@ -578,6 +598,34 @@ int xt_net_set_direct(xt_net* net, xt_direct_comm* comm);
 int xt_net_keras_impala_step(xt_net* net, const void* obs, const int32_t* idx, int32_t B, const float* adv,
                              const float* onehot, const float* target_v, float ent_coef, float* loss_out,
                              float* loss_acc, void* stream);
+
+/* One whole `IMPALA.train` of the non-opt algorithm in ONE call that never synchronises (appended under ABI 12):
+ *   1. forward over all n_frag*(T+1) resident observation rows (obs_row_bytes each) in chunks of at most the net's
+ *      max batch, logits / value into the caller's buffers;
+ *   2. xt_vtrace_probs_f64 (logits mode) -> pg_adv / target, row layout as documented there;
+ *   3. for every entry e of the HOST table, in order: xt_net_keras_impala_step on idx[e.off .. e.off + e.rows) with the
+ *      labels pg_adv / onehot / target, its loss accumulated into acc[2*e.chunk .. +2), then xt_adam_keras with e.lr_t.
+ * acc [2*n_chunks] f32 is zeroed first; the epoch loss of algorithm chunk c (one `model.fit`) is acc[2c] / acc[2c+1].
+ * idx holds observation ROWS (f*(T+1) + t, never a slot t = T).  seg_off / seg_size / table are host arrays.
+ * Categorical heads only; refused while a gradient exchange or the data-parallel tail is installed. */
+typedef struct xt_keras_fit_entry {
+  int32_t off, rows;            /* minibatch = idx[off .. off + rows), 1 <= rows <= 128                     */
+  int32_t chunk;                /* BATCH_SIZE chunk of the algorithm this minibatch belongs to               */
+  float lr_t;                   /* step size of xt_adam_keras for this update                               */
+} xt_keras_fit_entry;
+typedef struct xt_keras_train_cfg {
+  float ent_coef, clipnorm, beta1, beta2, eps;
+  double gamma;
+  int32_t n_seg;                /* tensors of the flat parameter buffer, as for xt_adam_keras               */
+  const int64_t* seg_off;
+  const int64_t* seg_size;
+  float* adam_scratch;          /* >= 16 * n_seg floats on the device                                       */
+} xt_keras_train_cfg;
+int xt_net_keras_impala_train(xt_net* net, const xt_keras_train_cfg* cfg, const void* obs, int64_t obs_row_bytes,
+                              int32_t n_frag, int32_t T, const float* onehot, const float* behaviour,
+                              const double* reward, const uint8_t* done, float* logits, float* value, float* pg_adv,
+                              float* target, const int32_t* idx, int32_t n_idx, const xt_keras_fit_entry* table,
+                              int32_t n_entries, int32_t n_chunks, float* acc, void* stream);
 
 typedef struct xt_impala_cfg {
   float lr, beta1, beta2, eps;

@@ -9,6 +9,10 @@ c[j], xt/model/impala/vtrace.py:94-96 -- the two are NOT the same recursion, SUR
 (state, pg_advantage) / (one-hot action, v-trace target) to ``Model.train`` in sequential BATCH_SIZE chunks.
 Everything is float64 on the host except what the model returns; the model (``ImpalaCnn`` / ``ImpalaMlp``) runs the
 forward and the update on the GPU.
+
+Opt-in (``alg_config: {DEVICE_VTRACE: true}``, default off) ``train`` hands the stacked fragments to the model's
+``train_fragments`` instead: forward, the same recursion as a float64 kernel (``xt_vtrace_probs_f64``, rho from a
+float64 softmax of the logits) and every fit minibatch in one device-resident pass.
 """
 import os
 
@@ -20,6 +24,7 @@ from xingtian_amd.algorithm.impala.default_config import BATCH_SIZE, GAMMA
 from xingtian_amd.register import Registers, import_config
 
 LOG_EPS = 1e-10
+DEVICE_MAX_T, DEVICE_MAX_A = 1024, 64     # limits of the device v-trace kernel (xt_vtrace_probs_f64)
 
 
 def chosen_logp(prob, onehot):
@@ -33,8 +38,18 @@ def vtrace_from_probs(target_prob, behaviour_prob, onehot, reward, done, value, 
     target_prob / behaviour_prob / onehot: [F, T, A]; reward / done: [F, T, 1]; value / value_next: [F, T, 1]
     (V(s_t) and V(s_{t+1})).  Returns (pg_advantage, vtrace_target), both [F, T, 1] float64.
     """
+    return vtrace_from_rho(rho_from_probs(target_prob, behaviour_prob, onehot), reward, done, value, value_next, gamma)
+
+
+def rho_from_probs(target_prob, behaviour_prob, onehot):
+    """Truncated importance weights min(1, pi(a|s) / mu(a|s)) of the taken actions, [F, T, 1]."""
+    return np.minimum(np.exp(chosen_logp(target_prob, onehot) - chosen_logp(behaviour_prob, onehot)), 1.0)[..., None]
+
+
+def vtrace_from_rho(rho, reward, done, value, value_next, gamma):
+    """The recursion of ``vtrace_from_probs`` on given importance weights ``rho`` [F, T, 1] (what the device kernel
+    ``xt_vtrace_probs_f64`` evaluates with the same roundings).  Returns (pg_advantage, vtrace_target)."""
     discount = np.logical_not(done) * gamma
-    rho = np.minimum(np.exp(chosen_logp(target_prob, onehot) - chosen_logp(behaviour_prob, onehot)), 1.0)[..., None]
     acc = rho * (reward + discount * value_next - value)          # per-step corrected TD errors
     for j in reversed(range(acc.shape[1] - 1)):                   # suffix accumulation, reference index convention
         acc[:, j] += acc[:, j + 1] * discount[:, j + 1] * rho[:, j + 1]
@@ -88,7 +103,19 @@ class IMPALA(Algorithm):
         flat = lambda x: x.reshape((-1,) + x.shape[2:])
         return flat(frag(states, s)[:, :-1]), flat(pg_adv), flat(target), flat(onehot_f)
 
+    def _device_train_ok(self):
+        """``DEVICE_VTRACE`` (default off): forward, v-trace and every fit minibatch in one device-resident pass
+        (``_KerasImpalaModel.train_fragments``), where the actor has it and the v-trace kernel holds the fragment."""
+        return (bool(self.alg_config.get("DEVICE_VTRACE", False)) and hasattr(self.actor, "train_fragments")
+                and self.episode_len <= DEVICE_MAX_T and self.action_dim <= DEVICE_MAX_A)
+
     def train(self, **kwargs):
+        if self._device_train_ok():
+            states, onehot, dones, behaviour, rewards = self._rollout.stacked()
+            loss = self.actor.train_fragments(states, onehot, behaviour, rewards, dones, self.episode_len, GAMMA,
+                                              BATCH_SIZE)
+            self._rollout.reset()
+            return loss
         states, pg_adv, target, onehot = self._train_proc()
         losses = []
         for lo in range(0, len(states), BATCH_SIZE):

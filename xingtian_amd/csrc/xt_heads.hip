@@ -1027,6 +1027,89 @@ __global__ __launch_bounds__(256) void gae_f64_ragged_kernel(const float* __rest
   }
 }
 
+// ---------------------------------------------------------------- v-trace of the non-opt IMPALA (float64)
+// Host v-trace of xt/algorithm/impala/impala.py:139-167 (NOT the recursion of vtrace.py), one workgroup per fragment.
+// Every per-transition array is indexed by OBSERVATION row f*(T+1)+t (slot t = T of a fragment carries no transition),
+// so that the fit's loss kernel gathers its labels through the same idx as the observations.
+//   disc = done ? 0 : gamma ;  rho = min(exp(log(pt + 1e-10) - log(pb + 1e-10)), 1)
+//   acc_t = rho_t*((r_t + disc_t*V_{t+1}) - V_t) ;  acc_j += (acc_{j+1}*disc_{j+1})*rho_{j+1}  (serial, newest first)
+//   target_t = V_t + acc_t ;  pg_t = rho_t*((r_t + disc_t*target_{t+1}) - V_t),  target_T := V_T
+// pt = sum_a p_a*onehot_a with p = the float64 softmax of the logits row (max subtracted) or the float32 probabilities
+// as they are; pb likewise from the behaviour probabilities.  Everything after rho carries explicit roundings (numpy's
+// association, no contraction): bit-for-bit numpy on the same rho.  Slot t = T: pg_adv = 0, target = V_T, rho = 0.
+constexpr int kVtraceMaxT = 1024, kVtraceMaxA = 64;
+__global__ __launch_bounds__(256) void vtrace_probs_f64_kernel(const float* __restrict__ policy, int is_logits,
+                                                               const float* __restrict__ value, const float* __restrict__ onehot,
+                                                               const float* __restrict__ behaviour,
+                                                               const double* __restrict__ reward, const uint8_t* __restrict__ done,
+                                                               int T, int A, double gamma, float* __restrict__ pg_adv,
+                                                               float* __restrict__ target, double* __restrict__ dbg,
+                                                               long long n_rows) {
+  __shared__ double s_a[kVtraceMaxT], s_rho[kVtraceMaxT], s_dc[kVtraceMaxT];   // acc ; rho ; discount
+  const int t = threadIdx.x;
+  const size_t r0 = (size_t)blockIdx.x * (T + 1);
+  const float* v = value + r0;
+  for (int j = t; j < T; j += 256) {
+    const float* pr = policy + (r0 + j) * A;
+    const float* oh = onehot + (r0 + j) * A;
+    const float* bh = behaviour + (r0 + j) * A;
+    double pt = 0.0, pb = 0.0;
+    if (is_logits) {
+      float mx = pr[0];
+      for (int a = 1; a < A; ++a) mx = fmaxf(mx, pr[a]);
+      double s = 0.0;
+      for (int a = 0; a < A; ++a) s = __dadd_rn(s, exp((double)pr[a] - (double)mx));
+      for (int a = 0; a < A; ++a) pt = __dadd_rn(pt, __dmul_rn(exp((double)pr[a] - (double)mx) / s, (double)oh[a]));
+    } else {
+      for (int a = 0; a < A; ++a) pt = __dadd_rn(pt, __dmul_rn((double)pr[a], (double)oh[a]));
+    }
+    for (int a = 0; a < A; ++a) pb = __dadd_rn(pb, __dmul_rn((double)bh[a], (double)oh[a]));
+    const double rho = fmin(exp(__dsub_rn(log(__dadd_rn(pt, 1e-10)), log(__dadd_rn(pb, 1e-10)))), 1.0);
+    const double disc = done[r0 + j] ? 0.0 : gamma;
+    const double vj = (double)v[j], vn = (double)v[j + 1];
+    s_a[j] = __dmul_rn(rho, __dsub_rn(__dadd_rn(reward[r0 + j], __dmul_rn(disc, vn)), vj));
+    s_rho[j] = rho;
+    s_dc[j] = disc;
+  }
+  __syncthreads();
+  if (t == 0) {
+    double carry = 0.0, cd = 0.0, cr = 0.0;          // acc, discount, rho of step j + 1
+    for (int j0 = T; j0 > 0; j0 -= 16) {             // steps j0-1 .. j0-16, newest first
+      double da[16], dd[16], dr[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int j = j0 - 1 - u;
+        const int jc = j >= 0 ? j : 0;
+        da[u] = s_a[jc]; dd[u] = s_dc[jc]; dr[u] = s_rho[jc];
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int j = j0 - 1 - u;
+        if (j >= 0) {
+          double a = da[u];
+          if (j < T - 1) a = __dadd_rn(da[u], __dmul_rn(__dmul_rn(carry, cd), cr));
+          s_a[j] = a;
+          carry = a; cd = dd[u]; cr = dr[u];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int j = t; j <= T; j += 256) {
+    const double vj = (double)v[j];
+    double rho = 0.0, pg = 0.0, tg = vj;
+    if (j < T) {
+      rho = s_rho[j];
+      tg = __dadd_rn(vj, s_a[j]);
+      const double tn = j + 1 < T ? __dadd_rn((double)v[j + 1], s_a[j + 1]) : (double)v[T];
+      pg = __dmul_rn(rho, __dsub_rn(__dadd_rn(reward[r0 + j], __dmul_rn(s_dc[j], tn)), vj));
+    }
+    pg_adv[r0 + j] = (float)pg;
+    target[r0 + j] = (float)tg;
+    if (dbg) { dbg[r0 + j] = rho; dbg[n_rows + r0 + j] = pg; dbg[2 * n_rows + r0 + j] = tg; }
+  }
+}
+
 // zero-pad the innermost axis of a [rows, c_src] array to [rows, c_dst] (elements of 1 or 4 bytes): image observations
 // whose channel count is not a multiple of 4 (examples/ant_ppo.yaml: [84, 84, 3]) enter the first layer as C = 4 with a
 // zero plane -- the weights' fourth input-channel rows see a zero operand, get a zero gradient and stay zero (exact).
@@ -1297,6 +1380,20 @@ int xt_gae_f64_ragged(const float* value_rows, const float* boot, const double* 
   XT_REQUIRE(value_rows && boot && reward && done && offsets && adv && target_value, "xt_gae_f64_ragged: null argument");
   hipLaunchKernelGGL(xt::gae_f64_ragged_kernel, dim3(n_traj), dim3(256), 0, xt::as_stream(stream), value_rows, boot, reward,
                      done, offsets, adv, target_value, gamma, lam);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+
+int xt_vtrace_probs_f64(const float* policy, int32_t policy_is_logits, const float* value, const float* onehot,
+                        const float* behaviour, const double* reward, const uint8_t* done, int32_t n_frag, int32_t T,
+                        int32_t A, double gamma, float* pg_adv, float* target, double* debug, void* stream) {
+  XT_REQUIRE(T >= 1 && T <= xt::kVtraceMaxT, "xt_vtrace_probs_f64: T=%d outside [1,%d]", T, xt::kVtraceMaxT);
+  XT_REQUIRE(A >= 1 && A <= xt::kVtraceMaxA, "xt_vtrace_probs_f64: A=%d outside [1,%d]", A, xt::kVtraceMaxA);
+  XT_REQUIRE(n_frag >= 1 && (long long)n_frag * (T + 1) * A < (1ll << 31), "xt_vtrace_probs_f64: bad fragment count %d", n_frag);
+  XT_REQUIRE(policy && value && onehot && behaviour && reward && done && pg_adv && target, "xt_vtrace_probs_f64: null argument");
+  hipLaunchKernelGGL(xt::vtrace_probs_f64_kernel, dim3(n_frag), dim3(256), 0, xt::as_stream(stream), policy,
+                     policy_is_logits ? 1 : 0, value, onehot, behaviour, reward, done, T, A, gamma, pg_adv, target, debug,
+                     (long long)n_frag * (T + 1));
   XT_LAUNCH_CHECK();
   return 0;
 }

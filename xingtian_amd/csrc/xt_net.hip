@@ -1538,6 +1538,51 @@ int xt_net_keras_impala_step(xt_net* n, const void* obs, const int32_t* idx, int
   return xt::grads_finish(n, B, nullptr, st);
 }
 
+int xt_net_keras_impala_train(xt_net* n, const xt_keras_train_cfg* c, const void* obs, int64_t obs_row_bytes,
+                              int32_t n_frag, int32_t T, const float* onehot, const float* behaviour,
+                              const double* reward, const uint8_t* done, float* logits, float* value, float* pg_adv,
+                              float* target, const int32_t* idx, int32_t n_idx, const xt_keras_fit_entry* table,
+                              int32_t n_entries, int32_t n_chunks, float* acc, void* stream) {
+  XT_REQUIRE(n && c && obs && onehot && behaviour && reward && done && logits && value && pg_adv && target && idx && table && acc,
+             "xt_net_keras_impala_train: null argument");
+  XT_REQUIRE(n->params && n->ws && n->m && n->v, "xt_net_keras_impala_train: buffers not bound");
+  XT_REQUIRE(n->action_type == XT_ACTION_CATEGORICAL, "xt_net_keras_impala_train: categorical heads only");
+  XT_REQUIRE(!n->xchg && n->dp_world == 0 && !n->direct,
+             "xt_net_keras_impala_train: no data parallelism (a gradient exchange / data-parallel tail is installed)");
+  XT_REQUIRE(n_frag >= 1 && T >= 1 && T <= 1024 && n->A <= 64 && obs_row_bytes > 0,
+             "xt_net_keras_impala_train: bad sizes (fragments=%d T=%d A=%d)", n_frag, T, n->A);
+  const long long rows = (long long)n_frag * (T + 1);
+  XT_REQUIRE(rows * n->A < (1ll << 31), "xt_net_keras_impala_train: %lld rows are too many", rows);
+  XT_REQUIRE(n_entries >= 1 && n_chunks >= 1 && n_idx >= 1 && n_idx <= (long long)n_frag * T,
+             "xt_net_keras_impala_train: bad table (entries=%d chunks=%d idx=%d)", n_entries, n_chunks, n_idx);
+  for (int e = 0; e < n_entries; ++e)
+    XT_REQUIRE(table[e].rows >= 1 && table[e].rows <= 128 && table[e].rows <= n->maxB && table[e].off >= 0 &&
+                   (long long)table[e].off + table[e].rows <= n_idx && table[e].chunk >= 0 && table[e].chunk < n_chunks,
+               "xt_net_keras_impala_train: bad table entry %d (off=%d rows=%d chunk=%d)", e, table[e].off, table[e].rows,
+               table[e].chunk);
+  hipStream_t st = xt::as_stream(stream);
+  for (long long s = 0; s < rows; s += n->maxB) {         // chunk boundaries need not fall on fragment boundaries
+    const int B = (int)(rows - s < n->maxB ? rows - s : n->maxB);
+    if (int rc = xt::net_forward(n, static_cast<const char*>(obs) + s * obs_row_bytes, nullptr, B, true, st)) return rc;
+    XT_CHECK_HIP(hipMemcpyAsync(logits + s * n->A, n->ws + n->off_logits, sizeof(float) * B * n->A, hipMemcpyDeviceToDevice, st));
+    XT_CHECK_HIP(hipMemcpyAsync(value + s, n->ws + n->off_value, sizeof(float) * B, hipMemcpyDeviceToDevice, st));
+  }
+  if (int rc = xt_vtrace_probs_f64(logits, 1, value, onehot, behaviour, reward, done, n_frag, T, n->A, c->gamma, pg_adv,
+                                   target, nullptr, stream))
+    return rc;
+  XT_CHECK_HIP(hipMemsetAsync(acc, 0, sizeof(float) * 2 * n_chunks, st));
+  for (int e = 0; e < n_entries; ++e) {
+    const xt_keras_fit_entry& t = table[e];
+    if (int rc = xt_net_keras_impala_step(n, obs, idx + t.off, t.rows, pg_adv, onehot, target, c->ent_coef, nullptr,
+                                          acc + 2 * t.chunk, stream))
+      return rc;
+    if (int rc = xt_adam_keras(n->params, n->grads, n->m, n->v, c->n_seg, c->seg_off, c->seg_size, c->clipnorm, t.lr_t,
+                               c->beta1, c->beta2, c->eps, c->adam_scratch, stream))
+      return rc;
+  }
+  return 0;
+}
+
 int xt_net_set_grad_exchange_ex(xt_net* net, xt_grad_exchange_fn fn, void* user, int32_t flags) {
   XT_REQUIRE(net, "xt_net_set_grad_exchange: null net");
   XT_REQUIRE((flags & ~XT_XCHG_OVERLAP) == 0, "xt_net_set_grad_exchange_ex: unknown flags 0x%x", flags);

@@ -73,6 +73,18 @@ class TrainIO(ctypes.Structure):
                 ("wait_dma_ticket", ctypes.c_uint64)]
 
 
+class KerasFitEntry(Structure):
+    """xt_keras_fit_entry of include/xt_mi355x.h: one ``model.fit`` minibatch of xt_net_keras_impala_train"""
+    _fields_ = [("off", c_int32), ("rows", c_int32), ("chunk", c_int32), ("lr_t", c_float)]
+
+
+class KerasTrainCfg(Structure):
+    """xt_keras_train_cfg of include/xt_mi355x.h"""
+    _fields_ = [("ent_coef", c_float), ("clipnorm", c_float), ("beta1", c_float), ("beta2", c_float), ("eps", c_float),
+                ("gamma", c_double), ("n_seg", c_int32), ("seg_off", c_void_p), ("seg_size", c_void_p),
+                ("adam_scratch", c_void_p)]
+
+
 OPT_TYPE = {"adam": 0, "rmsprop": 1}
 XCHG_OVERLAP = 1         # XT_XCHG_OVERLAP
 DIRECT_HANDLE_BYTES = 64  # XT_DIRECT_HANDLE_BYTES
@@ -162,6 +174,9 @@ SIGNATURES = {
     "xt_net_io_seq": (ctypes.c_uint32, [_P]),
     "xt_net_io_loss_ready": (c_int32, [_P]),
     "xt_net_io_publish_wait": (c_int32, [_P, ctypes.c_uint32, c_int32]),
+    "xt_vtrace_probs_f64": (c_int32, [_P, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P]),
+    "xt_net_keras_impala_train": (c_int32, [_P, POINTER(KerasTrainCfg), _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P,
+                                            _P, _P, _P, _P, c_int32, POINTER(KerasFitEntry), c_int32, c_int32, _P, _P]),
 }
 
 

@@ -14,6 +14,27 @@ from xingtian_amd import lib as L
 from xingtian_amd.model.cpu_net import initial_weights
 
 
+def keras_lr_t(lr, iterations, decay=0.0, beta1=0.9, beta2=0.999):
+    """Step size of tf.keras Adam's update number ``iterations + 1``: the time-decayed learning rate times the bias
+    correction, in float32 as the optimizer's graph computes it (what ``xt_adam_keras`` takes as ``lr_t``)."""
+    t = iterations + 1
+    lr_t = np.float32(lr) / (np.float32(1.0) + np.float32(decay) * np.float32(iterations))
+    return lr_t * np.sqrt(np.float32(1.0) - np.float32(beta2) ** t) / (np.float32(1.0) - np.float32(beta1) ** t)
+
+
+def keras_fit_table(n_rows, batch_size, fit_batch, iterations, lr, decay):
+    """The minibatches of one ``IMPALA.train`` over ``n_rows`` transitions, in execution order: the algorithm calls
+    ``model.fit`` once per sequential ``batch_size`` chunk, a fit walks its chunk in minibatches of ``fit_batch`` and
+    every minibatch is one Adam update.  -> [(offset into the concatenated per-chunk orders, rows, chunk number,
+    lr_t)], ``lr_t`` = ``keras_lr_t`` at ``iterations`` + the number of updates before this one."""
+    table = []
+    for chunk, lo in enumerate(range(0, n_rows, batch_size)):
+        n = min(batch_size, n_rows - lo)
+        for m in range(0, n, fit_batch):
+            table.append((lo + m, min(fit_batch, n - m), chunk, float(keras_lr_t(lr, iterations + len(table), decay))))
+    return table
+
+
 class _MailboxDone(object):
     """see ``HipActorCritic.io_publish_done``"""
     __slots__ = ("net", "seq")
@@ -600,6 +621,16 @@ class HipActorCritic(object):
     def adam_keras(self, lr, iterations, clipnorm=0.0, decay=0.0, beta1=0.9, beta2=0.999, eps=1e-7):
         """tf.keras Adam on the flat buffers: per-TENSOR clip_by_norm (kernel and bias are separate tensors), time-decayed
         learning rate; ``iterations`` = number of updates applied so far."""
+        offs, sizes, n = self._keras_segments()
+        lr_t = keras_lr_t(lr, iterations, decay, beta1, beta2)
+        self.touch()
+        L.check(self.lib.xt_adam_keras(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.adam_m), L.ptr(self.adam_v), n,
+                                       offs.data_ptr(), sizes.data_ptr(), float(clipnorm), float(lr_t), beta1, beta2,
+                                       eps, L.ptr(self._keras_scratch), L.stream_ptr()), "xt_adam_keras")
+
+    def _keras_segments(self):
+        """(offsets, sizes, count) of the parameter TENSORS in the flat buffer (host int64 tensors) for ``xt_adam_keras``'s
+        per-tensor clip; allocates its device scratch on first use."""
         if not hasattr(self, "_keras_segs"):
             offs, sizes = [], []
             for name in self.spec.names:      # (a channel-padded kernel: its storage block; the padding is zero)
@@ -609,14 +640,42 @@ class HipActorCritic(object):
             dev = self.device
             self._keras_segs = (torch.tensor(offs, dtype=torch.int64), torch.tensor(sizes, dtype=torch.int64), len(offs))
             self._keras_scratch = torch.zeros((16 * len(offs),), dtype=torch.float32, device=dev)
-        offs, sizes, n = self._keras_segs
-        t = iterations + 1
-        lr_t = np.float32(lr) / (np.float32(1.0) + np.float32(decay) * np.float32(iterations))
-        lr_t = lr_t * np.sqrt(np.float32(1.0) - np.float32(beta2) ** t) / (np.float32(1.0) - np.float32(beta1) ** t)
+        return self._keras_segs
+
+    def keras_impala_train(self, obs, n_frag, t, onehot, behaviour, reward, done, idx, table, gamma, ent_coef,
+                           clipnorm=0.0, beta1=0.9, beta2=0.999, eps=1e-7):
+        """One whole train of the non-opt IMPALA in one C call that never synchronises (C ABI
+        ``xt_net_keras_impala_train``): forward over the ``n_frag * (t + 1)`` resident observation rows, the float64
+        v-trace kernel, then every minibatch of ``table`` (``keras_fit_table``) with its own Adam step.  All per-transition
+        device arrays are in observation-ROW layout (row ``f * (t + 1) + s``, slot ``s = t`` unused); ``idx`` (int32,
+        device) holds observation rows.  -> dict of the device buffers it filled: ``logits`` / ``value`` / ``pg_adv`` /
+        ``target`` [rows] and ``acc`` [chunks, 2] (epoch loss of chunk c = acc[c, 0] / acc[c, 1])."""
+        rows, a = int(n_frag) * (int(t) + 1), self.spec.action_dim
+        want = {"obs": (obs, rows, None), "onehot": (onehot, rows * a, torch.float32),
+                "behaviour": (behaviour, rows * a, torch.float32), "reward": (reward, rows, torch.float64),
+                "done": (done, rows, torch.uint8), "idx": (idx, None, torch.int32)}
+        for name, (x, numel, dtype) in want.items():
+            ok = x.is_cuda and x.is_contiguous() and (dtype is None or x.dtype == dtype)
+            ok = ok and (numel is None or (x.shape[0] == rows if name == "obs" else x.numel() == numel))
+            if not ok:
+                raise ValueError("keras_impala_train: {} must be a contiguous device tensor in row layout "
+                                 "({} rows)".format(name, rows))
+        if not table or any(off < 0 or off + n > idx.numel() for off, n, _, _ in table):
+            raise ValueError("keras_impala_train: the minibatch table does not fit idx ({} entries)".format(idx.numel()))
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        n_chunks = max(e[2] for e in table) + 1
+        out = dict(logits=new(rows, a), value=new(rows), pg_adv=new(rows), target=new(rows), acc=new(n_chunks, 2))
+        offs, sizes, n_seg = self._keras_segments()
+        cfg = L.KerasTrainCfg(float(ent_coef), float(clipnorm), beta1, beta2, eps, float(gamma), n_seg, offs.data_ptr(),
+                              sizes.data_ptr(), self._keras_scratch.data_ptr())
+        tab = (L.KerasFitEntry * len(table))(*table)
         self.touch()
-        L.check(self.lib.xt_adam_keras(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.adam_m), L.ptr(self.adam_v), n,
-                                       offs.data_ptr(), sizes.data_ptr(), float(clipnorm), float(lr_t), beta1, beta2,
-                                       eps, L.ptr(self._keras_scratch), L.stream_ptr()), "xt_adam_keras")
+        L.check(self.lib.xt_net_keras_impala_train(
+            self.handle, ctypes.byref(cfg), L.ptr(obs), obs[0].numel() * obs.element_size(), int(n_frag), int(t),
+            L.ptr(onehot), L.ptr(behaviour), L.ptr(reward), L.ptr(done), L.ptr(out["logits"]), L.ptr(out["value"]),
+            L.ptr(out["pg_adv"]), L.ptr(out["target"]), L.ptr(idx), int(idx.numel()), tab, len(table), n_chunks,
+            L.ptr(out["acc"]), L.stream_ptr()), "xt_net_keras_impala_train")
+        return out
 
     def apply(self, lr, clip_norm, grad_scale=1.0):
         self.touch()
