@@ -847,6 +847,33 @@ int xt_layer_wgrad_slabs(const xt_conv_geom* g, const xt_input_xform* xf, int32_
                          const float* dy, float* dwb, float* slabs, int32_t slab_cap, int32_t msplit, void* stream,
                          int32_t* path_out);
 
+/* Model.predict on the device (appended; the ABI version stays): the trunk, then ONE head launch that leaves logits and
+ * value exactly as xt_net_forward does (bit for bit) and adds the sampled action and its log-probability.
+ *   Categorical   action = first argmax_a (logits[a] + g[a]) in float32, g = injected noise or -log(-log(u));
+ *                 logp = log_softmax(logits)[action] by the expressions and summation order of xt_ppo_loss
+ *   DiagGaussian  action[a] = mean[a] + exp(pi_logstd[a]) * eps[a], eps = injected noise or Box-Muller;
+ *                 logp = the log-density of the stored action by the expressions of xt_ppo_loss_gauss
+ * so a loss kernel fed these outputs on unchanged weights computes ratio == 1 exactly.
+ * Generator: Philox4x32-10, key = (seed low, seed high), counter = (row0 + b, j, call low, call high), word w ->
+ * u = (float(w >> 9) + 0.5) * 2^-23 in [2^-24, 1 - 2^-24].  Categorical: action a draws word a & 3 of block j = a >> 2;
+ * DiagGaussian: dimension a draws words 2(a & 1) and 2(a & 1) + 1 of block j = a >> 1 as u1, u2 and
+ * eps = sqrt(-2 log u1) * cos(2 pi u2).  A row's draw depends on (seed, call, row0 + b, a) only.  action_dim <= 64. */
+typedef struct xt_act_cfg {
+  uint64_t seed, call;   /* the generator's key; the caller's running predict count                       */
+  int64_t row0;          /* index of this call's first row in the whole predict batch (chunked callers)   */
+  int32_t want_noise;    /* != 0: noise_out receives the noise each action was drawn with                 */
+} xt_act_cfg;
+int xt_net_act(xt_net* net, const xt_act_cfg* cfg, const void* obs, const int32_t* idx, int32_t B,
+               const float* noise /* [B,A] or NULL */, void* action /* int32 [B] | float32 [B,A], see XT_ACTION_* */,
+               float* logp /* [B] */, float* value /* [B] */, float* logits /* [B,A] */,
+               float* noise_out /* [B,A]; NULL unless cfg->want_noise */, void* stream);
+/* the head launch of xt_net_act alone, on given features and head weights like xt_heads_fwd (kernel tests);
+ * log_std: pi_logstd [A] for DiagGaussian, NULL for Categorical */
+int xt_act_heads(const float* f_pi, const float* f_v, int32_t B, int32_t F, int32_t A, const float* wpi,
+                 const float* bpi, const float* wv, const float* bv, const float* log_std, const xt_act_cfg* cfg,
+                 const float* noise, void* action, float* logp, float* value, float* logits, float* noise_out,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

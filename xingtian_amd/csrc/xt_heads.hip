@@ -1158,7 +1158,138 @@ int launch_act_apply(const float* z, float* y, long long count, int act, hipStre
 }
 }  // namespace xt
 
+namespace xt {
+// ---------------------------------------------------------------- acting heads (Model.predict on the device)
+// Philox4x32-10 (Salmon et al., SC'11), the standard constants.  Counter-based: a row's draw depends on
+// (seed, call, global row, action) only -- not on the chunking of the batch, the grid shape or the call history.
+struct Philox4 { uint32_t x, y, z, w; };
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                 uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return Philox4{c0, c1, c2, c3};
+}
+// word -> uniform in [2^-24, 1 - 2^-24]: every step is exact in fp32, so neither logarithm below sees 0 or 1
+__device__ __forceinline__ float philox_uniform(uint32_t w) { return ((float)(w >> 9) + 0.5f) * 0x1p-23f; }
+
+// Runs behind the trunk instead of heads_fwd_kernel: logits and value by heads_fwd_kernel's arithmetic (bit for bit),
+// then the action, its log-probability and the noise it was drawn with.  One wave per sample, four per block, lane a <->
+// action a (A <= 64).  Categorical: Gumbel-max, ties to the lowest index, and log-softmax by ppo_loss_kernel's
+// expressions in its order; DiagGaussian (log_std != null): ppo_loss_gauss_kernel's log-density of the action as it is
+// stored -- so the loss kernel, fed this launch's outputs on unchanged weights, recomputes the same logp to the bit.
+__global__ __launch_bounds__(256) void act_heads_kernel(const ActHeadArgs p) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= p.B) return;
+  const int F = p.F, A = p.A;
+  const bool la = lane < A;
+  const float* fp = p.f_pi + (size_t)b * F;
+  const float* fv = p.f_v + (size_t)b * F;
+  float mine = 0.f;                                   // lane a: logit a (DiagGaussian: mean a)
+  for (int a = 0; a < A; ++a) {
+    float s = 0.f;
+    for (int f = lane; f < F; f += 64) s = fmaf(fp[f], p.wpi[(size_t)f * A + a], s);
+    s = wave_sum(s);
+    if (lane == a) mine = s + p.bpi[a];
+  }
+  float sv = 0.f;
+  for (int f = lane; f < F; f += 64) sv = fmaf(fv[f], p.wv[f], sv);
+  const float v = wave_sum(sv) + p.bv[0];
+
+  const size_t e = (size_t)b * A + lane;              // this lane's element of the [B,A] arrays (lane < A only)
+  const uint32_t row = (uint32_t)(p.row0 + b);        // index in the whole predict batch
+  float noise = 0.f;
+  if (p.noise) {
+    if (la) noise = p.noise[e];
+  } else if (p.log_std) {
+    // Box-Muller: dimension a takes words 2(a&1), 2(a&1)+1 of block a >> 1
+    const Philox4 r = philox4x32_10(row, (uint32_t)(lane >> 1), p.call_lo, p.call_hi, p.seed_lo, p.seed_hi);
+    const float u1 = philox_uniform((lane & 1) ? r.z : r.x), u2 = philox_uniform((lane & 1) ? r.w : r.y);
+    noise = sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+  } else {
+    // Gumbel: action a takes word a & 3 of block a >> 2
+    const Philox4 r = philox4x32_10(row, (uint32_t)(lane >> 2), p.call_lo, p.call_hi, p.seed_lo, p.seed_hi);
+    const int q = lane & 3;
+    const float u = philox_uniform(q == 0 ? r.x : q == 1 ? r.y : q == 2 ? r.z : r.w);
+    noise = -logf(-logf(u));
+  }
+
+  float logp;
+  if (p.log_std) {
+    const float ls = la ? p.log_std[lane] : 0.f;
+    const float x = mine + expf(ls) * noise;
+    const float z = (x - mine) / expf(ls);
+    float ssq = 0.f, sls = 0.f;
+    for (int a = 0; a < A; ++a) {
+      const float za = __shfl(z, a, 64);
+      ssq += za * za;
+      sls += __shfl(ls, a, 64);
+    }
+    logp = -(0.9189385332046727f * (float)A + 0.5f * ssq + sls);
+    if (la) static_cast<float*>(p.action)[e] = x;
+  } else {
+    float mx = __shfl(mine, 0, 64);
+    for (int a = 1; a < A; ++a) mx = fmaxf(mx, __shfl(mine, a, 64));
+    float z = 0.f;
+    for (int a = 0; a < A; ++a) z += expf(__shfl(mine, a, 64) - mx);
+    const float logz = logf(z);
+    // first maximum of logit + noise, as numpy's argmax finds it (a NaN counts as the maximum)
+    const float score = mine + noise;
+    int act = 0;
+    float best = __shfl(score, 0, 64);
+    for (int a = 1; a < A; ++a) {
+      const float sa = __shfl(score, a, 64);
+      if (sa > best || (sa != sa && best == best)) { best = sa; act = a; }
+    }
+    logp = (__shfl(mine, act, 64) - mx) - logz;
+    if (lane == 0) static_cast<int32_t*>(p.action)[b] = act;
+  }
+  if (lane == 0) {
+    p.logp[b] = logp;
+    p.ws_value[b] = v;
+    if (p.value) p.value[b] = v;
+  }
+  if (la) {
+    p.ws_logits[e] = mine;
+    if (p.logits) p.logits[e] = mine;
+    if (p.noise_out) p.noise_out[e] = noise;
+  }
+}
+
+int launch_act_heads(const ActHeadArgs& a, hipStream_t st) {
+  XT_REQUIRE(a.B > 0 && a.F > 0 && a.A > 0, "act_heads: bad sizes");
+  XT_REQUIRE(a.A <= 64, "act_heads: A = %d exceeds 64 (one lane of the sample's wave per action)", a.A);
+  XT_REQUIRE(a.f_pi && a.f_v && a.wpi && a.bpi && a.wv && a.bv && a.action && a.logp && a.ws_logits && a.ws_value,
+             "act_heads: null argument");
+  hipLaunchKernelGGL(act_heads_kernel, dim3((a.B + 3) / 4), dim3(256), 0, st, a);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+}  // namespace xt
+
 extern "C" {
+
+int xt_act_heads(const float* f_pi, const float* f_v, int32_t B, int32_t F, int32_t A, const float* wpi,
+                 const float* bpi, const float* wv, const float* bv, const float* log_std, const xt_act_cfg* cfg,
+                 const float* noise, void* action, float* logp, float* value, float* logits, float* noise_out,
+                 void* stream) {
+  XT_REQUIRE(cfg && value && logits, "xt_act_heads: null argument");
+  XT_REQUIRE(!cfg->want_noise == !noise_out, "xt_act_heads: noise_out goes with cfg->want_noise");
+  xt::ActHeadArgs a;
+  a.f_pi = f_pi; a.f_v = f_v; a.B = B; a.F = F; a.A = A;
+  a.wpi = wpi; a.bpi = bpi; a.wv = wv; a.bv = bv; a.log_std = log_std; a.noise = noise;
+  a.seed_lo = (uint32_t)cfg->seed; a.seed_hi = (uint32_t)(cfg->seed >> 32);
+  a.call_lo = (uint32_t)cfg->call; a.call_hi = (uint32_t)(cfg->call >> 32);
+  a.row0 = cfg->row0;
+  a.ws_logits = logits; a.ws_value = value; a.action = action; a.logp = logp;
+  a.value = nullptr; a.logits = nullptr; a.noise_out = noise_out;
+  return xt::launch_act_heads(a, xt::as_stream(stream));
+}
 
 int xt_heads_fwd(const float* f_pi, const float* f_v, int32_t B, int32_t F, int32_t A, const float* wpi,
                  const float* bpi, const float* wv, const float* bv, float* logits, float* value, void* stream) {

@@ -95,6 +95,21 @@ int launch_ppo_loss_gauss(const float* mean, const float* log_std, const float* 
                           const double* target_v, float clip_ratio, float ent_coef, float vf_clip, float critic_coef,
                           float inv_b, float* dmean, float* dvalue, float* dls_rows, int ldls, float* terms,
                           hipStream_t st);
+// The acting heads (act_heads_kernel): heads forward + sampled action + its log-probability, one launch behind the trunk.
+struct ActHeadArgs {
+  const float *f_pi = nullptr, *f_v = nullptr;
+  int B = 0, F = 0, A = 0;
+  const float *wpi = nullptr, *bpi = nullptr, *wv = nullptr, *bv = nullptr;
+  const float* log_std = nullptr;      // pi_logstd [A]: DiagGaussian; null: Categorical
+  const float* noise = nullptr;        // injected noise [B,A] (Gumbel / standard normal), null: drawn from the generator
+  uint32_t seed_lo = 0, seed_hi = 0, call_lo = 0, call_hi = 0;   // Philox key / counter words 2, 3
+  long long row0 = 0;                  // global row of sample 0 (counter word 0 = row0 + b)
+  float *ws_logits = nullptr, *ws_value = nullptr;               // the workspace copies ([B,A], [B])
+  void* action = nullptr;              // int32 [B] | float32 [B,A]
+  float* logp = nullptr;               // [B]
+  float *value = nullptr, *logits = nullptr, *noise_out = nullptr;   // [B], [B,A], [B,A]; each may be null
+};
+int launch_act_heads(const ActHeadArgs& a, hipStream_t st);
 int launch_heads_dfeat(const float* f_pi, const float* f_v, int B, int F, int A, const float* wpi, const float* wv,
                        const float* dlogits, const float* dvalue, int act_prev, float* df_pi, float* df_v,
                        hipStream_t st);

@@ -967,6 +967,32 @@ int xt_net_forward(xt_net* n, const void* obs, const int32_t* idx, int32_t B, fl
   return 0;
 }
 
+int xt_net_act(xt_net* n, const xt_act_cfg* cfg, const void* obs, const int32_t* idx, int32_t B, const float* noise,
+               void* action, float* logp, float* value, float* logits, float* noise_out, void* stream) {
+  XT_REQUIRE(n && n->params && n->ws, "xt_net_act: buffers not bound");
+  XT_REQUIRE(cfg && obs && action && logp, "xt_net_act: null argument");
+  XT_REQUIRE(B > 0 && B <= n->maxB, "xt_net_act: batch %d outside (0,%d]", B, n->maxB);
+  XT_REQUIRE(n->A <= 64, "xt_net_act: A = %d exceeds 64 (one lane of the sample's wave per action)", n->A);
+  XT_REQUIRE(!cfg->want_noise == !noise_out, "xt_net_act: noise_out goes with cfg->want_noise");
+  hipStream_t st = xt::as_stream(stream);
+  if (int rc = xt::net_forward(n, obs, idx, B, false, st)) return rc;
+  xt::ActHeadArgs a;
+  const int F = n->feat;
+  a.f_pi = n->ws + n->layers[n->t_end[0] - 1].act_off;
+  a.f_v = n->ws + n->layers[n->t_end[n->n_trunks - 1] - 1].act_off;
+  a.B = B; a.F = F; a.A = n->A;
+  a.wpi = n->params + n->pi_off; a.bpi = n->params + n->pi_off + (int64_t)F * n->A;
+  a.wv = n->params + n->v_off; a.bv = n->params + n->v_off + F;
+  a.log_std = n->action_type == XT_ACTION_DIAG_GAUSSIAN ? n->params + n->logstd_off : nullptr;
+  a.noise = noise;
+  a.seed_lo = (uint32_t)cfg->seed; a.seed_hi = (uint32_t)(cfg->seed >> 32);
+  a.call_lo = (uint32_t)cfg->call; a.call_hi = (uint32_t)(cfg->call >> 32);
+  a.row0 = cfg->row0;
+  a.ws_logits = n->ws + n->off_logits; a.ws_value = n->ws + n->off_value;
+  a.action = action; a.logp = logp; a.value = value; a.logits = logits; a.noise_out = noise_out;
+  return xt::launch_act_heads(a, st);
+}
+
 int xt_net_ppo_step(xt_net* net, const xt_ppo_cfg* cfg, const void* obs, const int32_t* idx, int32_t B,
                     const void* action, const float* old_logp, const double* adv, const float* old_v,
                     const double* target_v, int32_t apply, float* loss_out, float* loss_acc, void* stream) {

@@ -85,6 +85,11 @@ class KerasTrainCfg(Structure):
                 ("adam_scratch", c_void_p)]
 
 
+class ActCfg(Structure):
+    """xt_act_cfg of include/xt_mi355x.h: the generator's key and counter words of one ``xt_net_act`` call"""
+    _fields_ = [("seed", ctypes.c_uint64), ("call", ctypes.c_uint64), ("row0", c_int64), ("want_noise", c_int32)]
+
+
 OPT_TYPE = {"adam": 0, "rmsprop": 1}
 XCHG_OVERLAP = 1         # XT_XCHG_OVERLAP
 DIRECT_HANDLE_BYTES = 64  # XT_DIRECT_HANDLE_BYTES
@@ -177,6 +182,9 @@ SIGNATURES = {
     "xt_vtrace_probs_f64": (c_int32, [_P, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P]),
     "xt_net_keras_impala_train": (c_int32, [_P, POINTER(KerasTrainCfg), _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P,
                                             _P, _P, _P, _P, c_int32, POINTER(KerasFitEntry), c_int32, c_int32, _P, _P]),
+    "xt_net_act": (c_int32, [_P, POINTER(ActCfg), _P, _P, c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "xt_act_heads": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, POINTER(ActCfg), _P, _P, _P, _P, _P,
+                               _P, _P]),
 }
 
 

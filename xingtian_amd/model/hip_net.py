@@ -379,6 +379,60 @@ class HipActorCritic(object):
                                             L.ptr(value[s:e]), L.stream_ptr()), "xt_net_forward")
         return logits, value
 
+    ACT_MAX_ACTIONS = 64        # xt_net_act: one lane of the sample's wave per action
+
+    def act(self, obs, seed, call, noise=None, want_noise=False):
+        """``Model.predict`` on the device (C ABI ``xt_net_act``): obs [B, ...] -> dict of host arrays ``action`` (int32 [B] |
+        float32 [B,A]), ``logp`` [B,1], ``value`` [B,1], ``logits`` [B,A] and -- ``want_noise`` -- ``noise`` [B,A], the Gumbel
+        / standard-normal noise every action was drawn with.  ``noise`` [B,A] injects it instead of drawing from the
+        counter-based generator keyed by (``seed``, ``call``, row, action).  All results land in ONE device block and reach
+        the host by one copy into one pinned block and one synchronisation, however many ``max_batch`` chunks the batch
+        takes.  The arrays are views of a private copy of that block."""
+        x = self.to_device_obs(obs)
+        b, a = int(x.shape[0]), self.spec.action_dim
+        gauss = self._desc.action_type == L.ACTION_TYPE["DiagGaussian"]
+        na = a if gauss else 1
+        want_noise = bool(want_noise)
+        blocks = getattr(self, "_act_blocks", None)
+        if blocks is None:
+            blocks = self._act_blocks = {}
+        blk = blocks.get((b, a, want_noise))
+        if blk is None:
+            if len(blocks) >= 16:       # (a caller whose batch size keeps changing: do not hoard pinned memory)
+                blocks.clear()
+            # float32 words: action [b*na] | logp [b] | value [b] | logits [b*a] | noise [b*a]
+            offs = np.cumsum([0, b * na, b, b, b * a, b * a if want_noise else 0])
+            dev = torch.empty(int(offs[-1]), dtype=torch.float32, device=self.device)
+            pin = torch.empty(int(offs[-1]), dtype=torch.float32, pin_memory=True)
+            blk = blocks[(b, a, want_noise)] = dict(dev=dev, pin=pin, np=pin.numpy(), offs=[int(o) for o in offs],
+                                                    base=dev.data_ptr(), cfg=L.ActCfg())
+        noise_dev = None
+        if noise is not None:
+            noise_dev = torch.as_tensor(np.ascontiguousarray(noise, dtype=np.float32)).to(self.device).reshape(b, a)
+        o_act, o_logp, o_val, o_lg, o_nz = blk["offs"][:5]
+        cfg, base = blk["cfg"], blk["base"]
+        cfg.seed, cfg.call = int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFFFFFFFFFF
+        cfg.want_noise = 1 if want_noise else 0
+        st = L.stream_ptr()
+        for s in range(0, b, self.max_batch):
+            e = min(b, s + self.max_batch)
+            cfg.row0 = s
+            L.check(self.lib.xt_net_act(
+                self.handle, ctypes.byref(cfg), L.ptr(x[s:e]), None, e - s,
+                L.ptr(noise_dev[s:e]) if noise_dev is not None else None, base + 4 * (o_act + s * na),
+                base + 4 * (o_logp + s), base + 4 * (o_val + s), base + 4 * (o_lg + s * a),
+                base + 4 * (o_nz + s * a) if want_noise else None, st), "xt_net_act")
+        cur = L.current_stream(self.device)
+        L.memcpy_async(blk["pin"].data_ptr(), base, blk["pin"].numel() * 4, L.D2H, cur)
+        cur.synchronize()
+        host = blk["np"].copy()
+        action = host[o_act:o_logp].reshape(b, a) if gauss else host[o_act:o_logp].view(np.int32)
+        out = dict(action=action, logp=host[o_logp:o_val].reshape(b, 1), value=host[o_val:o_lg].reshape(b, 1),
+                   logits=host[o_lg:o_nz].reshape(b, a))
+        if want_noise:
+            out["noise"] = host[o_nz:].reshape(b, a)
+        return out
+
     def set_dp(self, rank, world, loss_scale=1.0):
         """C ABI ``xt_net_set_dp``: switch the data-parallel tail on (``world`` >= 1: rows + loss shares of every rank travel
         behind the gradient in the same exchange, the optimiser adds the GLOBAL loss to ``loss_acc``) or off (``world`` = 0)"""

@@ -11,7 +11,7 @@ import torch
 
 from xingtian_amd.model import netspec
 from xingtian_amd.model.impala.default_config import GAMMA, LR  # noqa: F401
-from xingtian_amd.model.model import XTModel, as_numpy, build_net
+from xingtian_amd.model.model import XTModel, as_numpy, build_net, device_acting
 from xingtian_amd.register import Registers, import_config
 
 
@@ -81,6 +81,8 @@ class ImpalaCnnOpt(XTModel):
         self.net = build_net(model_info, spec, self.max_batch, self.seed, init="none")
         self.net.init_weights(self.seed, baseline_norm_std=0.01)   # custom_norm_initializer(0.01), :149
         self.actor_var = self.net
+        # PREDICT_ON_DEVICE: the action is sampled inside the head launch (None: on the host, as below)
+        self._act = device_acting(model_info.get("model_config"), self.net, self._rng, self.seed)
         if self.net.inference_only:
             self.stream_ingest = False
             return True
@@ -247,6 +249,10 @@ class ImpalaCnnOpt(XTModel):
 
     def predict(self, state):
         """-> [logits [B,A], baseline [B], action [B]] (impala_cnn_opt.py:267-277)."""
+        if self._act is not None:
+            out = self.net.act(np.asarray(state), self._act["seed"], self._act["call"])
+            self._act["call"] += 1
+            return [out["logits"], out["value"].reshape(-1), out["action"]]
         logits, value = self.net.forward(np.asarray(state))
         logits = as_numpy(logits)
         u = self._rng.random(logits.shape)

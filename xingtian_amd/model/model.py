@@ -62,6 +62,19 @@ def as_numpy(x):
     return x if isinstance(x, np.ndarray) else x.cpu().numpy()
 
 
+def device_acting(model_config, net, rng, seed):
+    """``model_config.PREDICT_ON_DEVICE`` (default false): ``predict`` samples the action and takes its log-probability
+    inside the head launch (``HipActorCritic.act``) instead of on the host.  -> None when the path is off: the key is
+    absent or false, the net is the inference-only CPU replica (which reads the same YAML: ignored silently) or the
+    action space is wider than the kernel's 64 lanes (host path); else the acting state {seed, call}.  The seed is
+    ``SEED`` when given, else drawn once from ``rng`` here; ``call`` counts the model's ``predict`` calls."""
+    if not bool((model_config or {}).get("PREDICT_ON_DEVICE", False)) or getattr(net, "inference_only", False):
+        return None
+    if net.spec.action_dim > net.ACT_MAX_ACTIONS:
+        return None
+    return dict(seed=int(seed) if seed is not None else int(rng.integers(0, 2 ** 63)), call=0)
+
+
 class XTModel(object):
     # every update enqueues the D2H of its new weights behind itself (the learner hands them out after every train when
     # train_per_checkpoint = 1, xt/framework/learner.py:361-363); the algorithm clears this when weights only go out every

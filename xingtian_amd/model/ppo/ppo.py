@@ -10,7 +10,7 @@ an index indirection inside the first conv kernel.
 import numpy as np
 import torch
 
-from xingtian_amd.model.model import XTModel, as_numpy, build_net
+from xingtian_amd.model.model import XTModel, as_numpy, build_net, device_acting
 from xingtian_amd.model.ppo.default_config import (  # noqa: F401
     LR, BATCH_SIZE, CRITIC_LOSS_COEF, ENTROPY_LOSS, LOSS_CLIPPING, MAX_GRAD_NORM, NUM_SGD_ITER, SUMMARY, VF_CLIP)
 from xingtian_amd.register import Registers, import_config
@@ -89,6 +89,8 @@ class PPO(XTModel):
         spec = self.build_spec()
         self.net = build_net(model_info, spec, self._batch_size, self.seed)
         self.actor_var = self.net
+        # PREDICT_ON_DEVICE: sampling and log-probability inside the head launch (None: the host path below)
+        self._act = device_acting(model_info.get("model_config"), self.net, self._rng, self.seed)
         if self.net.inference_only:
             self.stream_ingest = False
             return self.net
@@ -120,6 +122,10 @@ class PPO(XTModel):
     def predict(self, state):
         """-> (action [B] int32 | [B,A] f32, logp [B,1] f32, value [B,1] f32), xt/model/ppo/ppo.py:104-109."""
         state = np.asarray(state)
+        if self._act is not None:
+            out = self.net.act(state, self._act["seed"], self._act["call"])
+            self._act["call"] += 1
+            return out["action"], out["logp"], out["value"]
         logits, value = self.net.forward(state)
         logits = as_numpy(logits)
         value = as_numpy(value).reshape(-1, 1)
