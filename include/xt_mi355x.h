@@ -874,6 +874,58 @@ int xt_act_heads(const float* f_pi, const float* f_v, int32_t B, int32_t F, int3
                  const float* noise, void* action, float* logp, float* value, float* logits, float* noise_out,
                  void* stream);
 
+/* The fused head launches of xt_net_ppo_step / xt_net_impala_step stand-alone, on given buffers, for kernel tests
+ * (appended; the ABI version stays).  Each entry fills the argument struct the step fills and calls the step's launcher.
+ * *path_out (may be NULL) receives the kernel instance(s) taken: XT_HEAD_PATH_* | nq << XT_HEAD_NQ_SHIFT |
+ * part << XT_HEAD_PART_SHIFT | shared << XT_HEAD_SHARED_SHIFT | am << XT_HEAD_AM_SHIFT, 0 when nothing was launched:
+ *   nq      features per lane of the sample's wave: 1 / 2 / 4 / 8 for ceil(F / 64) <= 1 / 2 / 4 / 8
+ *   part    1 when the kernel sums split-K partial slabs, adds the trunk bias and applies the feature activation
+ *   shared  PPO: 1 for one trunk under both heads
+ *   am      IMPALA: actions the v-trace kernel holds in registers, 8 (A <= 8) or 32 */
+#define XT_HEAD_PATH_PPO_FUSED 1     /* ppo_heads_fused_kernel<nq, part, shared>                                      */
+#define XT_HEAD_PATH_IMPALA 2        /* impala_heads_fwd_kernel<nq, part> (nq = 0: not run), impala_vtrace_bwd_kernel<am> */
+#define XT_HEAD_NQ_SHIFT 4           /* 4 bits  */
+#define XT_HEAD_PART_SHIFT 8         /* 1 bit   */
+#define XT_HEAD_SHARED_SHIFT 9       /* 1 bit   */
+#define XT_HEAD_AM_SHIFT 10          /* 6 bits  */
+/* Heads forward + PPO loss + d(logits, value) + d(features), one launch.
+ *   f_pi, f_v       features [B,F] (shared: f_v is not read); not read when part_pi is given
+ *   part_pi, part_v NULL, or ksplit_pi / ksplit_v partial slabs [ksplit][part_stride floats] of the last trunk layer:
+ *                   feature = act_feat(sum of the slabs + tbias), also written to feat_pi_w / feat_v_w [B,F]
+ *                   (shared: part_v, tbias_v, feat_v_w and ksplit_v are not read)
+ *   idx             NULL, or [B] rows of the label pools action / old_logp / adv / old_v / target_v
+ *   cfg             clip_ratio, ent_coef, vf_clip and critic_coef are read
+ *   terms [B,4]     per sample: min(surr1, surr2), entropy, max(vf1, vf2), 0
+ *   df_pi, df_v     d(features) times the derivative of act_prev at the feature (shared: df_v is not written)
+ * Refused (before any device call): A > 8, F > 512, more than 16 slabs. */
+int xt_ppo_heads_fused_ex(const float* f_pi, const float* f_v, const float* part_pi, const float* part_v,
+                          int32_t ksplit_pi, int32_t ksplit_v, int64_t part_stride, const float* tbias_pi,
+                          const float* tbias_v, int32_t act_feat, int32_t B, int32_t F, int32_t A, int32_t shared,
+                          const float* wpi, const float* bpi, const float* wv, const float* bv, const int32_t* idx,
+                          const int32_t* action, const float* old_logp, const double* adv, const float* old_v,
+                          const double* target_v, const xt_ppo_cfg* cfg, float inv_b, int32_t act_prev, float* logits,
+                          float* value, float* dlogits, float* dvalue, float* terms, float* df_pi, float* df_v,
+                          float* feat_pi_w, float* feat_v_w, void* stream, int32_t* path_out);
+/* IMPALA (one trunk): heads forward, then v-trace + loss + d(logits, baseline) + d(features), then the loss sum.
+ *   run_fwd         1: logits / baseline [n_traj*T (,A)] are computed from feat [n_traj*T,F], or from `ksplit` partial
+ *                   slabs as above (the finished features go to feat_w, which the second launch reads);
+ *                   0: logits / baseline are inputs and feat is given -- the forward kernel holds A <= 8, the v-trace
+ *                   kernel A <= 32
+ *   vs, pg_adv      [n_traj, T-1], each may be NULL;  traj_loss [n_traj];  loss_out [1] their sum
+ * Refused (before any device call): T > 256, A > 32; with run_fwd also A > 8, F > 512, more than 16 slabs. */
+int xt_impala_heads_ex(const float* feat, const float* part, int32_t ksplit, int64_t part_stride, const float* tbias,
+                       int32_t act_feat, int32_t run_fwd, int32_t n_traj, int32_t T, int32_t F, int32_t A,
+                       const float* wpi, const float* bpi, const float* wv, const float* bv, const float* bp_logits,
+                       const int32_t* action, const uint8_t* done, const float* reward, float gamma, int32_t act_prev,
+                       float* feat_w, float* logits, float* baseline, float* dlogits, float* dbaseline, float* vs,
+                       float* pg_adv, float* dfeat, float* traj_loss, float* loss_out, void* stream, int32_t* path_out);
+/* Head weight-gradient partial slabs as every step writes them: chunk c of 8 samples leaves its share of
+ * [dWpi (F*A) | dbpi (A)] at slab_pi + c * stride_pi and of [dWv (F) | dbv (1)] at slab_v + c * stride_v (strides in
+ * floats); *nchunk_out = ceil(B / 8) slabs are written, for the caller (the gradient-reduction launch) to sum. */
+int xt_heads_wgrad_partial_ex(const float* f_pi, const float* f_v, int32_t B, int32_t F, int32_t A,
+                              const float* dlogits, const float* dvalue, float* slab_pi, int64_t stride_pi,
+                              float* slab_v, int64_t stride_v, int32_t* nchunk_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

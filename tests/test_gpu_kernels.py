@@ -374,7 +374,10 @@ def test_heads_and_ppo_loss(L, a_dim, shared):
             assert rel_err(df_v.cpu().numpy(), nets.act_bwd(dvf, f_v.astype(np.float64), act_prev)) < 3e-6
 
 
-@pytest.mark.parametrize("tlen,n_traj,a_dim", [(128, 3, 4), (50, 20, 6), (2, 1, 4), (5, 2, 18)])
+# (the rows from (64, 2, 5) on: both sides of the 64 / 128 / 256 thresholds between impala_loss_kernel's instances, and the
+# 1024-thread one at its longest T)
+@pytest.mark.parametrize("tlen,n_traj,a_dim", [(128, 3, 4), (50, 20, 6), (2, 1, 4), (5, 2, 18), (64, 2, 5), (65, 2, 5),
+                                               (129, 2, 4), (256, 1, 6), (257, 1, 4), (1024, 1, 3)])
 def test_impala_vtrace_loss(L, tlen, n_traj, a_dim):
     rng = np.random.default_rng(9)
     n = tlen * n_traj

@@ -538,6 +538,12 @@ __global__ __launch_bounds__(256) void heads_wgrad_partial_kernel(const HeadWgAr
   heads_wgrad_partial_body(h, blockIdx.x, blockIdx.y, smem);
 }
 
+// the instance a head launcher took, for last_path() (diagnostic: the stand-alone entries at the end hand it out)
+static inline int head_path_bits(int family, int nq, bool part, bool shared, int am) {
+  return family | (nq << XT_HEAD_NQ_SHIFT) | ((part ? 1 : 0) << XT_HEAD_PART_SHIFT) |
+         ((shared ? 1 : 0) << XT_HEAD_SHARED_SHIFT) | (am << XT_HEAD_AM_SHIFT);
+}
+
 // returns -1 when the geometry is outside the fused kernel's envelope (caller falls back to the 3 plain kernels)
 int launch_ppo_heads_fused(const PpoHeadArgs& a, hipStream_t st) {
   if (a.A > kHeadMaxA || a.F > 512) return -1;
@@ -555,6 +561,7 @@ int launch_ppo_heads_fused(const PpoHeadArgs& a, hipStream_t st) {
   } while (0)
   if (nq <= 1) XT_HEAD(1); else if (nq <= 2) XT_HEAD(2); else if (nq <= 4) XT_HEAD(4); else XT_HEAD(8);
 #undef XT_HEAD
+  last_path() = head_path_bits(XT_HEAD_PATH_PPO_FUSED, nq <= 1 ? 1 : nq <= 2 ? 2 : nq <= 4 ? 4 : 8, part, shared, 0);
   XT_LAUNCH_CHECK();
   return 0;
 }
@@ -675,6 +682,7 @@ int launch_impala_heads_fwd(const ImpalaHeadArgs& a, hipStream_t st) {
   } while (0)
   if (nq <= 1) XT_IH(1); else if (nq <= 2) XT_IH(2); else if (nq <= 4) XT_IH(4); else XT_IH(8);
 #undef XT_IH
+  last_path() = head_path_bits(XT_HEAD_PATH_IMPALA, nq <= 1 ? 1 : nq <= 2 ? 2 : nq <= 4 ? 4 : 8, part, false, 0);
   XT_LAUNCH_CHECK();
   return 0;
 }
@@ -862,6 +870,7 @@ int launch_impala_vtrace_bwd(const ImpalaLossArgs& a, int n_traj, hipStream_t st
   const dim3 grid(n_traj, (a.T + kVtRows - 1) / kVtRows);
   if (a.A <= 8) hipLaunchKernelGGL((impala_vtrace_bwd_kernel<8>), grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL((impala_vtrace_bwd_kernel<32>), grid, dim3(256), 0, st, a);
+  last_path() = head_path_bits(XT_HEAD_PATH_IMPALA, 0, false, false, a.A <= 8 ? 8 : 32);
   XT_LAUNCH_CHECK();
   return 0;
 }
@@ -1546,6 +1555,114 @@ int xt_pad_channels(const void* src, void* dst, int64_t rows, int32_t c_src, int
     hipLaunchKernelGGL((xt::pad_channels_kernel<float>), grid, dim3(256), 0, xt::as_stream(stream),
                        static_cast<const float*>(src), static_cast<float*>(dst), (long long)rows, c_src, c_dst, 0.f);
   XT_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------- the fused head launches stand-alone (kernel tests)
+int xt_ppo_heads_fused_ex(const float* f_pi, const float* f_v, const float* part_pi, const float* part_v,
+                          int32_t ksplit_pi, int32_t ksplit_v, int64_t part_stride, const float* tbias_pi,
+                          const float* tbias_v, int32_t act_feat, int32_t B, int32_t F, int32_t A, int32_t shared,
+                          const float* wpi, const float* bpi, const float* wv, const float* bv, const int32_t* idx,
+                          const int32_t* action, const float* old_logp, const double* adv, const float* old_v,
+                          const double* target_v, const xt_ppo_cfg* cfg, float inv_b, int32_t act_prev, float* logits,
+                          float* value, float* dlogits, float* dvalue, float* terms, float* df_pi, float* df_v,
+                          float* feat_pi_w, float* feat_v_w, void* stream, int32_t* path_out) {
+  if (path_out) *path_out = 0;
+  xt::last_path() = 0;
+  XT_REQUIRE(B > 0 && F > 0 && A > 0, "xt_ppo_heads_fused_ex: bad sizes (B=%d F=%d A=%d)", B, F, A);
+  const bool part = part_pi != nullptr, sh = shared != 0;
+  XT_REQUIRE(!part || (ksplit_pi >= 1 && (sh || ksplit_v >= 1) && part_stride >= (int64_t)B * F),
+             "xt_ppo_heads_fused_ex: bad slab counts %d / %d or slab stride %lld", ksplit_pi, ksplit_v,
+             (long long)part_stride);
+  XT_REQUIRE(cfg && wpi && bpi && wv && bv && action && old_logp && adv && old_v && target_v && logits && value &&
+                 dlogits && dvalue && terms && df_pi && (sh || df_v),
+             "xt_ppo_heads_fused_ex: null argument");
+  XT_REQUIRE(part ? (tbias_pi && feat_pi_w && (sh || (part_v && tbias_v && feat_v_w))) : (f_pi && (sh || f_v)),
+             "xt_ppo_heads_fused_ex: null feature argument");
+  xt::PpoHeadArgs h;
+  h.f_pi = part ? feat_pi_w : f_pi; h.f_v = sh ? h.f_pi : (part ? feat_v_w : f_v);
+  h.wpi = wpi; h.bpi = bpi; h.wv = wv; h.bv = bv;
+  h.idx = idx; h.action = action; h.old_logp = old_logp; h.old_v = old_v; h.adv = adv; h.target_v = target_v;
+  h.clip_ratio = cfg->clip_ratio; h.ent_coef = cfg->ent_coef; h.vf_clip = cfg->vf_clip; h.critic_coef = cfg->critic_coef;
+  h.inv_b = inv_b; h.B = B; h.F = F; h.A = A; h.act_prev = act_prev; h.shared = sh ? 1 : 0;
+  h.logits = logits; h.value = value; h.dlogits = dlogits; h.dvalue = dvalue; h.terms = terms;
+  h.df_pi = df_pi; h.df_v = sh ? df_pi : df_v;
+  h.part_pi = h.part_v = nullptr; h.tbias_pi = h.tbias_v = nullptr; h.feat_pi_w = h.feat_v_w = nullptr;
+  h.ksplit_pi = h.ksplit_v = 1; h.act_feat = act_feat; h.part_stride = part ? (long long)part_stride : (long long)B * F;
+  if (part) {
+    h.part_pi = part_pi; h.ksplit_pi = ksplit_pi; h.feat_pi_w = feat_pi_w; h.tbias_pi = tbias_pi;
+    if (!sh) { h.part_v = part_v; h.ksplit_v = ksplit_v; h.feat_v_w = feat_v_w; h.tbias_v = tbias_v; }
+  }
+  const int rc = xt::launch_ppo_heads_fused(h, xt::as_stream(stream));
+  if (rc > 0) return rc;
+  XT_REQUIRE(rc == 0, "xt_ppo_heads_fused_ex: the fused PPO head kernel refuses A=%d F=%d ksplit=%d/%d (A <= 8, F <= 512, ksplit <= 16)",
+             A, F, h.ksplit_pi, h.ksplit_v);
+  if (path_out) *path_out = xt::last_path();
+  return 0;
+}
+
+int xt_impala_heads_ex(const float* feat, const float* part, int32_t ksplit, int64_t part_stride, const float* tbias,
+                       int32_t act_feat, int32_t run_fwd, int32_t n_traj, int32_t T, int32_t F, int32_t A,
+                       const float* wpi, const float* bpi, const float* wv, const float* bv, const float* bp_logits,
+                       const int32_t* action, const uint8_t* done, const float* reward, float gamma, int32_t act_prev,
+                       float* feat_w, float* logits, float* baseline, float* dlogits, float* dbaseline, float* vs,
+                       float* pg_adv, float* dfeat, float* traj_loss, float* loss_out, void* stream, int32_t* path_out) {
+  if (path_out) *path_out = 0;
+  xt::last_path() = 0;
+  XT_REQUIRE(n_traj > 0 && T >= 2 && F > 0 && A > 0, "xt_impala_heads_ex: bad sizes (n_traj=%d T=%d F=%d A=%d)", n_traj, T,
+             F, A);
+  XT_REQUIRE(T <= 256 && A <= 32, "xt_impala_heads_ex: the fused v-trace kernel refuses T=%d A=%d (T <= 256, A <= 32)", T, A);
+  const long long rows = (long long)n_traj * T;
+  XT_REQUIRE(rows < (1ll << 31) / F, "xt_impala_heads_ex: too many rows");
+  XT_REQUIRE(run_fwd || !part, "xt_impala_heads_ex: partial slabs need the forward launch");
+  XT_REQUIRE(!part || (ksplit >= 1 && part_stride >= rows * F && tbias && feat_w),
+             "xt_impala_heads_ex: bad slab count %d, slab stride %lld or null slab argument", ksplit, (long long)part_stride);
+  XT_REQUIRE((part || feat) && wpi && bpi && wv && bv && bp_logits && action && done && reward && logits && baseline &&
+                 dlogits && dbaseline && dfeat && traj_loss && loss_out,
+             "xt_impala_heads_ex: null argument");
+  hipStream_t st = xt::as_stream(stream);
+  int path = 0;
+  if (run_fwd) {
+    xt::ImpalaHeadArgs h{};
+    h.feat = part ? feat_w : feat; h.wpi = wpi; h.bpi = bpi; h.wv = wv; h.bv = bv; h.B = (int)rows; h.F = F; h.A = A;
+    h.logits = logits; h.value = baseline; h.act_feat = act_feat;
+    h.ksplit = 1; h.part_stride = rows * F;
+    if (part) { h.part = part; h.ksplit = ksplit; h.feat_w = feat_w; h.tbias = tbias; h.part_stride = part_stride; }
+    const int rc = xt::launch_impala_heads_fwd(h, st);
+    if (rc > 0) return rc;
+    XT_REQUIRE(rc == 0, "xt_impala_heads_ex: the fused head kernel refuses A=%d F=%d ksplit=%d (A <= 8, F <= 512, ksplit <= 16)",
+               A, F, h.ksplit);
+    path = xt::last_path();
+  }
+  xt::ImpalaLossArgs q{};
+  q.logits = logits; q.baseline = baseline; q.bp_logits = bp_logits; q.action = action; q.done = done; q.reward = reward;
+  q.T = T; q.A = A; q.F = F; q.act_prev = act_prev; q.gamma = gamma;
+  q.dlogits = dlogits; q.dbaseline = dbaseline; q.traj_loss = traj_loss; q.vs_out = vs; q.pg_out = pg_adv;
+  q.feat = part ? feat_w : feat; q.wpi = wpi; q.wv = wv; q.dfeat = dfeat;
+  int rc = xt::launch_impala_vtrace_bwd(q, n_traj, st);
+  if (rc > 0) return rc;
+  XT_REQUIRE(rc == 0, "xt_impala_heads_ex: the fused v-trace kernel refuses T=%d A=%d", T, A);
+  path |= xt::last_path();
+  rc = xt::launch_impala_loss_reduce(traj_loss, n_traj, loss_out, nullptr, st);
+  if (rc) return rc;
+  if (path_out) *path_out = path;
+  return 0;
+}
+
+int xt_heads_wgrad_partial_ex(const float* f_pi, const float* f_v, int32_t B, int32_t F, int32_t A,
+                              const float* dlogits, const float* dvalue, float* slab_pi, int64_t stride_pi,
+                              float* slab_v, int64_t stride_v, int32_t* nchunk_out, void* stream) {
+  if (nchunk_out) *nchunk_out = 0;
+  XT_REQUIRE(B > 0 && F > 0 && A > 0 && A < 256, "xt_heads_wgrad_partial_ex: bad sizes (B=%d F=%d A=%d)", B, F, A);
+  XT_REQUIRE(stride_pi >= (int64_t)F * A + A && stride_v >= (int64_t)F + 1,
+             "xt_heads_wgrad_partial_ex: slab strides %lld / %lld below F*A+A / F+1", (long long)stride_pi,
+             (long long)stride_v);
+  XT_REQUIRE(f_pi && f_v && dlogits && dvalue && slab_pi && slab_v && nchunk_out, "xt_heads_wgrad_partial_ex: null argument");
+  int nchunk = 0;
+  const int rc = xt::launch_heads_wgrad_partial(f_pi, f_v, B, F, A, dlogits, dvalue, slab_pi, stride_pi, slab_v,
+                                                stride_v, &nchunk, xt::as_stream(stream));
+  if (rc) return rc;
+  *nchunk_out = nchunk;
   return 0;
 }
 

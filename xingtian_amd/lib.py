@@ -185,6 +185,14 @@ SIGNATURES = {
     "xt_net_act": (c_int32, [_P, POINTER(ActCfg), _P, _P, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "xt_act_heads": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, POINTER(ActCfg), _P, _P, _P, _P, _P,
                                _P, _P]),
+    "xt_ppo_heads_fused_ex": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int64, _P, _P, c_int32, c_int32, c_int32,
+                                        c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(PpoCfg), c_float,
+                                        c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(c_int32)]),
+    "xt_impala_heads_ex": (c_int32, [_P, _P, c_int32, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                     _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                     _P, _P, POINTER(c_int32)]),
+    "xt_heads_wgrad_partial_ex": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_int64, _P, c_int64,
+                                            POINTER(c_int32), _P]),
 }
 
 
