@@ -181,6 +181,49 @@ static int join_pending_update(xt_net* n, hipStream_t st) {
   return 0;
 }
 
+static inline const float* w_of(const xt_net* n, const Layer& L) { return n->params + L.poff; }
+static inline const float* b_of(const xt_net* n, const Layer& L) { return n->params + L.poff + (int64_t)L.K * L.g.N; }
+
+// The two heads: the last layer of the pi trunk and of the v trunk (one layer for a one-trunk net), the features they
+// read, what the activation derivative reads (the pre-activation where one is kept) and the head parameters
+struct Heads {
+  Layer *Lp, *Lv;
+  const float *f_pi, *f_v, *fd_pi, *fd_v, *wpi, *bpi, *wv, *bv;
+  int F, A;
+};
+static Heads heads_of(xt_net* n) {
+  Heads h;
+  h.Lp = &n->layers[n->t_end[0] - 1];
+  h.Lv = &n->layers[n->t_end[n->n_trunks - 1] - 1];
+  h.f_pi = n->ws + h.Lp->act_off; h.f_v = n->ws + h.Lv->act_off;
+  h.fd_pi = n->ws + (h.Lp->z_off >= 0 ? h.Lp->z_off : h.Lp->act_off);
+  h.fd_v = n->ws + (h.Lv->z_off >= 0 ? h.Lv->z_off : h.Lv->act_off);
+  h.F = n->feat; h.A = n->A;
+  h.wpi = n->params + n->pi_off; h.bpi = h.wpi + (int64_t)h.F * h.A;
+  h.wv = n->params + n->v_off; h.bv = h.wv + h.F;
+  return h;
+}
+static int heads_forward(xt_net* n, int B, hipStream_t st) {
+  const Heads h = heads_of(n);
+  return xt_heads_fwd(h.f_pi, h.f_v, B, h.F, h.A, h.wpi, h.bpi, h.wv, h.bv, n->ws + n->off_logits, n->ws + n->off_value, st);
+}
+// (launch_heads_dfeat reads the features only for the activation derivative: the pre-activation where one is kept)
+static int heads_dfeat(xt_net* n, int B, hipStream_t st) {
+  const Heads h = heads_of(n);
+  return launch_heads_dfeat(h.fd_pi, h.fd_v, B, h.F, h.A, h.wpi, h.wv, n->ws + n->off_dlogits, n->ws + n->off_dvalue,
+                            h.Lp->g.act, n->ws + h.Lp->dact_off, n->ws + h.Lv->dact_off, st);
+}
+
+// The launch_fwd call of trunk layer L: geometry g (L.g, or its XT_ACT_NONE copy) on input x into y.  defer: the split-K
+// partials stay in the layer's own region, un-finished, and L.last_ksplit says how many.  (Only a relu first layer has a
+// sign mask, so a layer that writes its pre-activation passes none.)
+static int layer_forward(xt_net* n, Layer& L, const xt_conv_geom* g, bool first, int B, const void* x, const int32_t* idx,
+                         float* y, bool defer, hipStream_t st) {
+  return launch_fwd(g, first ? &n->xf : nullptr, B, x, first ? idx : nullptr, w_of(n, L), b_of(n, L), y,
+                    n->ws + (defer ? L.part_off : n->off_partial), fwd_split(L, B), st, defer ? &L.last_ksplit : nullptr,
+                    L.mask_off >= 0 ? reinterpret_cast<uint32_t*>(n->ws + L.mask_off) : nullptr, &L.mask_valid);
+}
+
 // defer_last: leave the split-K partials of every trunk's LAST layer un-finished (the fused PPO head kernel
 // sums them); each such layer has its own partial region.
 static int net_forward(xt_net* n, const void* obs, const int32_t* idx, int B, bool with_heads, hipStream_t st,
@@ -201,9 +244,8 @@ static int net_forward(xt_net* n, const void* obs, const int32_t* idx, int B, bo
         // LDS for conv2; both activations still go to their workspace buffers for the backward pass).  -1: not that geometry
         Layer& L2 = n->layers[l + 1];
         if (int rcj = join_pending_update(n, st)) return rcj;      // (the launch reads the second layer's weights too)
-        const int rc = launch_conv12_same_fwd(&L.g, &n->xf, &L2.g, B, x, idx, n->params + L.poff,
-                                              n->params + L.poff + (int64_t)L.K * L.g.N, n->ws + L.act_off, n->params + L2.poff,
-                                              n->params + L2.poff + (int64_t)L2.K * L2.g.N, n->ws + L2.act_off, st);
+        const int rc = launch_conv12_same_fwd(&L.g, &n->xf, &L2.g, B, x, idx, w_of(n, L), b_of(n, L), n->ws + L.act_off,
+                                              w_of(n, L2), b_of(n, L2), n->ws + L2.act_off, st);
         if (rc > 0) return rc;
         if (rc == 0) {
           L2.last_ksplit = 1;
@@ -218,30 +260,17 @@ static int net_forward(xt_net* n, const void* obs, const int32_t* idx, int B, bo
         // produces the output the next layer reads -- a slow path, taken by no bundled configuration
         xt_conv_geom gz = L.g;
         gz.act = XT_ACT_NONE;
-        if (int rc = launch_fwd(&gz, first ? &n->xf : nullptr, B, x, first ? idx : nullptr, n->params + L.poff,
-                                n->params + L.poff + (int64_t)L.K * L.g.N, n->ws + L.z_off, n->ws + n->off_partial,
-                                fwd_split(L, B), st, nullptr, nullptr, nullptr))
-          return rc;
+        if (int rc = layer_forward(n, L, &gz, first, B, x, idx, n->ws + L.z_off, false, st)) return rc;
         if (int rc = launch_act_apply(n->ws + L.z_off, n->ws + L.act_off, (long long)B * L.OHOW * L.g.N, L.g.act, st)) return rc;
         x = n->ws + L.act_off;
         continue;
       }
-      if (int rc = launch_fwd(&L.g, first ? &n->xf : nullptr, B, x, first ? idx : nullptr, n->params + L.poff,
-                              n->params + L.poff + (int64_t)L.K * L.g.N, n->ws + L.act_off,
-                              n->ws + (defer ? L.part_off : n->off_partial), fwd_split(L, B), st,
-                              defer ? &L.last_ksplit : nullptr,
-                              L.mask_off >= 0 ? reinterpret_cast<uint32_t*>(n->ws + L.mask_off) : nullptr, &L.mask_valid))
-        return rc;
+      if (int rc = layer_forward(n, L, &L.g, first, B, x, idx, n->ws + L.act_off, defer, st)) return rc;
       x = n->ws + L.act_off;
     }
   }
   if (int rc = join_pending_update(n, st)) return rc;     // (one-layer trunks: before the heads read their weights)
-  if (!with_heads) return 0;
-  const float* f_pi = n->ws + n->layers[n->t_end[0] - 1].act_off;
-  const float* f_v = n->ws + n->layers[n->t_end[n->n_trunks - 1] - 1].act_off;
-  const int F = n->feat, A = n->A;
-  return xt_heads_fwd(f_pi, f_v, B, F, A, n->params + n->pi_off, n->params + n->pi_off + (int64_t)F * A,
-                      n->params + n->v_off, n->params + n->v_off + F, n->ws + n->off_logits, n->ws + n->off_value, st);
+  return with_heads ? heads_forward(n, B, st) : 0;
 }
 
 constexpr int kMaxNormPartials = 16384;
@@ -254,9 +283,8 @@ static int layer_wgrad(xt_net* n, int l, bool first, const void* obs, const int3
 }
 
 static int heads_wgrad(xt_net* n, int B, hipStream_t st) {
-  Layer& Lp = n->layers[n->t_end[0] - 1];
-  Layer& Lv = n->layers[n->t_end[n->n_trunks - 1] - 1];
-  return launch_heads_wgrad_partial(n->ws + Lp.act_off, n->ws + Lv.act_off, B, n->feat, n->A, n->ws + n->off_dlogits,
+  const Heads h = heads_of(n);
+  return launch_heads_wgrad_partial(h.f_pi, h.f_v, B, h.F, h.A, n->ws + n->off_dlogits,
                                     n->ws + n->off_dvalue, n->ws + n->off_hslab_pi, n->hstride_pi,
                                     n->ws + n->off_hslab_v, n->hstride_v, &n->head_chunks, st);
 }
@@ -271,7 +299,7 @@ static BwdLayerCall bwd_layer_call(xt_net* n, int l, int B, hipStream_t st) {
   c.x = n->ws + Lprev.act_off;
   if (Lprev.z_off >= 0) c.x_grad = n->ws + Lprev.z_off;
   c.dy = n->ws + L.dact_off;
-  c.w = n->params + L.poff;
+  c.w = w_of(n, L);
   c.act_prev = Lprev.g.act;
   if (Lprev.mask_valid) c.xmask = reinterpret_cast<const uint32_t*>(n->ws + Lprev.mask_off);
   c.dx = n->ws + Lprev.dact_off;
@@ -319,13 +347,12 @@ static int trunk_backward(xt_net* n, const void* obs, const int32_t* idx, int B,
       }
       HeadWgArgs hw;
       if (!heads_done) {
-        Layer& Lp = n->layers[n->t_end[0] - 1];
-        Layer& Lv = n->layers[n->t_end[n->n_trunks - 1] - 1];
-        hw.f_pi = n->ws + Lp.act_off; hw.f_v = n->ws + Lv.act_off;
+        const Heads h = heads_of(n);
+        hw.f_pi = h.f_pi; hw.f_v = h.f_v;
         hw.dlogits = n->ws + n->off_dlogits; hw.dvalue = n->ws + n->off_dvalue;
         hw.slab_pi = n->ws + n->off_hslab_pi; hw.slab_v = n->ws + n->off_hslab_v;
         hw.stride_pi = n->hstride_pi; hw.stride_v = n->hstride_v;
-        hw.B = B; hw.F = n->feat; hw.A = n->A; hw.gx = (n->feat + 63) / 64; hw.nchunk = (B + 7) / 8;
+        hw.B = B; hw.F = h.F; hw.A = h.A; hw.gx = (h.F + 63) / 64; hw.nchunk = (B + 7) / 8;
         n->head_chunks = hw.nchunk;
         c.hw = &hw;
         heads_done = true;
@@ -502,6 +529,83 @@ static int tail_fork_first_bucket(void* arg) {
   return 0;
 }
 
+// The optimiser a step or a data-parallel train ends in, with the clip settings that go with it
+struct OptCfg {
+  int opt_type;                 // XT_OPT_ADAM, or XT_OPT_RMSPROP_CENTERED (IMPALA only)
+  float lr, beta1, beta2, eps, rms_decay, rms_eps, clip, gscale;
+  const float* lr_dev;          // IMPALA: the step size in device memory (may be null)
+};
+static OptCfg ppo_opt(const xt_ppo_cfg* c) {
+  return OptCfg{XT_OPT_ADAM, c->lr, c->beta1, c->beta2, c->eps, 0.f, 0.f, c->max_grad_norm, c->grad_scale, nullptr};
+}
+static OptCfg impala_opt(const xt_impala_cfg* c, const float* lr_dev) {
+  return OptCfg{c->opt_type, c->lr, c->beta1, c->beta2, c->eps, c->rms_decay, c->rms_eps, c->grad_norm_clip, c->grad_scale,
+                lr_dev};
+}
+static unsigned int* ticket_counter(xt_net* n) { return reinterpret_cast<unsigned int*>(n->ws + n->off_counter); }
+// (ticket: pass the counter; the loss fields stay with the caller)
+static FinalizeArgs finalize_args(xt_net* n, int enable, bool ticket, const OptCfg& o) {
+  FinalizeArgs fin{};
+  fin.enable = enable; fin.counter = ticket ? ticket_counter(n) : nullptr; fin.clip_norm = o.clip; fin.grad_scale = o.gscale;
+  fin.lr = o.lr; fin.beta1 = o.beta1; fin.beta2 = o.beta2; fin.state = n->state; fin.lr_dev = o.lr_dev;
+  return fin;
+}
+// The apply == 1 tail: join the forked first bucket and finish part 2, or finish everything -- as the fused tail where
+// may_fuse (the caller's own condition) and the knobs allow; then split Adam (tov & 2) or the configured optimiser's launch
+static int step_tail_apply(xt_net* n, int B, FinalizeArgs fin, const OptCfg& o, bool forked, int tov, bool may_fuse,
+                           bool defer_join, hipStream_t st, const char* who) {
+  bool fused = false;
+  if (forked) {
+    XT_CHECK_HIP(hipStreamWaitEvent(st, n->tail_join, 0));
+    if (int rc = grads_finish(n, B, &fin, st, 2)) return rc;
+  } else {
+    if (may_fuse && !tov && tuning().tail_fused) {
+      fin.enable = 3; fin.counter = ticket_counter(n);
+      fin.ap.params = n->params; fin.ap.m = n->m; fin.ap.v = n->v; fin.ap.grads = n->grads; fin.ap.eps = o.eps;
+    }
+    if (int rc = grads_finish(n, B, &fin, st, 0, &fused)) return rc;
+  }
+  if (fused) return 0;
+  if (tov & 2) {
+    if (int rc = net_apply_split(n, o.beta1, o.beta2, o.eps, o.clip, o.gscale, st)) return rc;
+    return defer_join ? 0 : join_pending_update(n, st);
+  }
+  if (o.opt_type == XT_OPT_RMSPROP_CENTERED)
+    return launch_rmsprop_clip(n->params, n->grads, n->m, n->v, n->P, o.lr, o.rms_decay, o.rms_eps, n->state,
+                               n->ws + n->off_norm, n->norm_blocks, o.clip, o.gscale, st, o.lr_dev);
+  XT_REQUIRE(o.opt_type == XT_OPT_ADAM, "%s: unknown opt_type %d", who, o.opt_type);
+  // (enable == 1: the last block of the reduction has finalised already)
+  return net_apply(n, o.lr, o.beta1, o.beta2, o.eps, o.clip, o.gscale, fin.enable == 1 ? 2 : 3, nullptr, st);
+}
+
+// The apply == 3 tail (see ppo_step): the gradient reduction with its extra block and the data-parallel extras, no update
+static int step_tail_dp(xt_net* n, int B, FinalizeArgs fin, hipStream_t st) {
+  DpFinish dpf;
+  if (int rc = dp_finish_args(n, &dpf)) return rc;
+  fin.counter = ticket_counter(n);      // (the scatter ticket of the fused exchange)
+  if (n->dp_world >= 1) fin.loss.acc = nullptr;      // the GLOBAL loss is added on the optimiser side, from the exchanged tail
+  return grads_finish(n, B, &fin, st, 0, nullptr, &dpf);
+}
+// exchange -> squared norm of the EXCHANGED gradient -> the configured optimiser (Adam, or centred RMSProp), every block
+// deriving the clip factor from the partials itself
+static int dp_apply(xt_net* n, const OptCfg& o, float* loss_acc, hipStream_t st, const char* who) {
+  DpApply da;
+  if (int rc = dp_exchange(n, st, loss_acc, &da)) return rc;
+  if (o.opt_type == XT_OPT_RMSPROP_CENTERED)
+    return launch_rmsprop_clip(n->params, da.g, n->m, n->v, n->P, o.lr, o.rms_decay, o.rms_eps, n->state, da.partial,
+                               da.npartial, o.clip, o.gscale, st, o.lr_dev, &da.step, da.block_cap);
+  XT_REQUIRE(o.opt_type == XT_OPT_ADAM, "%s: unknown opt_type %d", who, o.opt_type);
+  return launch_adam_clip(n->params, da.g, n->m, n->v, n->P, o.beta1, o.beta2, o.eps, n->state, da.partial, da.npartial,
+                          o.clip, o.gscale, st, &da.step, da.block_cap);
+}
+
+// A rank's balanced contiguous share of `count` items: the C++ twin of xingtian_amd/parallel.py::shard_range
+static void shard_slice(int rank, int world, int count, int* begin, int* len) {
+  const int base = count / world, rem = count % world;
+  *begin = rank * base + (rank < rem ? rank : rem);
+  *len = base + (rank < rem ? 1 : 0);
+}
+
 static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32_t* idx, int B,
                     const void* action_v, const float* old_logp, const double* adv, const float* old_v,
                     const double* target_v, int apply, float* loss_out, float* loss_acc, hipStream_t st,
@@ -516,20 +620,18 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
              "xt_net_ppo_step: the overlapped exchange mode needs a hook installed with XT_XCHG_OVERLAP");
   const bool gauss = (n->action_type == XT_ACTION_DIAG_GAUSSIAN);
   const int32_t* action = static_cast<const int32_t*>(action_v);
-  Layer& Lp0 = n->layers[n->t_end[0] - 1];
-  Layer& Lv0 = n->layers[n->t_end[n->n_trunks - 1] - 1];
-  bool fused_head = (!gauss && n->A <= 8 && n->feat <= 512 && Lp0.z_off < 0 && Lv0.z_off < 0);
+  const Heads hd = heads_of(n);
+  Layer &Lp = *hd.Lp, &Lv = *hd.Lv;
+  bool fused_head = (!gauss && n->A <= 8 && n->feat <= 512 && Lp.z_off < 0 && Lv.z_off < 0);
   const int no_defer = tuning().defer_splitk ? 0 : 1;
   if (int rc = net_forward(n, obs, idx, B, false, st, fused_head && !no_defer)) return rc;
   const float inv_b = 1.f / (float)(c->global_batch > 0 ? c->global_batch : B);
-  Layer& Lp = n->layers[n->t_end[0] - 1];
-  Layer& Lv = n->layers[n->t_end[n->n_trunks - 1] - 1];
-  const int F = n->feat, A = n->A;
+  const int F = hd.F, A = hd.A;
   float* lo = loss_out ? loss_out : n->ws + n->off_loss;
   if (fused_head) {
     PpoHeadArgs h;
-    h.f_pi = n->ws + Lp.act_off; h.f_v = n->ws + Lv.act_off;
-    h.wpi = n->params + n->pi_off; h.bpi = h.wpi + (int64_t)F * A; h.wv = n->params + n->v_off; h.bv = h.wv + F;
+    h.f_pi = hd.f_pi; h.f_v = hd.f_v;
+    h.wpi = hd.wpi; h.bpi = hd.bpi; h.wv = hd.wv; h.bv = hd.bv;
     h.idx = idx; h.action = action; h.old_logp = old_logp; h.old_v = old_v; h.adv = adv; h.target_v = target_v;
     h.clip_ratio = c->clip_ratio; h.ent_coef = c->ent_coef; h.vf_clip = c->vf_clip; h.critic_coef = c->critic_coef;
     h.inv_b = inv_b; h.B = B; h.F = F; h.A = A; h.act_prev = Lp.g.act; h.shared = (n->n_trunks == 1);
@@ -540,11 +642,11 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
     h.ksplit_pi = h.ksplit_v = 1; h.act_feat = Lp.g.act; h.part_stride = (long long)B * F;
     if (Lp.last_ksplit > 1) {
       h.part_pi = n->ws + Lp.part_off; h.ksplit_pi = Lp.last_ksplit; h.feat_pi_w = n->ws + Lp.act_off;
-      h.tbias_pi = n->params + Lp.poff + (int64_t)Lp.K * Lp.g.N;
+      h.tbias_pi = b_of(n, Lp);
     }
     if (n->n_trunks == 2 && Lv.last_ksplit > 1) {
       h.part_v = n->ws + Lv.part_off; h.ksplit_v = Lv.last_ksplit; h.feat_v_w = n->ws + Lv.act_off;
-      h.tbias_v = n->params + Lv.poff + (int64_t)Lv.K * Lv.g.N;
+      h.tbias_v = b_of(n, Lv);
     }
     XT_REQUIRE(n->n_trunks == 1 || ((Lp.last_ksplit > 1) == (Lv.last_ksplit > 1)),
                "xt_net: pi and v trunks ended in different split-K states (unequal trunk shapes are not supported)");
@@ -552,10 +654,7 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
     if (hrc > 0) return hrc;
     XT_REQUIRE(hrc == 0, "xt_net: fused PPO head kernel rejected the geometry (A=%d F=%d)", A, F);
   } else {
-    if (int rc = xt_heads_fwd(n->ws + Lp.act_off, n->ws + Lv.act_off, B, F, A, n->params + n->pi_off,
-                              n->params + n->pi_off + (int64_t)F * A, n->params + n->v_off, n->params + n->v_off + F,
-                              n->ws + n->off_logits, n->ws + n->off_value, st))
-      return rc;
+    if (int rc = heads_forward(n, B, st)) return rc;
     if (gauss) {
       if (int rc = launch_ppo_loss_gauss(n->ws + n->off_logits, n->params + n->logstd_off, n->ws + n->off_value, B, A,
                                          idx, static_cast<const float*>(action_v), old_logp, adv, old_v, target_v,
@@ -568,12 +667,7 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
                                     old_v, target_v, c->clip_ratio, c->ent_coef, c->vf_clip, c->critic_coef, inv_b,
                                     n->ws + n->off_dlogits, n->ws + n->off_dvalue, n->ws + n->off_terms, st))
       return rc;
-    // (launch_heads_dfeat reads the features only for the activation derivative: the pre-activation where one is kept)
-    if (int rc = launch_heads_dfeat(n->ws + (Lp.z_off >= 0 ? Lp.z_off : Lp.act_off), n->ws + (Lv.z_off >= 0 ? Lv.z_off : Lv.act_off),
-                                    B, F, A, n->params + n->pi_off,
-                                    n->params + n->v_off, n->ws + n->off_dlogits, n->ws + n->off_dvalue, Lp.g.act,
-                                    n->ws + Lp.dact_off, n->ws + Lv.dact_off, st))
-      return rc;
+    if (int rc = heads_dfeat(n, B, st)) return rc;
   }
   // data-parallel overlap (apply == 2): reduce + exchange the last trunk layer's and the heads' gradient right after
   // the first backward launch, on the side stream, while the conv backward runs
@@ -610,43 +704,17 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
     if (n->dp_world >= 1) return 0;        // (loss share already in the tail of the first bucket)
     return xt_ppo_loss_reduce(n->ws + n->off_terms, B, c->ent_coef, c->critic_coef, inv_b, lo, loss_acc, st);
   }
-  LossArgs la{};
-  la.terms = n->ws + n->off_terms; la.B = B; la.ent_coef = c->ent_coef; la.critic_coef = c->critic_coef;
-  la.inv_b = inv_b; la.out = lo; la.acc = loss_acc;
-  if (apply == 3) {
-    FinalizeArgs fin{};
-    fin.enable = 2; fin.counter = reinterpret_cast<unsigned int*>(n->ws + n->off_counter);
-    fin.clip_norm = c->max_grad_norm; fin.grad_scale = c->grad_scale; fin.lr = c->lr; fin.beta1 = c->beta1;
-    fin.beta2 = c->beta2; fin.state = n->state; fin.loss = la;
-    DpFinish dpf;
-    if (int rc = dp_finish_args(n, &dpf)) return rc;
-    if (n->dp_world >= 1) fin.loss.acc = nullptr;      // the GLOBAL loss is added on the optimiser side, from the exchanged tail
-    return grads_finish(n, B, &fin, st, 0, nullptr, &dpf);
-  }
-  if (apply == 1) {
-    const int tail_mode = tuning().finalize_ticket ? 1 : 2;     // 1: the old "last block finalises" form (A/B)
-    FinalizeArgs fin{};
-    fin.enable = tail_mode; fin.counter = reinterpret_cast<unsigned int*>(n->ws + n->off_counter);
-    fin.clip_norm = c->max_grad_norm; fin.grad_scale = c->grad_scale; fin.lr = c->lr; fin.beta1 = c->beta1;
-    fin.beta2 = c->beta2; fin.state = n->state; fin.loss = la;
-    bool fused = false;
-    if (tfk.done) {
-      XT_CHECK_HIP(hipStreamWaitEvent(st, n->tail_join, 0));
-      if (int rc = grads_finish(n, B, &fin, st, 2)) return rc;
-    } else {
-      if (tail_mode == 2 && !tov && tuning().tail_fused) {
-        fin.enable = 3;
-        fin.ap.params = n->params; fin.ap.m = n->m; fin.ap.v = n->v; fin.ap.grads = n->grads; fin.ap.eps = c->eps;
-      }
-      if (int rc = grads_finish(n, B, &fin, st, 0, &fused)) return rc;
-    }
-    if (fused) return 0;
-    if (tov & 2) {
-      if (int rc = net_apply_split(n, c->beta1, c->beta2, c->eps, c->max_grad_norm, c->grad_scale, st)) return rc;
-      return defer_join ? 0 : join_pending_update(n, st);
-    }
-    return net_apply(n, c->lr, c->beta1, c->beta2, c->eps, c->max_grad_norm, c->grad_scale, tail_mode == 1 ? 2 : 3,
-                     nullptr, st);
+  if (apply == 1 || apply == 3) {
+    const OptCfg o = ppo_opt(c);
+    // PPO alone honours finalize_ticket, and only in the full step
+    const int tail_mode = (apply == 1 && tuning().finalize_ticket) ? 1 : 2;     // 1: the old "last block finalises" form (A/B)
+    FinalizeArgs fin = finalize_args(n, tail_mode, /*ticket*/ true, o);      // PPO always passes the counter
+    LossArgs& la = fin.loss;
+    la.terms = n->ws + n->off_terms; la.B = B; la.ent_coef = c->ent_coef; la.critic_coef = c->critic_coef;
+    la.inv_b = inv_b; la.out = lo; la.acc = loss_acc;
+    if (apply == 3) return step_tail_dp(n, B, fin, st);
+    // (the fused tail replaces the enable == 2 form only)
+    return step_tail_apply(n, B, fin, o, tfk.done, tov, /*may_fuse*/ tail_mode == 2, defer_join, st, "xt_net_ppo_step");
   }
   if (int rc = grads_finish(n, B, nullptr, st)) return rc;
   // gradient only (data parallel): still report the local loss
@@ -692,9 +760,9 @@ static int impala_step(xt_net* n, const xt_impala_cfg* c, const void* obs, int n
   XT_REQUIRE(T >= 2 && nfr > 0 && nfr % T == 0, "xt_net_impala_step: n=%d must be a multiple of sample_batch_step=%d",
              nfr, T);
   XT_REQUIRE(nfr <= n->maxB, "xt_net_impala_step: %d frames > max batch %d", nfr, n->maxB);
-  const int ntraj = nfr / T, F = n->feat, A = n->A;
-  Layer& Lp = n->layers[n->t_end[0] - 1];
-  Layer& Lv = n->layers[n->t_end[n->n_trunks - 1] - 1];
+  const Heads hd = heads_of(n);
+  const int ntraj = nfr / T, F = hd.F, A = hd.A;
+  Layer& Lp = *hd.Lp;
   float* lo = n->ws + n->off_loss;   // [0] = loss, [4 .. 4 + n_traj) per-trajectory sums
   // fused form (ImpalaCnnOpt: one trunk, A <= 8, T <= 256): split-K finish + heads in one launch, v-trace + loss +
   // d(heads) + d(features) in the next, loss scalar in the gradient-reduction launch
@@ -709,13 +777,13 @@ static int impala_step(xt_net* n, const xt_impala_cfg* c, const void* obs, int n
   if (fused) {
     if (int rc = net_forward(n, obs, nullptr, nfr, false, st, true)) return rc;
     ImpalaHeadArgs h{};
-    h.feat = n->ws + Lp.act_off; h.wpi = n->params + n->pi_off; h.bpi = h.wpi + (int64_t)F * A;
-    h.wv = n->params + n->v_off; h.bv = h.wv + F; h.B = nfr; h.F = F; h.A = A;
+    h.feat = hd.f_pi; h.wpi = hd.wpi; h.bpi = hd.bpi;
+    h.wv = hd.wv; h.bv = hd.bv; h.B = nfr; h.F = F; h.A = A;
     h.logits = n->ws + n->off_logits; h.value = n->ws + n->off_value; h.act_feat = Lp.g.act;
     h.ksplit = 1; h.part_stride = (long long)nfr * F;
     if (Lp.last_ksplit > 1) {
       h.part = n->ws + Lp.part_off; h.ksplit = Lp.last_ksplit; h.feat_w = n->ws + Lp.act_off;
-      h.tbias = n->params + Lp.poff + (int64_t)Lp.K * Lp.g.N;
+      h.tbias = b_of(n, Lp);
     }
     int rc = launch_impala_heads_fwd(h, st);
     if (rc > 0) return rc;
@@ -724,7 +792,7 @@ static int impala_step(xt_net* n, const xt_impala_cfg* c, const void* obs, int n
     q.logits = n->ws + n->off_logits; q.baseline = n->ws + n->off_value; q.bp_logits = bp_logits; q.action = action;
     q.done = done; q.reward = reward; q.T = T; q.A = A; q.F = F; q.act_prev = Lp.g.act; q.gamma = c->gamma;
     q.dlogits = n->ws + n->off_dlogits; q.dbaseline = n->ws + n->off_dvalue; q.traj_loss = lo + 4;
-    q.feat = n->ws + Lp.act_off; q.wpi = n->params + n->pi_off; q.wv = n->params + n->v_off;
+    q.feat = hd.f_pi; q.wpi = hd.wpi; q.wv = hd.wv;
     q.dfeat = n->ws + Lp.dact_off;
     rc = launch_impala_vtrace_bwd(q, ntraj, st);
     if (rc > 0) return rc;
@@ -738,10 +806,7 @@ static int impala_step(xt_net* n, const xt_impala_cfg* c, const void* obs, int n
                                 nullptr, nullptr, st))
       return rc;
     if (loss_out) XT_CHECK_HIP(hipMemcpyAsync(loss_out, lo, sizeof(float), hipMemcpyDeviceToDevice, st));
-    if (int rc = launch_heads_dfeat(n->ws + (Lp.z_off >= 0 ? Lp.z_off : Lp.act_off), n->ws + (Lv.z_off >= 0 ? Lv.z_off : Lv.act_off), nfr, F, A, n->params + n->pi_off,
-                                    n->params + n->v_off, n->ws + n->off_dlogits, n->ws + n->off_dvalue, Lp.g.act,
-                                    n->ws + Lp.dact_off, n->ws + Lv.dact_off, st))
-      return rc;
+    if (int rc = heads_dfeat(n, nfr, st)) return rc;
   }
   const int tov = (apply == 1 && c->opt_type == XT_OPT_ADAM) ? tail_overlap_mode(n) : 0;
   TailFork tfk{n, nfr, st, false};
@@ -754,9 +819,8 @@ static int impala_step(xt_net* n, const xt_impala_cfg* c, const void* obs, int n
   }
   // step size bookkeeping (and the fused form's loss scalar) in an extra grads_finish block, clip factor inside the
   // Adam kernel: no finalize launch
-  FinalizeArgs fin{};
-  fin.enable = 2; fin.counter = nullptr; fin.clip_norm = c->grad_norm_clip; fin.grad_scale = c->grad_scale;
-  fin.lr = c->lr; fin.beta1 = c->beta1; fin.beta2 = c->beta2; fin.state = n->state; fin.lr_dev = lr_dev;
+  const OptCfg o = impala_opt(c, lr_dev);
+  FinalizeArgs fin = finalize_args(n, 2, /*ticket*/ false, o);      // (only the fused tail and apply == 3 need the ticket)
   if (loss_pending) {
     fin.loss.traj_loss = lo + 4; fin.loss.n_traj = ntraj; fin.loss.out = loss_out ? loss_out : lo; fin.loss.acc = loss_acc;
     fin.loss.acc_set = set_acc ? 1 : 0;
@@ -767,34 +831,35 @@ static int impala_step(xt_net* n, const xt_impala_cfg* c, const void* obs, int n
     if (!loss_pending) {      // (unfused heads: the loss scalar sits in lo[0] already; as a one-trajectory sum for the block)
       fin.loss.traj_loss = lo; fin.loss.n_traj = 1; fin.loss.out = loss_out ? loss_out : lo; fin.loss.acc = nullptr;
     }
-    DpFinish dpf;
-    if (int rc = dp_finish_args(n, &dpf)) return rc;
-    fin.counter = reinterpret_cast<unsigned int*>(n->ws + n->off_counter);      // (the scatter ticket of the fused exchange)
-    if (n->dp_world >= 1) fin.loss.acc = nullptr;
-    else if (!loss_pending) fin.loss.traj_loss = nullptr;      // (xt_impala_loss has added it to loss_acc itself)
-    return grads_finish(n, nfr, &fin, st, 0, nullptr, &dpf);
+    if (n->dp_world < 1 && !loss_pending) fin.loss.traj_loss = nullptr;      // (xt_impala_loss has added it to loss_acc itself)
+    return step_tail_dp(n, nfr, fin, st);
   }
-  bool fused_tail = false;
-  if (tfk.done) {
-    XT_CHECK_HIP(hipStreamWaitEvent(st, n->tail_join, 0));
-    if (int rc = grads_finish(n, nfr, &fin, st, 2)) return rc;
-  } else {
-    if (!tov && tuning().tail_fused && c->opt_type == XT_OPT_ADAM) {
-      fin.enable = 3; fin.counter = reinterpret_cast<unsigned int*>(n->ws + n->off_counter);
-      fin.ap.params = n->params; fin.ap.m = n->m; fin.ap.v = n->v; fin.ap.grads = n->grads; fin.ap.eps = c->eps;
-    }
-    if (int rc = grads_finish(n, nfr, &fin, st, 0, &fused_tail)) return rc;
+  // (the fused tail applies Adam: not for centred RMSProp)
+  return step_tail_apply(n, nfr, fin, o, tfk.done, tov, /*may_fuse*/ c->opt_type == XT_OPT_ADAM, defer_join, st,
+                         "xt_net_impala_step");
+}
+
+// HIP-event timing of `one`: warm once, record, run it `reps` times, record, synchronise -> *ms_out = mean milliseconds
+static int time_reps(int (*one)(xt_net*, void*, hipStream_t), xt_net* n, void* arg, int reps, float* ms_out,
+                     hipStream_t st) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int rc = [&]() -> int {
+    XT_CHECK_HIP(hipEventCreate(&e0));
+    XT_CHECK_HIP(hipEventCreate(&e1));
+    return one(n, arg, st);   // warm
+  }();
+  if (!rc) {
+    hipEventRecord(e0, st);
+    for (int i = 0; i < reps && !rc; ++i) rc = one(n, arg, st);
+    hipEventRecord(e1, st);
+    hipEventSynchronize(e1);
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, e0, e1);
+    *ms_out = ms / reps;
   }
-  if (fused_tail) return 0;
-  if (tov & 2) {
-    if (int rc = net_apply_split(n, c->beta1, c->beta2, c->eps, c->grad_norm_clip, c->grad_scale, st)) return rc;
-    return defer_join ? 0 : join_pending_update(n, st);
-  }
-  if (c->opt_type == XT_OPT_RMSPROP_CENTERED)
-    return launch_rmsprop_clip(n->params, n->grads, n->m, n->v, n->P, c->lr, c->rms_decay, c->rms_eps, n->state,
-                               n->ws + n->off_norm, n->norm_blocks, c->grad_norm_clip, c->grad_scale, st, lr_dev);
-  XT_REQUIRE(c->opt_type == XT_OPT_ADAM, "xt_net_impala_step: unknown opt_type %d", c->opt_type);
-  return net_apply(n, c->lr, c->beta1, c->beta2, c->eps, c->grad_norm_clip, c->grad_scale, 3, nullptr, st);
+  if (e0) hipEventDestroy(e0);
+  if (e1) hipEventDestroy(e1);
+  return rc;
 }
 
 }  // namespace xt
@@ -977,12 +1042,10 @@ int xt_net_act(xt_net* n, const xt_act_cfg* cfg, const void* obs, const int32_t*
   hipStream_t st = xt::as_stream(stream);
   if (int rc = xt::net_forward(n, obs, idx, B, false, st)) return rc;
   xt::ActHeadArgs a;
-  const int F = n->feat;
-  a.f_pi = n->ws + n->layers[n->t_end[0] - 1].act_off;
-  a.f_v = n->ws + n->layers[n->t_end[n->n_trunks - 1] - 1].act_off;
-  a.B = B; a.F = F; a.A = n->A;
-  a.wpi = n->params + n->pi_off; a.bpi = n->params + n->pi_off + (int64_t)F * n->A;
-  a.wv = n->params + n->v_off; a.bv = n->params + n->v_off + F;
+  const xt::Heads hd = xt::heads_of(n);
+  a.f_pi = hd.f_pi; a.f_v = hd.f_v;
+  a.B = B; a.F = hd.F; a.A = hd.A;
+  a.wpi = hd.wpi; a.bpi = hd.bpi; a.wv = hd.wv; a.bv = hd.bv;
   a.log_std = n->action_type == XT_ACTION_DIAG_GAUSSIAN ? n->params + n->logstd_off : nullptr;
   a.noise = noise;
   a.seed_lo = (uint32_t)cfg->seed; a.seed_hi = (uint32_t)(cfg->seed >> 32);
@@ -1025,11 +1088,10 @@ static int ppo_train_enqueue(xt_net* net, const xt_ppo_cfg* c, const void* obs, 
                    c->shard_world);
         XT_REQUIRE(net->xchg, "xt_net_ppo_train: sharded minibatches need a gradient exchange (xt_net_set_rccl / "
                               "xt_net_set_grad_exchange)");
-        const int base = B / c->shard_world, rem = B % c->shard_world;
-        const int b0 = c->shard_rank * base + (c->shard_rank < rem ? c->shard_rank : rem);
+        int b0 = 0;
         cc.global_batch = B;
+        xt::shard_slice(c->shard_rank, c->shard_world, B, &b0, &B);
         rows += b0;
-        B = base + (c->shard_rank < rem ? 1 : 0);
       }
       if (!net->xchg) {
         if (int rc = xt::ppo_step(net, &cc, obs, rows, B, action, old_logp, adv, old_v,
@@ -1063,11 +1125,7 @@ static int ppo_train_enqueue(xt_net* net, const xt_ppo_cfg* c, const void* obs, 
       // rows and loss share -- the optimiser's block 0 adds the GLOBAL loss, no host collective per train; xt_net_set_direct:
       // the gradient reduction scattered straight into the owners' inboxes, dp_exchange is ONE small reduce launch that also
       // leaves the squared-norm partials, Adam reads the exchange block: three launches after the backward pass.
-      xt::DpApply da;
-      if (int rc = xt::dp_exchange(net, st, loss_acc, &da)) return rc;
-      if (int rc = xt::launch_adam_clip(net->params, da.g, net->m, net->v, net->P, cc.beta1, cc.beta2, cc.eps, net->state,
-                                        da.partial, da.npartial, cc.max_grad_norm, cc.grad_scale, st, &da.step, da.block_cap))
-        return rc;
+      if (int rc = xt::dp_apply(net, xt::ppo_opt(&cc), loss_acc, st, "xt_net_ppo_train")) return rc;
     }
   }
   return xt::join_pending_update(net, st);
@@ -1135,11 +1193,11 @@ static int impala_train_enqueue(xt_net* net, const xt_impala_cfg* c, const void*
       // strict sharding (ABI >= 10): whole-trajectory shard of this chunk (xingtian_amd/parallel.py::shard_range)
       XT_REQUIRE(c->shard_rank >= 0 && c->shard_rank < c->shard_world, "xt_net_impala_train: shard_rank %d outside [0,%d)",
                  c->shard_rank, c->shard_world);
-      const int T = c->sample_batch_step, ntraj = nfr / T;
-      const int base = ntraj / c->shard_world, rem = ntraj % c->shard_world;
-      const int b0 = c->shard_rank * base + (c->shard_rank < rem ? c->shard_rank : rem);
+      const int T = c->sample_batch_step;
+      int b0 = 0, ntraj_s = 0;
+      xt::shard_slice(c->shard_rank, c->shard_world, nfr / T, &b0, &ntraj_s);
       lo_s = lo + b0 * T;
-      nfr_s = (base + (c->shard_rank < rem ? 1 : 0)) * T;
+      nfr_s = ntraj_s * T;
     }
     if (nfr_s > 0) {
       // gradient of this rank's trajectories + the loss scalar + the step-size advance (lr_schedule's value is read on the
@@ -1159,21 +1217,7 @@ static int impala_train_enqueue(xt_net* net, const xt_impala_cfg* c, const void*
       if (net->direct && net->dp_world >= 1)
         if (int rc = xt::direct_launch_scatter(net->direct, net->grads, xc, st)) return rc;
     }
-    // exchange -> squared norm of the EXCHANGED gradient -> the configured optimiser (Adam, or centred RMSProp), every block
-    // deriving the clip factor from the partials itself
-    xt::DpApply da;
-    if (int rc = xt::dp_exchange(net, st, loss_acc, &da)) return rc;
-    if (c->opt_type == XT_OPT_RMSPROP_CENTERED) {
-      if (int rc = xt::launch_rmsprop_clip(net->params, da.g, net->m, net->v, net->P, c->lr, c->rms_decay, c->rms_eps,
-                                           net->state, da.partial, da.npartial, c->grad_norm_clip, c->grad_scale, st,
-                                           lr_dev, &da.step, da.block_cap))
-        return rc;
-    } else {
-      XT_REQUIRE(c->opt_type == XT_OPT_ADAM, "xt_net_impala_train: unknown opt_type %d", c->opt_type);
-      if (int rc = xt::launch_adam_clip(net->params, da.g, net->m, net->v, net->P, c->beta1, c->beta2, c->eps, net->state,
-                                        da.partial, da.npartial, c->grad_norm_clip, c->grad_scale, st, &da.step, da.block_cap))
-        return rc;
-    }
+    if (int rc = xt::dp_apply(net, xt::impala_opt(c, lr_dev), loss_acc, st, "xt_net_impala_train")) return rc;
   }
   return xt::join_pending_update(net, st);
 }
@@ -1554,12 +1598,7 @@ int xt_net_keras_impala_step(xt_net* n, const void* obs, const int32_t* idx, int
                                     ent_coef, n->ws + n->off_dlogits, n->ws + n->off_dvalue, lo, loss_acc, st))
     return rc;
   if (loss_out) XT_CHECK_HIP(hipMemcpyAsync(loss_out, lo, 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-  xt::Layer& Lp = n->layers[n->t_end[0] - 1];
-  xt::Layer& Lv = n->layers[n->t_end[n->n_trunks - 1] - 1];
-  if (int rc = xt::launch_heads_dfeat(n->ws + (Lp.z_off >= 0 ? Lp.z_off : Lp.act_off), n->ws + (Lv.z_off >= 0 ? Lv.z_off : Lv.act_off), B, n->feat, n->A, n->params + n->pi_off,
-                                      n->params + n->v_off, n->ws + n->off_dlogits, n->ws + n->off_dvalue, Lp.g.act,
-                                      n->ws + Lp.dact_off, n->ws + Lv.dact_off, st))
-    return rc;
+  if (int rc = xt::heads_dfeat(n, B, st)) return rc;
   if (int rc = xt::trunk_backward(n, obs, idx, B, st)) return rc;
   return xt::grads_finish(n, B, nullptr, st);
 }
@@ -1694,39 +1733,18 @@ int xt_net_apply(xt_net* n, float lr, float beta1, float beta2, float eps, float
 
 int xt_net_time_tail(xt_net* n, float lr, float clip_norm, int32_t reps, float* ms_out, void* stream) {
   XT_REQUIRE(n && n->params && n->ws && ms_out && reps > 0, "xt_net_time_tail: bad arguments");
-  hipStream_t st = xt::as_stream(stream);
-  auto one = [&]() -> int {
-    xt::FinalizeArgs fin{};
-    fin.enable = 2; fin.counter = reinterpret_cast<unsigned int*>(n->ws + n->off_counter);
-    fin.clip_norm = clip_norm; fin.grad_scale = 1.f; fin.lr = lr; fin.beta1 = 0.9f; fin.beta2 = 0.999f; fin.state = n->state;
+  xt::OptCfg opt{XT_OPT_ADAM, lr, 0.9f, 0.999f, 1e-8f, 0.f, 0.f, clip_norm, 1.f, nullptr};
+  auto one = [](xt_net* n, void* arg, hipStream_t st) -> int {
+    const xt::OptCfg& o = *static_cast<xt::OptCfg*>(arg);
+    const xt::FinalizeArgs fin = xt::finalize_args(n, 2, /*ticket*/ true, o);
     if (n->xchg || n->dp_world >= 1) {
-      xt::DpFinish dpf;
-      if (int rc = xt::dp_finish_args(n, &dpf)) return rc;
-      if (int rc = xt::grads_finish(n, 1, &fin, st, 0, nullptr, &dpf)) return rc;
-      xt::DpApply da;
-      if (int rc = xt::dp_exchange(n, st, nullptr, &da)) return rc;
-      return xt::launch_adam_clip(n->params, da.g, n->m, n->v, n->P, 0.9f, 0.999f, 1e-8f, n->state, da.partial, da.npartial,
-                                  clip_norm, 1.f, st, &da.step, da.block_cap);
+      if (int rc = xt::step_tail_dp(n, 1, fin, st)) return rc;
+      return xt::dp_apply(n, o, nullptr, st, "xt_net_time_tail");
     }
-    if (int rc = xt::grads_finish(n, 1, &fin, st)) return rc;
-    return xt::net_apply(n, lr, 0.9f, 0.999f, 1e-8f, clip_norm, 1.f, 3, nullptr, st);
+    return xt::step_tail_apply(n, 1, fin, o, /*forked*/ false, /*tov*/ 0, /*may_fuse*/ false, /*defer_join*/ false, st,
+                               "xt_net_time_tail");
   };
-  hipEvent_t e0, e1;
-  XT_CHECK_HIP(hipEventCreate(&e0));
-  XT_CHECK_HIP(hipEventCreate(&e1));
-  int rc = one();
-  if (!rc) {
-    hipEventRecord(e0, st);
-    for (int i = 0; i < reps && !rc; ++i) rc = one();
-    hipEventRecord(e1, st);
-    hipEventSynchronize(e1);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
-    *ms_out = ms / reps;
-  }
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  return rc;
+  return xt::time_reps(one, n, &opt, reps, ms_out, xt::as_stream(stream));
 }
 
 int xt_net_layer_offsets(const xt_net* n, int32_t layer, int64_t* out4) {
@@ -1741,51 +1759,29 @@ int xt_net_time_layer(xt_net* n, int32_t layer, int32_t which, const void* obs, 
   XT_REQUIRE(n && n->params && n->ws && ms_out, "xt_net_time_layer: bad arguments");
   XT_REQUIRE(layer >= 0 && layer < (int)n->layers.size() && reps > 0 && B > 0 && B <= n->maxB,
              "xt_net_time_layer: bad layer/reps/batch");
-  hipStream_t st = xt::as_stream(stream);
-  xt::Layer& L = n->layers[layer];
-  bool first = false;
-  for (int tr = 0; tr < n->n_trunks; ++tr) first |= (layer == n->t_begin[tr]);
-  const void* x = first ? obs : (const void*)(n->ws + n->layers[layer - 1].act_off);
+  const bool first = (layer == n->t_begin[n->layers[layer].trunk]);
   XT_REQUIRE(which == 0 || which == 1 || ((which == 2 || which == 3) && !first), "xt_net_time_layer: bad kernel selector");
-  hipEvent_t e0, e1;
-  XT_CHECK_HIP(hipEventCreate(&e0));
-  XT_CHECK_HIP(hipEventCreate(&e1));
-  int rc = 0;
-  auto one = [&]() -> int {
-    if (which == 0) {
+  struct Call { int layer, which; bool first; const void* obs; const int32_t* idx; int B; };
+  Call call{layer, which, first, obs, idx, B};
+  auto one = [](xt_net* n, void* arg, hipStream_t st) -> int {
+    const Call& c = *static_cast<Call*>(arg);
+    xt::Layer& L = n->layers[c.layer];
+    if (c.which == 0) {
       // a trunk's last layer runs as the update runs it: split-K partials left for the fused head kernel to finish
       // (timing it with its stand-alone finish launch charged the layer for a kernel the update never launches: 13.7 vs
       // 7.9 us in-graph for ImpalaCnnOpt's 11x11 layer, round 3)
       const bool defer = L.part_off >= 0 && L.z_off < 0 && xt::tuning().defer_splitk != 0;
-      return xt::launch_fwd(&L.g, first ? &n->xf : nullptr, B, x, first ? idx : nullptr, n->params + L.poff,
-                            n->params + L.poff + (int64_t)L.K * L.g.N, n->ws + L.act_off,
-                            n->ws + (defer ? L.part_off : n->off_partial), xt::fwd_split(L, B), st,
-                            defer ? &L.last_ksplit : nullptr,
-                            L.mask_off >= 0 ? reinterpret_cast<uint32_t*>(n->ws + L.mask_off) : nullptr, &L.mask_valid);
+      const void* x = c.first ? c.obs : (const void*)(n->ws + n->layers[c.layer - 1].act_off);
+      return xt::layer_forward(n, L, &L.g, c.first, c.B, x, c.idx, n->ws + L.act_off, defer, st);
     }
-    if (which == 1)
-      return xt::launch_wgrad(&L.g, first ? &n->xf : nullptr, B, x, first ? idx : nullptr, n->ws + L.dact_off,
-                              n->grads + L.poff, n->ws + L.slab_off, xt::wgrad_split(L, B), st, 0, &L.last_msplit,
-                              L.slab_cap);
-    xt::Layer& Lp = n->layers[layer - 1];
-    if (which == 3)   // the fused per-layer backward launch (dgrad + wgrad) used by the update loop
-      return xt::launch_bwd_layer(xt::bwd_layer_call(n, layer, B, st));
-    return xt::launch_dgrad(&L.g, B, n->ws + L.dact_off, n->params + L.poff, n->ws + Lp.act_off, Lp.g.act,
+    if (c.which == 1) return xt::layer_wgrad(n, c.layer, c.first, c.obs, c.idx, c.B, st);
+    xt::Layer& Lp = n->layers[c.layer - 1];
+    if (c.which == 3)   // the fused per-layer backward launch (dgrad + wgrad) used by the update loop
+      return xt::launch_bwd_layer(xt::bwd_layer_call(n, c.layer, c.B, st));
+    return xt::launch_dgrad(&L.g, c.B, n->ws + L.dact_off, xt::w_of(n, L), n->ws + Lp.act_off, Lp.g.act,
                             n->ws + Lp.dact_off, st);
   };
-  rc = one();   // warm
-  if (!rc) {
-    hipEventRecord(e0, st);
-    for (int i = 0; i < reps && !rc; ++i) rc = one();
-    hipEventRecord(e1, st);
-    hipEventSynchronize(e1);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, e0, e1);
-    *ms_out = ms / reps;
-  }
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  return rc;
+  return xt::time_reps(one, n, &call, reps, ms_out, xt::as_stream(stream));
 }
 
 }  // extern "C"
