@@ -479,6 +479,46 @@ int xt_net_ppo_train(xt_net* net, const xt_ppo_cfg* cfg, const void* obs, int32_
                      const double* adv, const float* old_v, const double* target_v,
                      float* loss_acc, int32_t use_graph, void* stream);
 
+/* Per-update PPO training diagnostics, accumulated on the device inside the step's own launches (appended under ABI 12;
+ * opt-in).  `stats`: XT_TRAIN_STATS_DOUBLES doubles, `rows`: [max_batch, 4] floats of scratch (16-byte aligned), both
+ * device memory owned by the caller like every other buffer of the net; xt_net_workspace_bytes does not change.  NULL,
+ * NULL switches the diagnostics off (the default): every launch is then the one of a net that never had them.  Refused
+ * while the net has a data-parallel tail or a gradient exchange hook (the row statistics would be rank-local).
+ *
+ * With the buffers set, the head launch of every PPO step also stores one float4 per sample,
+ *     rows[b] = {old_logp - logp, (!in_rng) + 2 * (!in_v), tv, tv - v}
+ * (its own clip predicates; tv = the float32-rounded target it uses), the loss reduction of the step -- the extra block of
+ * the gradient-reduction launch in the default tail form, off the critical path; on it in the ticket form and behind a
+ * gradient-only step -- reduces the four columns (tv and tv - v also squared, products in double) with the fixed-order
+ * double tree of the loss terms, and the thread that writes the pre-clip global norm into adam_state[4] adds it.  Every
+ * slot of `stats` is a sum over the SGD steps since the block was cleared, except XT_TRAIN_STATS_GNORM_MAX (a maximum);
+ * the sums are taken in one fixed order, so a replayed hipGraph and the eager call give the same bits.  xt_net_ppo_train
+ * clears the block at its start; xt_net_ppo_step only accumulates (its caller clears), and with apply == 0 it leaves the
+ * three gradient-norm slots alone (no norm is formed).  The pointers are part of xt_net_ppo_train's hipGraph key. */
+#define XT_TRAIN_STATS_DOUBLES 16
+#define XT_TRAIN_STATS_STEPS 0          /* SGD steps                                                        */
+#define XT_TRAIN_STATS_ROWS 1           /* rows visited (sum of the minibatch sizes)                        */
+#define XT_TRAIN_STATS_SURR 2           /* sum of the steps' mean clipped surrogate (float, as the loss)    */
+#define XT_TRAIN_STATS_ENT 3            /* ... mean entropy                                                 */
+#define XT_TRAIN_STATS_VF 4             /* ... critic loss                                                  */
+#define XT_TRAIN_STATS_KL 5             /* sum over rows of old_logp - logp                                 */
+#define XT_TRAIN_STATS_CLIPPED 6        /* rows with the ratio outside [1 - clip, 1 + clip]                 */
+#define XT_TRAIN_STATS_VF_CLIPPED 7     /* rows with |v - old_v| > vf_clip                                  */
+#define XT_TRAIN_STATS_TV 8             /* sum over rows of tv                                              */
+#define XT_TRAIN_STATS_TV_SQ 9          /* ... tv^2                                                         */
+#define XT_TRAIN_STATS_ERR 10           /* ... tv - v                                                       */
+#define XT_TRAIN_STATS_ERR_SQ 11        /* ... (tv - v)^2                                                   */
+#define XT_TRAIN_STATS_GNORM_SUM 12     /* sum over steps of the pre-clip global gradient norm              */
+#define XT_TRAIN_STATS_GNORM_MAX 13     /* its maximum                                                      */
+#define XT_TRAIN_STATS_GNORM_CLIPPED 14 /* steps with the norm above max_grad_norm                          */
+#define XT_TRAIN_STATS_RESERVED 15      /* 0                                                                */
+int xt_net_set_train_stats(xt_net* net, double* stats, float* rows);
+/* Which head / loss kernel the most recent PPO step of this net launched (diagnostic): the XT_HEAD_PATH_PPO_FUSED word
+ * of xt_ppo_heads_fused_ex for the fused kernel, else one of the two codes below; 0 before the first step. */
+#define XT_NET_HEAD_PLAIN 0x10000       /* heads forward + ppo_loss_kernel + heads d(features)              */
+#define XT_NET_HEAD_GAUSS 0x20000       /* heads forward + ppo_loss_gauss_kernel + heads d(features)        */
+int32_t xt_net_last_head_path(const xt_net* net);
+
 /* Gradient exchange hook of xt_net_ppo_train (ABI >= 4): the reference's learner is single-process
  * (its grad_communicate host averaging, xt/framework/trainer.py:89-92, is dead code); data parallelism is this
  * library's own extension.  When a hook is set, every SGD step of xt_net_ppo_train runs as

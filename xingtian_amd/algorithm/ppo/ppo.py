@@ -87,6 +87,11 @@ class PPO(Algorithm):
         self._forget_rollout()
         return loss
 
+    def train_stats(self):
+        """The model's diagnostics of the last update (``model_config.TRAIN_STATS``), or None"""
+        fn = getattr(self.actor, "train_stats", None)
+        return fn() if fn is not None else None
+
     def predict(self, state):
         """One state (or a list of per-agent states) -> a batch for ``Model.predict``."""
         if isinstance(state, (list, tuple)):

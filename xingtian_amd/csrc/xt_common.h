@@ -196,6 +196,10 @@ struct LossArgs {
   const float* traj_loss;
   int n_traj;
   int acc_set;          // != 0: this is the FIRST chunk of a train -- acc = {loss, 1} instead of +=: no memset node in front of it
+  // xt_net_set_train_stats (both null: off): the head kernel's per-sample diagnostic rows [B,4] = {old_logp - logp,
+  // (!in_rng) + 2 * (!in_v), tv, tv - v} and the XT_TRAIN_STATS_DOUBLES running sums they are reduced into
+  const float* rows;
+  double* stats;
 };
 
 // One entry per parameter block: sum `nslab` partial slabs (fixed order) into dst and accumulate the
@@ -231,6 +235,7 @@ struct PpoHeadArgs {
   float *feat_pi_w, *feat_v_w;
   int ksplit_pi, ksplit_v, act_feat;
   long long part_stride;
+  float* rows;          // xt_net_set_train_stats: [B,4] per-sample diagnostic rows (LossArgs::rows), written by the STATS instances
 };
 
 // IMPALA (ImpalaCnnOpt, one shared trunk): heads forward with the deferred split-K finish of the last trunk layer

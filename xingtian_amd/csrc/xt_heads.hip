@@ -38,6 +38,8 @@ __global__ __launch_bounds__(256) void heads_fwd_kernel(const float* __restrict_
 
 // ---------------------------------------------------------------- PPO loss
 // one thread per sample (A is tiny); tf_dist.py:103-113 + model/ppo/__init__.py:4-25
+// STATS (xt_net_set_train_stats): also rows[b] = {old_logp - logp, (!in_rng) + 2 * (!in_v), tv, tv - v}, one 16-byte store
+template <bool STATS>
 __global__ __launch_bounds__(256) void ppo_loss_kernel(const float* __restrict__ logits, const float* __restrict__ value,
                                                        int B, int A, const int32_t* __restrict__ idx,
                                                        const int32_t* __restrict__ action, const float* __restrict__ old_logp,
@@ -45,7 +47,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const float* __restrict__
                                                        const double* __restrict__ target_v, float clip_ratio,
                                                        float ent_coef, float vf_clip, float critic_coef, float inv_b,
                                                        float* __restrict__ dlogits, float* __restrict__ dvalue,
-                                                       float* __restrict__ terms) {
+                                                       float* __restrict__ terms, float* __restrict__ rows) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
   const int s = idx ? idx[b] : b;
@@ -65,7 +67,8 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const float* __restrict__
   const float advf = (float)adv[s];            // float32 placeholder cast (ppo.py:65-68)
   const float tv = (float)target_v[s];
   const float ov = old_v[s];
-  const float ratio = expf(logp - old_logp[s]);
+  const float olp = old_logp[s];
+  const float ratio = expf(logp - olp);
   const float surr1 = ratio * advf;
   const float rc = fminf(fmaxf(ratio, 1.f - clip_ratio), 1.f + clip_ratio);
   const float surr2 = rc * advf;
@@ -94,12 +97,15 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const float* __restrict__
   }
   float* tm = terms + (size_t)b * 4;
   tm[0] = surr; tm[1] = ent; tm[2] = fmaxf(vf1, vf2); tm[3] = 0.f;
+  if (STATS)
+    reinterpret_cast<float4*>(rows)[b] = make_float4(olp - logp, (in_rng ? 0.f : 1.f) + (in_v ? 0.f : 2.f), tv, tv - v);
 }
 
 // The same loss over DiagGaussianDist (xt/model/tf_dist.py:47-87; dist_param = concat([pi_latent,
 // pi_latent*0 + pi_logstd]), xt/model/ppo/ppo.py:75-79).  One thread per sample.  dls_rows [B][ldls] gets every
 // sample's share of d loss / d pi_logstd (surrogate part + the -ent_coef * mean(entropy) part); the gradient is
-// their fixed-order sum (grads_finish_kernel treats the rows as B partial slabs).
+// their fixed-order sum (grads_finish_kernel treats the rows as B partial slabs).  STATS: as ppo_loss_kernel.
+template <bool STATS>
 __global__ __launch_bounds__(256) void ppo_loss_gauss_kernel(const float* __restrict__ mean, const float* __restrict__ log_std,
                                                              const float* __restrict__ value, int B, int A,
                                                              const int32_t* __restrict__ idx,
@@ -110,7 +116,7 @@ __global__ __launch_bounds__(256) void ppo_loss_gauss_kernel(const float* __rest
                                                              float ent_coef, float vf_clip, float critic_coef, float inv_b,
                                                              float* __restrict__ dmean, float* __restrict__ dvalue,
                                                              float* __restrict__ dls_rows, int ldls,
-                                                             float* __restrict__ terms) {
+                                                             float* __restrict__ terms, float* __restrict__ rows) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
   const int s = idx ? idx[b] : b;
@@ -129,7 +135,8 @@ __global__ __launch_bounds__(256) void ppo_loss_gauss_kernel(const float* __rest
   const float advf = (float)adv[s];
   const float tv = (float)target_v[s];
   const float ov = old_v[s];
-  const float ratio = expf(logp - old_logp[s]);
+  const float olp = old_logp[s];
+  const float ratio = expf(logp - olp);
   const float surr1 = ratio * advf;
   const float rc = fminf(fmaxf(ratio, 1.f - clip_ratio), 1.f + clip_ratio);
   const float surr2 = rc * advf;
@@ -156,6 +163,8 @@ __global__ __launch_bounds__(256) void ppo_loss_gauss_kernel(const float* __rest
   }
   float* tm = terms + (size_t)b * 4;
   tm[0] = surr; tm[1] = ent; tm[2] = fmaxf(vf1, vf2); tm[3] = 0.f;
+  if (STATS)
+    reinterpret_cast<float4*>(rows)[b] = make_float4(olp - logp, (in_rng ? 0.f : 1.f) + (in_v ? 0.f : 2.f), tv, tv - v);
 }
 
 // single block, fixed-order tree: loss scalars from the per-sample terms
@@ -370,7 +379,9 @@ __device__ __forceinline__ float wave_max(float v) {
 constexpr int kHeadMaxA = 8;          // actions handled by the fused kernel (A <= 8)
 constexpr int kMaxHeadSplit = 16;     // split-K partial slabs the fused head kernel can finish
 
-template <int NQ, bool PART, bool SHARED>
+// STATS (xt_net_set_train_stats): lane 0 stores one more float4 per sample, the diagnostic row {old_logp - logp,
+// (!in_rng) + 2 * (!in_v), tv, tv - v} -- values the wave holds anyway, no load added; STATS = false is today's code.
+template <int NQ, bool PART, bool SHARED, bool STATS = false>
 __global__ __launch_bounds__(64) void ppo_heads_fused_kernel(const PpoHeadArgs p) {
   const int lane = threadIdx.x;
   const int b = blockIdx.x;
@@ -512,6 +523,8 @@ __global__ __launch_bounds__(64) void ppo_heads_fused_kernel(const PpoHeadArgs p
     p.dvalue[b] = dv;
     float* tm = p.terms + (size_t)b * 4;
     tm[0] = fminf(surr1, surr2); tm[1] = ent; tm[2] = fmaxf(vf1, vf2); tm[3] = 0.f;
+    if (STATS)
+      reinterpret_cast<float4*>(p.rows)[b] = make_float4(olp - logp, (in_rng ? 0.f : 1.f) + (in_v ? 0.f : 2.f), tv, tv - v);
   }
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
@@ -552,15 +565,18 @@ int launch_ppo_heads_fused(const PpoHeadArgs& a, hipStream_t st) {
   if (part && (a.ksplit_pi > kMaxHeadSplit || (!shared && (!a.part_v || a.ksplit_v > kMaxHeadSplit)))) return -1;
   const int nq = (a.F + 63) / 64;
   const dim3 grid(a.B), blk(64);
-#define XT_HEAD(NQV)                                                                                         \
-  do {                                                                                                       \
-    if (part && shared) hipLaunchKernelGGL((ppo_heads_fused_kernel<NQV, true, true>), grid, blk, 0, st, a);  \
-    else if (part) hipLaunchKernelGGL((ppo_heads_fused_kernel<NQV, true, false>), grid, blk, 0, st, a);      \
-    else if (shared) hipLaunchKernelGGL((ppo_heads_fused_kernel<NQV, false, true>), grid, blk, 0, st, a);    \
-    else hipLaunchKernelGGL((ppo_heads_fused_kernel<NQV, false, false>), grid, blk, 0, st, a);               \
+#define XT_HEAD_S(NQV, ST)                                                                                       \
+  do {                                                                                                           \
+    if (part && shared) hipLaunchKernelGGL((ppo_heads_fused_kernel<NQV, true, true, ST>), grid, blk, 0, st, a);  \
+    else if (part) hipLaunchKernelGGL((ppo_heads_fused_kernel<NQV, true, false, ST>), grid, blk, 0, st, a);      \
+    else if (shared) hipLaunchKernelGGL((ppo_heads_fused_kernel<NQV, false, true, ST>), grid, blk, 0, st, a);    \
+    else hipLaunchKernelGGL((ppo_heads_fused_kernel<NQV, false, false, ST>), grid, blk, 0, st, a);               \
   } while (0)
+#define XT_HEAD(NQV) do { if (a.rows) XT_HEAD_S(NQV, true); else XT_HEAD_S(NQV, false); } while (0)
+  XT_REQUIRE(!a.rows || ((uintptr_t)a.rows & 15) == 0, "ppo_heads_fused: the diagnostic rows must be 16-byte aligned");
   if (nq <= 1) XT_HEAD(1); else if (nq <= 2) XT_HEAD(2); else if (nq <= 4) XT_HEAD(4); else XT_HEAD(8);
 #undef XT_HEAD
+#undef XT_HEAD_S
   last_path() = head_path_bits(XT_HEAD_PATH_PPO_FUSED, nq <= 1 ? 1 : nq <= 2 ? 2 : nq <= 4 ? 4 : 8, part, shared, 0);
   XT_LAUNCH_CHECK();
   return 0;
@@ -1136,11 +1152,35 @@ int launch_ppo_loss_gauss(const float* mean, const float* log_std, const float* 
                           const float* action, const float* old_logp, const double* adv, const float* old_v,
                           const double* target_v, float clip_ratio, float ent_coef, float vf_clip, float critic_coef,
                           float inv_b, float* dmean, float* dvalue, float* dls_rows, int ldls, float* terms,
-                          hipStream_t st) {
+                          hipStream_t st, float* rows) {
   XT_REQUIRE(B > 0 && A > 0 && ldls >= A && mean && log_std && action && dls_rows, "xt_ppo_loss_gauss: bad arguments");
-  hipLaunchKernelGGL(ppo_loss_gauss_kernel, dim3((B + 255) / 256), dim3(256), 0, st, mean, log_std, value, B, A, idx,
-                     action, old_logp, adv, old_v, target_v, clip_ratio, ent_coef, vf_clip, critic_coef, inv_b, dmean,
-                     dvalue, dls_rows, ldls, terms);
+  XT_REQUIRE(((uintptr_t)rows & 15) == 0, "xt_ppo_loss_gauss: the diagnostic rows must be 16-byte aligned");
+  if (rows)
+    hipLaunchKernelGGL(ppo_loss_gauss_kernel<true>, dim3((B + 255) / 256), dim3(256), 0, st, mean, log_std, value, B, A, idx,
+                       action, old_logp, adv, old_v, target_v, clip_ratio, ent_coef, vf_clip, critic_coef, inv_b, dmean,
+                       dvalue, dls_rows, ldls, terms, rows);
+  else
+    hipLaunchKernelGGL(ppo_loss_gauss_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, st, mean, log_std, value, B, A, idx,
+                       action, old_logp, adv, old_v, target_v, clip_ratio, ent_coef, vf_clip, critic_coef, inv_b, dmean,
+                       dvalue, dls_rows, ldls, terms, rows);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_ppo_loss(const float* logits, const float* value, int B, int A, const int32_t* idx, const int32_t* action,
+                    const float* old_logp, const double* adv, const float* old_v, const double* target_v,
+                    float clip_ratio, float ent_coef, float vf_clip, float critic_coef, float inv_b, float* dlogits,
+                    float* dvalue, float* terms, float* rows, hipStream_t st) {
+  XT_REQUIRE(B > 0 && A > 0, "xt_ppo_loss: bad sizes");
+  XT_REQUIRE(((uintptr_t)rows & 15) == 0, "xt_ppo_loss: the diagnostic rows must be 16-byte aligned");
+  if (rows)
+    hipLaunchKernelGGL(ppo_loss_kernel<true>, dim3((B + 255) / 256), dim3(256), 0, st, logits, value, B, A, idx, action,
+                       old_logp, adv, old_v, target_v, clip_ratio, ent_coef, vf_clip, critic_coef, inv_b, dlogits, dvalue,
+                       terms, rows);
+  else
+    hipLaunchKernelGGL(ppo_loss_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, st, logits, value, B, A, idx, action,
+                       old_logp, adv, old_v, target_v, clip_ratio, ent_coef, vf_clip, critic_coef, inv_b, dlogits, dvalue,
+                       terms, rows);
   XT_LAUNCH_CHECK();
   return 0;
 }
@@ -1313,12 +1353,8 @@ int xt_ppo_loss(const float* logits, const float* value, int32_t B, int32_t A, c
                 const int32_t* action, const float* old_logp, const double* adv, const float* old_v,
                 const double* target_v, float clip_ratio, float ent_coef, float vf_clip, float critic_coef,
                 float inv_b, float* dlogits, float* dvalue, float* loss_terms, void* stream) {
-  XT_REQUIRE(B > 0 && A > 0, "xt_ppo_loss: bad sizes");
-  hipLaunchKernelGGL(xt::ppo_loss_kernel, dim3((B + 255) / 256), dim3(256), 0, xt::as_stream(stream), logits, value, B, A,
-                     idx, action, old_logp, adv, old_v, target_v, clip_ratio, ent_coef, vf_clip, critic_coef, inv_b,
-                     dlogits, dvalue, loss_terms);
-  XT_LAUNCH_CHECK();
-  return 0;
+  return xt::launch_ppo_loss(logits, value, B, A, idx, action, old_logp, adv, old_v, target_v, clip_ratio, ent_coef, vf_clip,
+                             critic_coef, inv_b, dlogits, dvalue, loss_terms, nullptr, xt::as_stream(stream));
 }
 
 int xt_ppo_loss_gauss(const float* mean, const float* log_std, const float* value, int32_t B, int32_t A,
@@ -1328,7 +1364,7 @@ int xt_ppo_loss_gauss(const float* mean, const float* log_std, const float* valu
                       float* loss_terms, void* stream) {
   return xt::launch_ppo_loss_gauss(mean, log_std, value, B, A, idx, action, old_logp, adv, old_v, target_v, clip_ratio,
                                    ent_coef, vf_clip, critic_coef, inv_b, dmean, dvalue, dlogstd_rows, A, loss_terms,
-                                   xt::as_stream(stream));
+                                   xt::as_stream(stream), nullptr);
 }
 
 namespace xt {
@@ -1589,6 +1625,7 @@ int xt_ppo_heads_fused_ex(const float* f_pi, const float* f_v, const float* part
   h.df_pi = df_pi; h.df_v = sh ? df_pi : df_v;
   h.part_pi = h.part_v = nullptr; h.tbias_pi = h.tbias_v = nullptr; h.feat_pi_w = h.feat_v_w = nullptr;
   h.ksplit_pi = h.ksplit_v = 1; h.act_feat = act_feat; h.part_stride = part ? (long long)part_stride : (long long)B * F;
+  h.rows = nullptr;
   if (part) {
     h.part_pi = part_pi; h.ksplit_pi = ksplit_pi; h.feat_pi_w = feat_pi_w; h.tbias_pi = tbias_pi;
     if (!sh) { h.part_v = part_v; h.ksplit_v = ksplit_v; h.feat_v_w = feat_v_w; h.tbias_v = tbias_v; }

@@ -94,7 +94,12 @@ int launch_ppo_loss_gauss(const float* mean, const float* log_std, const float* 
                           const float* action, const float* old_logp, const double* adv, const float* old_v,
                           const double* target_v, float clip_ratio, float ent_coef, float vf_clip, float critic_coef,
                           float inv_b, float* dmean, float* dvalue, float* dls_rows, int ldls, float* terms,
-                          hipStream_t st);
+                          hipStream_t st, float* rows = nullptr);
+// xt_ppo_loss with the optional diagnostic rows of xt_net_set_train_stats (LossArgs::rows; null: the kernel of xt_ppo_loss)
+int launch_ppo_loss(const float* logits, const float* value, int B, int A, const int32_t* idx, const int32_t* action,
+                    const float* old_logp, const double* adv, const float* old_v, const double* target_v,
+                    float clip_ratio, float ent_coef, float vf_clip, float critic_coef, float inv_b, float* dlogits,
+                    float* dvalue, float* terms, float* rows, hipStream_t st);
 // The acting heads (act_heads_kernel): heads forward + sampled action + its log-probability, one launch behind the trunk.
 struct ActHeadArgs {
   const float *f_pi = nullptr, *f_v = nullptr;
@@ -127,13 +132,17 @@ int launch_norm_finalize(const float* partial, int nblocks, float clip_norm, flo
                          const float* lr_dev = nullptr);
 int launch_grads_finish(GradTable* tab, float* partial, int max_partials, int* nblocks_out, const FinalizeArgs* fin,
                         hipStream_t st, unsigned select = 0, unsigned early = 0, const DpFinish* dpf = nullptr);
-int grads_finish_resident_blocks();
+int grads_finish_resident_blocks(bool stats = false);
 int grads_finish_fused_grid(const GradTable* tab);
 int launch_adam(float* param, const float* grad, float* m, float* v, long long count, float beta1, float beta2,
                 float eps, const float* state, hipStream_t st);
 int launch_adam_clip(float* param, const float* grad, float* m, float* v, long long count, float beta1, float beta2,
                      float eps, float* state, const float* partial, int nblocks, float clip_norm, float grad_scale,
-                     hipStream_t st, const DpStep* dp = nullptr, int block_cap = 0, const IoFold* io = nullptr);
+                     hipStream_t st, const DpStep* dp = nullptr, int block_cap = 0, const IoFold* io = nullptr,
+                     double* stats = nullptr);
+// xt_net_set_train_stats: the row / loss shares of a gradient-only step into the running sums; the sums cleared
+int launch_train_stats_reduce(const LossArgs* la, hipStream_t st);
+int launch_train_stats_clear(double* stats, hipStream_t st);
 int launch_rmsprop_clip(float* param, const float* grad, float* mg, float* ms, long long count, float lr, float decay,
                         float eps, float* state, const float* partial, int nblocks, float clip_norm, float grad_scale,
                         hipStream_t st, const float* lr_dev = nullptr, const DpStep* dp = nullptr, int block_cap = 0);

@@ -131,6 +131,11 @@ struct xt_net {
   long long io_calls = 0;
   int64_t off_iofwd = 0;              // 4 floats of the workspace: {destination (64 bit), sequence number} handed kernel to kernel
   int64_t off_ioacc = 0;              // 4 floats: the loss accumulator of tail_in_graph trains (no memset node in their graph)
+  // xt_net_set_train_stats: the caller's running sums and per-sample diagnostic rows (both null: off), and the head / loss
+  // kernel the last PPO step launched (xt_net_last_head_path)
+  double* tstats = nullptr;
+  float* trows = nullptr;
+  int last_head_path = 0;
 };
 
 namespace xt {
@@ -417,7 +422,7 @@ static int grads_finish(xt_net* n, int B, const FinalizeArgs* fin, hipStream_t s
   if (fused_out) *fused_out = false;
   if (fin && fin->enable == 3) {
     f2 = *fin;
-    const int cap = grads_finish_resident_blocks();
+    const int cap = grads_finish_resident_blocks(fin->loss.stats != nullptr);
     if (part == 0 && cap > 0 && grads_finish_fused_grid(&tab) <= cap) {
       if (fused_out) *fused_out = true;
     } else {
@@ -480,11 +485,12 @@ static int dp_exchange(xt_net* n, hipStream_t st, float* loss_acc, DpApply* a) {
 // mode 0: gradient was changed after grads_finish (all-reduce) -> recompute the norm;
 // mode 1: squared-norm partials of grads_finish are valid -> finalize kernel;  mode 2: already finalized in-kernel;
 // mode 3: partials valid, loss/step size done by grads_finish's extra block -> Adam derives the clip factor itself
+// stats (mode 3 only): the training-statistics sums the launch's block 0 adds the gradient norm to (may be null)
 static int net_apply(xt_net* n, float lr, float b1, float b2, float eps, float clip, float gscale, int mode,
-                     const LossArgs* la, hipStream_t st) {
+                     const LossArgs* la, hipStream_t st, double* stats = nullptr) {
   if (mode == 3)
     return launch_adam_clip(n->params, n->grads, n->m, n->v, n->P, b1, b2, eps, n->state, n->ws + n->off_norm,
-                            n->norm_blocks, clip, gscale, st, nullptr, 0, n->io_fold);
+                            n->norm_blocks, clip, gscale, st, nullptr, 0, n->io_fold, stats);
   if (mode == 1) {
     if (int rc = launch_norm_finalize(n->ws + n->off_norm, n->norm_blocks, clip, gscale, lr, b1, b2, 1, n->state, la, st))
       return rc;
@@ -498,12 +504,14 @@ static int net_apply(xt_net* n, float lr, float b1, float b2, float eps, float c
 // tail_overlap bit 2: Adam (mode 3: every block derives the clip factor from the partials) as two launches -- the first
 // layer's parameters on the compute stream, everything else on the side stream, where the next step's first-layer
 // forward overlaps it.  Element-wise, same clip factor in both: bitwise the single launch's result.
-static int net_apply_split(xt_net* n, float b1, float b2, float eps, float clip, float gscale, hipStream_t st) {
+// (stats: added by ONE of the two launches, the compute stream's)
+static int net_apply_split(xt_net* n, float b1, float b2, float eps, float clip, float gscale, hipStream_t st,
+                           double* stats = nullptr) {
   const Layer& L0 = n->layers[0];
   const int64_t c0 = (int64_t)(L0.K + 1) * L0.g.N;
   if (c0 % 4 != 0 || c0 >= n->P)
     return launch_adam_clip(n->params, n->grads, n->m, n->v, n->P, b1, b2, eps, n->state, n->ws + n->off_norm,
-                            n->norm_blocks, clip, gscale, st);
+                            n->norm_blocks, clip, gscale, st, nullptr, 0, nullptr, stats);
   XT_CHECK_HIP(hipEventRecord(n->adam_fork, st));
   XT_CHECK_HIP(hipStreamWaitEvent(n->tail_stream, n->adam_fork, 0));
   if (int rc = launch_adam_clip(n->params + c0, n->grads + c0, n->m + c0, n->v + c0, n->P - c0, b1, b2, eps, n->state,
@@ -512,7 +520,7 @@ static int net_apply_split(xt_net* n, float b1, float b2, float eps, float clip,
   XT_CHECK_HIP(hipEventRecord(n->adam_join, n->tail_stream));
   n->adam_pending = true;
   return launch_adam_clip(n->params, n->grads, n->m, n->v, c0, b1, b2, eps, n->state, n->ws + n->off_norm,
-                          n->norm_blocks, clip, gscale, st);
+                          n->norm_blocks, clip, gscale, st, nullptr, 0, nullptr, stats);
 }
 
 // tail_overlap bit 1: called right after the first backward launch (last trunk layer + head weight gradients): their
@@ -534,6 +542,7 @@ struct OptCfg {
   int opt_type;                 // XT_OPT_ADAM, or XT_OPT_RMSPROP_CENTERED (IMPALA only)
   float lr, beta1, beta2, eps, rms_decay, rms_eps, clip, gscale;
   const float* lr_dev;          // IMPALA: the step size in device memory (may be null)
+  double* stats = nullptr;      // PPO: the training-statistics sums (xt_net_set_train_stats; may be null)
 };
 static OptCfg ppo_opt(const xt_ppo_cfg* c) {
   return OptCfg{XT_OPT_ADAM, c->lr, c->beta1, c->beta2, c->eps, 0.f, 0.f, c->max_grad_norm, c->grad_scale, nullptr};
@@ -567,7 +576,7 @@ static int step_tail_apply(xt_net* n, int B, FinalizeArgs fin, const OptCfg& o, 
   }
   if (fused) return 0;
   if (tov & 2) {
-    if (int rc = net_apply_split(n, o.beta1, o.beta2, o.eps, o.clip, o.gscale, st)) return rc;
+    if (int rc = net_apply_split(n, o.beta1, o.beta2, o.eps, o.clip, o.gscale, st, o.stats)) return rc;
     return defer_join ? 0 : join_pending_update(n, st);
   }
   if (o.opt_type == XT_OPT_RMSPROP_CENTERED)
@@ -575,7 +584,8 @@ static int step_tail_apply(xt_net* n, int B, FinalizeArgs fin, const OptCfg& o, 
                                n->ws + n->off_norm, n->norm_blocks, o.clip, o.gscale, st, o.lr_dev);
   XT_REQUIRE(o.opt_type == XT_OPT_ADAM, "%s: unknown opt_type %d", who, o.opt_type);
   // (enable == 1: the last block of the reduction has finalised already)
-  return net_apply(n, o.lr, o.beta1, o.beta2, o.eps, o.clip, o.gscale, fin.enable == 1 ? 2 : 3, nullptr, st);
+  return net_apply(n, o.lr, o.beta1, o.beta2, o.eps, o.clip, o.gscale, fin.enable == 1 ? 2 : 3, nullptr, st,
+                   fin.enable == 1 ? nullptr : o.stats);
 }
 
 // The apply == 3 tail (see ppo_step): the gradient reduction with its extra block and the data-parallel extras, no update
@@ -618,8 +628,10 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
   XT_REQUIRE(apply >= 0 && apply <= 3, "xt_net_ppo_step: bad apply mode %d", apply);
   XT_REQUIRE(apply != 2 || (n->xchg && n->xchg_stream && n->xchg_fork && n->xchg_join),
              "xt_net_ppo_step: the overlapped exchange mode needs a hook installed with XT_XCHG_OVERLAP");
+  XT_REQUIRE(!n->tstats || apply <= 1, "xt_net_ppo_step: the training statistics are not kept under data parallelism");
   const bool gauss = (n->action_type == XT_ACTION_DIAG_GAUSSIAN);
   const int32_t* action = static_cast<const int32_t*>(action_v);
+  float* const trows = n->tstats ? n->trows : nullptr;
   const Heads hd = heads_of(n);
   Layer &Lp = *hd.Lp, &Lv = *hd.Lv;
   bool fused_head = (!gauss && n->A <= 8 && n->feat <= 512 && Lp.z_off < 0 && Lv.z_off < 0);
@@ -640,6 +652,7 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
     h.df_pi = n->ws + Lp.dact_off; h.df_v = n->ws + Lv.dact_off;
     h.part_pi = h.part_v = nullptr; h.tbias_pi = h.tbias_v = nullptr; h.feat_pi_w = h.feat_v_w = nullptr;
     h.ksplit_pi = h.ksplit_v = 1; h.act_feat = Lp.g.act; h.part_stride = (long long)B * F;
+    h.rows = trows;
     if (Lp.last_ksplit > 1) {
       h.part_pi = n->ws + Lp.part_off; h.ksplit_pi = Lp.last_ksplit; h.feat_pi_w = n->ws + Lp.act_off;
       h.tbias_pi = b_of(n, Lp);
@@ -653,6 +666,7 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
     const int hrc = launch_ppo_heads_fused(h, st);
     if (hrc > 0) return hrc;
     XT_REQUIRE(hrc == 0, "xt_net: fused PPO head kernel rejected the geometry (A=%d F=%d)", A, F);
+    n->last_head_path = last_path();
   } else {
     if (int rc = heads_forward(n, B, st)) return rc;
     if (gauss) {
@@ -660,13 +674,17 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
                                          idx, static_cast<const float*>(action_v), old_logp, adv, old_v, target_v,
                                          c->clip_ratio, c->ent_coef, c->vf_clip, c->critic_coef, inv_b,
                                          n->ws + n->off_dlogits, n->ws + n->off_dvalue, n->ws + n->off_dls,
-                                         (int)align4(A), n->ws + n->off_terms, st))
+                                         (int)align4(A), n->ws + n->off_terms, st, trows))
         return rc;
       n->dls_rows = B;
-    } else if (int rc = xt_ppo_loss(n->ws + n->off_logits, n->ws + n->off_value, B, A, idx, action, old_logp, adv,
-                                    old_v, target_v, c->clip_ratio, c->ent_coef, c->vf_clip, c->critic_coef, inv_b,
-                                    n->ws + n->off_dlogits, n->ws + n->off_dvalue, n->ws + n->off_terms, st))
-      return rc;
+      n->last_head_path = XT_NET_HEAD_GAUSS;
+    } else {
+      if (int rc = launch_ppo_loss(n->ws + n->off_logits, n->ws + n->off_value, B, A, idx, action, old_logp, adv, old_v,
+                                   target_v, c->clip_ratio, c->ent_coef, c->vf_clip, c->critic_coef, inv_b,
+                                   n->ws + n->off_dlogits, n->ws + n->off_dvalue, n->ws + n->off_terms, trows, st))
+        return rc;
+      n->last_head_path = XT_NET_HEAD_PLAIN;
+    }
     if (int rc = heads_dfeat(n, B, st)) return rc;
   }
   // data-parallel overlap (apply == 2): reduce + exchange the last trunk layer's and the heads' gradient right after
@@ -705,20 +723,28 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
     return xt_ppo_loss_reduce(n->ws + n->off_terms, B, c->ent_coef, c->critic_coef, inv_b, lo, loss_acc, st);
   }
   if (apply == 1 || apply == 3) {
-    const OptCfg o = ppo_opt(c);
+    OptCfg o = ppo_opt(c);
+    o.stats = n->tstats;
     // PPO alone honours finalize_ticket, and only in the full step
     const int tail_mode = (apply == 1 && tuning().finalize_ticket) ? 1 : 2;     // 1: the old "last block finalises" form (A/B)
     FinalizeArgs fin = finalize_args(n, tail_mode, /*ticket*/ true, o);      // PPO always passes the counter
     LossArgs& la = fin.loss;
     la.terms = n->ws + n->off_terms; la.B = B; la.ent_coef = c->ent_coef; la.critic_coef = c->critic_coef;
     la.inv_b = inv_b; la.out = lo; la.acc = loss_acc;
+    la.rows = trows; la.stats = n->tstats;
     if (apply == 3) return step_tail_dp(n, B, fin, st);
     // (the fused tail replaces the enable == 2 form only)
     return step_tail_apply(n, B, fin, o, tfk.done, tov, /*may_fuse*/ tail_mode == 2, defer_join, st, "xt_net_ppo_step");
   }
   if (int rc = grads_finish(n, B, nullptr, st)) return rc;
   // gradient only (data parallel): still report the local loss
-  return xt_ppo_loss_reduce(n->ws + n->off_terms, B, c->ent_coef, c->critic_coef, inv_b, lo, loss_acc, st);
+  if (int rc = xt_ppo_loss_reduce(n->ws + n->off_terms, B, c->ent_coef, c->critic_coef, inv_b, lo, loss_acc, st)) return rc;
+  if (!n->tstats) return 0;
+  // ... and the step's share of the training statistics (no norm is formed: the three gradient-norm slots stay)
+  LossArgs la{};
+  la.terms = n->ws + n->off_terms; la.B = B; la.ent_coef = c->ent_coef; la.critic_coef = c->critic_coef; la.inv_b = inv_b;
+  la.rows = trows; la.stats = n->tstats;
+  return launch_train_stats_reduce(&la, st);
 }
 
 // Replay the hipGraph cached under `key`, capturing `enqueue` (on the net's private stream) on a miss.
@@ -1070,6 +1096,11 @@ static int ppo_train_enqueue(xt_net* net, const xt_ppo_cfg* c, const void* obs, 
                              const void* action, const float* old_logp, const double* adv, const float* old_v,
                              const double* target_v, float* loss_acc, hipStream_t st) {
   if (int rc = xt::clear_loss_acc(net, loss_acc, st)) return rc;
+  if (net->tstats) {
+    XT_REQUIRE(!net->xchg && net->dp_world < 1, "xt_net_ppo_train: the training statistics are not kept under data "
+                                                 "parallelism (xt_net_set_train_stats(net, NULL, NULL) first)");
+    if (int rc = xt::launch_train_stats_clear(net->tstats, st)) return rc;
+  }
   XT_REQUIRE(n < (1 << 24), "xt_net_ppo_train: %d rows do not fit the data-parallel tail's float slot", n);
   net->dp_rows = (float)n;
   for (int ep = 0; ep < c->num_sgd_iter; ++ep) {
@@ -1141,14 +1172,14 @@ int xt_net_ppo_train(xt_net* net, const xt_ppo_cfg* c, const void* obs, int32_t 
   (void)xt::tail_overlap_mode(net);      // (creates the side stream outside of any capture)
   if (!use_graph)
     return ppo_train_enqueue(net, c, obs, n, perm, action, old_logp, adv, old_v, target_v, loss_acc, st);
-  char key[512];
-  snprintf(key, sizeof(key), "P%d.%d.%d.%d.%d.%g.%p|%p|%p|%p|%d|%p|%p|%p|%p|%p|%p|%p|%g|%g|%g|%g|%g|%g|%g|%g|%g|%d|%d|%g|%d",
+  char key[640];
+  snprintf(key, sizeof(key), "P%d.%d.%d.%d.%d.%g.%p|%p|%p|%p|%d|%p|%p|%p|%p|%p|%p|%p|%g|%g|%g|%g|%g|%g|%g|%g|%g|%d|%d|%g|%d|%p|%p",
            net->xchg_flags, c->shard_rank, c->shard_world, net->dp_rank, net->dp_world, net->dp_loss_scale, (void*)net->direct,
            (void*)net->xchg, net->xchg_user, obs, n,
            (const void*)perm, (const void*)action, (const void*)old_logp, (const void*)adv, (const void*)old_v,
            (const void*)target_v, (void*)loss_acc, c->lr, c->beta1, c->beta2, c->eps, c->clip_ratio, c->ent_coef,
            c->vf_clip, c->critic_coef, c->max_grad_norm, c->batch_size, c->num_sgd_iter, c->grad_scale,
-           c->global_batch);
+           c->global_batch, (void*)net->tstats, (void*)net->trows);      // (stats on / off: never each other's graph)
   return xt::graph_run(net, key, st, [&](hipStream_t cs) {
     return ppo_train_enqueue(net, c, obs, n, perm, action, old_logp, adv, old_v, target_v, loss_acc, cs);
   });
@@ -1651,6 +1682,8 @@ int xt_net_keras_impala_train(xt_net* n, const xt_keras_train_cfg* c, const void
 int xt_net_set_grad_exchange_ex(xt_net* net, xt_grad_exchange_fn fn, void* user, int32_t flags) {
   XT_REQUIRE(net, "xt_net_set_grad_exchange: null net");
   XT_REQUIRE((flags & ~XT_XCHG_OVERLAP) == 0, "xt_net_set_grad_exchange_ex: unknown flags 0x%x", flags);
+  XT_REQUIRE(!fn || !net->tstats, "xt_net_set_grad_exchange: switch the training statistics off first "
+                                  "(xt_net_set_train_stats(net, NULL, NULL)): they are not kept under data parallelism");
   net->xchg = fn;
   net->xchg_user = fn ? user : nullptr;
   net->xchg_flags = fn ? flags : 0;
@@ -1661,6 +1694,24 @@ int xt_net_set_grad_exchange_ex(xt_net* net, xt_grad_exchange_fn fn, void* user,
   }
   return 0;
 }
+
+int xt_net_set_train_stats(xt_net* net, double* stats, float* rows) {
+  XT_REQUIRE(net, "xt_net_set_train_stats: null net");
+  if (!stats && !rows) {
+    net->tstats = nullptr; net->trows = nullptr;
+    return 0;
+  }
+  XT_REQUIRE(stats && rows, "xt_net_set_train_stats: stats and rows go together (NULL, NULL switches the statistics off)");
+  XT_REQUIRE(((uintptr_t)stats & 7) == 0 && ((uintptr_t)rows & 15) == 0,
+             "xt_net_set_train_stats: stats must be 8-byte aligned, rows 16-byte aligned");
+  XT_REQUIRE(!net->xchg && net->dp_world < 1 && !net->direct,
+             "xt_net_set_train_stats: refused on a net with a data-parallel tail or a gradient exchange hook (the row "
+             "statistics would be rank-local)");
+  net->tstats = stats; net->trows = rows;
+  return 0;
+}
+
+int32_t xt_net_last_head_path(const xt_net* net) { return net ? net->last_head_path : 0; }
 
 int xt_net_set_grad_exchange(xt_net* net, xt_grad_exchange_fn fn, void* user) {
   return xt_net_set_grad_exchange_ex(net, fn, user, 0);
@@ -1676,6 +1727,8 @@ int xt_net_set_dp(xt_net* net, int32_t rank, int32_t world, float loss_scale) {
   XT_REQUIRE(world <= xt::kDpMaxWorld && rank >= 0 && rank < world, "xt_net_set_dp: rank %d / world %d (max %d)", rank, world,
              xt::kDpMaxWorld);
   XT_REQUIRE(net->grads, "xt_net_set_dp: buffers not bound");
+  XT_REQUIRE(!net->tstats, "xt_net_set_dp: switch the training statistics off first (xt_net_set_train_stats(net, NULL, "
+                           "NULL)): they are not kept under data parallelism");
   net->dp_rank = rank; net->dp_world = world; net->dp_loss_scale = loss_scale;
   return 0;
 }

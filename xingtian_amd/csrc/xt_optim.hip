@@ -13,9 +13,11 @@ namespace xt {
 
 constexpr int kNormBlocks = 512;   // partial sums; scratch must hold >= kNormBlocks floats
 
+template <bool STATS>
 __device__ void finalize_body(const float* partial, int nblocks, float clip_norm, float grad_scale, float lr,
                               float beta1, float beta2, int advance, float* state, const LossArgs& la, double* sh);
 
+template <bool STATS>
 __device__ void loss_reduce_body(const LossArgs& la, double* sh);
 __device__ double sqnorm_total_coherent(const float* partial, int nblocks, double* sh);
 __device__ __forceinline__ void clip_scale(double sq, float clip_norm, float grad_scale, float* gnorm, float* scale);
@@ -46,8 +48,12 @@ __device__ __forceinline__ bool grid_wait(unsigned int* flag, unsigned int sense
   return false;
 }
 __device__ __forceinline__ void adam_advance(float* state, float lr, float beta1, float beta2);
-__device__ void finalize_body(const float* partial, int nblocks, float clip_norm, float grad_scale, float lr,
-                              float beta1, float beta2, int advance, float* state, const LossArgs& la, double* sh);
+// xt_net_set_train_stats: the pre-clip global norm of one step into the running sums, by the thread that writes state[4]
+__device__ __forceinline__ void stats_add_gnorm(double* stats, float gnorm, float clip_norm) {
+  stats[XT_TRAIN_STATS_GNORM_SUM] += (double)gnorm;
+  stats[XT_TRAIN_STATS_GNORM_MAX] = fmax(stats[XT_TRAIN_STATS_GNORM_MAX], (double)gnorm);
+  stats[XT_TRAIN_STATS_GNORM_CLIPPED] += gnorm > clip_norm ? 1.0 : 0.0;
+}
 
 // data-parallel tail slots of THIS rank for one step: [rank] = rows, [16 + rank] = loss share, everything else zero
 __device__ __forceinline__ float dp_tail_value(int i, int rank, float rows, float loss) {
@@ -72,6 +78,9 @@ __device__ __forceinline__ void dp_scatter_ticket(const DpFinish& d, unsigned in
     __hip_atomic_store(d.peers.flags[q] + kReadyOff + d.rank, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// STATS (xt_net_set_train_stats): the instance whose loss reduction also reduces the diagnostic rows and whose norm sites add
+// the gradient norm to the running sums; STATS = false is the kernel of every other path, unchanged
+template <bool STATS>
 __global__ __launch_bounds__(256) void grads_finish_kernel(const GradTable tab, float* __restrict__ partial,
                                                            const FinalizeArgs fin, const DpFinish dpf) {
   __shared__ float4 sh4[256];
@@ -87,7 +96,7 @@ __global__ __launch_bounds__(256) void grads_finish_kernel(const GradTable tab, 
   if (fin.enable >= 2 && blockIdx.x == gridDim.x - 1) {
     // extra block of the "Adam computes the clip scale itself" form: everything of the old last-block finalize
     // that does not depend on the gradient norm (loss scalars, beta powers, step size) -- off the critical path
-    loss_reduce_body(fin.loss, reinterpret_cast<double*>(sh4));
+    loss_reduce_body<STATS>(fin.loss, reinterpret_cast<double*>(sh4));
     if (threadIdx.x == 0) {
       adam_advance(fin.state, fin.lr_dev ? fin.lr_dev[0] : fin.lr, fin.beta1, fin.beta2);
       if (fin.enable == 3) {      // the step size crosses the barrier: write-through, drained, then arrive (and leave)
@@ -244,7 +253,10 @@ __global__ __launch_bounds__(256) void grads_finish_kernel(const GradTable tab, 
       clip_scale(sqt, fin.clip_norm, fin.grad_scale, &gnorm, &sc);
       shs[0] = sc;
       shs[1] = __hip_atomic_load(fin.state + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (blockIdx.x == 0) { fin.state[2] = sc; fin.state[4] = gnorm; }
+      if (blockIdx.x == 0) {
+        fin.state[2] = sc; fin.state[4] = gnorm;
+        if (STATS && fin.loss.stats) stats_add_gnorm(fin.loss.stats, gnorm, fin.clip_norm);
+      }
     }
     __syncthreads();
     const float scale = shs[0], alpha = shs[1];
@@ -307,8 +319,8 @@ __global__ __launch_bounds__(256) void grads_finish_kernel(const GradTable tab, 
   __syncthreads();
   XT_TL(3);
   if (!s_last) return;
-  finalize_body(partial, gridDim.x, fin.clip_norm, fin.grad_scale, fin.lr_dev ? fin.lr_dev[0] : fin.lr, fin.beta1, fin.beta2,
-                1, fin.state, fin.loss, reinterpret_cast<double*>(sh4));
+  finalize_body<STATS>(partial, gridDim.x, fin.clip_norm, fin.grad_scale, fin.lr_dev ? fin.lr_dev[0] : fin.lr, fin.beta1,
+                       fin.beta2, 1, fin.state, fin.loss, reinterpret_cast<double*>(sh4));
   XT_TL(4);
 }
 
@@ -370,6 +382,7 @@ __global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __rest
 
 // state: [0]=b1^t [1]=b2^t [2]=scale [3]=alpha [4]=gnorm [5]=step
 // PPO loss scalars from the per-sample terms (fixed-order tree), xt/model/ppo/__init__.py
+template <bool STATS>
 __device__ void loss_reduce_body(const LossArgs& la, double* sh) {
   if (!la.terms) {
     if (la.traj_loss && threadIdx.x == 0) {     // IMPALA: sum of the per-trajectory sums, trajectory order (float, as
@@ -406,6 +419,41 @@ __device__ void loss_reduce_body(const LossArgs& la, double* sh) {
     const float loss = actor + la.critic_coef * vf;
     if (la.out) { la.out[0] = loss; la.out[1] = actor; la.out[2] = vf; la.out[3] = ent; }
     if (la.acc) { la.acc[0] += loss; la.acc[1] += 1.f; }
+    if (STATS && la.stats) {
+      la.stats[XT_TRAIN_STATS_STEPS] += 1.0;
+      la.stats[XT_TRAIN_STATS_ROWS] += (double)la.B;
+      la.stats[XT_TRAIN_STATS_SURR] += (double)surr;
+      la.stats[XT_TRAIN_STATS_ENT] += (double)ent;
+      la.stats[XT_TRAIN_STATS_VF] += (double)vf;
+    }
+  }
+  if (STATS && la.stats && la.rows) {
+    // the diagnostic rows of the head kernel, same fixed-order double tree: {old_logp - logp, flags, tv, tv - v} -> the seven
+    // sums XT_TRAIN_STATS_KL .. XT_TRAIN_STATS_ERR_SQ (tv and tv - v also squared; the products are taken in double)
+    double r7[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < la.B; b += 256) {
+      const float4 r = reinterpret_cast<const float4*>(la.rows)[b];
+      const int fl = (int)r.y;
+      const double tv = (double)r.z, er = (double)r.w;
+      r7[0] += (double)r.x;
+      r7[1] += (double)(fl & 1);
+      r7[2] += (double)((fl >> 1) & 1);
+      r7[3] += tv;
+      r7[4] += tv * tv;
+      r7[5] += er;
+      r7[6] += er * er;
+    }
+    for (int q = 0; q < 7; ++q) {
+      __syncthreads();
+      sh[threadIdx.x] = r7[q];
+      __syncthreads();
+      for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+      }
+      if (threadIdx.x == 0) la.stats[XT_TRAIN_STATS_KL + q] += sh[0];
+    }
+    __syncthreads();
   }
 }
 
@@ -472,15 +520,17 @@ __device__ __forceinline__ void adam_advance(float* state, float lr, float beta1
   state[5] += 1.f;
 }
 
+template <bool STATS>
 __device__ void finalize_body(const float* partial, int nblocks, float clip_norm, float grad_scale, float lr,
                               float beta1, float beta2, int advance, float* state, const LossArgs& la, double* sh) {
-  loss_reduce_body(la, sh);
+  loss_reduce_body<STATS>(la, sh);
   const double sq = sqnorm_total(partial, nblocks, sh);
   if (threadIdx.x == 0) {
     float gnorm, sc;
     clip_scale(sq, clip_norm, grad_scale, &gnorm, &sc);
     state[2] = sc;
     state[4] = gnorm;
+    if (STATS && la.stats) stats_add_gnorm(la.stats, gnorm, clip_norm);
     if (advance) adam_advance(state, lr, beta1, beta2);
   }
 }
@@ -490,7 +540,19 @@ __global__ __launch_bounds__(256) void norm_finalize_kernel(const float* __restr
                                                             int advance, float* __restrict__ state, LossArgs la,
                                                             const float* __restrict__ lr_dev) {
   __shared__ double sh[256];
-  finalize_body(partial, nblocks, clip_norm, grad_scale, lr_dev ? lr_dev[0] : lr, beta1, beta2, advance, state, la, sh);
+  finalize_body<false>(partial, nblocks, clip_norm, grad_scale, lr_dev ? lr_dev[0] : lr, beta1, beta2, advance, state, la, sh);
+}
+
+// xt_net_set_train_stats, gradient-only step (xt_net_ppo_step with apply == 0, which ends in ppo_loss_reduce_kernel): one block
+// that adds the step's shares to the running sums and writes nothing else
+__global__ __launch_bounds__(256) void train_stats_reduce_kernel(LossArgs la) {
+  __shared__ double sh[256];
+  loss_reduce_body<true>(la, sh);
+}
+// the XT_TRAIN_STATS_DOUBLES running sums of a train, cleared by a kernel (a 16-byte memset node captured into a hipGraph
+// has written garbage on replay: xt_net.hip, clear_loss_acc)
+__global__ void train_stats_clear_kernel(double* stats) {
+  if (threadIdx.x < XT_TRAIN_STATS_DOUBLES) stats[threadIdx.x] = 0.0;
 }
 
 __global__ __launch_bounds__(256) void adam_tf_kernel(float* __restrict__ p, const float* __restrict__ g,
@@ -656,12 +718,14 @@ __device__ void dp_step_end(const DpStep& dp) {
 // the host through the mailbox (the sums are final before the optimiser runs), every block also writes its updated parameters
 // to the snapshot buffer with system-scope write-through stores (the SDMA engine that copies it out reads memory, not an XCD's
 // L2), and the last block to finish reports the snapshot.  IO = false is the kernel of every other path, unchanged.
-template <bool IO>
+// STATS (xt_net_set_train_stats): block 0 also adds the gradient norm to the running sums `stats`.
+template <bool IO, bool STATS = false>
 __global__ __launch_bounds__(256) void adam_tf_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                            float* __restrict__ m, float* __restrict__ v, long long count,
                                                            float beta1, float beta2, float eps, float* __restrict__ state,
                                                            const float* __restrict__ partial, int nblocks,
-                                                           float clip_norm, float grad_scale, const DpStep dp, const IoFold io) {
+                                                           float clip_norm, float grad_scale, const DpStep dp, const IoFold io,
+                                                           double* __restrict__ stats) {
   __shared__ double sh[256];
   __shared__ float s_scale;
   const bool ok = dp_step_begin(dp);
@@ -690,7 +754,10 @@ __global__ __launch_bounds__(256) void adam_tf_clip_kernel(float* __restrict__ p
     float gnorm, sc;
     clip_scale(sq, clip_norm, grad_scale, &gnorm, &sc);
     s_scale = sc;
-    if (blockIdx.x == 0) { state[2] = sc; state[4] = gnorm; }
+    if (blockIdx.x == 0) {
+      state[2] = sc; state[4] = gnorm;
+      if (STATS && stats) stats_add_gnorm(stats, gnorm, clip_norm);
+    }
   }
   __syncthreads();
   const float scale = s_scale, alpha = state[3];
@@ -857,21 +924,28 @@ int launch_grads_finish(GradTable* tab, float* partial, int max_partials, int* n
                  "grads_finish: entry %d lies outside the exchanged buffer", i);
     }
   }
-  hipLaunchKernelGGL(grads_finish_kernel, dim3(grid + (f.enable >= 2 ? 1 : 0)), dim3(256), 0, st, sub, partial, f, d);
+  if (f.loss.stats) {
+    XT_REQUIRE(!d.tail && !d.scatter, "grads_finish: the training statistics are not kept under data parallelism");
+    hipLaunchKernelGGL(grads_finish_kernel<true>, dim3(grid + (f.enable >= 2 ? 1 : 0)), dim3(256), 0, st, sub, partial, f, d);
+  } else {
+    hipLaunchKernelGGL(grads_finish_kernel<false>, dim3(grid + (f.enable >= 2 ? 1 : 0)), dim3(256), 0, st, sub, partial, f, d);
+  }
   XT_LAUNCH_CHECK();
   *nblocks_out = blk;
   return 0;
 }
 
 // how many workgroups of the fused tail can be resident at once on this device (its grid barrier needs all of them)
-int grads_finish_resident_blocks() {
-  static std::atomic<int> cached_dev[64];      // per device: a process may drive several (different) GPUs
+int grads_finish_resident_blocks(bool stats) {
+  static std::atomic<int> cached_dev[2][64];   // per instance and device: a process may drive several (different) GPUs
   int per_cu = 0, cus = 0, dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
-  std::atomic<int>& cached = cached_dev[dev & 63];
+  std::atomic<int>& cached = cached_dev[stats ? 1 : 0][dev & 63];
   int v = cached.load();
   if (v > 0) return v;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, grads_finish_kernel, 256, 0) != hipSuccess) return 0;
+  const hipError_t oe = stats ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, grads_finish_kernel<true>, 256, 0)
+                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, grads_finish_kernel<false>, 256, 0);
+  if (oe != hipSuccess) return 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
   v = per_cu * cus;
   cached.store(v);
@@ -909,7 +983,7 @@ int launch_rmsprop_clip(float* param, const float* grad, float* mg, float* ms, l
 
 int launch_adam_clip(float* param, const float* grad, float* m, float* v, long long count, float beta1, float beta2,
                      float eps, float* state, const float* partial, int nblocks, float clip_norm, float grad_scale,
-                     hipStream_t st, const DpStep* dp, int block_cap, const IoFold* io) {
+                     hipStream_t st, const DpStep* dp, int block_cap, const IoFold* io, double* stats) {
   XT_REQUIRE((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
              "adam: buffers must be 16-byte aligned");
   int nb = (int)((count / 4 + 255) / 256);
@@ -928,11 +1002,16 @@ int launch_adam_clip(float* param, const float* grad, float* m, float* v, long l
   if (io) {
     XT_REQUIRE(count * 4 < 0x7fffffffLL, "adam: %lld parameters exceed the snapshot store's 2 GiB offset range", count);
     f = *io;
-    hipLaunchKernelGGL(adam_tf_clip_kernel<true>, dim3(nb), dim3(256), 0, st, param, grad, m, v, count, beta1, beta2, eps,
-                       state, partial, nblocks, clip_norm, grad_scale, d, f);
+    XT_REQUIRE(!stats, "adam: the training statistics do not ride in the folded IO tail");
+    hipLaunchKernelGGL((adam_tf_clip_kernel<true, false>), dim3(nb), dim3(256), 0, st, param, grad, m, v, count, beta1, beta2,
+                       eps, state, partial, nblocks, clip_norm, grad_scale, d, f, nullptr);
+  } else if (stats) {
+    XT_REQUIRE(!dp, "adam: the training statistics are not kept under data parallelism");
+    hipLaunchKernelGGL((adam_tf_clip_kernel<false, true>), dim3(nb), dim3(256), 0, st, param, grad, m, v, count, beta1, beta2,
+                       eps, state, partial, nblocks, clip_norm, grad_scale, d, f, stats);
   } else {
-    hipLaunchKernelGGL(adam_tf_clip_kernel<false>, dim3(nb), dim3(256), 0, st, param, grad, m, v, count, beta1, beta2, eps,
-                       state, partial, nblocks, clip_norm, grad_scale, d, f);
+    hipLaunchKernelGGL((adam_tf_clip_kernel<false, false>), dim3(nb), dim3(256), 0, st, param, grad, m, v, count, beta1, beta2,
+                       eps, state, partial, nblocks, clip_norm, grad_scale, d, f, nullptr);
   }
   XT_LAUNCH_CHECK();
   return 0;
@@ -1022,6 +1101,21 @@ int launch_norm_finalize(const float* partial, int nblocks, float clip_norm, flo
   if (la) l = *la;
   hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(256), 0, st, partial, nblocks, clip_norm, grad_scale, lr, beta1,
                      beta2, advance, state, l, lr_dev);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_train_stats_reduce(const LossArgs* la, hipStream_t st) {
+  XT_REQUIRE(la && la->terms && la->rows && la->stats && la->B > 0, "train_stats_reduce: bad arguments");
+  LossArgs l = *la;
+  l.out = nullptr; l.acc = nullptr;
+  hipLaunchKernelGGL(train_stats_reduce_kernel, dim3(1), dim3(256), 0, st, l);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+int launch_train_stats_clear(double* stats, hipStream_t st) {
+  XT_REQUIRE(stats, "train_stats_clear: null argument");
+  hipLaunchKernelGGL(train_stats_clear_kernel, dim3(1), dim3(64), 0, st, stats);
   XT_LAUNCH_CHECK();
   return 0;
 }

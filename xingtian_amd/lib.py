@@ -96,6 +96,11 @@ DIRECT_HANDLE_BYTES = 64  # XT_DIRECT_HANDLE_BYTES
 DP_TAIL_FLOATS = 32       # XT_DP_TAIL_FLOATS: 2 x 16 slots behind the gradient (rows / loss share of every rank)
 DP_ERR_BITS = {1: "a peer's gradient slices never arrived (scatter wait)", 2: "a peer's reduced slice never arrived (reduce wait)",
                4: "the ranks hold different numbers of rows"}
+TRAIN_STATS_DOUBLES = 16  # XT_TRAIN_STATS_DOUBLES: the running sums of xt_net_set_train_stats
+# XT_TRAIN_STATS_<name>: slot of every sum (include/xt_mi355x.h)
+TRAIN_STATS_SLOTS = {"STEPS": 0, "ROWS": 1, "SURR": 2, "ENT": 3, "VF": 4, "KL": 5, "CLIPPED": 6, "VF_CLIPPED": 7, "TV": 8,
+                     "TV_SQ": 9, "ERR": 10, "ERR_SQ": 11, "GNORM_SUM": 12, "GNORM_MAX": 13, "GNORM_CLIPPED": 14, "RESERVED": 15}
+NET_HEAD_PLAIN, NET_HEAD_GAUSS = 0x10000, 0x20000      # XT_NET_HEAD_*: xt_net_last_head_path beside the fused kernel's word
 _P = c_void_p
 # name -> (restype, argtypes); every symbol include/xt_mi355x.h declares
 SIGNATURES = {
@@ -143,6 +148,8 @@ SIGNATURES = {
     "xt_net_forward": (c_int32, [_P, _P, _P, c_int32, _P, _P, _P]),
     "xt_net_ppo_step": (c_int32, [_P, POINTER(PpoCfg), _P, _P, c_int32, _P, _P, _P, _P, _P, c_int32, _P, _P, _P]),
     "xt_net_ppo_train": (c_int32, [_P, POINTER(PpoCfg), _P, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int32, _P]),
+    "xt_net_set_train_stats": (c_int32, [_P, _P, _P]),
+    "xt_net_last_head_path": (c_int32, [_P]),
     "xt_net_set_grad_exchange": (c_int32, [_P, _P, _P]),
     "xt_net_set_grad_exchange_ex": (c_int32, [_P, _P, _P, c_int32]),
     "xt_keras_impala_loss": (c_int32, [_P, _P, c_int32, c_int32, _P, _P, _P, _P, c_float, _P, _P, _P, _P, _P]),

@@ -438,6 +438,53 @@ class HipActorCritic(object):
         behind the gradient in the same exchange, the optimiser adds the GLOBAL loss to ``loss_acc``) or off (``world`` = 0)"""
         L.check(self.lib.xt_net_set_dp(self.handle, int(rank), int(world), float(loss_scale)), "xt_net_set_dp")
 
+    # ------------------------------------------------------------------ per-update training diagnostics (opt-in)
+    train_stats_on = False
+
+    def set_train_stats(self, on=True):
+        """C ABI ``xt_net_set_train_stats``: switch the per-update PPO diagnostics on (the net then owns the 16 running sums
+        and the [max_batch, 4] row scratch) or off.  Refused by the library while a data-parallel tail or a gradient
+        exchange hook is attached."""
+        if on:
+            if getattr(self, "_tstats", None) is None:
+                pin = torch.zeros((2, L.TRAIN_STATS_DOUBLES), dtype=torch.float64, pin_memory=True)
+                self._tstats = dict(acc=torch.zeros(L.TRAIN_STATS_DOUBLES, dtype=torch.float64, device=self.device),
+                                    rows=torch.zeros((self.max_batch, 4), dtype=torch.float32, device=self.device),
+                                    pin=pin, np=pin.numpy(), slot=0, last=None)
+            L.check(self.lib.xt_net_set_train_stats(self.handle, L.ptr(self._tstats["acc"]), L.ptr(self._tstats["rows"])),
+                    "xt_net_set_train_stats")
+        else:
+            L.check(self.lib.xt_net_set_train_stats(self.handle, None, None), "xt_net_set_train_stats")
+            if getattr(self, "_tstats", None) is not None:
+                self._tstats["last"] = None
+        self.train_stats_on = bool(on)
+
+    def clear_train_stats(self):
+        """zero the running sums (``xt_net_ppo_train`` does it itself; a caller of ``ppo_step`` does it here)"""
+        self._tstats["acc"].zero_()
+
+    def enqueue_train_stats(self):
+        """One 128-byte D2H of the running sums into the next of two alternating pinned blocks, in stream order behind
+        everything enqueued so far and with no synchronisation of its own: ``read_loss`` records and awaits its event
+        behind this copy, so the block is complete once the loss is."""
+        ts = self._tstats
+        i = ts["slot"]
+        L.memcpy_async(ts["pin"][i].data_ptr(), ts["acc"].data_ptr(), 8 * L.TRAIN_STATS_DOUBLES, L.D2H,
+                       L.current_stream(self.device))
+        ts["slot"], ts["last"] = i ^ 1, i
+
+    def train_stats_sums(self):
+        """float64 [16]: the sums the last ``enqueue_train_stats`` copied (None before the first); valid once a
+        ``read_loss`` behind it has returned"""
+        ts = getattr(self, "_tstats", None)
+        if ts is None or ts["last"] is None:
+            return None
+        return ts["np"][ts["last"]].copy()
+
+    def last_head_path(self):
+        """the head / loss kernel the most recent PPO step launched (C ABI ``xt_net_last_head_path``; diagnostic)"""
+        return int(self.lib.xt_net_last_head_path(self.handle))
+
     def read_loss(self, acc=None, wait=True):
         """[sum of step losses, number of steps, data-parallel error bits, -] of the train(s) enqueued so far: ONE 16-byte D2H
         into a pinned block + an event wait instead of a pageable ``.cpu()`` (a staging copy, an allocation and a device-wide

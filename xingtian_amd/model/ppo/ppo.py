@@ -55,6 +55,7 @@ class PPO(XTModel):
         self._resident = None
         self._ingest = None
         self._dp = None
+        self._last_loss = None
         self._perm_dense = None
         self._perm_pin = None           # two pinned [NUM_SGD_ITER, n] blocks: this update's shuffles / the next one's
         self._perm_last, self._perm_next = 0, None    # block of the last H2D; block holding shuffles drawn ahead
@@ -117,7 +118,29 @@ class PPO(XTModel):
                 self._perm_rng = np.random.default_rng(self._dp.shared_seed(self.seed))      # the SAME shuffles everywhere
             else:
                 self._perm_rng = np.random.default_rng(None if self.seed is None else [int(self.seed), self._dp.rank])
+        # TRAIN_STATS: the per-update diagnostics (approximate KL, clip fractions, explained variance, gradient norm, ...)
+        # accumulated on the device inside the update's own launches and read back with the loss (``train_stats()``)
+        mcfg = model_info.get("model_config") or {}
+        if bool(mcfg.get("TRAIN_STATS", False)):
+            # (an explicit DP: strict / weak counts even where this process found no peers: the same YAML must not change
+            # its meaning with the number of ranks it is launched on)
+            if self._dp is not None or mcfg.get("DP") in ("strict", "weak"):
+                raise ValueError("TRAIN_STATS is not available under data parallelism (DP {}): the row statistics would "
+                                 "be rank-local".format(self._dp.mode if self._dp is not None else mcfg.get("DP")))
+            self.net.set_train_stats(True)
         return self.net
+
+    def train_stats(self):
+        """The diagnostics of the LAST ``train`` / ``train_ingested`` as a dict of Python floats
+        (``xingtian_amd.ops.ppo_stats_from_sums``), or None: ``model_config.TRAIN_STATS`` is off, this is the CPU replica,
+        or no update has run yet."""
+        if not getattr(self.net, "train_stats_on", False) or self._last_loss is None:
+            return None
+        sums = self.net.train_stats_sums()
+        if sums is None:
+            return None
+        from xingtian_amd.ops import ppo_stats_from_sums
+        return ppo_stats_from_sums(sums, loss=self._last_loss, ent_coef=self.ent_coef, critic_coef=self.critic_loss_coef)
 
     def predict(self, state):
         """-> (action [B] int32 | [B,A] f32, logp [B,1] f32, value [B,1] f32), xt/model/ppo/ppo.py:104-109."""
@@ -249,8 +272,13 @@ class PPO(XTModel):
         self._draw_ahead(n)
         # data parallel: the GLOBAL loss (every rank's share travelled in the tail of the exchanged gradient, summed in
         # rank order on the device: the same bits on every rank) -- no host collective; error bits raise
+        stats = self.net.train_stats_on
+        if stats:
+            self.net.enqueue_train_stats()      # (in front of read_loss's event: no synchronisation of its own)
         a = self.net.read_loss(acc)
-        return np.float32(a[0] / max(a[1], 1.0))
+        loss = np.float32(a[0] / max(a[1], 1.0))
+        self._last_loss = float(loss) if stats else None
+        return loss
 
     def _perm_block(self, n):
         """The pinned block the NEXT shuffles are written to: the one whose H2D is not the most recent (that copy may

@@ -30,3 +30,35 @@ def gae(value, reward, done, gamma=0.99, lam=0.95, device="cuda:0"):
     L.check(lib.xt_gae_f64(L.ptr(v), L.ptr(r), L.ptr(d), L.ptr(adv), L.ptr(tgt), L.ptr(ov), n, t,
                            float(gamma), float(lam), L.stream_ptr()), "xt_gae_f64")
     return adv.cpu().numpy(), ov.cpu().numpy(), tgt.cpu().numpy()
+
+
+def ppo_stats_from_sums(acc16, loss=None, ent_coef=0.0, critic_coef=1.0):
+    """The per-update PPO diagnostics from the XT_TRAIN_STATS_DOUBLES running sums one train leaves on the device (C ABI
+    ``xt_net_set_train_stats``; slots ``lib.TRAIN_STATS_SLOTS``).  Pure host arithmetic in float64, no GPU needed.
+
+    -> None when no step was counted, else a dict of Python floats: ``policy_loss`` / ``entropy`` / ``value_loss`` are
+    means of the minibatch means (as the reference's loss is), ``approx_kl`` / ``clip_fraction`` / ``vf_clip_fraction`` /
+    ``explained_variance`` are row-weighted (every visited row counts once), ``grad_norm`` / ``grad_norm_max`` /
+    ``grad_clip_fraction`` run over the steps.  ``explained_variance`` = 1 - Var(tv - v) / Var(tv), ``nan`` when Var(tv) is
+    zero (to within the rounding of the sums: 1e-12 of the mean square).  ``loss`` is the mean minibatch loss: ``loss``
+    when the caller has it (``Model.train`` returns it), else ``policy_loss - ent_coef * entropy + critic_coef *
+    value_loss``."""
+    a = np.asarray(acc16, np.float64).reshape(-1)
+    if a.shape[0] != L.TRAIN_STATS_DOUBLES:
+        raise ValueError("ppo_stats_from_sums: {} sums expected, got {}".format(L.TRAIN_STATS_DOUBLES, a.shape[0]))
+    s = L.TRAIN_STATS_SLOTS
+    steps, rows = float(a[s["STEPS"]]), float(a[s["ROWS"]])
+    if steps <= 0.0:
+        return None
+    per_row = (lambda k: float(a[s[k]]) / rows) if rows > 0.0 else (lambda k: float("nan"))
+    policy_loss, entropy, value_loss = -float(a[s["SURR"]]) / steps, float(a[s["ENT"]]) / steps, float(a[s["VF"]]) / steps
+    tv_sq, err_sq = per_row("TV_SQ"), per_row("ERR_SQ")
+    var_tv, var_err = tv_sq - per_row("TV") ** 2, err_sq - per_row("ERR") ** 2
+    explained = 1.0 - var_err / var_tv if var_tv > 1e-12 * tv_sq else float("nan")
+    if loss is None:
+        loss = policy_loss - float(ent_coef) * entropy + float(critic_coef) * value_loss
+    return dict(loss=float(loss), policy_loss=policy_loss, entropy=entropy, value_loss=value_loss,
+                approx_kl=per_row("KL"), clip_fraction=per_row("CLIPPED"), vf_clip_fraction=per_row("VF_CLIPPED"),
+                explained_variance=explained, grad_norm=float(a[s["GNORM_SUM"]]) / steps,
+                grad_norm_max=float(a[s["GNORM_MAX"]]), grad_clip_fraction=float(a[s["GNORM_CLIPPED"]]) / steps,
+                steps=steps, rows=rows)
