@@ -966,6 +966,69 @@ int xt_heads_wgrad_partial_ex(const float* f_pi, const float* f_v, int32_t B, in
                               const float* dlogits, const float* dvalue, float* slab_pi, int64_t stride_pi,
                               float* slab_v, int64_t stride_v, int32_t* nchunk_out, void* stream);
 
+/* Per-train IMPALA v-trace diagnostics (ImpalaCnnOpt's path: xt_net_impala_step / xt_net_impala_train / _train_io),
+ * accumulated on the device inside the train's own launches (appended under ABI 12; opt-in).  `stats`:
+ * XT_IMPALA_STATS_DOUBLES doubles (8-byte aligned), `traj_stats`: [max_traj, XT_IMPALA_TRAJ_STATS_FLOATS] floats of scratch
+ * (16-byte aligned), both device memory owned by the caller; xt_net_workspace_bytes does not change.  NULL, NULL switches
+ * the diagnostics off (the default): every launch is then the one of a net that never had them.  Refused on a net with a
+ * data-parallel tail, a gradient exchange hook or a direct comm (the row statistics would be rank-local), and
+ * xt_net_set_dp / xt_net_set_grad_exchange are refused while they are on.
+ *
+ * With the buffers set, the v-trace / loss kernel of every chunk is its STATS instance: the lead workgroup of a trajectory
+ * also leaves one row of traj_stats -- per column a float sum over the transitions t < T - 1 (wave sums, then the waves in
+ * wave order; never an atomic) of values the kernel holds anyway:
+ *     column 0 ce * pg   1 entropy   2 (vs - v)^2   3 vs - v   4 vs   5 vs^2   6 blp - tlp (= -log rho)   7 rho
+ *            8 [rho > 1] (the transitions the rho_bar = c_bar = 1 clip cuts)   9 max rho (a maximum)   10 T - 1   11 0
+ * (tlp / blp: log-probability of the taken action under the target / behaviour logits).  Wherever the chunk's loss scalar
+ * is formed -- the extra block of the gradient-reduction launch, or the loss-reduce launch of the unfused heads and of a
+ * gradient-only step -- one thread per column adds the rows in trajectory order, in double, to the slots below, and the
+ * thread that writes the pre-clip global norm into adam_state[4] (Adam, its folded-IO instance, centred RMSProp, the fused
+ * and the ticket tail) adds the norm.  One fixed order everywhere: a replayed hipGraph and the eager call give the same
+ * bits.  xt_net_impala_train(_io) clears the block at its start with a kernel inside the graph; xt_net_impala_step only
+ * accumulates (its caller clears), and with apply == 0 it leaves the three gradient-norm slots alone.  The pointers are part
+ * of the IMPALA trains' hipGraph key.  max_traj: rows of traj_stats; a chunk with more trajectories is refused. */
+#define XT_IMPALA_STATS_DOUBLES 16
+#define XT_IMPALA_TRAJ_STATS_FLOATS 12
+#define XT_IMPALA_STATS_CHUNKS 0         /* chunks (optimiser steps)                                          */
+#define XT_IMPALA_STATS_TRANSITIONS 1    /* transitions that carry loss: trajectories x (T - 1)               */
+#define XT_IMPALA_STATS_PG 2             /* sum of ce * pg_advantage (the policy-gradient piece of the loss)  */
+#define XT_IMPALA_STATS_ENT 3            /* ... entropy of the target policy                                  */
+#define XT_IMPALA_STATS_VERR_SQ 4        /* ... (vs - v)^2                                                    */
+#define XT_IMPALA_STATS_VERR 5           /* ... vs - v                                                        */
+#define XT_IMPALA_STATS_VS 6             /* ... vs                                                            */
+#define XT_IMPALA_STATS_VS_SQ 7          /* ... vs^2                                                          */
+#define XT_IMPALA_STATS_NEG_LOG_RHO 8    /* ... blp - tlp: KL(behaviour || target) on behaviour samples       */
+#define XT_IMPALA_STATS_RHO 9            /* ... rho = exp(tlp - blp)                                          */
+#define XT_IMPALA_STATS_RHO_CLIPPED 10   /* transitions with rho > 1                                          */
+#define XT_IMPALA_STATS_RHO_MAX 11       /* largest rho (a maximum)                                           */
+#define XT_IMPALA_STATS_GNORM_SUM 12     /* sum over chunks of the pre-clip global gradient norm              */
+#define XT_IMPALA_STATS_GNORM_MAX 13     /* its maximum                                                       */
+#define XT_IMPALA_STATS_GNORM_CLIPPED 14 /* chunks with the norm above grad_norm_clip                         */
+#define XT_IMPALA_STATS_RESERVED 15      /* 0                                                                 */
+int xt_net_set_impala_stats(xt_net* net, double* stats, float* traj_stats, int32_t max_traj);
+/* xt_impala_heads_ex / xt_impala_loss through the STATS instances, for kernel tests: the same arguments and launchers, plus
+ * traj_stats [n_traj, XT_IMPALA_TRAJ_STATS_FLOATS] (16-byte aligned) and stats [XT_IMPALA_STATS_DOUBLES], which the loss-reduce
+ * launch ADDS to (the caller clears; the gradient-norm slots are not touched).  The instance is recorded as the existing
+ * entries record theirs: *path_out of xt_impala_heads_stats_ex carries XT_IMPALA_PATH_STATS_BIT on top of
+ * xt_impala_heads_ex's word; xt_impala_loss_stats returns through *path_out (may be NULL)
+ *     XT_IMPALA_PATH_LOSS | (MAXT / 64) << XT_HEAD_AM_SHIFT | XT_IMPALA_PATH_STATS_BIT
+ * for impala_loss_kernel<MAXT, true>, MAXT = 64 / 128 / 256 / 1024 (the smallest that holds T).  xt_net_last_head_path
+ * returns the same words (without the bit when the statistics are off) after an IMPALA step. */
+#define XT_IMPALA_PATH_LOSS 3
+#define XT_IMPALA_PATH_STATS_BIT 0x10000
+int xt_impala_heads_stats_ex(const float* feat, const float* part, int32_t ksplit, int64_t part_stride, const float* tbias,
+                             int32_t act_feat, int32_t run_fwd, int32_t n_traj, int32_t T, int32_t F, int32_t A,
+                             const float* wpi, const float* bpi, const float* wv, const float* bv, const float* bp_logits,
+                             const int32_t* action, const uint8_t* done, const float* reward, float gamma, int32_t act_prev,
+                             float* feat_w, float* logits, float* baseline, float* dlogits, float* dbaseline, float* vs,
+                             float* pg_adv, float* dfeat, float* traj_loss, float* loss_out, void* stream, int32_t* path_out,
+                             float* traj_stats, double* stats);
+int xt_impala_loss_stats(const float* logits, const float* baseline, const float* bp_logits,
+                         const int32_t* action, const uint8_t* done, const float* reward,
+                         int32_t n_traj, int32_t T, int32_t A, float gamma,
+                         float* dlogits, float* dbaseline, float* out, float* acc,
+                         float* vs, float* pg_adv, void* stream, float* traj_stats, double* stats, int32_t* path_out);
+
 #ifdef __cplusplus
 }
 #endif

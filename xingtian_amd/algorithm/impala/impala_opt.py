@@ -124,6 +124,11 @@ class IMPALAOpt(Algorithm):
             self.dp.new_rollout()
         return loss
 
+    def train_stats(self):
+        """The model's diagnostics of the last train (``model_config.TRAIN_STATS``), or None"""
+        fn = getattr(self.actor, "train_stats", None)
+        return fn() if fn is not None else None
+
     def predict(self, state):
         return self.actor.predict(state)
 

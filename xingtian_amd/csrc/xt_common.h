@@ -200,7 +200,35 @@ struct LossArgs {
   // (!in_rng) + 2 * (!in_v), tv, tv - v} and the XT_TRAIN_STATS_DOUBLES running sums they are reduced into
   const float* rows;
   double* stats;
+  // xt_net_set_impala_stats (null: off; IMPALA's form, terms == nullptr): the v-trace kernel's per-trajectory rows
+  // [n_traj][XT_IMPALA_TRAJ_STATS_FLOATS], reduced into the XT_IMPALA_STATS_DOUBLES running sums `stats`
+  const float* traj_stats;
 };
+
+// ---- xt_net_set_impala_stats: what the STATS instances of the two v-trace kernels and the loss reductions share
+constexpr int kImpalaStatCols = 10;      // reduced columns of a traj_stats row; column 10 = T - 1, column 11 = 0
+constexpr int kImpalaStatMaxCol = 9;     // ... of which this one is a maximum
+// one transition's share of the ten columns (column c feeds slot XT_IMPALA_STATS_PG + c), from values the kernel holds anyway
+__device__ __forceinline__ void impala_stats_columns(float* col, float ce, float pg, float ent, float dvv, float vs, float nlr,
+                                                     float rho) {
+  col[0] = ce * pg; col[1] = ent; col[2] = dvv * dvv; col[3] = dvv; col[4] = vs; col[5] = vs * vs;
+  col[6] = nlr; col[7] = rho; col[8] = rho > 1.f ? 1.f : 0.f; col[9] = rho;
+}
+// the chunk's rows into the running sums: thread `c` of the caller (12 of them) owns one column and walks the trajectories
+// in order, in double; c == 10 counts the transitions, c == 11 the chunk
+__device__ __forceinline__ void impala_stats_reduce(const float* traj_stats, int n_traj, double* stats, int c) {
+  static_assert(XT_IMPALA_STATS_RHO_MAX == XT_IMPALA_STATS_PG + kImpalaStatMaxCol &&
+                XT_IMPALA_TRAJ_STATS_FLOATS >= kImpalaStatCols + 2, "column c <-> slot XT_IMPALA_STATS_PG + c");
+  if (c < 0 || c > kImpalaStatCols + 1) return;
+  if (c == kImpalaStatCols + 1) { stats[XT_IMPALA_STATS_CHUNKS] += 1.0; return; }
+  double s = 0.0;
+  for (int i = 0; i < n_traj; ++i) {
+    const double x = (double)traj_stats[(size_t)i * XT_IMPALA_TRAJ_STATS_FLOATS + c];
+    s = c == kImpalaStatMaxCol ? fmax(s, x) : s + x;
+  }
+  if (c == kImpalaStatMaxCol) stats[XT_IMPALA_STATS_RHO_MAX] = fmax(stats[XT_IMPALA_STATS_RHO_MAX], s);
+  else stats[c == kImpalaStatCols ? XT_IMPALA_STATS_TRANSITIONS : XT_IMPALA_STATS_PG + c] += s;
+}
 
 // One entry per parameter block: sum `nslab` partial slabs (fixed order) into dst and accumulate the
 // squared norm of the result.  nslab == 1 with src == dst only accumulates the norm.
@@ -259,6 +287,7 @@ struct ImpalaLossArgs {
   float *dlogits, *dbaseline, *traj_loss, *vs_out, *pg_out;
   const float *feat, *wpi, *wv;
   float* dfeat;
+  float* traj_stats;    // xt_net_set_impala_stats: [n_traj][XT_IMPALA_TRAJ_STATS_FLOATS] (LossArgs::traj_stats), written by the STATS instances
 };
 
 // norm finalisation executed by the last block of grads_finish_kernel (ticket counter)

@@ -11,6 +11,11 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
 
 // ---------------------------------------------------------------- heads forward
 // one wave per sample; lanes stride the feature axis
@@ -198,19 +203,23 @@ __global__ __launch_bounds__(256) void ppo_loss_reduce_kernel(const float* __res
 // ---------------------------------------------------------------- IMPALA v-trace loss
 // one block per trajectory, thread t = time step.  Phases: (1) per-step rho/c/delta in
 // parallel, (2) serial reverse scan by thread 0 over LDS, (3) per-step pg_adv + grads.
-template <int MAXT>
+// STATS (xt_net_set_impala_stats): also the trajectory's row of traj_stats [n_traj][XT_IMPALA_TRAJ_STATS_FLOATS] (columns: see
+// impala_stats_columns) -- per column wave sums, then the waves in wave order; STATS = false is the kernel of every other path.
+template <int MAXT, bool STATS = false>
 __global__ __launch_bounds__(MAXT) void impala_loss_kernel(const float* __restrict__ logits, const float* __restrict__ baseline,
                                                            const float* __restrict__ bp_logits, const int32_t* __restrict__ action,
                                                            const uint8_t* __restrict__ done, const float* __restrict__ reward,
                                                            int T, int A, float gamma, float* __restrict__ dlogits,
                                                            float* __restrict__ dbaseline, float* __restrict__ traj_loss,
-                                                           float* __restrict__ vs_out, float* __restrict__ pg_out) {
+                                                           float* __restrict__ vs_out, float* __restrict__ pg_out,
+                                                           float* __restrict__ traj_stats) {
   __shared__ float s_delta[MAXT], s_dc[MAXT], s_vs[MAXT + 1], s_red[MAXT];
   const int t = threadIdx.x;
   const int traj = blockIdx.x;
   const int Tm = T - 1;                      // steps that carry loss; step T-1 is the bootstrap only
   const size_t base = (size_t)traj * T;
   float rho = 0.f, disc = 0.f, rew = 0.f, val = 0.f, ce = 0.f, ent = 0.f, logz = 0.f, mx = 0.f, z = 1.f;
+  float nlr = 0.f, st_pg = 0.f, st_vs = 0.f, st_dvv = 0.f;      // (STATS only)
   int act = 0;
   if (t < Tm) {
     const float* lg = logits + (base + t) * A;
@@ -227,6 +236,7 @@ __global__ __launch_bounds__(MAXT) void impala_loss_kernel(const float* __restri
     const float blp = (bl[act] - bmx) - logf(bz);
     ce = -tlp;
     rho = expf(tlp - blp);
+    if (STATS) nlr = blp - tlp;
     disc = done[base + t] ? 0.f : gamma;
     rew = fminf(fmaxf(reward[base + t], -1.f), 1.f);
     val = baseline[base + t];
@@ -266,6 +276,7 @@ __global__ __launch_bounds__(MAXT) void impala_loss_kernel(const float* __restri
     lterm = ce * pg + 0.5f * (0.5f * dvv * dvv) + 0.01f * (-ent);
     if (vs_out) vs_out[(size_t)traj * Tm + t] = vs;
     if (pg_out) pg_out[(size_t)traj * Tm + t] = pg;
+    if (STATS) { st_pg = pg; st_vs = vs; st_dvv = dvv; }
   } else if (t == Tm) {
     for (int a = 0; a < A; ++a) dlogits[(base + t) * A + a] = 0.f;
     dbaseline[base + t] = 0.f;
@@ -277,6 +288,28 @@ __global__ __launch_bounds__(MAXT) void impala_loss_kernel(const float* __restri
     for (int q = 0; q < T; ++q) s += s_red[q];
     traj_loss[traj] = s;
   }
+  if (STATS) {
+    constexpr int NW = MAXT / 64;
+    float col[kImpalaStatCols];
+    impala_stats_columns(col, ce, st_pg, ent, st_dvv, st_vs, nlr, rho);      // (all zero beyond the last transition)
+    __syncthreads();                              // thread 0 has read the loss terms: s_red is scratch from here
+#pragma unroll
+    for (int k = 0; k < kImpalaStatCols; ++k) {
+      const float w = k == kImpalaStatMaxCol ? wave_max(col[k]) : wave_sum(col[k]);
+      if ((t & 63) == 0) s_red[k * NW + (t >> 6)] = w;
+    }
+    __syncthreads();
+    if (t < XT_IMPALA_TRAJ_STATS_FLOATS) {
+      float s = 0.f;
+      if (t < kImpalaStatCols) {
+        s = s_red[t * NW];
+        for (int w = 1; w < NW; ++w) s = t == kImpalaStatMaxCol ? fmaxf(s, s_red[t * NW + w]) : s + s_red[t * NW + w];
+      } else if (t == kImpalaStatCols) {
+        s = (float)Tm;
+      }
+      traj_stats[(size_t)traj * XT_IMPALA_TRAJ_STATS_FLOATS + t] = s;
+    }
+  }
 }
 
 __global__ void impala_loss_reduce_kernel(const float* __restrict__ traj_loss, int n, float* __restrict__ out,
@@ -287,6 +320,20 @@ __global__ void impala_loss_reduce_kernel(const float* __restrict__ traj_loss, i
     out[0] = s;
     if (acc) { acc[0] += s; acc[1] += 1.f; }
   }
+}
+// xt_net_set_impala_stats: the same launch with a second wave that adds the chunk's traj_stats rows to the running sums, one
+// thread per column, in trajectory order (impala_stats_reduce) -- beside thread 0's serial loop, not behind it
+__global__ __launch_bounds__(128) void impala_loss_reduce_stats_kernel(const float* __restrict__ traj_loss, int n,
+                                                                       float* __restrict__ out, float* __restrict__ acc,
+                                                                       const float* __restrict__ traj_stats,
+                                                                       double* __restrict__ stats) {
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int i = 0; i < n; ++i) s += traj_loss[i];
+    out[0] = s;
+    if (acc) { acc[0] += s; acc[1] += 1.f; }
+  }
+  if (threadIdx.x >= 64) impala_stats_reduce(traj_stats, n, stats, threadIdx.x - 64);
 }
 
 // ---------------------------------------------------------------- heads backward
@@ -365,12 +412,6 @@ __global__ __launch_bounds__(256) void heads_wgrad_kernel(const float* __restric
 // heads forward + PPO loss + d(logits,value) + gradient w.r.t. the trunk features, one wave per
 // sample, lane a <-> action a (A <= 64).  Same arithmetic as heads_fwd_kernel / ppo_loss_kernel /
 // heads_dfeat_kernel; the loss scalar is reduced later (norm_finalize_kernel) from `terms`.
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // One wave (= one 64-thread workgroup) per sample, specialised on NQ = ceil(F/64) features per lane, on whether
 // the split-K partial slabs of the last trunk layer still have to be summed (PART) and on shared/separate trunks.
 // EVERY global load of the wave is issued before the first dependent instruction (the kernel is a pure latency
@@ -709,8 +750,10 @@ int launch_impala_heads_fwd(const ImpalaHeadArgs& a, hipStream_t st) {
 // produces d(features) of its own kVtRows rows -- one workgroup per trajectory walking all T rows was a chain of
 // T/4 dependent global-load round trips (47 us at T = 128 for breakout_impala's single trajectory).  The reverse scan (tf.scan,
 // vtrace.py:94-106) is a wave-parallel suffix scan over affine maps (round 3, see below).
+// STATS (xt_net_set_impala_stats): the lead block also leaves the trajectory's row of traj_stats (as impala_loss_kernel<., true>;
+// s_red holds the wave results: no LDS added); STATS = false is the kernel of every other path.
 constexpr int kVtRows = 8;
-template <int AM>
+template <int AM, bool STATS = false>
 __global__ __launch_bounds__(256) void impala_vtrace_bwd_kernel(const ImpalaLossArgs p) {
   constexpr int MAXT = 256;
   __shared__ float s_delta[MAXT], s_dc[MAXT], s_val[MAXT + 1], s_vs[MAXT + 1], s_red[MAXT], s_dv[MAXT];
@@ -737,6 +780,7 @@ __global__ __launch_bounds__(256) void impala_vtrace_bwd_kernel(const ImpalaLoss
     }
   }
   float rho = 0.f, disc = 0.f, rew = 0.f, val = 0.f, ce = 0.f, ent = 0.f, logz = 0.f, mx = 0.f, z = 1.f, p_nval = 0.f;
+  float nlr = 0.f, st_pg = 0.f, st_vs = 0.f, st_dvv = 0.f;      // (STATS only)
   int act = 0;
   // every global operand of this thread's time step is requested before the first use: as rolled loops over the A
   // actions (runtime trip count) the logits were fetched one per iteration, each followed by s_waitcnt vmcnt(0) -- three
@@ -778,6 +822,7 @@ __global__ __launch_bounds__(256) void impala_vtrace_bwd_kernel(const ImpalaLoss
     const float blp = (bla - bmx) - logf(bz);
     ce = -tlp;
     rho = expf(tlp - blp);
+    if (STATS) nlr = blp - tlp;
     disc = dn ? 0.f : p.gamma;
     rew = fminf(fmaxf(rraw, -1.f), 1.f);
     p_nval = nval;
@@ -833,6 +878,7 @@ __global__ __launch_bounds__(256) void impala_vtrace_bwd_kernel(const ImpalaLoss
     lterm = ce * pg + 0.5f * (0.5f * dvv * dvv) + 0.01f * (-ent);
     if (lead && p.vs_out) p.vs_out[(size_t)traj * Tm + t] = vs;
     if (lead && p.pg_out) p.pg_out[(size_t)traj * Tm + t] = pg;
+    if (STATS) { st_pg = pg; st_vs = vs; st_dvv = dvv; }
   } else if (t == Tm) {
     for (int a = 0; a < A; ++a) { if (lead) p.dlogits[(base + t) * A + a] = 0.f; s_dl[t * AM + a] = 0.f; }
     if (lead) p.dbaseline[base + t] = 0.f;
@@ -842,8 +888,27 @@ __global__ __launch_bounds__(256) void impala_vtrace_bwd_kernel(const ImpalaLoss
     const float ws = wave_sum(lterm);
     if ((t & 63) == 0) s_red[t >> 6] = ws;
   }
+  if (STATS && lead) {                            // column k's four wave results at s_red[4 + 4 k ..]
+    float col[kImpalaStatCols];
+    impala_stats_columns(col, ce, st_pg, ent, st_dvv, st_vs, nlr, rho);      // (all zero beyond the last transition)
+#pragma unroll
+    for (int k = 0; k < kImpalaStatCols; ++k) {
+      const float w = k == kImpalaStatMaxCol ? wave_max(col[k]) : wave_sum(col[k]);
+      if ((t & 63) == 0) s_red[4 + 4 * k + (t >> 6)] = w;
+    }
+  }
   __syncthreads();
   if (t == 0 && blockIdx.y == 0) p.traj_loss[traj] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+  if (STATS && lead && t < XT_IMPALA_TRAJ_STATS_FLOATS) {
+    float s = 0.f;
+    if (t < kImpalaStatCols) {
+      const float* r = s_red + 4 + 4 * t;
+      s = t == kImpalaStatMaxCol ? fmaxf(fmaxf(r[0], r[1]), fmaxf(r[2], r[3])) : (r[0] + r[1]) + (r[2] + r[3]);
+    } else if (t == kImpalaStatCols) {
+      s = (float)Tm;
+    }
+    p.traj_stats[(size_t)traj * XT_IMPALA_TRAJ_STATS_FLOATS + t] = s;
+  }
   // d(features)[r, f] = (sum_a dlogits[r,a] Wpi[f,a] + dbaseline[r] Wv[f]) * act'(feature)   (heads_dfeat_kernel)
   // for this block's kVtRows rows: every row's feature load is issued before the first use
   for (int f = t; f < F; f += 256) {
@@ -884,17 +949,57 @@ __global__ __launch_bounds__(256) void impala_vtrace_bwd_kernel(const ImpalaLoss
 int launch_impala_vtrace_bwd(const ImpalaLossArgs& a, int n_traj, hipStream_t st) {
   if (a.T > 256 || a.A > 32 || n_traj < 1) return -1;
   const dim3 grid(n_traj, (a.T + kVtRows - 1) / kVtRows);
-  if (a.A <= 8) hipLaunchKernelGGL((impala_vtrace_bwd_kernel<8>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((impala_vtrace_bwd_kernel<32>), grid, dim3(256), 0, st, a);
-  last_path() = head_path_bits(XT_HEAD_PATH_IMPALA, 0, false, false, a.A <= 8 ? 8 : 32);
+  if (a.traj_stats) {
+    XT_REQUIRE(((uintptr_t)a.traj_stats & 15) == 0, "impala_vtrace_bwd: the trajectory statistics must be 16-byte aligned");
+    if (a.A <= 8) hipLaunchKernelGGL((impala_vtrace_bwd_kernel<8, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((impala_vtrace_bwd_kernel<32, true>), grid, dim3(256), 0, st, a);
+  } else {
+    if (a.A <= 8) hipLaunchKernelGGL((impala_vtrace_bwd_kernel<8>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((impala_vtrace_bwd_kernel<32>), grid, dim3(256), 0, st, a);
+  }
+  last_path() = head_path_bits(XT_HEAD_PATH_IMPALA, 0, false, false, a.A <= 8 ? 8 : 32) |
+                (a.traj_stats ? XT_IMPALA_PATH_STATS_BIT : 0);
   XT_LAUNCH_CHECK();
   return 0;
 }
 
-int launch_impala_loss_reduce(const float* traj_loss, int n, float* out, float* acc, hipStream_t st) {
-  hipLaunchKernelGGL(impala_loss_reduce_kernel, dim3(1), dim3(64), 0, st, traj_loss, n, out, acc);
+// (traj_stats / stats: both null -> the launch of every other path; else the chunk's rows are added to the running sums)
+int launch_impala_loss_reduce(const float* traj_loss, int n, float* out, float* acc, hipStream_t st, const float* traj_stats,
+                              double* stats) {
+  if (traj_stats || stats) {
+    XT_REQUIRE(traj_stats && stats, "impala_loss_reduce: traj_stats and stats go together");
+    hipLaunchKernelGGL(impala_loss_reduce_stats_kernel, dim3(1), dim3(128), 0, st, traj_loss, n, out, acc, traj_stats, stats);
+  } else {
+    hipLaunchKernelGGL(impala_loss_reduce_kernel, dim3(1), dim3(64), 0, st, traj_loss, n, out, acc);
+  }
   XT_LAUNCH_CHECK();
   return 0;
+}
+
+// xt_impala_loss: the unfused v-trace / loss kernel of the smallest MAXT that holds T, then the loss sum.  traj_stats / stats
+// (both null: the two launches of xt_impala_loss as ever): the STATS instance and the reduce launch that adds its rows
+int launch_impala_loss(const float* logits, const float* baseline, const float* bp_logits, const int32_t* action,
+                       const uint8_t* done, const float* reward, int n_traj, int T, int A, float gamma, float* dlogits,
+                       float* dbaseline, float* out, float* acc, float* vs, float* pg_adv, float* traj_stats, double* stats,
+                       hipStream_t st) {
+  XT_REQUIRE(n_traj > 0 && T >= 2 && T <= 1024, "xt_impala_loss: need 2 <= T <= 1024 (got %d)", T);
+  XT_REQUIRE(n_traj <= 4096, "xt_impala_loss: n_traj too large");
+  XT_REQUIRE((traj_stats != nullptr) == (stats != nullptr), "xt_impala_loss: traj_stats and stats go together");
+  XT_REQUIRE(((uintptr_t)traj_stats & 15) == 0 && ((uintptr_t)stats & 7) == 0,
+             "xt_impala_loss: traj_stats must be 16-byte aligned, stats 8-byte aligned");
+  // traj_loss scratch lives in out[4..4+n_traj)
+  float* traj_loss = out + 4;
+  const int maxt = T <= 64 ? 64 : T <= 128 ? 128 : T <= 256 ? 256 : 1024;
+#define XT_IL(M, S)                                                                                                          \
+  hipLaunchKernelGGL((impala_loss_kernel<M, S>), dim3(n_traj), dim3(M), 0, st, logits, baseline, bp_logits, action, done,    \
+                     reward, T, A, gamma, dlogits, dbaseline, traj_loss, vs, pg_adv, traj_stats)
+#define XT_IL_S(M) do { if (traj_stats) XT_IL(M, true); else XT_IL(M, false); } while (0)
+  if (maxt == 64) XT_IL_S(64); else if (maxt == 128) XT_IL_S(128); else if (maxt == 256) XT_IL_S(256); else XT_IL_S(1024);
+#undef XT_IL_S
+#undef XT_IL
+  last_path() = XT_IMPALA_PATH_LOSS | ((maxt / 64) << XT_HEAD_AM_SHIFT) | (traj_stats ? XT_IMPALA_PATH_STATS_BIT : 0);
+  XT_LAUNCH_CHECK();
+  return launch_impala_loss_reduce(traj_loss, n_traj, out, acc, st, traj_stats, stats);
 }
 
 // ---------------------------------------------------------------- GAE (float64, bit-exact with numpy)
@@ -1487,26 +1592,21 @@ int xt_impala_loss(const float* logits, const float* baseline, const float* bp_l
                    const uint8_t* done, const float* reward, int32_t n_traj, int32_t T, int32_t A, float gamma,
                    float* dlogits, float* dbaseline, float* out, float* acc, float* vs, float* pg_adv,
                    void* stream) {
-  XT_REQUIRE(n_traj > 0 && T >= 2 && T <= 1024, "xt_impala_loss: need 2 <= T <= 1024 (got %d)", T);
-  XT_REQUIRE(n_traj <= 4096, "xt_impala_loss: n_traj too large");
-  // traj_loss scratch lives in out[4..4+n_traj)
-  float* traj_loss = out + 4;
-  hipStream_t st = xt::as_stream(stream);
-  if (T <= 64)
-    hipLaunchKernelGGL((xt::impala_loss_kernel<64>), dim3(n_traj), dim3(64), 0, st, logits, baseline, bp_logits, action,
-                       done, reward, T, A, gamma, dlogits, dbaseline, traj_loss, vs, pg_adv);
-  else if (T <= 128)
-    hipLaunchKernelGGL((xt::impala_loss_kernel<128>), dim3(n_traj), dim3(128), 0, st, logits, baseline, bp_logits, action,
-                       done, reward, T, A, gamma, dlogits, dbaseline, traj_loss, vs, pg_adv);
-  else if (T <= 256)
-    hipLaunchKernelGGL((xt::impala_loss_kernel<256>), dim3(n_traj), dim3(256), 0, st, logits, baseline, bp_logits, action,
-                       done, reward, T, A, gamma, dlogits, dbaseline, traj_loss, vs, pg_adv);
-  else
-    hipLaunchKernelGGL((xt::impala_loss_kernel<1024>), dim3(n_traj), dim3(1024), 0, st, logits, baseline, bp_logits,
-                       action, done, reward, T, A, gamma, dlogits, dbaseline, traj_loss, vs, pg_adv);
-  XT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(xt::impala_loss_reduce_kernel, dim3(1), dim3(64), 0, st, traj_loss, n_traj, out, acc);
-  XT_LAUNCH_CHECK();
+  return xt::launch_impala_loss(logits, baseline, bp_logits, action, done, reward, n_traj, T, A, gamma, dlogits, dbaseline, out,
+                                acc, vs, pg_adv, nullptr, nullptr, xt::as_stream(stream));
+}
+
+int xt_impala_loss_stats(const float* logits, const float* baseline, const float* bp_logits, const int32_t* action,
+                         const uint8_t* done, const float* reward, int32_t n_traj, int32_t T, int32_t A, float gamma,
+                         float* dlogits, float* dbaseline, float* out, float* acc, float* vs, float* pg_adv, void* stream,
+                         float* traj_stats, double* stats, int32_t* path_out) {
+  if (path_out) *path_out = 0;
+  xt::last_path() = 0;
+  XT_REQUIRE(traj_stats && stats, "xt_impala_loss_stats: null traj_stats / stats");
+  const int rc = xt::launch_impala_loss(logits, baseline, bp_logits, action, done, reward, n_traj, T, A, gamma, dlogits,
+                                        dbaseline, out, acc, vs, pg_adv, traj_stats, stats, xt::as_stream(stream));
+  if (rc) return rc;
+  if (path_out) *path_out = xt::last_path();
   return 0;
 }
 
@@ -1638,12 +1738,14 @@ int xt_ppo_heads_fused_ex(const float* f_pi, const float* f_v, const float* part
   return 0;
 }
 
-int xt_impala_heads_ex(const float* feat, const float* part, int32_t ksplit, int64_t part_stride, const float* tbias,
-                       int32_t act_feat, int32_t run_fwd, int32_t n_traj, int32_t T, int32_t F, int32_t A,
-                       const float* wpi, const float* bpi, const float* wv, const float* bv, const float* bp_logits,
-                       const int32_t* action, const uint8_t* done, const float* reward, float gamma, int32_t act_prev,
-                       float* feat_w, float* logits, float* baseline, float* dlogits, float* dbaseline, float* vs,
-                       float* pg_adv, float* dfeat, float* traj_loss, float* loss_out, void* stream, int32_t* path_out) {
+// xt_impala_heads_ex, and with traj_stats / stats (both or neither) xt_impala_heads_stats_ex
+static int impala_heads_ex(const float* feat, const float* part, int32_t ksplit, int64_t part_stride, const float* tbias,
+                           int32_t act_feat, int32_t run_fwd, int32_t n_traj, int32_t T, int32_t F, int32_t A,
+                           const float* wpi, const float* bpi, const float* wv, const float* bv, const float* bp_logits,
+                           const int32_t* action, const uint8_t* done, const float* reward, float gamma, int32_t act_prev,
+                           float* feat_w, float* logits, float* baseline, float* dlogits, float* dbaseline, float* vs,
+                           float* pg_adv, float* dfeat, float* traj_loss, float* loss_out, void* stream, int32_t* path_out,
+                           float* traj_stats, double* stats) {
   if (path_out) *path_out = 0;
   xt::last_path() = 0;
   XT_REQUIRE(n_traj > 0 && T >= 2 && F > 0 && A > 0, "xt_impala_heads_ex: bad sizes (n_traj=%d T=%d F=%d A=%d)", n_traj, T,
@@ -1676,14 +1778,41 @@ int xt_impala_heads_ex(const float* feat, const float* part, int32_t ksplit, int
   q.T = T; q.A = A; q.F = F; q.act_prev = act_prev; q.gamma = gamma;
   q.dlogits = dlogits; q.dbaseline = dbaseline; q.traj_loss = traj_loss; q.vs_out = vs; q.pg_out = pg_adv;
   q.feat = part ? feat_w : feat; q.wpi = wpi; q.wv = wv; q.dfeat = dfeat;
+  q.traj_stats = traj_stats;
   int rc = xt::launch_impala_vtrace_bwd(q, n_traj, st);
   if (rc > 0) return rc;
   XT_REQUIRE(rc == 0, "xt_impala_heads_ex: the fused v-trace kernel refuses T=%d A=%d", T, A);
   path |= xt::last_path();
-  rc = xt::launch_impala_loss_reduce(traj_loss, n_traj, loss_out, nullptr, st);
+  rc = xt::launch_impala_loss_reduce(traj_loss, n_traj, loss_out, nullptr, st, traj_stats, stats);
   if (rc) return rc;
   if (path_out) *path_out = path;
   return 0;
+}
+
+int xt_impala_heads_ex(const float* feat, const float* part, int32_t ksplit, int64_t part_stride, const float* tbias,
+                       int32_t act_feat, int32_t run_fwd, int32_t n_traj, int32_t T, int32_t F, int32_t A,
+                       const float* wpi, const float* bpi, const float* wv, const float* bv, const float* bp_logits,
+                       const int32_t* action, const uint8_t* done, const float* reward, float gamma, int32_t act_prev,
+                       float* feat_w, float* logits, float* baseline, float* dlogits, float* dbaseline, float* vs,
+                       float* pg_adv, float* dfeat, float* traj_loss, float* loss_out, void* stream, int32_t* path_out) {
+  return impala_heads_ex(feat, part, ksplit, part_stride, tbias, act_feat, run_fwd, n_traj, T, F, A, wpi, bpi, wv, bv,
+                         bp_logits, action, done, reward, gamma, act_prev, feat_w, logits, baseline, dlogits, dbaseline, vs,
+                         pg_adv, dfeat, traj_loss, loss_out, stream, path_out, nullptr, nullptr);
+}
+
+int xt_impala_heads_stats_ex(const float* feat, const float* part, int32_t ksplit, int64_t part_stride, const float* tbias,
+                             int32_t act_feat, int32_t run_fwd, int32_t n_traj, int32_t T, int32_t F, int32_t A,
+                             const float* wpi, const float* bpi, const float* wv, const float* bv, const float* bp_logits,
+                             const int32_t* action, const uint8_t* done, const float* reward, float gamma, int32_t act_prev,
+                             float* feat_w, float* logits, float* baseline, float* dlogits, float* dbaseline, float* vs,
+                             float* pg_adv, float* dfeat, float* traj_loss, float* loss_out, void* stream, int32_t* path_out,
+                             float* traj_stats, double* stats) {
+  if (path_out) *path_out = 0;
+  XT_REQUIRE(traj_stats && stats && ((uintptr_t)stats & 7) == 0,
+             "xt_impala_heads_stats_ex: null traj_stats / stats, or stats not 8-byte aligned");
+  return impala_heads_ex(feat, part, ksplit, part_stride, tbias, act_feat, run_fwd, n_traj, T, F, A, wpi, bpi, wv, bv,
+                         bp_logits, action, done, reward, gamma, act_prev, feat_w, logits, baseline, dlogits, dbaseline, vs,
+                         pg_adv, dfeat, traj_loss, loss_out, stream, path_out, traj_stats, stats);
 }
 
 int xt_heads_wgrad_partial_ex(const float* f_pi, const float* f_v, int32_t B, int32_t F, int32_t A,

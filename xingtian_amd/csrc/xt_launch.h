@@ -89,7 +89,13 @@ int launch_act_apply(const float* z, float* y, long long count, int act, hipStre
 int launch_ppo_heads_fused(const PpoHeadArgs& a, hipStream_t st);
 int launch_impala_heads_fwd(const ImpalaHeadArgs& a, hipStream_t st);
 int launch_impala_vtrace_bwd(const ImpalaLossArgs& a, int n_traj, hipStream_t st);
-int launch_impala_loss_reduce(const float* traj_loss, int n, float* out, float* acc, hipStream_t st);
+int launch_impala_loss_reduce(const float* traj_loss, int n, float* out, float* acc, hipStream_t st,
+                              const float* traj_stats = nullptr, double* stats = nullptr);
+// xt_impala_loss with the optional trajectory rows / running sums of xt_net_set_impala_stats (both null: its two launches)
+int launch_impala_loss(const float* logits, const float* baseline, const float* bp_logits, const int32_t* action,
+                       const uint8_t* done, const float* reward, int n_traj, int T, int A, float gamma, float* dlogits,
+                       float* dbaseline, float* out, float* acc, float* vs, float* pg_adv, float* traj_stats, double* stats,
+                       hipStream_t st);
 int launch_ppo_loss_gauss(const float* mean, const float* log_std, const float* value, int B, int A, const int32_t* idx,
                           const float* action, const float* old_logp, const double* adv, const float* old_v,
                           const double* target_v, float clip_ratio, float ent_coef, float vf_clip, float critic_coef,
@@ -145,7 +151,8 @@ int launch_train_stats_reduce(const LossArgs* la, hipStream_t st);
 int launch_train_stats_clear(double* stats, hipStream_t st);
 int launch_rmsprop_clip(float* param, const float* grad, float* mg, float* ms, long long count, float lr, float decay,
                         float eps, float* state, const float* partial, int nblocks, float clip_norm, float grad_scale,
-                        hipStream_t st, const float* lr_dev = nullptr, const DpStep* dp = nullptr, int block_cap = 0);
+                        hipStream_t st, const float* lr_dev = nullptr, const DpStep* dp = nullptr, int block_cap = 0,
+                        double* stats = nullptr);
 int launch_dp_tail_write(float* tail, int rank, float rows, const float* loss, float* state, float lr,
                          const float* lr_dev, float beta1, float beta2, int advance, hipStream_t st);
 int launch_dp_tail_consume(const DpStep* dp, hipStream_t st);

@@ -136,6 +136,11 @@ struct xt_net {
   double* tstats = nullptr;
   float* trows = nullptr;
   int last_head_path = 0;
+  // xt_net_set_impala_stats: the caller's running sums and per-trajectory rows [itraj_max][XT_IMPALA_TRAJ_STATS_FLOATS] (both
+  // null: off)
+  double* istats = nullptr;
+  float* itraj = nullptr;
+  int itraj_max = 0;
 };
 
 namespace xt {
@@ -542,7 +547,7 @@ struct OptCfg {
   int opt_type;                 // XT_OPT_ADAM, or XT_OPT_RMSPROP_CENTERED (IMPALA only)
   float lr, beta1, beta2, eps, rms_decay, rms_eps, clip, gscale;
   const float* lr_dev;          // IMPALA: the step size in device memory (may be null)
-  double* stats = nullptr;      // PPO: the training-statistics sums (xt_net_set_train_stats; may be null)
+  double* stats = nullptr;      // the training-statistics sums (xt_net_set_train_stats / xt_net_set_impala_stats; may be null)
 };
 static OptCfg ppo_opt(const xt_ppo_cfg* c) {
   return OptCfg{XT_OPT_ADAM, c->lr, c->beta1, c->beta2, c->eps, 0.f, 0.f, c->max_grad_norm, c->grad_scale, nullptr};
@@ -581,7 +586,7 @@ static int step_tail_apply(xt_net* n, int B, FinalizeArgs fin, const OptCfg& o, 
   }
   if (o.opt_type == XT_OPT_RMSPROP_CENTERED)
     return launch_rmsprop_clip(n->params, n->grads, n->m, n->v, n->P, o.lr, o.rms_decay, o.rms_eps, n->state,
-                               n->ws + n->off_norm, n->norm_blocks, o.clip, o.gscale, st, o.lr_dev);
+                               n->ws + n->off_norm, n->norm_blocks, o.clip, o.gscale, st, o.lr_dev, nullptr, 0, o.stats);
   XT_REQUIRE(o.opt_type == XT_OPT_ADAM, "%s: unknown opt_type %d", who, o.opt_type);
   // (enable == 1: the last block of the reduction has finalised already)
   return net_apply(n, o.lr, o.beta1, o.beta2, o.eps, o.clip, o.gscale, fin.enable == 1 ? 2 : 3, nullptr, st,
@@ -788,6 +793,10 @@ static int impala_step(xt_net* n, const xt_impala_cfg* c, const void* obs, int n
   XT_REQUIRE(nfr <= n->maxB, "xt_net_impala_step: %d frames > max batch %d", nfr, n->maxB);
   const Heads hd = heads_of(n);
   const int ntraj = nfr / T, F = hd.F, A = hd.A;
+  XT_REQUIRE(!n->istats || apply <= 1, "xt_net_impala_step: the v-trace statistics are not kept under data parallelism");
+  XT_REQUIRE(!n->istats || ntraj <= n->itraj_max, "xt_net_impala_step: %d trajectories > the %d rows of traj_stats "
+                                                  "(xt_net_set_impala_stats)", ntraj, n->itraj_max);
+  float* const itraj = n->istats ? n->itraj : nullptr;
   Layer& Lp = *hd.Lp;
   float* lo = n->ws + n->off_loss;   // [0] = loss, [4 .. 4 + n_traj) per-trajectory sums
   // fused form (ImpalaCnnOpt: one trunk, A <= 8, T <= 256): split-K finish + heads in one launch, v-trace + loss +
@@ -820,17 +829,21 @@ static int impala_step(xt_net* n, const xt_impala_cfg* c, const void* obs, int n
     q.dlogits = n->ws + n->off_dlogits; q.dbaseline = n->ws + n->off_dvalue; q.traj_loss = lo + 4;
     q.feat = hd.f_pi; q.wpi = hd.wpi; q.wv = hd.wv;
     q.dfeat = n->ws + Lp.dact_off;
+    q.traj_stats = itraj;
     rc = launch_impala_vtrace_bwd(q, ntraj, st);
     if (rc > 0) return rc;
     XT_REQUIRE(rc == 0, "xt_net_impala_step: fused v-trace kernel rejected the geometry (T=%d A=%d)", T, A);
+    n->last_head_path = last_path();
     loss_pending = true;
   } else {
     if (int rc = net_forward(n, obs, nullptr, nfr, true, st)) return rc;
-    if (int rc = xt_impala_loss(n->ws + n->off_logits, n->ws + n->off_value, bp_logits, action, done, reward, ntraj, T,
-                                A, c->gamma, n->ws + n->off_dlogits, n->ws + n->off_dvalue, lo,
-                                (apply == 3 && n->dp_world >= 1) ? nullptr : loss_acc,      // (tail mode: the optimiser side adds the GLOBAL loss)
-                                nullptr, nullptr, st))
+    // (with the statistics on, the loss-reduce launch behind the kernel also adds the chunk's rows to the running sums)
+    if (int rc = launch_impala_loss(n->ws + n->off_logits, n->ws + n->off_value, bp_logits, action, done, reward, ntraj, T,
+                                    A, c->gamma, n->ws + n->off_dlogits, n->ws + n->off_dvalue, lo,
+                                    (apply == 3 && n->dp_world >= 1) ? nullptr : loss_acc,      // (tail mode: the optimiser side adds the GLOBAL loss)
+                                    nullptr, nullptr, itraj, n->istats, st))
       return rc;
+    n->last_head_path = last_path();
     if (loss_out) XT_CHECK_HIP(hipMemcpyAsync(loss_out, lo, sizeof(float), hipMemcpyDeviceToDevice, st));
     if (int rc = heads_dfeat(n, nfr, st)) return rc;
   }
@@ -840,16 +853,20 @@ static int impala_step(xt_net* n, const xt_impala_cfg* c, const void* obs, int n
   if (int rc = trunk_backward(n, obs, nullptr, nfr, st, (tov & 1) ? &tf : nullptr)) return rc;
   if (!apply) {
     if (int rc = grads_finish(n, nfr, nullptr, st)) return rc;
-    if (loss_pending) return launch_impala_loss_reduce(lo + 4, ntraj, loss_out ? loss_out : lo, loss_acc, st);
+    // (gradient only: no norm is formed, the three gradient-norm slots of the statistics stay)
+    if (loss_pending) return launch_impala_loss_reduce(lo + 4, ntraj, loss_out ? loss_out : lo, loss_acc, st, itraj, n->istats);
     return 0;
   }
   // step size bookkeeping (and the fused form's loss scalar) in an extra grads_finish block, clip factor inside the
   // Adam kernel: no finalize launch
-  const OptCfg o = impala_opt(c, lr_dev);
+  OptCfg o = impala_opt(c, lr_dev);
+  o.stats = n->istats;
   FinalizeArgs fin = finalize_args(n, 2, /*ticket*/ false, o);      // (only the fused tail and apply == 3 need the ticket)
+  fin.loss.stats = n->istats;        // (the fused tail adds the norm through it; the unfused heads have reduced their rows already)
   if (loss_pending) {
     fin.loss.traj_loss = lo + 4; fin.loss.n_traj = ntraj; fin.loss.out = loss_out ? loss_out : lo; fin.loss.acc = loss_acc;
     fin.loss.acc_set = set_acc ? 1 : 0;
+    fin.loss.traj_stats = itraj;
   }
   if (apply == 3) {
     // the data-parallel chunk of xt_net_impala_train: gradient + loss scalar + step-size advance (+ the tail / the scatter
@@ -1199,6 +1216,12 @@ static int impala_train_enqueue(xt_net* net, const xt_impala_cfg* c, const void*
                                 const xt::IoFold* fold = nullptr) {
   if (clear && net->xchg)       // (without an exchange the first chunk clears it itself: impala_step, first_chunk)
     if (int rc = xt::clear_loss_acc(net, loss_acc, st)) return rc;
+  if (net->istats) {            // a train's statistics start from zero: a kernel inside the graph (no memset node: clear_loss_acc)
+    XT_REQUIRE(!net->xchg && net->dp_world < 1 && !net->direct,
+               "xt_net_impala_train: the v-trace statistics are not kept under data parallelism "
+               "(xt_net_set_impala_stats(net, NULL, NULL, 0) first)");
+    if (int rc = xt::launch_train_stats_clear(net->istats, st)) return rc;
+  }
   XT_REQUIRE(n < (1 << 24), "xt_net_impala_train: %d frames do not fit the data-parallel tail's float slot", n);
   net->dp_rows = (float)n;
   const size_t frame = (size_t)net->in_h * net->in_w * net->in_c * (net->xf.is_u8 ? 1 : 4);
@@ -1402,13 +1425,14 @@ static int impala_train_run(xt_net* net, const xt_impala_cfg* c, const void* obs
     return (io_tail && !fold) ? xt::io_tail_enqueue(net, loss_acc, io_tail, cs) : 0;
   };
   if (!use_graph) return enqueue(st);
-  char key[512];
-  snprintf(key, sizeof(key), "I%d.%d.%d.%d.%p|%p|%p|%p|%d|%d|%p|%p|%p|%p|%p|%p|%g|%g|%g|%g|%g|%g|%d|%g|%d|%g|%g|%p|%d",
+  char key[640];
+  snprintf(key, sizeof(key), "I%d.%d.%d.%d.%p|%p|%p|%p|%d|%d|%p|%p|%p|%p|%p|%p|%g|%g|%g|%g|%g|%g|%d|%g|%d|%g|%g|%p|%d|%p|%p",
            c->shard_rank, c->shard_world, net->dp_rank, net->dp_world, (void*)net->direct, (void*)net->xchg, net->xchg_user, obs, n, batch_size, (const void*)bp_logits, (const void*)action,
            (const void*)done, (const void*)reward, (const void*)lr_steps, (void*)loss_acc, c->lr, c->beta1, c->beta2,
            c->eps, c->grad_norm_clip, c->gamma, c->sample_batch_step, c->grad_scale, c->opt_type, c->rms_decay, c->rms_eps,
            io_tail ? (void*)(reinterpret_cast<char*>(net->io_mb_dev) + io_tail) : nullptr,
-           fold ? 1 + (int)(io_seq & 1) : 0);      // (folded: the snapshot buffer of the train's parity is a kernel argument)
+           fold ? 1 + (int)(io_seq & 1) : 0,       // (folded: the snapshot buffer of the train's parity is a kernel argument)
+           (void*)net->istats, (void*)net->itraj);  // (statistics on / off: never each other's graph)
   return xt::graph_run(net, key, st, enqueue);
 }
 
@@ -1684,6 +1708,8 @@ int xt_net_set_grad_exchange_ex(xt_net* net, xt_grad_exchange_fn fn, void* user,
   XT_REQUIRE((flags & ~XT_XCHG_OVERLAP) == 0, "xt_net_set_grad_exchange_ex: unknown flags 0x%x", flags);
   XT_REQUIRE(!fn || !net->tstats, "xt_net_set_grad_exchange: switch the training statistics off first "
                                   "(xt_net_set_train_stats(net, NULL, NULL)): they are not kept under data parallelism");
+  XT_REQUIRE(!fn || !net->istats, "xt_net_set_grad_exchange: switch the v-trace statistics off first "
+                                  "(xt_net_set_impala_stats(net, NULL, NULL, 0)): they are not kept under data parallelism");
   net->xchg = fn;
   net->xchg_user = fn ? user : nullptr;
   net->xchg_flags = fn ? flags : 0;
@@ -1713,6 +1739,23 @@ int xt_net_set_train_stats(xt_net* net, double* stats, float* rows) {
 
 int32_t xt_net_last_head_path(const xt_net* net) { return net ? net->last_head_path : 0; }
 
+int xt_net_set_impala_stats(xt_net* net, double* stats, float* traj_stats, int32_t max_traj) {
+  XT_REQUIRE(net, "xt_net_set_impala_stats: null net");
+  if (!stats && !traj_stats) {
+    net->istats = nullptr; net->itraj = nullptr; net->itraj_max = 0;
+    return 0;
+  }
+  XT_REQUIRE(stats && traj_stats && max_traj > 0,
+             "xt_net_set_impala_stats: stats and traj_stats go together, with max_traj > 0 (NULL, NULL switches the statistics off)");
+  XT_REQUIRE(((uintptr_t)stats & 7) == 0 && ((uintptr_t)traj_stats & 15) == 0,
+             "xt_net_set_impala_stats: stats must be 8-byte aligned, traj_stats 16-byte aligned");
+  XT_REQUIRE(!net->xchg && net->dp_world < 1 && !net->direct,
+             "xt_net_set_impala_stats: refused on a net with a data-parallel tail, a gradient exchange hook or a direct comm "
+             "(the row statistics would be rank-local)");
+  net->istats = stats; net->itraj = traj_stats; net->itraj_max = max_traj;
+  return 0;
+}
+
 int xt_net_set_grad_exchange(xt_net* net, xt_grad_exchange_fn fn, void* user) {
   return xt_net_set_grad_exchange_ex(net, fn, user, 0);
 }
@@ -1729,6 +1772,8 @@ int xt_net_set_dp(xt_net* net, int32_t rank, int32_t world, float loss_scale) {
   XT_REQUIRE(net->grads, "xt_net_set_dp: buffers not bound");
   XT_REQUIRE(!net->tstats, "xt_net_set_dp: switch the training statistics off first (xt_net_set_train_stats(net, NULL, "
                            "NULL)): they are not kept under data parallelism");
+  XT_REQUIRE(!net->istats, "xt_net_set_dp: switch the v-trace statistics off first (xt_net_set_impala_stats(net, NULL, NULL, "
+                           "0)): they are not kept under data parallelism");
   net->dp_rank = rank; net->dp_world = world; net->dp_loss_scale = loss_scale;
   return 0;
 }

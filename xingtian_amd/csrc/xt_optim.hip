@@ -49,6 +49,10 @@ __device__ __forceinline__ bool grid_wait(unsigned int* flag, unsigned int sense
 }
 __device__ __forceinline__ void adam_advance(float* state, float lr, float beta1, float beta2);
 // xt_net_set_train_stats: the pre-clip global norm of one step into the running sums, by the thread that writes state[4]
+// (xt_net_set_impala_stats keeps the same three slots)
+static_assert(XT_IMPALA_STATS_GNORM_SUM == XT_TRAIN_STATS_GNORM_SUM && XT_IMPALA_STATS_GNORM_MAX == XT_TRAIN_STATS_GNORM_MAX &&
+              XT_IMPALA_STATS_GNORM_CLIPPED == XT_TRAIN_STATS_GNORM_CLIPPED && XT_IMPALA_STATS_DOUBLES == XT_TRAIN_STATS_DOUBLES,
+              "the PPO and the IMPALA statistics share stats_add_gnorm and train_stats_clear_kernel");
 __device__ __forceinline__ void stats_add_gnorm(double* stats, float gnorm, float clip_norm) {
   stats[XT_TRAIN_STATS_GNORM_SUM] += (double)gnorm;
   stats[XT_TRAIN_STATS_GNORM_MAX] = fmax(stats[XT_TRAIN_STATS_GNORM_MAX], (double)gnorm);
@@ -394,6 +398,10 @@ __device__ void loss_reduce_body(const LossArgs& la, double* sh) {
         else { la.acc[0] += s; la.acc[1] += 1.f; }
       }
     }
+    // xt_net_set_impala_stats: the chunk's trajectory rows into the running sums, by the second wave -- beside thread 0's
+    // serial loop, not behind it
+    if (STATS && la.stats && la.traj_stats && threadIdx.x >= 64)
+      impala_stats_reduce(la.traj_stats, la.n_traj, la.stats, (int)threadIdx.x - 64);
     return;
   }
   double t3[3] = {0.0, 0.0, 0.0};
@@ -824,12 +832,15 @@ __global__ __launch_bounds__(256) void adam_tf_clip_kernel(float* __restrict__ p
 // tf.train.RMSPropOptimizer(centered=True, momentum=0) after tf.clip_by_global_norm, TF1 apply_centered_rms_prop:
 //   ms = decay*ms + (1-decay)*g^2;  mg = decay*mg + (1-decay)*g;  var -= lr * g / sqrt(ms - mg^2 + epsilon)
 // (impala_cnn_opt.py:205-215).  Same structure as adam_tf_clip_kernel: every block derives the clip factor itself.
+// STATS (xt_net_set_impala_stats): block 0 also adds the gradient norm to the running sums `stats`.
+template <bool STATS = false>
 __global__ __launch_bounds__(256) void rmsprop_tf_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                               float* __restrict__ mg, float* __restrict__ ms,
                                                               long long count, float lr_arg, float decay, float eps,
                                                               float* __restrict__ state, const float* __restrict__ partial,
                                                               int nblocks, float clip_norm, float grad_scale,
-                                                              const float* __restrict__ lr_dev, const DpStep dp) {
+                                                              const float* __restrict__ lr_dev, const DpStep dp,
+                                                              double* __restrict__ stats) {
   __shared__ double sh[256];
   __shared__ float s_scale;
   const float lr = lr_dev ? lr_dev[0] : lr_arg;
@@ -841,7 +852,10 @@ __global__ __launch_bounds__(256) void rmsprop_tf_clip_kernel(float* __restrict_
     float gnorm, sc;
     clip_scale(sq, clip_norm, grad_scale, &gnorm, &sc);
     s_scale = sc;
-    if (blockIdx.x == 0) { state[2] = sc; state[4] = gnorm; }
+    if (blockIdx.x == 0) {
+      state[2] = sc; state[4] = gnorm;
+      if (STATS && stats) stats_add_gnorm(stats, gnorm, clip_norm);
+    }
   }
   __syncthreads();
   const float scale = s_scale, omd = 1.f - decay;
@@ -967,7 +981,7 @@ int grads_finish_fused_grid(const GradTable* tab) {
 
 int launch_rmsprop_clip(float* param, const float* grad, float* mg, float* ms, long long count, float lr, float decay,
                         float eps, float* state, const float* partial, int nblocks, float clip_norm, float grad_scale,
-                        hipStream_t st, const float* lr_dev, const DpStep* dp, int block_cap) {
+                        hipStream_t st, const float* lr_dev, const DpStep* dp, int block_cap, double* stats) {
   int nb = (int)((count + 255) / 256);
   if (nb > 2048) nb = 2048;
   if (block_cap > 0 && nb > block_cap) nb = block_cap;      // (blocks that wait for other ranks must all be resident)
@@ -975,8 +989,14 @@ int launch_rmsprop_clip(float* param, const float* grad, float* mg, float* ms, l
   DpStep d;
   if (dp) d = *dp; else memset(&d, 0, sizeof(d));
 
-  hipLaunchKernelGGL(rmsprop_tf_clip_kernel, dim3(nb), dim3(256), 0, st, param, grad, mg, ms, count, lr, decay, eps,
-                     state, partial, nblocks, clip_norm, grad_scale, lr_dev, d);
+  if (stats) {
+    XT_REQUIRE(!dp, "rmsprop: the training statistics are not kept under data parallelism");
+    hipLaunchKernelGGL(rmsprop_tf_clip_kernel<true>, dim3(nb), dim3(256), 0, st, param, grad, mg, ms, count, lr, decay, eps,
+                       state, partial, nblocks, clip_norm, grad_scale, lr_dev, d, stats);
+  } else {
+    hipLaunchKernelGGL(rmsprop_tf_clip_kernel<false>, dim3(nb), dim3(256), 0, st, param, grad, mg, ms, count, lr, decay, eps,
+                       state, partial, nblocks, clip_norm, grad_scale, lr_dev, d, nullptr);
+  }
   XT_LAUNCH_CHECK();
   return 0;
 }
@@ -1002,9 +1022,15 @@ int launch_adam_clip(float* param, const float* grad, float* m, float* v, long l
   if (io) {
     XT_REQUIRE(count * 4 < 0x7fffffffLL, "adam: %lld parameters exceed the snapshot store's 2 GiB offset range", count);
     f = *io;
-    XT_REQUIRE(!stats, "adam: the training statistics do not ride in the folded IO tail");
-    hipLaunchKernelGGL((adam_tf_clip_kernel<true, false>), dim3(nb), dim3(256), 0, st, param, grad, m, v, count, beta1, beta2,
-                       eps, state, partial, nblocks, clip_norm, grad_scale, d, f, nullptr);
+    XT_REQUIRE(!stats || !dp, "adam: the training statistics are not kept under data parallelism");
+    // (the folded tail reports the loss before the norm is formed: the sums are complete when the launch is, which is what a
+    // reader of the statistics waits for)
+    if (stats)
+      hipLaunchKernelGGL((adam_tf_clip_kernel<true, true>), dim3(nb), dim3(256), 0, st, param, grad, m, v, count, beta1, beta2,
+                         eps, state, partial, nblocks, clip_norm, grad_scale, d, f, stats);
+    else
+      hipLaunchKernelGGL((adam_tf_clip_kernel<true, false>), dim3(nb), dim3(256), 0, st, param, grad, m, v, count, beta1, beta2,
+                         eps, state, partial, nblocks, clip_norm, grad_scale, d, f, nullptr);
   } else if (stats) {
     XT_REQUIRE(!dp, "adam: the training statistics are not kept under data parallelism");
     hipLaunchKernelGGL((adam_tf_clip_kernel<false, true>), dim3(nb), dim3(256), 0, st, param, grad, m, v, count, beta1, beta2,

@@ -100,6 +100,13 @@ TRAIN_STATS_DOUBLES = 16  # XT_TRAIN_STATS_DOUBLES: the running sums of xt_net_s
 # XT_TRAIN_STATS_<name>: slot of every sum (include/xt_mi355x.h)
 TRAIN_STATS_SLOTS = {"STEPS": 0, "ROWS": 1, "SURR": 2, "ENT": 3, "VF": 4, "KL": 5, "CLIPPED": 6, "VF_CLIPPED": 7, "TV": 8,
                      "TV_SQ": 9, "ERR": 10, "ERR_SQ": 11, "GNORM_SUM": 12, "GNORM_MAX": 13, "GNORM_CLIPPED": 14, "RESERVED": 15}
+IMPALA_STATS_DOUBLES = 16       # XT_IMPALA_STATS_DOUBLES: the running sums of xt_net_set_impala_stats
+IMPALA_TRAJ_STATS_FLOATS = 12   # XT_IMPALA_TRAJ_STATS_FLOATS: floats per trajectory row of its scratch
+# XT_IMPALA_STATS_<name>: slot of every sum (include/xt_mi355x.h); column c of a trajectory row feeds slot PG + c
+IMPALA_STATS_SLOTS = {"CHUNKS": 0, "TRANSITIONS": 1, "PG": 2, "ENT": 3, "VERR_SQ": 4, "VERR": 5, "VS": 6, "VS_SQ": 7,
+                      "NEG_LOG_RHO": 8, "RHO": 9, "RHO_CLIPPED": 10, "RHO_MAX": 11, "GNORM_SUM": 12, "GNORM_MAX": 13,
+                      "GNORM_CLIPPED": 14, "RESERVED": 15}
+IMPALA_PATH_LOSS, IMPALA_PATH_STATS_BIT = 3, 0x10000      # XT_IMPALA_PATH_*: the unfused loss kernel's word, the STATS instances
 NET_HEAD_PLAIN, NET_HEAD_GAUSS = 0x10000, 0x20000      # XT_NET_HEAD_*: xt_net_last_head_path beside the fused kernel's word
 _P = c_void_p
 # name -> (restype, argtypes); every symbol include/xt_mi355x.h declares
@@ -150,6 +157,12 @@ SIGNATURES = {
     "xt_net_ppo_train": (c_int32, [_P, POINTER(PpoCfg), _P, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int32, _P]),
     "xt_net_set_train_stats": (c_int32, [_P, _P, _P]),
     "xt_net_last_head_path": (c_int32, [_P]),
+    "xt_net_set_impala_stats": (c_int32, [_P, _P, _P, c_int32]),
+    "xt_impala_loss_stats": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P, _P,
+                                       _P, _P, POINTER(c_int32)]),
+    "xt_impala_heads_stats_ex": (c_int32, [_P, _P, c_int32, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                           _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_int32, _P, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _P, POINTER(c_int32), _P, _P]),
     "xt_net_set_grad_exchange": (c_int32, [_P, _P, _P]),
     "xt_net_set_grad_exchange_ex": (c_int32, [_P, _P, _P, c_int32]),
     "xt_keras_impala_loss": (c_int32, [_P, _P, c_int32, c_int32, _P, _P, _P, _P, c_float, _P, _P, _P, _P, _P]),

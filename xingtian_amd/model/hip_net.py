@@ -482,8 +482,42 @@ class HipActorCritic(object):
         return ts["np"][ts["last"]].copy()
 
     def last_head_path(self):
-        """the head / loss kernel the most recent PPO step launched (C ABI ``xt_net_last_head_path``; diagnostic)"""
+        """the head / loss kernel the most recent PPO or IMPALA step launched (C ABI ``xt_net_last_head_path``; diagnostic)"""
         return int(self.lib.xt_net_last_head_path(self.handle))
+
+    # ------------------------------------------------------------------ per-train IMPALA v-trace diagnostics (opt-in)
+    impala_stats_on = False
+
+    def set_impala_stats(self, on=True):
+        """C ABI ``xt_net_set_impala_stats``: switch the per-train v-trace diagnostics on (the net then owns the 16 running
+        sums and one row of scratch per trajectory a chunk can hold) or off.  Refused by the library while a data-parallel
+        tail, a gradient exchange hook or a direct comm is attached."""
+        if on:
+            if getattr(self, "_istats", None) is None:
+                rows = max(int(self.max_batch) // 2, 1)         # (a trajectory has at least two frames)
+                pin = torch.zeros(L.IMPALA_STATS_DOUBLES, dtype=torch.float64, pin_memory=True)
+                self._istats = dict(acc=torch.zeros(L.IMPALA_STATS_DOUBLES, dtype=torch.float64, device=self.device),
+                                    traj=torch.zeros((rows, L.IMPALA_TRAJ_STATS_FLOATS), dtype=torch.float32,
+                                                     device=self.device), rows=rows, pin=pin, np=pin.numpy())
+            ts = self._istats
+            L.check(self.lib.xt_net_set_impala_stats(self.handle, L.ptr(ts["acc"]), L.ptr(ts["traj"]), ts["rows"]),
+                    "xt_net_set_impala_stats")
+        else:
+            L.check(self.lib.xt_net_set_impala_stats(self.handle, None, None, 0), "xt_net_set_impala_stats")
+        self.impala_stats_on = bool(on)
+
+    def clear_impala_stats(self):
+        """zero the running sums (``xt_net_impala_train`` does it itself; a caller of ``impala_step`` does it here)"""
+        self._istats["acc"].zero_()
+
+    def fetch_impala_stats(self):
+        """float64 [16]: the running sums as the work enqueued so far leaves them -- ONE 128-byte D2H into a pinned block
+        and one wait for the stream, both issued by this call (nothing rides behind a train when nobody asks)"""
+        ts = self._istats
+        cur = L.current_stream(self.device)
+        L.memcpy_async(ts["pin"].data_ptr(), ts["acc"].data_ptr(), 8 * L.IMPALA_STATS_DOUBLES, L.D2H, cur)
+        torch.cuda.current_stream(self.device).synchronize()
+        return ts["np"].copy()
 
     def read_loss(self, acc=None, wait=True):
         """[sum of step losses, number of steps, data-parallel error bits, -] of the train(s) enqueued so far: ONE 16-byte D2H

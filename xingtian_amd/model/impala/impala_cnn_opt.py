@@ -73,6 +73,22 @@ class ImpalaCnnOpt(XTModel):
         self._ingest = None
         self._dp = None
         self._lr_host = self._lr_dev = None
+        # TRAIN_STATS (default off): the per-train v-trace diagnostics (behaviour KL, importance ratios and their clip share,
+        # entropy, the three loss pieces, explained variance, gradient norm) accumulated on the device inside the train's own
+        # launches; ``train_stats()`` fetches them on demand -- nothing is enqueued per train when nobody asks
+        self._train_stats = bool(model_config.get("TRAIN_STATS", False))
+        self._last_loss = None
+        if self._train_stats:
+            import os
+            if self.async_loss:
+                raise ValueError("TRAIN_STATS is not available with ASYNC_LOSS: the reported loss belongs to the previous "
+                                 "train, the statistics could not be matched to it")
+            # (an explicit DP: strict / weak counts even where this process found no peers: the same YAML must not change
+            # its meaning with the number of ranks it is launched on)
+            world = int(os.environ.get("WORLD_SIZE", "1"))
+            if model_config.get("DP") in ("strict", "weak") or (world > 1 and model_config.get("DP") != "off"):
+                raise ValueError("TRAIN_STATS is not available under data parallelism (DP {}, WORLD_SIZE {}): the row "
+                                 "statistics would be rank-local".format(model_config.get("DP"), world))
         super().__init__(model_info)
 
     def create_model(self, model_info):
@@ -103,7 +119,22 @@ class ImpalaCnnOpt(XTModel):
                 self._cfg = self.net.make_impala_cfg(self.lr, self.grad_norm_clip, self.sample_batch_steps, GAMMA,
                                                      opt_type=self.opt_type, shard_rank=self._dp.rank,
                                                      shard_world=self._dp.world)
+        if self._train_stats:
+            if self._dp is not None:
+                raise ValueError("TRAIN_STATS is not available under data parallelism (DP {}): the row statistics would be "
+                                 "rank-local".format(self._dp.mode))
+            self.net.set_impala_stats(True)
         return True
+
+    def train_stats(self):
+        """The diagnostics of the LAST ``train`` / ``train_ingested`` as a dict of Python floats
+        (``xingtian_amd.ops.impala_stats_from_sums``), or None: ``model_config.TRAIN_STATS`` is off, this is the CPU replica,
+        or no train has run yet.  Valid from the return of ``train`` until the next train is launched; costs one 128-byte
+        pinned D2H and one wait for the stream, issued here."""
+        if not getattr(self.net, "impala_stats_on", False) or self._last_loss is None:
+            return None
+        from xingtian_amd.ops import impala_stats_from_sums
+        return impala_stats_from_sums(self.net.fetch_impala_stats(), loss=self._last_loss)
 
     # ---- resident rollout: every train goes pinned staging -> async H2D -> ONE C call (hipGraph replay) -------
     def _ingest_obj(self):
@@ -219,7 +250,9 @@ class ImpalaCnnOpt(XTModel):
             if a is None:
                 a = self.net.impala_wait_loss()
         # Data parallel: the sum is the GLOBAL one (the ranks' shares travelled in the tail of the exchanged gradient)
-        return np.float32(float(a[0]) / max(float(a[1]), 1.0))
+        loss = np.float32(float(a[0]) / max(float(a[1]), 1.0))
+        self._last_loss = float(loss) if self.net.impala_stats_on else None
+        return loss
 
     def train(self, state, label):
         """One chunk: state [n,...], label=[bp_logits, actions, dones, rewards] -> loss

@@ -32,6 +32,41 @@ def gae(value, reward, done, gamma=0.99, lam=0.95, device="cuda:0"):
     return adv.cpu().numpy(), ov.cpu().numpy(), tgt.cpu().numpy()
 
 
+def impala_stats_from_sums(sums, loss=None):
+    """The per-train IMPALA v-trace diagnostics from the XT_IMPALA_STATS_DOUBLES running sums one train leaves on the device
+    (C ABI ``xt_net_set_impala_stats``; slots ``lib.IMPALA_STATS_SLOTS``).  Pure host arithmetic in float64, no GPU needed.
+
+    -> None when no chunk was counted, else a dict of Python floats.  Per transition (every transition that carries loss
+    counts once): ``behaviour_kl`` = mean(-log rho), an estimator of KL(behaviour || target) on behaviour samples;
+    ``rho_mean``; ``rho_clip_fraction`` = share of rho > 1, the transitions the rho_bar = c_bar = 1 clip cuts; ``entropy``;
+    ``vs_mean``; ``explained_variance`` = 1 - Var(vs - v) / Var(vs) (``nan`` when Var(vs) is zero to within the rounding of
+    the sums: 1e-12 of the mean square).  ``rho_max`` is a maximum.  ``pg_loss`` / ``baseline_loss`` / ``entropy_loss`` are
+    the three sum-form pieces as per-chunk means, so that ``pg_loss + 0.5 * baseline_loss + 0.01 * entropy_loss`` is the mean
+    chunk loss (the kernel's constants).  ``grad_norm`` / ``grad_norm_max`` / ``grad_clip_fraction`` run over the chunks.
+    ``loss`` is the mean chunk loss: ``loss`` when the caller has it (``Model.train`` returns it), else the recombination."""
+    a = np.asarray(sums, np.float64).reshape(-1)
+    if a.shape[0] != L.IMPALA_STATS_DOUBLES:
+        raise ValueError("impala_stats_from_sums: {} sums expected, got {}".format(L.IMPALA_STATS_DOUBLES, a.shape[0]))
+    s = L.IMPALA_STATS_SLOTS
+    chunks, trans = float(a[s["CHUNKS"]]), float(a[s["TRANSITIONS"]])
+    if chunks <= 0.0:
+        return None
+    per_t = (lambda k: float(a[s[k]]) / trans) if trans > 0.0 else (lambda k: float("nan"))
+    pg_loss = float(a[s["PG"]]) / chunks
+    baseline_loss = 0.5 * float(a[s["VERR_SQ"]]) / chunks
+    entropy_loss = -float(a[s["ENT"]]) / chunks
+    vs_sq, err_sq = per_t("VS_SQ"), per_t("VERR_SQ")
+    var_vs, var_err = vs_sq - per_t("VS") ** 2, err_sq - per_t("VERR") ** 2
+    explained = 1.0 - var_err / var_vs if var_vs > 1e-12 * vs_sq else float("nan")
+    if loss is None:
+        loss = pg_loss + 0.5 * baseline_loss + 0.01 * entropy_loss
+    return dict(chunks=chunks, transitions=trans, behaviour_kl=per_t("NEG_LOG_RHO"), rho_mean=per_t("RHO"),
+                rho_max=float(a[s["RHO_MAX"]]), rho_clip_fraction=per_t("RHO_CLIPPED"), entropy=per_t("ENT"),
+                pg_loss=pg_loss, baseline_loss=baseline_loss, entropy_loss=entropy_loss, explained_variance=explained,
+                vs_mean=per_t("VS"), grad_norm=float(a[s["GNORM_SUM"]]) / chunks, grad_norm_max=float(a[s["GNORM_MAX"]]),
+                grad_clip_fraction=float(a[s["GNORM_CLIPPED"]]) / chunks, loss=float(loss))
+
+
 def ppo_stats_from_sums(acc16, loss=None, ent_coef=0.0, critic_coef=1.0):
     """The per-update PPO diagnostics from the XT_TRAIN_STATS_DOUBLES running sums one train leaves on the device (C ABI
     ``xt_net_set_train_stats``; slots ``lib.TRAIN_STATS_SLOTS``).  Pure host arithmetic in float64, no GPU needed.
