@@ -514,10 +514,21 @@ int xt_net_ppo_train(xt_net* net, const xt_ppo_cfg* cfg, const void* obs, int32_
 #define XT_TRAIN_STATS_RESERVED 15      /* 0                                                                */
 int xt_net_set_train_stats(xt_net* net, double* stats, float* rows);
 /* Which head / loss kernel the most recent PPO step of this net launched (diagnostic): the XT_HEAD_PATH_PPO_FUSED word
- * of xt_ppo_heads_fused_ex for the fused kernel, else one of the two codes below; 0 before the first step. */
+ * of xt_ppo_heads_fused_ex for the fused kernel (the XT_HEAD_PATH_PPO_GAUSS_FUSED word of xt_ppo_gauss_heads_fused_ex for
+ * the fused DiagGaussian one, see xt_net_set_gauss_fused), else one of the two codes below; 0 before the first step. */
 #define XT_NET_HEAD_PLAIN 0x10000       /* heads forward + ppo_loss_kernel + heads d(features)              */
 #define XT_NET_HEAD_GAUSS 0x20000       /* heads forward + ppo_loss_gauss_kernel + heads d(features)        */
 int32_t xt_net_last_head_path(const xt_net* net);
+/* The fused head launch for a DiagGaussian policy (appended under ABI 12; opt-in, per net).  on == 0 (the default): every
+ * launch is the one of a net that never had the switch (heads forward + ppo_loss_gauss_kernel + heads d(features);
+ * xt_net_last_head_path == XT_NET_HEAD_GAUSS).  on != 0: a PPO step whose head is inside the fused kernel's envelope
+ * (A <= 8, features <= 512, no layer that keeps its pre-activation) runs ppo_gauss_heads_fused_kernel instead, the last
+ * trunk layer's split-K finish deferred into it as for a categorical policy; xt_net_last_head_path then returns
+ * XT_HEAD_PATH_PPO_GAUSS_FUSED | nq | part | shared (see xt_ppo_gauss_heads_fused_ex).  Outside the envelope the step
+ * silently keeps the three launches.  The fused kernel takes the sums over the action dimensions as wave sums, so its
+ * float32 results differ from the default's in the last bits.  Refused on a categorical net.  The flag is part of
+ * xt_net_ppo_train's hipGraph key. */
+int xt_net_set_gauss_fused(xt_net* net, int32_t on);
 
 /* Gradient exchange hook of xt_net_ppo_train (ABI >= 4): the reference's learner is single-process
  * (its grad_communicate host averaging, xt/framework/trainer.py:89-92, is dead code); data parallelism is this
@@ -946,6 +957,28 @@ int xt_ppo_heads_fused_ex(const float* f_pi, const float* f_v, const float* part
                           const double* target_v, const xt_ppo_cfg* cfg, float inv_b, int32_t act_prev, float* logits,
                           float* value, float* dlogits, float* dvalue, float* terms, float* df_pi, float* df_v,
                           float* feat_pi_w, float* feat_v_w, void* stream, int32_t* path_out);
+/* The same launch for a DiagGaussian policy (appended under ABI 12): ppo_gauss_heads_fused_kernel<nq, part, shared>, the
+ * head launch of a net with xt_net_set_gauss_fused(net, 1).  As xt_ppo_heads_fused_ex, except
+ *   log_std         pi_logstd [A]
+ *   action          [pool, A] float32 rows, picked through idx like the other labels
+ *   mean, dmean     [B,A] (the categorical entry's logits / dlogits)
+ *   dls_rows        [B][ldls] (ldls >= A): every sample's share of d loss / d pi_logstd, columns < A written
+ *   rows            NULL, or [B,4] floats (16-byte aligned): the diagnostic rows of xt_net_set_train_stats, written by the
+ *                   STATS instances
+ * *path_out = XT_HEAD_PATH_PPO_GAUSS_FUSED | nq | part | shared.  Refused (before any device call): A > 8, F > 512, more
+ * than 16 slabs. */
+#define XT_HEAD_PATH_PPO_GAUSS_FUSED (4) /* ppo_gauss_heads_fused_kernel<nq, part, shared>; its case table is
+                                          * tests/test_gpu_gauss_heads.py (the plain-integer XT_HEAD_PATH_* macros above are
+                                          * the families whose tables tests/test_gpu_heads_branch.py holds) */
+int xt_ppo_gauss_heads_fused_ex(const float* f_pi, const float* f_v, const float* part_pi, const float* part_v,
+                                int32_t ksplit_pi, int32_t ksplit_v, int64_t part_stride, const float* tbias_pi,
+                                const float* tbias_v, int32_t act_feat, int32_t B, int32_t F, int32_t A, int32_t shared,
+                                const float* wpi, const float* bpi, const float* wv, const float* bv,
+                                const float* log_std, const int32_t* idx, const float* action, const float* old_logp,
+                                const double* adv, const float* old_v, const double* target_v, const xt_ppo_cfg* cfg,
+                                float inv_b, int32_t act_prev, float* mean, float* value, float* dmean, float* dvalue,
+                                float* dls_rows, int32_t ldls, float* terms, float* df_pi, float* df_v,
+                                float* feat_pi_w, float* feat_v_w, float* rows, void* stream, int32_t* path_out);
 /* IMPALA (one trunk): heads forward, then v-trace + loss + d(logits, baseline) + d(features), then the loss sum.
  *   run_fwd         1: logits / baseline [n_traj*T (,A)] are computed from feat [n_traj*T,F], or from `ksplit` partial
  *                   slabs as above (the finished features go to feat_w, which the second launch reads);

@@ -52,8 +52,9 @@ class PPO(Algorithm):
             return                  # DP_FEED round_robin: this trajectory belongs to another learner rank
         streaming = getattr(self.actor, "stream_ingest", False) and hasattr(self.actor, "ingest_trajectory")
         if "adv" not in train_data and not streaming:
-            # raw value/reward/done without the streaming ingest (continuous actions, odd vector widths): GAE on the
-            # learner GPU per message; the streaming path below batches it into ONE launch per rollout instead
+            # raw value/reward/done without the streaming ingest (STREAM_INGEST: false; continuous actions or odd vector
+            # widths under data parallelism): GAE on the learner GPU per message; the streaming path below -- every action
+            # type and observation width on one GPU -- batches it into ONE launch per rollout instead
             from xingtian_amd import ops
             adv, old_v, tgt = ops.gae(np.asarray(train_data["value"], np.float32).reshape(1, -1),
                                       np.asarray(train_data["reward"], np.float64).reshape(1, -1),

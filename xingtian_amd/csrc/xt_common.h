@@ -266,6 +266,16 @@ struct PpoHeadArgs {
   float* rows;          // xt_net_set_train_stats: [B,4] per-sample diagnostic rows (LossArgs::rows), written by the STATS instances
 };
 
+// The DiagGaussian sibling (ppo_gauss_heads_fused_kernel): everything of PpoHeadArgs but `action` (null), plus the float
+// action rows, pi_logstd and the per-sample pi_logstd gradient rows.  h.logits / h.dlogits hold the mean and d(mean).
+struct PpoGaussHeadArgs {
+  PpoHeadArgs h;
+  const float* action;   // [pool, A] float32, rows picked through h.idx
+  const float* log_std;  // pi_logstd [A]
+  float* dls_rows;       // [B][ldls]: every sample's share of d loss / d pi_logstd (grads_finish sums them as B slabs)
+  int ldls;
+};
+
 // IMPALA (ImpalaCnnOpt, one shared trunk): heads forward with the deferred split-K finish of the last trunk layer
 struct ImpalaHeadArgs {
   const float *feat, *wpi, *bpi, *wv, *bv;

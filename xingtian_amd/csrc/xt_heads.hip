@@ -623,6 +623,208 @@ int launch_ppo_heads_fused(const PpoHeadArgs& a, hipStream_t st) {
   return 0;
 }
 
+// ---------------------------------------------------------------- fused PPO head, DiagGaussian policy
+// The sibling of ppo_heads_fused_kernel for a DiagGaussian policy (xt_net_set_gauss_fused): same instance grid, same
+// envelope, same issue-everything-first structure (the one two-hop chain is idx -> labels, which here include the sample's
+// float action row).  Lane a < A owns action dimension a: mean = features . Wpi + bpi, then ppo_loss_gauss_kernel's
+// expressions (xt/model/tf_dist.py:47-87) with the three sums over a as wave sums, d(mean), the sample's pi_logstd row and
+// d(features) as the categorical kernel forms it from d(logits).
+// (waves_per_eu(1, 1): the register allocator may use the whole file -- without it the <4, PART, separate trunks> instance
+// spills 48 bytes per lane while AGPRs stand idle; the registers an instance really takes still decide how many waves a
+// SIMD holds, and a step launches B <= a few hundred one-wave workgroups.)
+template <int NQ, bool PART, bool SHARED, bool STATS = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void ppo_gauss_heads_fused_kernel(const PpoGaussHeadArgs g) {
+  const PpoHeadArgs& p = g.h;
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x;
+  const int F = p.F, A = p.A;
+  const size_t row = (size_t)b * F;
+  const bool la = lane < A;
+  const int lcl = la ? lane : 0;
+  // ---------------- issue phase (no dependent use in here)
+  const int s = p.idx ? p.idx[b] : b;
+  float praw[PART ? NQ : 1][kMaxHeadSplit], vraw[(PART && !SHARED) ? NQ : 1][kMaxHeadSplit];
+  float xin[NQ], xvin[NQ], tb[NQ], tbv[NQ], wvv[NQ], wp[NQ][kHeadMaxA];
+  int fcl[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int f = lane + 64 * q;
+    fcl[q] = f < F ? f : 0;
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    if (PART) {
+#pragma unroll
+      for (int z = 0; z < kMaxHeadSplit; ++z)
+        praw[q][z] = p.part_pi[(size_t)(z < p.ksplit_pi ? z : p.ksplit_pi - 1) * p.part_stride + row + fcl[q]];
+      tb[q] = p.tbias_pi[fcl[q]];
+      if (!SHARED) {
+#pragma unroll
+        for (int z = 0; z < kMaxHeadSplit; ++z)
+          vraw[q][z] = p.part_v[(size_t)(z < p.ksplit_v ? z : p.ksplit_v - 1) * p.part_stride + row + fcl[q]];
+        tbv[q] = p.tbias_v[fcl[q]];
+      }
+    } else {
+      xin[q] = p.f_pi[row + fcl[q]];
+      if (!SHARED) xvin[q] = p.f_v[row + fcl[q]];
+    }
+    wvv[q] = p.wv[fcl[q]];
+#pragma unroll
+    for (int a = 0; a < kHeadMaxA; ++a) wp[q][a] = p.wpi[(size_t)fcl[q] * A + (a < A ? a : 0)];
+  }
+  const float mybias = p.bpi[lcl];
+  const float ls = g.log_std[lcl];
+  const float bvv = p.bv[0];
+  // labels (second hop of idx)
+  const float xa = g.action[(size_t)s * A + lcl];
+  const float advf = (float)p.adv[s];
+  const float tv = (float)p.target_v[s];
+  const float ov = p.old_v[s];
+  const float olp = p.old_logp[s];
+
+  // ---------------- features
+  float fpi[NQ], fvv[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const bool ok = lane + 64 * q < F;
+    float x, xv;
+    if (PART) {
+      float sacc = 0.f;
+#pragma unroll
+      for (int z = 0; z < kMaxHeadSplit; z += 4)
+        sacc += ((z < p.ksplit_pi ? praw[q][z] : 0.f) + (z + 1 < p.ksplit_pi ? praw[q][z + 1] : 0.f)) +
+                ((z + 2 < p.ksplit_pi ? praw[q][z + 2] : 0.f) + (z + 3 < p.ksplit_pi ? praw[q][z + 3] : 0.f));
+      x = act_apply(sacc + tb[q], p.act_feat);
+      xv = x;
+      if (!SHARED) {
+        float vacc = 0.f;
+#pragma unroll
+        for (int z = 0; z < kMaxHeadSplit; z += 4)
+          vacc += ((z < p.ksplit_v ? vraw[q][z] : 0.f) + (z + 1 < p.ksplit_v ? vraw[q][z + 1] : 0.f)) +
+                  ((z + 2 < p.ksplit_v ? vraw[q][z + 2] : 0.f) + (z + 3 < p.ksplit_v ? vraw[q][z + 3] : 0.f));
+        xv = act_apply(vacc + tbv[q], p.act_feat);
+      }
+    } else {
+      x = xin[q];
+      xv = SHARED ? x : xvin[q];
+    }
+    fpi[q] = ok ? x : 0.f;
+    fvv[q] = ok ? xv : 0.f;
+  }
+  // ---------------- mean (lane a keeps mean a) and value
+  float acc[kHeadMaxA];
+#pragma unroll
+  for (int a = 0; a < kHeadMaxA; ++a) {
+    float t = 0.f;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) t = fmaf(fpi[q], wp[q][a], t);
+    acc[a] = t;
+  }
+  float sv = 0.f;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) sv = fmaf(fvv[q], wvv[q], sv);
+  float mymean = 0.f;
+#pragma unroll
+  for (int a = 0; a < kHeadMaxA; ++a) {
+    const float t = wave_sum(acc[a]);
+    if (a < A && lane == a) mymean = t + mybias;
+  }
+  const float v = wave_sum(sv) + bvv;
+
+  // ---------------- loss: neglog_prob = 0.5*log(2*pi)*A + 0.5*sum(z^2) + sum(log_std); entropy = sum(ls + 0.5*(log(2*pi)+1))
+  const float sd = expf(ls);
+  const float z = la ? (xa - mymean) / sd : 0.f;
+  const float ssq = wave_sum(z * z);
+  const float sls = wave_sum(la ? ls : 0.f);
+  const float ent = wave_sum(la ? ls + 1.4189385332046727f : 0.f);
+  const float logp = -(0.9189385332046727f * (float)A + 0.5f * ssq + sls);
+  const float ratio = expf(logp - olp);
+  const float surr1 = ratio * advf;
+  const float rc = fminf(fmaxf(ratio, 1.f - p.clip_ratio), 1.f + p.clip_ratio);
+  const float surr2 = rc * advf;
+  const bool first = surr1 <= surr2;
+  const bool in_rng = (ratio >= 1.f - p.clip_ratio) && (ratio <= 1.f + p.clip_ratio);
+  const float dsurr = (first || in_rng) ? advf : 0.f;
+  const float dlogp = -(dsurr * ratio) * p.inv_b;
+  const float d1 = v - tv, vf1 = d1 * d1;
+  const float vcl = ov + fminf(fmaxf(v - ov, -p.vf_clip), p.vf_clip);
+  const float d2 = vcl - tv, vf2 = d2 * d2;
+  const bool take1 = vf1 >= vf2;
+  const bool in_v = fabsf(v - ov) <= p.vf_clip;
+  const float dvr = take1 ? 2.f * d1 : (in_v ? 2.f * d2 : 0.f);
+  const float dv = p.critic_coef * 0.5f * p.inv_b * dvr;
+  const float dm = la ? dlogp * z / sd : 0.f;                                   // d logp / d mean = (x-mean)/std^2
+  // ---------------- d(features) = dmean . Wpi^T (+ dvalue . Wv^T), times the producer's activation gradient
+  float dacc[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) dacc[q] = 0.f;
+#pragma unroll
+  for (int a = 0; a < kHeadMaxA; ++a) {
+    const float dma = __shfl(dm, a, 64);          // dm == 0 for lanes >= A
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) dacc[q] = fmaf(dma, wp[q][a], dacc[q]);
+  }
+  // ---------------- stores
+  if (la) {
+    p.logits[(size_t)b * A + lane] = mymean;
+    p.dlogits[(size_t)b * A + lane] = dm;
+    g.dls_rows[(size_t)b * g.ldls + lane] = dlogp * (z * z - 1.f) - p.ent_coef * p.inv_b;   // d logp / d log_std = z^2 - 1; dH/dls = 1
+  }
+  if (lane == 0) {
+    p.value[b] = v;
+    p.dvalue[b] = dv;
+    float* tm = p.terms + (size_t)b * 4;
+    tm[0] = fminf(surr1, surr2); tm[1] = ent; tm[2] = fmaxf(vf1, vf2); tm[3] = 0.f;
+    if (STATS)
+      reinterpret_cast<float4*>(p.rows)[b] = make_float4(olp - logp, (in_rng ? 0.f : 1.f) + (in_v ? 0.f : 2.f), tv, tv - v);
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int f = lane + 64 * q;
+    if (f < F) {
+      if (PART) {
+        p.feat_pi_w[row + f] = fpi[q];
+        if (!SHARED) p.feat_v_w[row + f] = fvv[q];
+      }
+      const float svv = dv * wvv[q];
+      if (SHARED) {
+        p.df_pi[row + f] = (dacc[q] + svv) * act_grad(fpi[q], p.act_prev);
+      } else {
+        p.df_pi[row + f] = dacc[q] * act_grad(fpi[q], p.act_prev);
+        p.df_v[row + f] = svv * act_grad(fvv[q], p.act_prev);
+      }
+    }
+  }
+}
+
+// returns -1 when the geometry is outside the kernel's envelope (the caller keeps heads forward + ppo_loss_gauss_kernel +
+// heads d(features))
+int launch_ppo_gauss_heads_fused(const PpoGaussHeadArgs& g, hipStream_t st) {
+  const PpoHeadArgs& a = g.h;
+  if (a.A > kHeadMaxA || a.F > 512) return -1;
+  const bool part = a.part_pi != nullptr;
+  const bool shared = a.shared != 0;
+  if (part && (a.ksplit_pi > kMaxHeadSplit || (!shared && (!a.part_v || a.ksplit_v > kMaxHeadSplit)))) return -1;
+  XT_REQUIRE(g.action && g.log_std && g.dls_rows && g.ldls >= a.A, "ppo_gauss_heads_fused: bad arguments");
+  XT_REQUIRE(!a.rows || ((uintptr_t)a.rows & 15) == 0, "ppo_gauss_heads_fused: the diagnostic rows must be 16-byte aligned");
+  const int nq = (a.F + 63) / 64;
+  const dim3 grid(a.B), blk(64);
+#define XT_GHEAD_S(NQV, ST)                                                                                            \
+  do {                                                                                                                 \
+    if (part && shared) hipLaunchKernelGGL((ppo_gauss_heads_fused_kernel<NQV, true, true, ST>), grid, blk, 0, st, g);  \
+    else if (part) hipLaunchKernelGGL((ppo_gauss_heads_fused_kernel<NQV, true, false, ST>), grid, blk, 0, st, g);      \
+    else if (shared) hipLaunchKernelGGL((ppo_gauss_heads_fused_kernel<NQV, false, true, ST>), grid, blk, 0, st, g);    \
+    else hipLaunchKernelGGL((ppo_gauss_heads_fused_kernel<NQV, false, false, ST>), grid, blk, 0, st, g);               \
+  } while (0)
+#define XT_GHEAD(NQV) do { if (a.rows) XT_GHEAD_S(NQV, true); else XT_GHEAD_S(NQV, false); } while (0)
+  if (nq <= 1) XT_GHEAD(1); else if (nq <= 2) XT_GHEAD(2); else if (nq <= 4) XT_GHEAD(4); else XT_GHEAD(8);
+#undef XT_GHEAD
+#undef XT_GHEAD_S
+  last_path() = head_path_bits(XT_HEAD_PATH_PPO_GAUSS_FUSED, nq <= 1 ? 1 : nq <= 2 ? 2 : nq <= 4 ? 4 : 8, part, shared, 0);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_heads_dfeat(const float* f_pi, const float* f_v, int B, int F, int A, const float* wpi, const float* wv,
                        const float* dlogits, const float* dvalue, int act_prev, float* df_pi, float* df_v,
                        hipStream_t st) {
@@ -1733,6 +1935,53 @@ int xt_ppo_heads_fused_ex(const float* f_pi, const float* f_v, const float* part
   const int rc = xt::launch_ppo_heads_fused(h, xt::as_stream(stream));
   if (rc > 0) return rc;
   XT_REQUIRE(rc == 0, "xt_ppo_heads_fused_ex: the fused PPO head kernel refuses A=%d F=%d ksplit=%d/%d (A <= 8, F <= 512, ksplit <= 16)",
+             A, F, h.ksplit_pi, h.ksplit_v);
+  if (path_out) *path_out = xt::last_path();
+  return 0;
+}
+
+int xt_ppo_gauss_heads_fused_ex(const float* f_pi, const float* f_v, const float* part_pi, const float* part_v,
+                                int32_t ksplit_pi, int32_t ksplit_v, int64_t part_stride, const float* tbias_pi,
+                                const float* tbias_v, int32_t act_feat, int32_t B, int32_t F, int32_t A, int32_t shared,
+                                const float* wpi, const float* bpi, const float* wv, const float* bv,
+                                const float* log_std, const int32_t* idx, const float* action, const float* old_logp,
+                                const double* adv, const float* old_v, const double* target_v, const xt_ppo_cfg* cfg,
+                                float inv_b, int32_t act_prev, float* mean, float* value, float* dmean, float* dvalue,
+                                float* dls_rows, int32_t ldls, float* terms, float* df_pi, float* df_v,
+                                float* feat_pi_w, float* feat_v_w, float* rows, void* stream, int32_t* path_out) {
+  if (path_out) *path_out = 0;
+  xt::last_path() = 0;
+  XT_REQUIRE(B > 0 && F > 0 && A > 0, "xt_ppo_gauss_heads_fused_ex: bad sizes (B=%d F=%d A=%d)", B, F, A);
+  const bool part = part_pi != nullptr, sh = shared != 0;
+  XT_REQUIRE(!part || (ksplit_pi >= 1 && (sh || ksplit_v >= 1) && part_stride >= (int64_t)B * F),
+             "xt_ppo_gauss_heads_fused_ex: bad slab counts %d / %d or slab stride %lld", ksplit_pi, ksplit_v,
+             (long long)part_stride);
+  XT_REQUIRE(cfg && wpi && bpi && wv && bv && log_std && action && old_logp && adv && old_v && target_v && mean && value &&
+                 dmean && dvalue && dls_rows && terms && df_pi && (sh || df_v),
+             "xt_ppo_gauss_heads_fused_ex: null argument");
+  XT_REQUIRE(ldls >= A, "xt_ppo_gauss_heads_fused_ex: ldls %d below A=%d", ldls, A);
+  XT_REQUIRE(part ? (tbias_pi && feat_pi_w && (sh || (part_v && tbias_v && feat_v_w))) : (f_pi && (sh || f_v)),
+             "xt_ppo_gauss_heads_fused_ex: null feature argument");
+  xt::PpoGaussHeadArgs g;
+  xt::PpoHeadArgs& h = g.h;
+  h.f_pi = part ? feat_pi_w : f_pi; h.f_v = sh ? h.f_pi : (part ? feat_v_w : f_v);
+  h.wpi = wpi; h.bpi = bpi; h.wv = wv; h.bv = bv;
+  h.idx = idx; h.action = nullptr; h.old_logp = old_logp; h.old_v = old_v; h.adv = adv; h.target_v = target_v;
+  h.clip_ratio = cfg->clip_ratio; h.ent_coef = cfg->ent_coef; h.vf_clip = cfg->vf_clip; h.critic_coef = cfg->critic_coef;
+  h.inv_b = inv_b; h.B = B; h.F = F; h.A = A; h.act_prev = act_prev; h.shared = sh ? 1 : 0;
+  h.logits = mean; h.value = value; h.dlogits = dmean; h.dvalue = dvalue; h.terms = terms;
+  h.df_pi = df_pi; h.df_v = sh ? df_pi : df_v;
+  h.part_pi = h.part_v = nullptr; h.tbias_pi = h.tbias_v = nullptr; h.feat_pi_w = h.feat_v_w = nullptr;
+  h.ksplit_pi = h.ksplit_v = 1; h.act_feat = act_feat; h.part_stride = part ? (long long)part_stride : (long long)B * F;
+  h.rows = rows;
+  if (part) {
+    h.part_pi = part_pi; h.ksplit_pi = ksplit_pi; h.feat_pi_w = feat_pi_w; h.tbias_pi = tbias_pi;
+    if (!sh) { h.part_v = part_v; h.ksplit_v = ksplit_v; h.feat_v_w = feat_v_w; h.tbias_v = tbias_v; }
+  }
+  g.action = action; g.log_std = log_std; g.dls_rows = dls_rows; g.ldls = ldls;
+  const int rc = xt::launch_ppo_gauss_heads_fused(g, xt::as_stream(stream));
+  if (rc > 0) return rc;
+  XT_REQUIRE(rc == 0, "xt_ppo_gauss_heads_fused_ex: the fused DiagGaussian head kernel refuses A=%d F=%d ksplit=%d/%d (A <= 8, F <= 512, ksplit <= 16)",
              A, F, h.ksplit_pi, h.ksplit_v);
   if (path_out) *path_out = xt::last_path();
   return 0;

@@ -87,6 +87,7 @@ int launch_conv12_same_fwd(const xt_conv_geom* g, const xt_input_xform* xf, cons
 // ------------------------------------------------------------------ xt_heads.hip: heads and losses
 int launch_act_apply(const float* z, float* y, long long count, int act, hipStream_t st);
 int launch_ppo_heads_fused(const PpoHeadArgs& a, hipStream_t st);
+int launch_ppo_gauss_heads_fused(const PpoGaussHeadArgs& a, hipStream_t st);
 int launch_impala_heads_fwd(const ImpalaHeadArgs& a, hipStream_t st);
 int launch_impala_vtrace_bwd(const ImpalaLossArgs& a, int n_traj, hipStream_t st);
 int launch_impala_loss_reduce(const float* traj_loss, int n, float* out, float* acc, hipStream_t st,

@@ -136,6 +136,7 @@ struct xt_net {
   double* tstats = nullptr;
   float* trows = nullptr;
   int last_head_path = 0;
+  int gauss_fused = 0;                // xt_net_set_gauss_fused: a DiagGaussian step inside the envelope takes the fused head launch
   // xt_net_set_impala_stats: the caller's running sums and per-trajectory rows [itraj_max][XT_IMPALA_TRAJ_STATS_FLOATS] (both
   // null: off)
   double* istats = nullptr;
@@ -639,14 +640,15 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
   float* const trows = n->tstats ? n->trows : nullptr;
   const Heads hd = heads_of(n);
   Layer &Lp = *hd.Lp, &Lv = *hd.Lv;
-  bool fused_head = (!gauss && n->A <= 8 && n->feat <= 512 && Lp.z_off < 0 && Lv.z_off < 0);
+  const bool fused_head = ((!gauss || n->gauss_fused) && n->A <= 8 && n->feat <= 512 && Lp.z_off < 0 && Lv.z_off < 0);
   const int no_defer = tuning().defer_splitk ? 0 : 1;
   if (int rc = net_forward(n, obs, idx, B, false, st, fused_head && !no_defer)) return rc;
   const float inv_b = 1.f / (float)(c->global_batch > 0 ? c->global_batch : B);
   const int F = hd.F, A = hd.A;
   float* lo = loss_out ? loss_out : n->ws + n->off_loss;
   if (fused_head) {
-    PpoHeadArgs h;
+    PpoGaussHeadArgs gh;
+    PpoHeadArgs& h = gh.h;
     h.f_pi = hd.f_pi; h.f_v = hd.f_v;
     h.wpi = hd.wpi; h.bpi = hd.bpi; h.wv = hd.wv; h.bv = hd.bv;
     h.idx = idx; h.action = action; h.old_logp = old_logp; h.old_v = old_v; h.adv = adv; h.target_v = target_v;
@@ -668,7 +670,13 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
     }
     XT_REQUIRE(n->n_trunks == 1 || ((Lp.last_ksplit > 1) == (Lv.last_ksplit > 1)),
                "xt_net: pi and v trunks ended in different split-K states (unequal trunk shapes are not supported)");
-    const int hrc = launch_ppo_heads_fused(h, st);
+    if (gauss) {
+      h.action = nullptr;
+      gh.action = static_cast<const float*>(action_v); gh.log_std = n->params + n->logstd_off;
+      gh.dls_rows = n->ws + n->off_dls; gh.ldls = (int)align4(A);
+      n->dls_rows = B;
+    }
+    const int hrc = gauss ? launch_ppo_gauss_heads_fused(gh, st) : launch_ppo_heads_fused(h, st);
     if (hrc > 0) return hrc;
     XT_REQUIRE(hrc == 0, "xt_net: fused PPO head kernel rejected the geometry (A=%d F=%d)", A, F);
     n->last_head_path = last_path();
@@ -1190,13 +1198,14 @@ int xt_net_ppo_train(xt_net* net, const xt_ppo_cfg* c, const void* obs, int32_t 
   if (!use_graph)
     return ppo_train_enqueue(net, c, obs, n, perm, action, old_logp, adv, old_v, target_v, loss_acc, st);
   char key[640];
-  snprintf(key, sizeof(key), "P%d.%d.%d.%d.%d.%g.%p|%p|%p|%p|%d|%p|%p|%p|%p|%p|%p|%p|%g|%g|%g|%g|%g|%g|%g|%g|%g|%d|%d|%g|%d|%p|%p",
+  snprintf(key, sizeof(key), "P%d.%d.%d.%d.%d.%g.%p|%p|%p|%p|%d|%p|%p|%p|%p|%p|%p|%p|%g|%g|%g|%g|%g|%g|%g|%g|%g|%d|%d|%g|%d|%p|%p|%d",
            net->xchg_flags, c->shard_rank, c->shard_world, net->dp_rank, net->dp_world, net->dp_loss_scale, (void*)net->direct,
            (void*)net->xchg, net->xchg_user, obs, n,
            (const void*)perm, (const void*)action, (const void*)old_logp, (const void*)adv, (const void*)old_v,
            (const void*)target_v, (void*)loss_acc, c->lr, c->beta1, c->beta2, c->eps, c->clip_ratio, c->ent_coef,
            c->vf_clip, c->critic_coef, c->max_grad_norm, c->batch_size, c->num_sgd_iter, c->grad_scale,
-           c->global_batch, (void*)net->tstats, (void*)net->trows);      // (stats on / off: never each other's graph)
+           c->global_batch, (void*)net->tstats, (void*)net->trows,      // (stats on / off: never each other's graph)
+           net->gauss_fused);                          // (nor the two DiagGaussian head forms)
   return xt::graph_run(net, key, st, [&](hipStream_t cs) {
     return ppo_train_enqueue(net, c, obs, n, perm, action, old_logp, adv, old_v, target_v, loss_acc, cs);
   });
@@ -1738,6 +1747,14 @@ int xt_net_set_train_stats(xt_net* net, double* stats, float* rows) {
 }
 
 int32_t xt_net_last_head_path(const xt_net* net) { return net ? net->last_head_path : 0; }
+
+int xt_net_set_gauss_fused(xt_net* net, int32_t on) {
+  XT_REQUIRE(net, "xt_net_set_gauss_fused: null net");
+  XT_REQUIRE(net->action_type == XT_ACTION_DIAG_GAUSSIAN,
+             "xt_net_set_gauss_fused: refused on a categorical net (its head is ppo_heads_fused_kernel already)");
+  net->gauss_fused = on ? 1 : 0;
+  return 0;
+}
 
 int xt_net_set_impala_stats(xt_net* net, double* stats, float* traj_stats, int32_t max_traj) {
   XT_REQUIRE(net, "xt_net_set_impala_stats: null net");

@@ -40,6 +40,14 @@ PPO_FIELDS = (("action", torch.int32, 0), ("old_logp", torch.float32, 0), ("adv"
               ("old_v", torch.float32, 0), ("target_v", torch.float64, 0))
 
 
+def ppo_fields(action_type="Categorical", action_dim=0):
+    """label fields of a PPO trajectory for a policy of ``action_type``: ``PPO_FIELDS`` for Categorical (int32 action
+    indices); DiagGaussian stages the float32 action rows as an [n, action_dim] sub-array of the same label block."""
+    if action_type != "DiagGaussian":
+        return PPO_FIELDS
+    return (("action", torch.float32, int(action_dim)),) + PPO_FIELDS[1:]
+
+
 def impala_fields(action_dim):
     """label fields of an IMPALAOpt rollout message (xt/algorithm/impala/impala_opt.py:116-147): behaviour logits
     [n, A] f32, actions i32, dones (bool -> u8), rewards (float64 on the wire, float32 at the placeholder)."""
@@ -112,7 +120,8 @@ class RolloutIngest(object):
         self.obs_u8 = obs_u8
         self.fields = tuple(fields)
         # pad_channels = (c_dst, fill byte): image observations are staged with their own channel count and expanded on
-        # the device to the multiple of 4 the first layer reads (xt_pad_channels), see netspec._conv
+        # the device to the multiple of 4 the first layer reads (xt_pad_channels), see netspec._conv; vector observations
+        # whose width is no multiple of 4 likewise ([n, width] rows, fill byte 0: the zero columns of netspec._mlp)
         self.pad_channels = pad_channels
         self._n_raw = len(PPO_RAW_FIELDS) if self.fields[-len(PPO_RAW_FIELDS):] == PPO_RAW_FIELDS else 0
         self.raw_traj = 0               # trajectories of the current rollout that came without advantages

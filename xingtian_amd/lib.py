@@ -108,6 +108,7 @@ IMPALA_STATS_SLOTS = {"CHUNKS": 0, "TRANSITIONS": 1, "PG": 2, "ENT": 3, "VERR_SQ
                       "GNORM_CLIPPED": 14, "RESERVED": 15}
 IMPALA_PATH_LOSS, IMPALA_PATH_STATS_BIT = 3, 0x10000      # XT_IMPALA_PATH_*: the unfused loss kernel's word, the STATS instances
 NET_HEAD_PLAIN, NET_HEAD_GAUSS = 0x10000, 0x20000      # XT_NET_HEAD_*: xt_net_last_head_path beside the fused kernel's word
+HEAD_PATH_PPO_GAUSS_FUSED = 4      # XT_HEAD_PATH_PPO_GAUSS_FUSED: the family of ppo_gauss_heads_fused_kernel's path word
 _P = c_void_p
 # name -> (restype, argtypes); every symbol include/xt_mi355x.h declares
 SIGNATURES = {
@@ -157,6 +158,7 @@ SIGNATURES = {
     "xt_net_ppo_train": (c_int32, [_P, POINTER(PpoCfg), _P, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int32, _P]),
     "xt_net_set_train_stats": (c_int32, [_P, _P, _P]),
     "xt_net_last_head_path": (c_int32, [_P]),
+    "xt_net_set_gauss_fused": (c_int32, [_P, c_int32]),
     "xt_net_set_impala_stats": (c_int32, [_P, _P, _P, c_int32]),
     "xt_impala_loss_stats": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P, _P,
                                        _P, _P, POINTER(c_int32)]),
@@ -208,6 +210,10 @@ SIGNATURES = {
     "xt_ppo_heads_fused_ex": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int64, _P, _P, c_int32, c_int32, c_int32,
                                         c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(PpoCfg), c_float,
                                         c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, POINTER(c_int32)]),
+    "xt_ppo_gauss_heads_fused_ex": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int64, _P, _P, c_int32, c_int32, c_int32,
+                                              c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                              POINTER(PpoCfg), c_float, c_int32, _P, _P, _P, _P, _P, c_int32, _P, _P, _P,
+                                              _P, _P, _P, _P, POINTER(c_int32)]),
     "xt_impala_heads_ex": (c_int32, [_P, _P, c_int32, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                      _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                      _P, _P, POINTER(c_int32)]),

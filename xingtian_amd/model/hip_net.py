@@ -485,6 +485,15 @@ class HipActorCritic(object):
         """the head / loss kernel the most recent PPO or IMPALA step launched (C ABI ``xt_net_last_head_path``; diagnostic)"""
         return int(self.lib.xt_net_last_head_path(self.handle))
 
+    gauss_fused_on = False
+
+    def set_gauss_fused(self, on=True):
+        """C ABI ``xt_net_set_gauss_fused``: a DiagGaussian PPO step inside the fused head kernel's envelope (A <= 8,
+        features <= 512) runs ``ppo_gauss_heads_fused_kernel`` instead of heads forward + loss + heads d(features).  Off by
+        default; refused by the library on a categorical net."""
+        L.check(self.lib.xt_net_set_gauss_fused(self.handle, 1 if on else 0), "xt_net_set_gauss_fused")
+        self.gauss_fused_on = bool(on)
+
     # ------------------------------------------------------------------ per-train IMPALA v-trace diagnostics (opt-in)
     impala_stats_on = False
 

@@ -59,10 +59,11 @@ class PPO(XTModel):
         self._perm_dense = None
         self._perm_pin = None           # two pinned [NUM_SGD_ITER, n] blocks: this update's shuffles / the next one's
         self._perm_last, self._perm_next = 0, None    # block of the last H2D; block holding shuffles drawn ahead
-        # the streaming ingest stages int32 actions: discrete actions; vector observations must be 4-aligned (image
-        # observations with another channel count are expanded on the device, RolloutIngest.pad_channels)
-        self.stream_ingest = bool(model_config.get("STREAM_INGEST", True)) and not self.gauss and \
-            (len(self.state_dim) != 1 or int(self.state_dim[0]) % 4 == 0)
+        # the streaming ingest takes every action type (float32 action rows for DiagGaussian, ingest.ppo_fields) and every
+        # observation width (image channels and vector widths that are no multiple of 4 are expanded on the device,
+        # RolloutIngest.pad_channels); under data parallelism continuous actions and odd vector widths keep the
+        # non-streaming path (create_model)
+        self.stream_ingest = bool(model_config.get("STREAM_INGEST", True))
         self.gamma, self.lam = 0.99, 0.95       # GAE of raw trajectories; the PPO algorithm assigns its GAMMA / LAM
         super().__init__(model_info)
 
@@ -94,6 +95,8 @@ class PPO(XTModel):
         self._act = device_acting(model_info.get("model_config"), self.net, self._rng, self.seed)
         if self.net.inference_only:
             self.stream_ingest = False
+            if bool((model_info.get("model_config") or {}).get("GAUSS_FUSED_HEAD", False)):
+                self._set_gauss_fused()         # (logs that the key is ignored here)
             return self.net
         base = dict(LR=self._lr, LOSS_CLIPPING=self.clip_ratio, ENTROPY_LOSS=self.ent_coef, VF_CLIP=self.vf_clip,
                     CRITIC_LOSS_COEF=self.critic_loss_coef, MAX_GRAD_NORM=self._max_grad_norm,
@@ -107,6 +110,8 @@ class PPO(XTModel):
         if self._dp is not None:
             # (weak: the reported loss is the mean of the ranks' minibatch means; strict: the ranks' shares of one mean)
             self._dp.attach(self.net, loss_scale=1.0 / self._dp.world if self._dp.mode == "weak" else 1.0)
+            if self.gauss or (len(self.state_dim) == 1 and int(self.state_dim[0]) % 4 != 0):
+                self.stream_ingest = False      # (streaming these under data parallelism is not built)
             self._cfg, _ = self._dp.ppo_cfg(self.net, base)
             if self.adv_norm and not (self._dp.mode == "strict" and self._dp.feed == "replicated"):
                 # every rank would normalise with the mean / std of ITS trajectories only: not the single-GPU update
@@ -128,7 +133,19 @@ class PPO(XTModel):
                 raise ValueError("TRAIN_STATS is not available under data parallelism (DP {}): the row statistics would "
                                  "be rank-local".format(self._dp.mode if self._dp is not None else mcfg.get("DP")))
             self.net.set_train_stats(True)
+        # GAUSS_FUSED_HEAD: the DiagGaussian head as ONE launch (xt_net_set_gauss_fused); off by default, because the fused
+        # kernel takes the sums over the action dimensions in another order than the three launches it replaces
+        if bool(mcfg.get("GAUSS_FUSED_HEAD", False)):
+            self._set_gauss_fused()
         return self.net
+
+    def _set_gauss_fused(self):
+        import logging
+        if not self.gauss or self.net.inference_only:
+            logging.info("GAUSS_FUSED_HEAD ignored: %s", "this is the CPU replica" if self.net.inference_only
+                         else "the policy is {}".format(self.action_type))
+            return
+        self.net.set_gauss_fused(True)
 
     def train_stats(self):
         """The diagnostics of the LAST ``train`` / ``train_ingested`` as a dict of Python floats
@@ -217,12 +234,16 @@ class PPO(XTModel):
         (``pinned``: the arrays already live in page-locked memory -- a pinned transport ring -- and are copied to HBM
         straight from there)."""
         if self._ingest is None:
-            from xingtian_amd.ingest import PPO_FIELDS, PPO_RAW_FIELDS, RolloutIngest
+            from xingtian_amd.ingest import PPO_RAW_FIELDS, RolloutIngest, ppo_fields
             cpad = self.net.spec.obs_channels_padded
+            pad = (cpad, self.net.obs_fill_byte()) if cpad else None
+            lay0 = self.net.spec.layers[0]
+            if len(self.state_dim) == 1 and lay0.H == lay0.W == 1 and lay0.C != int(self.state_dim[0]):
+                pad = (lay0.C, 0)               # netspec._mlp zero padding: staged at its own width, expanded in finish()
             self._ingest = RolloutIngest(self.net.device, self.num_sgd_iter,
-                                         obs_u8=bool(self.net.spec.input_xform[0]), fields=PPO_FIELDS + PPO_RAW_FIELDS,
-                                         copy_streams=self.copy_streams,
-                                         pad_channels=(cpad, self.net.obs_fill_byte()) if cpad else None)
+                                         obs_u8=bool(self.net.spec.input_xform[0]),
+                                         fields=ppo_fields(self.action_type, self.action_dim) + PPO_RAW_FIELDS,
+                                         copy_streams=self.copy_streams, pad_channels=pad)
         if "adv" not in train_data:
             # value / reward / done as the explorer holds them before data_proc: GAE runs on the learner GPU, once per
             # rollout, inside train_ingested (no per-message launch, no read-back)
