@@ -1062,6 +1062,58 @@ int xt_impala_loss_stats(const float* logits, const float* baseline, const float
                          float* dlogits, float* dbaseline, float* out, float* acc,
                          float* vs, float* pg_adv, void* stream, float* traj_stats, double* stats, int32_t* path_out);
 
+/* ------------------------------------------------------------------ DQN (appended under ABI 12)
+ * The replay store lives in HBM as rings [capacity, row] (xt/algorithm/replay_buffer.py holds a host deque); a train
+ * gathers its minibatch out of them on the device.
+ *
+ * xt_replay_gather: dst[b] = ring[slots[b]] for b < B; ring [capacity, row_bytes], dst [B, row_bytes], slots int32 [B] on
+ * the device.  Rows are stored in the form the first layer reads (channel-padded images, feature-padded vectors), so
+ * row_bytes is a multiple of 16: anything else is refused.  16-byte loads and stores; slot * row_bytes is 64-bit
+ * arithmetic (the ring may be larger than 4 GB).  ring and dst 16-byte aligned.  A slot outside [0, capacity) is not
+ * read: its row of dst is zero. */
+int xt_replay_gather(const void* ring, int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, void* dst,
+                     void* stream);
+
+/* TD target and MSE head of DQN.train (xt/algorithm/dqn/dqn.py:61-103) + Keras `loss='mse'` on labels that equal the
+ * prediction except in the taken column.  Q from the heads: Q = logits [B,A], or with `dueling`
+ * Q_a = value + (logits_a - mean_a logits) (value: the 1-wide head [B]).
+ *     a*   = argmax_a Q_target(next)  (o_logits == NULL)  |  argmax_a Q_online(next)  (double DQN), first maximal index
+ *     maxq = Q_target(next)[a*]
+ *     y    = done ? (float)r : (float)(r + gamma * (double)maxq)          (r float64, one rounding)
+ *     L    = sum_b (Q_{b,a_b} - y_b)^2 / (B A);   g_b = 2 (Q_{b,a_b} - y_b) / (B A)
+ *     dueling: dlogits_{b,j} = g_b (1[j = a_b] - 1/A), dvalue_b = g_b;   else dlogits_{b,j} = g_b 1[j = a_b], dvalue_b = 0
+ * logits / value: online heads on the states; t_*: target-net heads on the next states; o_* (may be NULL): online heads
+ * on the next states.  The value pointers are read only with `dueling`.  slots (may be NULL: rows 0..B-1) gathers
+ * action int32 [N], reward float64 [N], done uint8 [N] (truthiness) from the label rings; an action outside [0, A) is
+ * clamped into it.  out: >= 4 + 2*B floats, 8-byte aligned; out[0] = L, out[1] = mean_b |Q_{b,a_b} - y_b|,
+ * out[2] = mean_b maxq_b, the rest is scratch (sums in double, fixed order).  y [B], astar [B], maxq [B] (each may be
+ * NULL): the per-row target, bootstrap action and bootstrap value.  acc (may be NULL): acc[0] += L, acc[1] += 1.
+ * One thread per sample plus a one-block reduction.  A <= 64. */
+int xt_dqn_loss(const float* logits, const float* value, const float* t_logits, const float* t_value,
+                const float* o_logits, const float* o_value, int32_t B, int32_t A, int32_t dueling, const int32_t* slots,
+                const int32_t* action, const double* reward, const uint8_t* done, double gamma, float* dlogits,
+                float* dvalue, float* out, float* y, int32_t* astar, float* maxq, float* acc, void* stream);
+
+/* One DQN.train up to the gradient, in ONE call that never synchronises.  Enqueued in order: gather of the next-state
+ * rows; target_net forward on them, its heads copied to q_scratch; double DQN only: net forward on them, copied too; gather
+ * of the state rows; net training forward; xt_dqn_loss; backward through the heads and the trunk; gradient reduction.  The
+ * flat gradient is left in net's gradient buffer for xt_adam_keras, as xt_net_keras_impala_step leaves it.
+ * target_net: a second net of the same description bound to its own parameter buffer and workspace (forward only).
+ * cur_ring / next_ring [capacity, row_bytes] with row_bytes = the first layer's input row; action / reward / done: the
+ * label rings [capacity]; slots int32 [B] on the device.  loss_out (may be NULL): 3 floats, out[0..2] of xt_dqn_loss.
+ * Categorical nets, A <= 64; refused while a gradient exchange or the data-parallel tail is installed. */
+typedef struct xt_dqn_cfg {
+  double gamma;
+  int32_t dueling;              /* Q = value + (logits - mean logits)                                       */
+  int32_t double_dqn;           /* the online net picks the bootstrap action                                */
+  void* cur_rows;               /* scratch [B, row_bytes], 16-byte aligned: the gathered state rows         */
+  void* next_rows;              /* scratch [B, row_bytes], 16-byte aligned: the gathered next-state rows    */
+  float* q_scratch;             /* scratch >= 2 * B * (A + 1) floats: the copied heads of the next states   */
+} xt_dqn_cfg;
+int xt_net_dqn_step(xt_net* net, xt_net* target_net, const xt_dqn_cfg* cfg, const void* cur_ring, const void* next_ring,
+                    int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, const int32_t* action,
+                    const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,113 @@
+"""Time of one ``DQN.train`` at breakout_dqn's shape, beside a Keras-IMPALA step of the same trunk.
+
+    python tools/dqn_probe.py [--windows 5] [--trains 200] [--capacity 4096] [--out profiles/dqn_step.md]
+
+Three things are timed at DqnCnn 84x84x4, A = 4, B = 32, each as a host clock around ``--trains`` calls that ends in a
+device synchronise, after a warm-up, in ``--windows`` windows taken in turn (so that drift of the box hits all alike):
+
+* ``DQN.train()`` as the learner loop calls it (sample, slot upload, ``xt_net_dqn_step``, ``xt_adam_keras``, the loss read
+  back as a float -- one synchronisation per train), without and with ``double_dqn``;
+* the same train without the read-back (``DqnModel.train_replay`` on pre-uploaded slots: what the device is given to do);
+* ``keras_impala_step`` + ``adam_keras`` on 32 rows of ``netspec.impala_cnn`` (the same trunk and heads, one network, no
+  gather), enqueue only.
+
+The ring holds ``--capacity`` transitions (a full breakout_dqn buffer is 22.6 GB; the gather reads 32 rows whatever the
+capacity is).  No threshold is attached to any of these numbers.  Needs a GPU.
+"""
+import argparse
+import os
+import random
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+B, A_DIM, DIM = 32, 4, 84
+
+
+def build_dqn(double, capacity):
+    from xingtian_amd.algorithm import alg_builder
+    info = {"actor": {"model_name": "DqnCnn", "type": "learner", "state_dim": [DIM, DIM, 4], "action_dim": A_DIM,
+                      "model_config": {"LR": 0.00015, "SEED": 0}}}
+    cfg = {"instance_num": 1, "agent_num": 1, "prepare_times_per_train": 4, "BUFFER_SIZE": capacity, "BATCH_SIZE": B,
+           "TARGET_UPDATE_FREQ": 1000, "double_dqn": double}
+    alg = alg_builder("DQN", info, cfg)
+    rng = np.random.default_rng(1)
+    for _ in range(capacity // 512):
+        n = 512
+        alg.prepare_data({"cur_state": rng.integers(0, 256, (n, DIM, DIM, 4), dtype=np.uint8),
+                          "next_state": rng.integers(0, 256, (n, DIM, DIM, 4), dtype=np.uint8),
+                          "action": rng.integers(0, A_DIM, n), "reward": rng.choice([-1.0, 0.0, 1.0], n),
+                          "done": rng.random(n) < 0.02})
+    return alg
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--trains", type=int, default=200)
+    ap.add_argument("--capacity", type=int, default=4096)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    from xingtian_amd.algorithm.dqn import dqn as dqn_mod
+    from xingtian_amd.model import netspec
+    from xingtian_amd.model.hip_net import HipActorCritic
+    assert torch.cuda.is_available(), "dqn_probe needs a GPU"
+    random.seed(0)
+    algs = {False: build_dqn(False, args.capacity), True: build_dqn(True, args.capacity)}
+    slots = {d: torch.tensor(a.buff.sample(B), dtype=torch.int32).cuda() for d, a in algs.items()}
+    rng = np.random.default_rng(2)
+    net = HipActorCritic(netspec.impala_cnn((DIM, DIM, 4), A_DIM), max_batch=B, seed=0)
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    obs, idx = up(rng.integers(0, 256, (B, DIM, DIM, 4), dtype=np.uint8)), up(np.arange(B, dtype=np.int32))
+    adv, tgt = up(rng.standard_normal(B).astype(np.float32)), up(rng.standard_normal(B).astype(np.float32))
+    hot = up(np.eye(A_DIM, dtype=np.float32)[rng.integers(0, A_DIM, B)])
+    state = {"it": 0}
+
+    def impala_step():
+        net.keras_impala_step(obs, idx, adv, hot, tgt, 0.01)
+        net.adam_keras(3e-4, state["it"], clipnorm=40.0)
+        state["it"] += 1
+
+    def replay(double):
+        alg = algs[double]
+        return lambda: alg.actor.train_replay(alg.target_actor, alg.buff, slots[double], dqn_mod.GAMMA, double)
+
+    cases = [("DQN.train (loss read back)", algs[False].train), ("DQN.train, double_dqn (loss read back)", algs[True].train),
+             ("dqn step + adam, enqueue only", replay(False)), ("dqn step + adam, double_dqn, enqueue only", replay(True)),
+             ("keras_impala_step + adam_keras, 32 rows, enqueue only", impala_step)]
+    for _, fn in cases:
+        for _ in range(20):
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in cases}
+    for _ in range(args.windows):
+        for name, fn in cases:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.trains):
+                fn()
+            torch.cuda.synchronize()
+            times[name].append(1e6 * (time.perf_counter() - t0) / args.trains)
+    lines = ["| what (DqnCnn 84x84x4, A = 4, B = 32) | us per call: median | min | max |", "|---|---|---|---|"]
+    for name, _ in cases:
+        t = sorted(times[name])
+        lines.append("| {} | {:.1f} | {:.1f} | {:.1f} |".format(name, t[len(t) // 2], t[0], t[-1]))
+    text = "\n".join(lines)
+    print(text)
+    print("device:", torch.cuda.get_device_name(0), "| windows", args.windows, "x", args.trains, "calls | ring capacity",
+          args.capacity)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n\ndevice: {} | {} windows x {} calls | ring capacity {}\n".format(
+                torch.cuda.get_device_name(0), args.windows, args.trains, args.capacity))
+
+
+if __name__ == "__main__":
+    main()

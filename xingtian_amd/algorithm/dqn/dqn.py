@@ -1,0 +1,170 @@
+"""``DQN``: deep Q-learning with a replay store that lives on the device.
+
+Reference behaviour (xt/algorithm/dqn/dqn.py:36-148, xt/algorithm/replay_buffer.py): ``prepare_data`` appends the
+``len(train_data["done"])`` transitions of a message to a ``deque(maxlen=BUFFER_SIZE)``; ``train`` draws
+``min(size, BATCH_SIZE)`` of them with ``random.sample``, bootstraps with ``a* = argmax_a Q_target(next)``
+(``double_dqn``: ``argmax_a Q_online(next)``), ``y = done ? r : r + GAMMA * Q_target(next)[a*]``, fits the taken column
+of the online network's own prediction to ``y`` (Keras 'mse') and copies the online weights to the target network
+every ``TARGET_UPDATE_FREQ``-th train.
+
+Here the deque is five rings in HBM (``DeviceReplay``: state, next state, action, reward, done); a train uploads the
+sampled slots (a few hundred bytes) and ONE C call gathers the minibatch, runs both networks, the TD / MSE head and the
+backward pass (``xt_net_dqn_step``), followed by tf.keras Adam (``xt_adam_keras``).  The target sync is one
+device-to-device copy of the flat parameter buffer.
+
+A model without the device step (anything that only implements the reference's ``predict`` / ``train(states, y_t)``)
+is driven the reference's way on the host (``_train_host``), with ``td_targets`` as the arithmetic.
+"""
+import random
+
+import numpy as np
+import torch
+
+from xingtian_amd.algorithm.algorithm import Algorithm
+from xingtian_amd.algorithm.dqn.default_config import BATCH_SIZE, BUFFER_SIZE, GAMMA, TARGET_UPDATE_FREQ
+from xingtian_amd.register import Registers, import_config
+
+
+def td_targets(reward, done, maxq, gamma):
+    """y = done ? r : r + gamma * maxq as the reference's loop evaluates it under NumPy 1.x: the reward is a float64
+    scalar, ``gamma * maxq`` promotes the float32 Q value to float64, and storing into the float32 prediction rounds
+    once.  ``done`` is truthiness."""
+    r = np.asarray(reward, np.float64).reshape(-1)
+    boot = r + float(gamma) * np.asarray(maxq, np.float32).reshape(-1).astype(np.float64)
+    return np.where(np.asarray(done).reshape(-1).astype(bool), r, boot).astype(np.float32)
+
+
+class DeviceReplay(object):
+    """``ReplayBuffer`` (a ``deque(maxlen=capacity)`` of transitions) as five rings on ``device``: ``cur_state`` /
+    ``next_state`` [capacity, ...] in the form the first layer reads (``to_rows``: ``HipActorCritic.to_device_obs``),
+    ``action`` int32, ``reward`` float64, ``done`` uint8 [capacity].  Logical index i (0 = oldest) lives in slot
+    ``(head + i) % capacity``.  The rings are allocated at the first ``add``."""
+
+    def __init__(self, capacity, device="cpu", to_rows=None):
+        if int(capacity) < 1:
+            raise ValueError("DeviceReplay: capacity must be positive, got {}".format(capacity))
+        self.capacity, self.device = int(capacity), torch.device(device)
+        self._to_rows = to_rows
+        self.head = self._size = 0
+        self.cur_state = self.next_state = self.action = self.reward = self.done = None
+
+    def size(self):
+        return self._size
+
+    def _rows(self, states):
+        if self._to_rows is not None:
+            return self._to_rows(np.asarray(states))
+        return torch.as_tensor(np.ascontiguousarray(states)).to(self.device)
+
+    def _allocate(self, state_rows):
+        row_shape, dtype = tuple(state_rows.shape[1:]), state_rows.dtype
+        row_bytes = int(np.prod(row_shape, dtype=np.int64)) * state_rows.element_size()
+        need = self.capacity * (2 * row_bytes + 4 + 8 + 1)
+        if self.device.type == "cuda":
+            free, _ = torch.cuda.mem_get_info(self.device)
+            if need > free:
+                raise RuntimeError("DeviceReplay: the rings of {} transitions need {} bytes of device memory ({} bytes per "
+                                   "state row), {} bytes are free -- lower BUFFER_SIZE".format(
+                                       self.capacity, need, row_bytes, free))
+        new = lambda shape, dt: torch.empty((self.capacity,) + shape, dtype=dt, device=self.device)
+        self.cur_state, self.next_state = new(row_shape, dtype), new(row_shape, dtype)
+        self.action, self.reward, self.done = new((), torch.int32), new((), torch.float64), new((), torch.uint8)
+        self.bytes = need
+
+    def add(self, cur_state, next_state, action, reward, done):
+        """Append the ``len(done)`` transitions of one message, evicting the oldest beyond the capacity: at most two
+        contiguous spans per ring.  Of a message longer than the capacity the last ``capacity`` rows stay."""
+        n = len(done)
+        if n == 0:
+            return
+        skip = max(0, n - self.capacity)
+        host = lambda x, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(x)[skip:].reshape(n - skip), dtype=dt))
+        cols = [self._rows(np.asarray(cur_state)[skip:]), self._rows(np.asarray(next_state)[skip:]),
+                host(action, np.int32).to(self.device), host(reward, np.float64).to(self.device),
+                host(np.asarray(done).astype(bool), np.uint8).to(self.device)]
+        if self.cur_state is None:
+            self._allocate(cols[0])
+        m, cap = n - skip, self.capacity
+        w = (self.head + self._size + skip) % cap
+        first = min(m, cap - w)
+        for ring, rows in zip((self.cur_state, self.next_state, self.action, self.reward, self.done), cols):
+            ring[w:w + first] = rows[:first]
+            if m > first:
+                ring[:m - first] = rows[first:]
+        total = self._size + n
+        if total > cap:
+            self.head, self._size = (self.head + total - cap) % cap, cap
+        else:
+            self._size = total
+
+    def slots_of(self, logical):
+        return [(self.head + int(i)) % self.capacity for i in logical]
+
+    def sample(self, k):
+        """The slots of ``random.sample(deque, k)``: the same draw from the global generator over the logical indices."""
+        return self.slots_of(random.sample(range(self._size), int(k)))
+
+
+@Registers.algorithm
+class DQN(Algorithm):
+    def __init__(self, model_info, alg_config, **kwargs):
+        import_config(globals(), alg_config)
+        from xingtian_amd.model import model_builder
+        actor_info = dict(model_info["actor"])
+        actor_info.setdefault("max_batch", int(BATCH_SIZE))
+        super().__init__(alg_name="dqn", model_info=actor_info, alg_config=alg_config)
+        self.target_actor = model_builder(actor_info)
+        self.double_dqn = alg_config.get("double_dqn", False)
+        net = getattr(self.actor, "net", None)
+        self.device_step = hasattr(self.actor, "train_replay") and not getattr(net, "inference_only", True)
+        if self.device_step:
+            self.buff = DeviceReplay(BUFFER_SIZE, net.device, net.to_device_obs)
+        else:
+            self.buff = DeviceReplay(BUFFER_SIZE)
+
+    def prepare_data(self, train_data, **kwargs):
+        self.buff.add(train_data["cur_state"], train_data["next_state"], train_data["action"], train_data["reward"],
+                      train_data["done"])
+
+    def train(self, **kwargs):
+        return self.train_on_slots(self.buff.sample(min(self.buff.size(), BATCH_SIZE)))
+
+    def train_on_slots(self, slots):
+        """One train on the given ring slots (``train`` draws them; tests inject them).  -> the loss as a float."""
+        if self.device_step:
+            d_slots = torch.tensor(slots, dtype=torch.int32).to(self.buff.device)
+            out = self.actor.train_replay(self.target_actor, self.buff, d_slots, GAMMA, self.double_dqn)
+            self.train_count += 1
+            if self.train_count % TARGET_UPDATE_FREQ == 0:
+                self.update_target()
+            return float(out[0].item())
+        return self._train_host(slots)
+
+    def _train_host(self, slots):
+        at = lambda ring: ring[torch.as_tensor(slots, dtype=torch.int64)].cpu().numpy()
+        states, new_states = at(self.buff.cur_state), at(self.buff.next_state)
+        y_t = self.actor.predict(states)
+        target_q = self.target_actor.predict(new_states)
+        pick = np.argmax(self.actor.predict(new_states) if self.double_dqn else target_q, 1)
+        rows = np.arange(len(slots))
+        y_t[rows, at(self.buff.action)] = td_targets(at(self.buff.reward), at(self.buff.done), target_q[rows, pick], GAMMA)
+        loss = self.actor.train(states, y_t)
+        self.train_count += 1
+        if self.train_count % TARGET_UPDATE_FREQ == 0:
+            self.update_target()
+        return loss
+
+    def update_target(self):
+        if hasattr(self.target_actor, "copy_weights_from"):
+            self.target_actor.copy_weights_from(self.actor)
+        else:
+            self.target_actor.set_weights(self.actor.get_weights())
+
+    def restore(self, model_name=None, model_weights=None):
+        """Both networks take the restored weights (dqn.py:105-119)."""
+        if model_weights is not None:
+            self.actor.set_weights(model_weights)
+            self.target_actor.set_weights(model_weights)
+        else:
+            self.actor.load_model(model_name)
+            self.target_actor.load_model(model_name)

@@ -1,0 +1,152 @@
+// DQN on the device: the row gather out of the HBM replay ring and the TD-target / MSE head
+// (xt/algorithm/dqn/dqn.py:61-103 + `model.compile(loss='mse')` of xt/model/dqn/dqn_cnn.py, dqn_mlp.py).
+// Both kernels are bandwidth- and latency-trivial (a minibatch is 32 rows); what matters is 64-bit addressing into a
+// ring of several GB, 16-byte accesses and a fixed reduction order.
+#include "xt_common.h"
+
+namespace xt {
+
+// dst[b] = ring[slots[b]], rows of row_bytes = 16 * nvec bytes.  Grid (ceil(nvec / 256), B): one 16-byte vector per
+// thread.  The row offset slot * row_bytes is formed in 64 bits (a 400 000-row ring of 84x84x4 frames is 11.3 GB).  A slot
+// outside [0, capacity) reads nothing and leaves a zero row.
+__global__ __launch_bounds__(256) void replay_gather_kernel(const uint4* __restrict__ ring, long long nvec,
+                                                            long long capacity, const int32_t* __restrict__ slots,
+                                                            uint4* __restrict__ dst) {
+  const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (v >= nvec) return;
+  const long long b = blockIdx.y;
+  const long long slot = slots[b];
+  uint4 x = make_uint4(0u, 0u, 0u, 0u);
+  if (slot >= 0 && slot < capacity) x = ring[slot * nvec + v];
+  dst[b * nvec + v] = x;
+}
+
+// Q of one row from the two heads: the [A] head as it is, or s + (l_a - mean_a l) with the 1-wide head s (dueling)
+__device__ __forceinline__ float dqn_mean(const float* __restrict__ l, int A) {
+  float s = 0.f;
+  for (int a = 0; a < A; ++a) s += l[a];
+  return s / (float)A;
+}
+__device__ __forceinline__ float dqn_q(const float* __restrict__ l, float s, float mean, int a, bool dueling) {
+  return dueling ? s + (l[a] - mean) : l[a];
+}
+// first maximal index, as np.argmax
+__device__ __forceinline__ int dqn_argmax(const float* __restrict__ l, float s, float mean, int A, bool dueling) {
+  int best = 0;
+  float qb = dqn_q(l, s, mean, 0, dueling);
+  for (int a = 1; a < A; ++a) {
+    const float q = dqn_q(l, s, mean, a, dueling);
+    if (q > qb) { qb = q; best = a; }
+  }
+  return best;
+}
+
+// One thread per sample: bootstrap action, TD target, d loss / d heads.  terms[b] = (delta_b, maxq_b).
+__global__ __launch_bounds__(256) void dqn_loss_kernel(const float* __restrict__ logits, const float* __restrict__ value,
+                                                       const float* __restrict__ t_logits, const float* __restrict__ t_value,
+                                                       const float* __restrict__ o_logits, const float* __restrict__ o_value,
+                                                       int B, int A, int dueling, const int32_t* __restrict__ slots,
+                                                       const int32_t* __restrict__ action, const double* __restrict__ reward,
+                                                       const uint8_t* __restrict__ done, double gamma,
+                                                       float* __restrict__ dlogits, float* __restrict__ dvalue,
+                                                       float2* __restrict__ terms, float* __restrict__ y_out,
+                                                       int32_t* __restrict__ astar_out, float* __restrict__ maxq_out) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const bool du = dueling != 0;
+  const long long row = slots ? (long long)slots[b] : (long long)b;
+  const float* tl = t_logits + (size_t)b * A;
+  const float ts = du ? t_value[b] : 0.f;
+  const float tmean = du ? dqn_mean(tl, A) : 0.f;
+  int astar;
+  if (o_logits) {                                  // double DQN: the online net picks, the target net evaluates
+    const float* ol = o_logits + (size_t)b * A;
+    astar = dqn_argmax(ol, du ? o_value[b] : 0.f, du ? dqn_mean(ol, A) : 0.f, A, du);
+  } else {
+    astar = dqn_argmax(tl, ts, tmean, A, du);
+  }
+  const float maxq = dqn_q(tl, ts, tmean, astar, du);
+  const double r = reward[row];
+  const float y = done[row] ? (float)r : (float)(r + gamma * (double)maxq);
+  int act = action[row];
+  act = act < 0 ? 0 : (act >= A ? A - 1 : act);    // (an action outside [0, A) never indexes outside the row)
+  const float* l = logits + (size_t)b * A;
+  const float mean = du ? dqn_mean(l, A) : 0.f;
+  const float delta = dqn_q(l, du ? value[b] : 0.f, mean, act, du) - y;
+  const float g = 2.f * delta / ((float)B * (float)A);
+  const float inv_a = 1.f / (float)A;
+  for (int a = 0; a < A; ++a) {
+    const float hot = a == act ? 1.f : 0.f;
+    dlogits[(size_t)b * A + a] = du ? g * (hot - inv_a) : g * hot;
+  }
+  dvalue[b] = du ? g : 0.f;
+  terms[b] = make_float2(delta, maxq);
+  if (y_out) y_out[b] = y;
+  if (astar_out) astar_out[b] = astar;
+  if (maxq_out) maxq_out[b] = maxq;
+}
+
+// fixed-order reduction of the per-sample terms by one block (double precision, LDS tree)
+__global__ __launch_bounds__(256) void dqn_loss_reduce_kernel(const float2* __restrict__ terms, int B, int A,
+                                                              float* __restrict__ out, float* __restrict__ acc) {
+  __shared__ double sq[256], sa[256], sm[256];
+  double q = 0.0, a = 0.0, m = 0.0;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const float d = terms[b].x;
+    q += (double)d * (double)d; a += (double)fabsf(d); m += (double)terms[b].y;
+  }
+  sq[threadIdx.x] = q; sa[threadIdx.x] = a; sm[threadIdx.x] = m;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      sq[threadIdx.x] += sq[threadIdx.x + o]; sa[threadIdx.x] += sa[threadIdx.x + o]; sm[threadIdx.x] += sm[threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float l = (float)(sq[0] / ((double)B * (double)A));
+    out[0] = l; out[1] = (float)(sa[0] / (double)B); out[2] = (float)(sm[0] / (double)B);
+    if (acc) { acc[0] += l; acc[1] += 1.f; }
+  }
+}
+
+}  // namespace xt
+
+extern "C" {
+
+int xt_replay_gather(const void* ring, int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, void* dst,
+                     void* stream) {
+  XT_REQUIRE(ring && slots && dst, "xt_replay_gather: null argument");
+  XT_REQUIRE(row_bytes > 0 && row_bytes % 16 == 0,
+             "xt_replay_gather: row_bytes = %lld is not a positive multiple of 16 (rows are stored as the first layer reads "
+             "them: channel-padded images / feature-padded vectors)", (long long)row_bytes);
+  XT_REQUIRE(capacity > 0 && B > 0 && B <= 65535, "xt_replay_gather: bad sizes (capacity=%lld B=%d)", (long long)capacity, B);
+  XT_REQUIRE((((uintptr_t)ring | (uintptr_t)dst) & 15) == 0, "xt_replay_gather: ring and dst must be 16-byte aligned");
+  const long long nvec = row_bytes / 16;
+  XT_REQUIRE((nvec + 255) / 256 < (1ll << 31), "xt_replay_gather: row_bytes = %lld is too large", (long long)row_bytes);
+  hipLaunchKernelGGL(xt::replay_gather_kernel, dim3((unsigned)((nvec + 255) / 256), (unsigned)B), dim3(256), 0,
+                     xt::as_stream(stream), static_cast<const uint4*>(ring), nvec, (long long)capacity, slots,
+                     static_cast<uint4*>(dst));
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+
+int xt_dqn_loss(const float* logits, const float* value, const float* t_logits, const float* t_value,
+                const float* o_logits, const float* o_value, int32_t B, int32_t A, int32_t dueling, const int32_t* slots,
+                const int32_t* action, const double* reward, const uint8_t* done, double gamma, float* dlogits,
+                float* dvalue, float* out, float* y, int32_t* astar, float* maxq, float* acc, void* stream) {
+  XT_REQUIRE(logits && t_logits && action && reward && done && dlogits && dvalue && out, "xt_dqn_loss: null argument");
+  XT_REQUIRE(!dueling || (value && t_value && (!o_logits || o_value)), "xt_dqn_loss: dueling needs the 1-wide heads");
+  XT_REQUIRE(B > 0 && A > 0 && A <= 64, "xt_dqn_loss: bad sizes (B=%d A=%d; A <= 64)", B, A);
+  XT_REQUIRE(((uintptr_t)out & 7) == 0, "xt_dqn_loss: out must be 8-byte aligned");
+  hipStream_t st = xt::as_stream(stream);
+  float2* terms = reinterpret_cast<float2*>(out + 4);       // out: >= 4 + 2*B floats
+  hipLaunchKernelGGL(xt::dqn_loss_kernel, dim3((B + 255) / 256), dim3(256), 0, st, logits, value, t_logits, t_value, o_logits,
+                     o_value, B, A, dueling, slots, action, reward, done, gamma, dlogits, dvalue, terms, y, astar, maxq);
+  XT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(xt::dqn_loss_reduce_kernel, dim3(1), dim3(256), 0, st, terms, B, A, out, acc);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // extern "C"

@@ -1712,6 +1712,51 @@ int xt_net_keras_impala_train(xt_net* n, const xt_keras_train_cfg* c, const void
   return 0;
 }
 
+int xt_net_dqn_step(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const void* cur_ring, const void* next_ring,
+                    int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, const int32_t* action,
+                    const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream) {
+  XT_REQUIRE(n && tn && c && cur_ring && next_ring && slots && action && reward && done, "xt_net_dqn_step: null argument");
+  XT_REQUIRE(c->cur_rows && c->next_rows && c->q_scratch, "xt_net_dqn_step: null scratch in cfg");
+  XT_REQUIRE(n != tn && n->params && n->ws && tn->params && tn->ws && tn->params != n->params && tn->ws != n->ws,
+             "xt_net_dqn_step: the two nets must be bound to their own parameter buffers and workspaces");
+  XT_REQUIRE(n->action_type == XT_ACTION_CATEGORICAL && tn->action_type == XT_ACTION_CATEGORICAL,
+             "xt_net_dqn_step: categorical heads only");
+  XT_REQUIRE(!n->xchg && n->dp_world == 0 && !n->direct,
+             "xt_net_dqn_step: no data parallelism (a gradient exchange / data-parallel tail is installed)");
+  XT_REQUIRE(tn->A == n->A && tn->feat == n->feat && tn->P == n->P && tn->layers.size() == n->layers.size() &&
+                 tn->in_h == n->in_h && tn->in_w == n->in_w && tn->in_c == n->in_c && tn->xf.is_u8 == n->xf.is_u8,
+             "xt_net_dqn_step: target_net is not a net of the same description");
+  XT_REQUIRE(n->A <= 64, "xt_net_dqn_step: A = %d exceeds 64", n->A);
+  XT_REQUIRE(B > 0 && B <= n->maxB && B <= tn->maxB, "xt_net_dqn_step: batch %d outside (0,%d]", B,
+             n->maxB < tn->maxB ? n->maxB : tn->maxB);
+  const int64_t in_row = (int64_t)n->in_h * n->in_w * n->in_c * (n->xf.is_u8 ? 1 : 4);
+  XT_REQUIRE(row_bytes == in_row, "xt_net_dqn_step: row_bytes = %lld, the first layer reads rows of %lld bytes",
+             (long long)row_bytes, (long long)in_row);
+  const int A = n->A;
+  float* t_logits = c->q_scratch;
+  float* t_value = t_logits + (int64_t)B * A;
+  float* o_logits = c->double_dqn ? t_value + B : nullptr;
+  float* o_value = c->double_dqn ? o_logits + (int64_t)B * A : nullptr;
+  hipStream_t st = xt::as_stream(stream);
+  if (int rc = xt_replay_gather(next_ring, row_bytes, capacity, slots, B, c->next_rows, stream)) return rc;
+  if (int rc = xt_net_forward(tn, c->next_rows, nullptr, B, t_logits, t_value, stream)) return rc;
+  if (c->double_dqn)
+    if (int rc = xt_net_forward(n, c->next_rows, nullptr, B, o_logits, o_value, stream)) return rc;
+  if (int rc = xt_replay_gather(cur_ring, row_bytes, capacity, slots, B, c->cur_rows, stream)) return rc;
+  if (int rc = xt::net_forward(n, c->cur_rows, nullptr, B, true, st)) return rc;
+  float* lo = n->ws + n->off_loss;
+  float* rows = n->ws + n->off_terms;                       // per-row y | a* | maxq, maxB each
+  if (int rc = xt_dqn_loss(n->ws + n->off_logits, n->ws + n->off_value, t_logits, t_value, o_logits, o_value, B, A,
+                           c->dueling, slots, action, reward, done, c->gamma, n->ws + n->off_dlogits,
+                           n->ws + n->off_dvalue, lo, rows, reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB,
+                           loss_acc, stream))
+    return rc;
+  if (loss_out) XT_CHECK_HIP(hipMemcpyAsync(loss_out, lo, 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (int rc = xt::heads_dfeat(n, B, st)) return rc;
+  if (int rc = xt::trunk_backward(n, c->cur_rows, nullptr, B, st)) return rc;
+  return xt::grads_finish(n, B, nullptr, st);
+}
+
 int xt_net_set_grad_exchange_ex(xt_net* net, xt_grad_exchange_fn fn, void* user, int32_t flags) {
   XT_REQUIRE(net, "xt_net_set_grad_exchange: null net");
   XT_REQUIRE((flags & ~XT_XCHG_OVERLAP) == 0, "xt_net_set_grad_exchange_ex: unknown flags 0x%x", flags);

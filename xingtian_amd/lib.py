@@ -85,6 +85,12 @@ class KerasTrainCfg(Structure):
                 ("adam_scratch", c_void_p)]
 
 
+class DqnCfg(Structure):
+    """xt_dqn_cfg of include/xt_mi355x.h"""
+    _fields_ = [("gamma", c_double), ("dueling", c_int32), ("double_dqn", c_int32), ("cur_rows", c_void_p),
+                ("next_rows", c_void_p), ("q_scratch", c_void_p)]
+
+
 class ActCfg(Structure):
     """xt_act_cfg of include/xt_mi355x.h: the generator's key and counter words of one ``xt_net_act`` call"""
     _fields_ = [("seed", ctypes.c_uint64), ("call", ctypes.c_uint64), ("row0", c_int64), ("want_noise", c_int32)]
@@ -219,6 +225,10 @@ SIGNATURES = {
                                      _P, _P, POINTER(c_int32)]),
     "xt_heads_wgrad_partial_ex": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_int64, _P, c_int64,
                                             POINTER(c_int32), _P]),
+    "xt_replay_gather": (c_int32, [_P, c_int64, c_int64, _P, c_int32, _P, _P]),
+    "xt_dqn_loss": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_double, _P, _P, _P, _P,
+                              _P, _P, _P, _P]),
+    "xt_net_dqn_step": (c_int32, [_P, _P, POINTER(DqnCfg), _P, _P, c_int64, c_int64, _P, c_int32, _P, _P, _P, _P, _P, _P]),
 }
 
 

@@ -821,6 +821,39 @@ class HipActorCritic(object):
             L.ptr(out["acc"]), L.stream_ptr()), "xt_net_keras_impala_train")
         return out
 
+    def dqn_step(self, target, cur_ring, next_ring, slots, action, reward, done, gamma, dueling, double_dqn,
+                 loss_acc=None):
+        """One ``DQN.train`` up to the gradient (C ABI ``xt_net_dqn_step``, never synchronises): the minibatch
+        ``slots`` (int32, device) is gathered out of the device rings ``cur_ring`` / ``next_ring`` [capacity, ...] (rows
+        as ``to_device_obs`` lays them out), ``target`` (a second ``HipActorCritic`` of the same spec) evaluates the next
+        states, this net the states; the TD / MSE head reads ``action`` int32 / ``reward`` float64 / ``done`` uint8
+        [capacity] through the same slots.  The gradient stays in ``self.grads`` for ``adam_keras``.  Returns the device
+        tensor [loss, mean |TD error|, mean bootstrap Q]."""
+        cap = int(cur_ring.shape[0])
+        row_bytes = cur_ring[0].numel() * cur_ring.element_size()
+        want = {"cur_ring": (cur_ring, None), "next_ring": (next_ring, cur_ring.dtype), "slots": (slots, torch.int32),
+                "action": (action, torch.int32), "reward": (reward, torch.float64), "done": (done, torch.uint8)}
+        for name, (x, dtype) in want.items():
+            ok = x.is_cuda and x.is_contiguous() and (dtype is None or x.dtype == dtype)
+            if not (ok and (name == "slots" or x.shape[0] == cap)):
+                raise ValueError("dqn_step: {} must be a contiguous device tensor ({} rows)".format(name, cap))
+        if next_ring.shape != cur_ring.shape:
+            raise ValueError("dqn_step: the two state rings differ in shape")
+        b, a = int(slots.numel()), self.spec.action_dim
+        if not hasattr(self, "_dqn_scratch"):
+            mb = self.max_batch
+            self._dqn_scratch = (torch.empty((mb, row_bytes), dtype=torch.uint8, device=self.device),
+                                 torch.empty((mb, row_bytes), dtype=torch.uint8, device=self.device),
+                                 torch.empty((2 * mb * (a + 1),), dtype=torch.float32, device=self.device))
+        cur_rows, next_rows, q = self._dqn_scratch
+        cfg = L.DqnCfg(float(gamma), int(bool(dueling)), int(bool(double_dqn)), cur_rows.data_ptr(), next_rows.data_ptr(),
+                       q.data_ptr())
+        L.check(self.lib.xt_net_dqn_step(self.handle, target.handle, ctypes.byref(cfg), L.ptr(cur_ring), L.ptr(next_ring),
+                                         row_bytes, cap, L.ptr(slots), b, L.ptr(action), L.ptr(reward), L.ptr(done),
+                                         L.ptr(self.loss_out), L.ptr(loss_acc) if loss_acc is not None else None,
+                                         L.stream_ptr()), "xt_net_dqn_step")
+        return self.loss_out
+
     def apply(self, lr, clip_norm, grad_scale=1.0):
         self.touch()
         L.check(self.lib.xt_net_apply(self.handle, lr, 0.9, 0.999, 1e-8, clip_norm, grad_scale, L.stream_ptr()),

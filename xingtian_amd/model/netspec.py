@@ -119,7 +119,7 @@ class NetSpec(object):
     """layers (trunk 0 first), heads, flat layout, name map."""
 
     def __init__(self, layers, n_trunks, feat, action_dim, pi_name, v_name, pi_kernel_shape, input_xform,
-                 state_dim, action_type="Categorical"):
+                 state_dim, action_type="Categorical", hidden_v=False):
         if action_type not in ("Categorical", "DiagGaussian"):
             raise NotImplementedError(
                 "action type: {} not match any implemented distributions.".format(action_type))
@@ -145,8 +145,13 @@ class NetSpec(object):
         self.names[pi_name + "/bias"] = (off + feat * action_dim, (action_dim,))
         off = (off + feat * action_dim + action_dim + 3) & ~3
         self.v_off = off
-        self.names[v_name + "/kernel"] = (off, (feat, 1))
-        self.names[v_name + "/bias"] = (off + feat, (1,))
+        # hidden_v (a Q-network without the dueling stream): the [F]+[1] block is still laid out, because the net
+        # description needs v_off, but it has no name -- absent from get_weights, checkpoints, the CPU replica's weights
+        # and the optimiser's tensors; it starts at zero and nothing ever updates it
+        self.hidden_v = bool(hidden_v)
+        if not hidden_v:
+            self.names[v_name + "/kernel"] = (off, (feat, 1))
+            self.names[v_name + "/bias"] = (off + feat, (1,))
         off = (off + feat + 1 + 3) & ~3
         self.logstd_off = 0
         if action_type == "DiagGaussian":       # tf.get_variable('pi_logstd', (1, A), zeros), xt/model/ppo/ppo.py:78
@@ -272,3 +277,25 @@ def impala_mlp(state_dim, action_dim, hidden_size=128, num_layers=1):
         cin = hidden_size
     return NetSpec(layers, 1, hidden_size, action_dim, "output_actions", "output_value", (hidden_size, action_dim),
                    (0, 0.0, 1.0), (1, 1, int(state_dim[0])))
+
+
+def _dqn_spec(layers, feat, action_dim, n_trunk_layers, dueling, xf, state_dim):
+    """The Q head is the Keras layer after the trunk (dense_<n>), the dueling 1-wide stream the one after it."""
+    return NetSpec(layers, 1, feat, action_dim, "dense_%d" % n_trunk_layers, "dense_%d" % (n_trunk_layers + 1),
+                   (feat, action_dim), xf, state_dim, hidden_v=not dueling)
+
+
+def dqn_cnn(state_dim, action_dim, dueling=False):
+    """Keras ``DqnCnn`` (xt/model/dqn/dqn_cnn.py:45-59): the trunk of ``impala_cnn`` (Conv2D 32@8x8/4, 64@4x4/2, 64@3x3/1
+    valid relu on uint8 / 255, Dense 256 relu), a linear Q head Dense(A) and, with ``dueling``, a 1-wide Dense stream:
+    Q_a = s + (l_a - mean_a l).  Variable names are Keras' automatic ones of a first-built model: conv2d, conv2d_1,
+    conv2d_2, dense, the Q head dense_1, the 1-wide stream dense_2."""
+    trunk = impala_cnn(state_dim, action_dim).layers
+    return _dqn_spec(trunk, 256, action_dim, 1, dueling, (1, 0.0, 255.0), state_dim)
+
+
+def dqn_mlp(state_dim, action_dim, hidden_size=128, num_layers=1, dueling=False):
+    """Keras ``DqnMlp`` (xt/model/dqn/dqn_mlp.py:43-56): ``impala_mlp``'s trunk (dense ... dense_{L-1}), the Q head
+    dense_L and, with ``dueling``, the 1-wide stream dense_{L+1}."""
+    trunk = impala_mlp(state_dim, action_dim, hidden_size, num_layers).layers
+    return _dqn_spec(trunk, hidden_size, action_dim, int(num_layers), dueling, (0, 0.0, 1.0), (1, 1, int(state_dim[0])))
