@@ -1114,6 +1114,77 @@ int xt_net_dqn_step(xt_net* net, xt_net* target_net, const xt_dqn_cfg* cfg, cons
                     int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, const int32_t* action,
                     const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream);
 
+/* ------------------------------------------------------------------ the step tail stand-alone (appended under ABI 12)
+ * The gradient-reduction launch and the optimiser launches every xt_net_*_step ends in, on given buffers, for kernel
+ * tests (tests/test_gpu_optim_branch.py).  Each entry fills the argument structs the step fills and calls the step's own
+ * launcher; the data-parallel arguments and the folded-IO form are passed as zero.
+ *
+ * xt_grad_entry: one parameter block.  dst[0..count) = sum of the `nslab` slabs src + z * stride (lane z0 of the entry's
+ * zl lanes adds slabs z0, z0 + zl, ... in order, then the lanes are added in order); nslab == 1 with src == dst writes
+ * nothing.  pre > 0: the producer has left dst final and `pre` squared-norm partials in the entry's slots already.
+ * src, dst 16-byte aligned, stride a multiple of 4.  zl / nblk / pblk0 are outputs: z lanes per block, blocks, first
+ * squared-norm partial slot (block j of the entry owns slot pblk0 + j; the entries named by `early` own the first slots). */
+typedef struct xt_grad_entry {
+  const float* src;
+  float* dst;
+  int32_t count, nslab;
+  int64_t stride;
+  int32_t pre;
+  int32_t zl, nblk, pblk0;      /* out */
+} xt_grad_entry;
+/* form: 0 = squared-norm partials only; 1 = the last block to arrive also finalises (norm, clip factor, step size, loss;
+ * `counter`); 2 = an extra block does the norm-independent scalars (loss, beta powers, step size), the optimiser derives
+ * the clip factor itself (xt_optim_clip_ex); 3 = fused tail: as 2, and the launch applies Adam behind a grid barrier
+ * (`counter`, params / m / v; entry dst - grads_base = offset into them).
+ * state: the 8 floats of xt_adam_state_init.  counter: 32 * 66 zeroed uint32 words, re-armed by every launch.
+ * partial: max_partials floats.  lr_dev (may be NULL): the step size in device memory instead of lr.
+ * Loss block (all NULL: none): PPO -- terms [B,4], ent_coef, critic_coef, inv_b, out [4], acc [2] (+=), and with stats
+ * (XT_TRAIN_STATS_DOUBLES doubles) the STATS instance, which also reduces rows [B,4]; or IMPALA -- traj_loss [n_traj],
+ * out [1], acc [2] (acc_set != 0: = instead of +=), and with stats (XT_IMPALA_STATS_DOUBLES) traj_stats
+ * [n_traj, XT_IMPALA_TRAJ_STATS_FLOATS]. */
+typedef struct xt_finish_args {
+  int32_t form;
+  float clip_norm, grad_scale, lr, beta1, beta2, eps;
+  const float* lr_dev;
+  float* state;
+  float* partial;
+  int32_t max_partials;
+  uint32_t* counter;
+  float *params, *m, *v;
+  const float* grads_base;
+  const float* terms;
+  int32_t B;
+  float ent_coef, critic_coef, inv_b;
+  float* out;
+  float* acc;
+  const float* rows;
+  double* stats;
+  const float* traj_loss;
+  int32_t n_traj, acc_set;
+  const float* traj_stats;
+} xt_finish_args;
+/* The host half of the gradient-reduction launch, no device call: zl / nblk / pblk0 of every entry, *npartials_out = slots
+ * of the whole table, *grid_out = blocks of the launch of `form` over the entries `select` names (bit i = entry i; 0 = all).
+ * Refused: a misaligned entry, a stride that is no multiple of 4, more slots than max_partials, form 1 with `select` or a
+ * pre-reduced entry, form 3 with `select`. */
+int xt_grads_finish_plan_ex(xt_grad_entry* entries, int32_t n, uint32_t select, uint32_t early, int32_t form,
+                            int32_t max_partials, int32_t* npartials_out, int32_t* grid_out);
+/* The launch (the plan above, unchanged).  *form_out = the form that ran: a request for 3 runs as 2 when the device cannot
+ * hold the fused grid resident at once (the step's own rule); form 3 without a counter is refused, as is everything the
+ * plan refuses -- before any device call. */
+int xt_grads_finish_ex(xt_grad_entry* entries, int32_t n, uint32_t select, uint32_t early, const xt_finish_args* a,
+                       void* stream, int32_t* form_out, int32_t* npartials_out);
+/* The optimiser launch behind forms 0 / 2: every block derives the clip factor from partial[0..nblocks) itself and block 0
+ * leaves it and the norm in state[2] / state[4].  opt_type XT_OPT_ADAM: the step size is state[3] (lr / lr_dev are not
+ * read); XT_OPT_RMSPROP_CENTERED: m = mg, v = ms, beta1 = decay, the step size is lr_dev[0] or lr.  stats (may be NULL): the
+ * three gradient-norm slots of the running sums are added to. */
+int xt_optim_clip_ex(int32_t opt_type, float* param, const float* grad, float* m, float* v, int64_t count, float lr,
+                     const float* lr_dev, float beta1, float beta2, float eps, float* state, const float* partial,
+                     int32_t nblocks, float clip_norm, float grad_scale, double* stats, void* stream);
+/* The one-block finalize launch on given partials (norm, clip factor, beta powers, step size, loss block); `a` as above,
+ * form / partial / counter / params are not read and the statistics are not kept. */
+int xt_norm_finalize_ex(const float* partial, int32_t nblocks, const xt_finish_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -408,8 +408,13 @@ def test_impala_vtrace_loss(L, tlen, n_traj, a_dim):
 
 
 # ------------------------------------------------------------------ optimiser
-@pytest.mark.parametrize("count,clip", [(847496, 5.0), (1003, 0.01), (4, 40.0)])
+@pytest.mark.parametrize("count,clip", [(847496, 5.0), (1003, 0.01), (4, 40.0), (1, 0.5), (2, 40.0), (5, 0.5)])
 def test_adam_tf_clip(L, count, clip):
+    """The three-launch xt_adam_tf_clip against the oracle (parameters of magnitude ~1 after steps of 2.5e-4: the bar on them
+    sees the norm and gross errors), the moments against float64 under the reference rules of test_gpu_optim_branch, and --
+    in a second run with lr = 0.05 on parameters of scale 0.1, where the update is comparable to the parameter -- m, v and
+    p_new - p_old in the relative 2-norm."""
+    from test_gpu_optim_branch import BAR_ELEM, adam_ref, adam_tf_clip_steps, rel2, report
     rng = np.random.default_rng(4)
     p = rng.standard_normal(count).astype(np.float32)
     params = {"w": p.copy()}
@@ -423,12 +428,21 @@ def test_adam_tf_clip(L, count, clip):
         g = (rng.standard_normal(count) * (0.01 if it % 2 else 1.0)).astype(np.float32)
         clipped, gn = nets.clip_by_global_norm({"w": g}, clip)
         opt.apply(params, clipped)
+        m_prev, v_prev = dm.cpu().numpy(), dv_.cpu().numpy()
         L.check(lib.xt_adam_tf_clip(L.ptr(dp), L.ptr(dev(g)), L.ptr(dm), L.ptr(dv_), count, 2.5e-4, 0.9, 0.999, 1e-8,
                                     clip, 1.0, L.ptr(state), L.ptr(scratch), None), "adam")
         st = state.cpu().numpy()
         assert abs(st[4] - gn) < 1e-5 * gn
         assert st[5] == it + 1
         np.testing.assert_allclose(dp.cpu().numpy(), params["w"], rtol=2e-5, atol=2e-7)
+        gn64 = np.sqrt((g.astype(np.float64) ** 2).sum())
+        clip32 = float(np.float32(clip))
+        mr, vr, _ = adam_ref(m_prev, g, m_prev, v_prev, clip32 * min(1.0 / gn64, 1.0 / clip32), 0.0)
+        err_m, err_v = rel2(dm.cpu().numpy(), mr), rel2(dv_.cpu().numpy(), vr)
+        print("test_adam_tf_clip[{}] step {} m {:.2e}/{:g} v {:.2e}/{:g}".format(count, it + 1, err_m, BAR_ELEM, err_v, BAR_ELEM))
+        assert err_m <= BAR_ELEM and err_v <= BAR_ELEM, (it, err_m, err_v)
+    side = "above" if clip < 1.0 else "below"
+    report("adam_tf_clip_c{}_{}".format(count, side), "xt_adam_tf_clip, lr 0.05", adam_tf_clip_steps(L, count, side, 1.0))
 
 
 @pytest.mark.parametrize("b,a_dim", [(37, 1), (200, 3), (64, 6)])

@@ -139,8 +139,16 @@ int launch_norm_finalize(const float* partial, int nblocks, float clip_norm, flo
                          const float* lr_dev = nullptr);
 int launch_grads_finish(GradTable* tab, float* partial, int max_partials, int* nblocks_out, const FinalizeArgs* fin,
                         hipStream_t st, unsigned select = 0, unsigned early = 0, const DpFinish* dpf = nullptr);
+// the host half of launch_grads_finish (no device call): the table the kernel gets, the partial slots, the grid
+struct GradsFinishPlan {
+  GradTable sub;
+  int npartials, grid;
+};
+int plan_grads_finish(GradTable* tab, int max_partials, int enable, bool has_counter, bool scatter, unsigned select,
+                      unsigned early, GradsFinishPlan* plan);
 int grads_finish_resident_blocks(bool stats = false);
 int grads_finish_fused_grid(const GradTable* tab);
+int grads_finish_fused_form(const GradTable* tab, bool stats);
 int launch_adam(float* param, const float* grad, float* m, float* v, long long count, float beta1, float beta2,
                 float eps, const float* state, hipStream_t st);
 int launch_adam_clip(float* param, const float* grad, float* m, float* v, long long count, float beta1, float beta2,

@@ -428,8 +428,7 @@ static int grads_finish(xt_net* n, int B, const FinalizeArgs* fin, hipStream_t s
   if (fused_out) *fused_out = false;
   if (fin && fin->enable == 3) {
     f2 = *fin;
-    const int cap = grads_finish_resident_blocks(fin->loss.stats != nullptr);
-    if (part == 0 && cap > 0 && grads_finish_fused_grid(&tab) <= cap) {
+    if (part == 0 && grads_finish_fused_form(&tab, fin->loss.stats != nullptr) == 3) {
       if (fused_out) *fused_out = true;
     } else {
       f2.enable = 2;

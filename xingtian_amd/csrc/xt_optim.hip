@@ -874,36 +874,45 @@ __global__ void adam_state_init_kernel(float* state) {
   if (threadIdx.x < 8) state[threadIdx.x] = (threadIdx.x < 2) ? 1.f : 0.f;
 }
 
-// entries: blk0/nblk/zl are filled here.  partial needs room for the returned block count.
+// z lanes of an entry's blocks.  Deep entries (the first layer's one-slab-per-workgroup gradients: 250 slabs) get up to 32:
+// their blocks were the stragglers of the launch (31 dependent slab loads per lane, 64 blocks) while ~800 shallow blocks had
+// finished; fewer z lanes = longer contiguous runs per wave (512 B at 8)
+static int reduce_lanes(int nslab) {
+  int zl = 1;
+  const int zcap = (tuning().reduce_deep_lanes > 0 && nslab >= tuning().reduce_deep_lanes) ? 32 : tuning().reduce_z_lanes;
+  while (zl < nslab && zl < zcap) zl <<= 1;
+  return zl;
+}
+static int reduce_blocks(int count, int zl) {
+  const int cols = 256 / zl;
+  return ((count + 3) / 4 + cols - 1) / cols;
+}
+
+// The host half of launch_grads_finish: zl / nblk / pblk0 of every entry of `tab` are filled here, plan->sub is the table
+// the kernel gets (the selected entries, blk0 set), plan->npartials the slots of the FULL table, plan->grid the launch's
+// blocks (the extra block of enable >= 2 included).  No device call.
 // `select` (bit i = entry i of the table is reduced by THIS launch; 0 = all).  The slot of every squared-norm partial
 // is that of the FULL table, so a table reduced by two partial launches leaves the same partial array (bitwise the
 // same norm) as one launch.  `early` = the entries whose slots come first: a partial launch of exactly these entries
 // may run before the slab counts of the others are known (their slots do not depend on them).
-int launch_grads_finish(GradTable* tab, float* partial, int max_partials, int* nblocks_out, const FinalizeArgs* fin,
-                        hipStream_t st, unsigned select, unsigned early, const DpFinish* dpf) {
+int plan_grads_finish(GradTable* tab, int max_partials, int enable, bool has_counter, bool scatter, unsigned select,
+                      unsigned early, GradsFinishPlan* plan) {
+  XT_REQUIRE(tab->n >= 1 && tab->n <= 12, "grads_finish: %d entries outside [1, 12]", tab->n);
   int blk = 0;
   for (int pass = 0; pass < 2; ++pass)
   for (int i = 0; i < tab->n; ++i) {
     if ((((early >> i) & 1u) != 0) != (pass == 0)) continue;
     GradEntry& E = tab->e[i];
-    int zl = 1;
-    // deep entries (the first layer's one-slab-per-workgroup gradients: 250 slabs) get up to 32 z lanes: their blocks
-    // were the stragglers of the launch (31 dependent slab loads per lane, 64 blocks) while ~800 shallow blocks had finished
-    const int zcap = (tuning().reduce_deep_lanes > 0 && E.nslab >= tuning().reduce_deep_lanes) ? 32 : tuning().reduce_z_lanes;
-    while (zl < E.nslab && zl < zcap) zl <<= 1;   // fewer z lanes = longer contiguous runs per wave (512 B at 8)
-    E.zl = zl;
-    const int cols = 256 / zl;
+    E.zl = reduce_lanes(E.nslab);
     E.pblk0 = blk;
-    E.nblk = ((E.count + 3) / 4 + cols - 1) / cols;
+    E.nblk = reduce_blocks(E.count, E.zl);
     blk += E.pre > 0 ? E.pre : E.nblk;        // (a pre-reduced entry owns as many slots as its producer had blocks)
     XT_REQUIRE((((uintptr_t)E.src | (uintptr_t)E.dst) & 15) == 0 && (E.stride % 4) == 0,
                "grads_finish: entry %d not 16-byte aligned", i);
   }
   XT_REQUIRE(blk > 0 && blk <= max_partials, "grads_finish: %d partial blocks > scratch %d", blk, max_partials);
-  FinalizeArgs f;
-  if (fin) f = *fin; else { memset(&f, 0, sizeof(f)); }
-  const bool fused = (f.enable == 3);
-  GradTable sub;
+  const bool fused = (enable == 3);
+  GradTable& sub = plan->sub;
   sub.n = 0;
   int grid = 0;
   bool any_pre = false;
@@ -912,7 +921,7 @@ int launch_grads_finish(GradTable* tab, float* partial, int max_partials, int* n
     if (tab->e[i].pre > 0) {
       any_pre = true;
       // reduced and squared by its producer; the fused tail still has to update it, the direct exchange still has to push it
-      if (!fused && !(dpf && dpf->scatter)) continue;
+      if (!fused && !scatter) continue;
     }
     GradEntry& E = sub.e[sub.n++];
     E = tab->e[i];
@@ -920,13 +929,27 @@ int launch_grads_finish(GradTable* tab, float* partial, int max_partials, int* n
     grid += E.nblk;
   }
   XT_REQUIRE(grid > 0, "grads_finish: empty selection");
-  XT_REQUIRE(f.enable != 1 || (!any_pre && !select),
+  XT_REQUIRE(enable != 1 || (!any_pre && !select),
              "grads_finish: the last-block finalize form needs the whole table in one launch (no partial launches, no "
              "pre-reduced entries)");
-  XT_REQUIRE(!fused || (!select && f.counter), "grads_finish: the fused tail takes the whole table and a barrier scratch");
-  if (fused) f.ap.npartials = blk;
+  XT_REQUIRE(!fused || (!select && has_counter), "grads_finish: the fused tail takes the whole table and a barrier scratch");
+  plan->npartials = blk;
+  plan->grid = grid + (enable >= 2 ? 1 : 0);
+  return 0;
+}
+
+// partial needs room for the returned block count.
+int launch_grads_finish(GradTable* tab, float* partial, int max_partials, int* nblocks_out, const FinalizeArgs* fin,
+                        hipStream_t st, unsigned select, unsigned early, const DpFinish* dpf) {
+  FinalizeArgs f;
+  if (fin) f = *fin; else { memset(&f, 0, sizeof(f)); }
   DpFinish d;
   if (dpf) d = *dpf; else memset(&d, 0, sizeof(d));
+  GradsFinishPlan plan;
+  if (int rc = plan_grads_finish(tab, max_partials, f.enable, f.counter != nullptr, d.scatter != 0, select, early, &plan))
+    return rc;
+  const GradTable& sub = plan.sub;
+  if (f.enable == 3) f.ap.npartials = plan.npartials;
   if (d.tail || d.scatter)
     XT_REQUIRE(f.enable == 2 && !select, "grads_finish: the data-parallel tail rides in the extra block of the whole-table launch");
   if (d.scatter) {
@@ -940,12 +963,12 @@ int launch_grads_finish(GradTable* tab, float* partial, int max_partials, int* n
   }
   if (f.loss.stats) {
     XT_REQUIRE(!d.tail && !d.scatter, "grads_finish: the training statistics are not kept under data parallelism");
-    hipLaunchKernelGGL(grads_finish_kernel<true>, dim3(grid + (f.enable >= 2 ? 1 : 0)), dim3(256), 0, st, sub, partial, f, d);
+    hipLaunchKernelGGL(grads_finish_kernel<true>, dim3(plan.grid), dim3(256), 0, st, sub, partial, f, d);
   } else {
-    hipLaunchKernelGGL(grads_finish_kernel<false>, dim3(grid + (f.enable >= 2 ? 1 : 0)), dim3(256), 0, st, sub, partial, f, d);
+    hipLaunchKernelGGL(grads_finish_kernel<false>, dim3(plan.grid), dim3(256), 0, st, sub, partial, f, d);
   }
   XT_LAUNCH_CHECK();
-  *nblocks_out = blk;
+  *nblocks_out = plan.npartials;
   return 0;
 }
 
@@ -968,15 +991,14 @@ int grads_finish_resident_blocks(bool stats) {
 // blocks the fused tail would launch for this table (pre-reduced entries included, + the scalar block)
 int grads_finish_fused_grid(const GradTable* tab) {
   int grid = 1;
-  for (int i = 0; i < tab->n; ++i) {
-    const GradEntry& E = tab->e[i];
-    int zl = 1;
-    const int zcap = (tuning().reduce_deep_lanes > 0 && E.nslab >= tuning().reduce_deep_lanes) ? 32 : tuning().reduce_z_lanes;
-    while (zl < E.nslab && zl < zcap) zl <<= 1;
-    const int cols = 256 / zl;
-    grid += ((E.count + 3) / 4 + cols - 1) / cols;
-  }
+  for (int i = 0; i < tab->n; ++i) grid += reduce_blocks(tab->e[i].count, reduce_lanes(tab->e[i].nslab));
   return grid;
+}
+// the form a request for the fused tail (enable == 3) runs in: 3 when its whole grid can be resident at once (the grid
+// barrier needs that), else 2 -- the extra-block form, with the optimiser's own launch behind it
+int grads_finish_fused_form(const GradTable* tab, bool stats) {
+  const int cap = grads_finish_resident_blocks(stats);
+  return (cap > 0 && grads_finish_fused_grid(tab) <= cap) ? 3 : 2;
 }
 
 int launch_rmsprop_clip(float* param, const float* grad, float* mg, float* ms, long long count, float lr, float decay,
@@ -1242,6 +1264,120 @@ int xt_adam_tf_clip(float* param, const float* grad, float* m, float* v, int64_t
                                       xt::as_stream(stream), nullptr, nullptr))
     return rc;
   return xt::launch_adam(param, grad, m, v, count, beta1, beta2, eps, state, xt::as_stream(stream));
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ the step tail stand-alone, for kernel tests
+namespace xt {
+static int grad_table_of(const xt_grad_entry* e, int32_t n, GradTable* tab, const char* who) {
+  XT_REQUIRE(e && n >= 1 && n <= 12, "%s: %d entries outside [1, 12]", who, n);
+  tab->n = n;
+  for (int i = 0; i < n; ++i) {
+    XT_REQUIRE(e[i].src && e[i].dst && e[i].count > 0 && e[i].nslab >= 1 && e[i].pre >= 0 &&
+               (e[i].nslab == 1 || e[i].stride >= e[i].count), "%s: bad entry %d", who, i);
+    GradEntry& E = tab->e[i];
+    memset(&E, 0, sizeof(E));
+    E.src = e[i].src; E.dst = e[i].dst; E.count = e[i].count; E.nslab = e[i].nslab; E.stride = e[i].stride; E.pre = e[i].pre;
+  }
+  return 0;
+}
+static void plan_into(const GradTable& tab, xt_grad_entry* e) {
+  for (int i = 0; i < tab.n; ++i) { e[i].zl = tab.e[i].zl; e[i].nblk = tab.e[i].nblk; e[i].pblk0 = tab.e[i].pblk0; }
+}
+static int loss_args_of(const xt_finish_args* a, LossArgs* la, const char* who) {
+  memset(la, 0, sizeof(*la));
+  XT_REQUIRE(!(a->terms && a->traj_loss), "%s: both a PPO and an IMPALA loss block", who);
+  XT_REQUIRE(!a->terms || a->B > 0, "%s: B=%d", who, a->B);
+  XT_REQUIRE(!a->traj_loss || a->n_traj > 0, "%s: n_traj=%d", who, a->n_traj);
+  XT_REQUIRE((((uintptr_t)a->stats) & 7) == 0 && (((uintptr_t)a->rows | (uintptr_t)a->terms) & 15) == 0,
+             "%s: stats not 8-byte or rows / terms not 16-byte aligned", who);
+  la->terms = a->terms; la->B = a->B; la->ent_coef = a->ent_coef; la->critic_coef = a->critic_coef; la->inv_b = a->inv_b;
+  la->out = a->out; la->acc = a->acc; la->traj_loss = a->traj_loss; la->n_traj = a->n_traj; la->acc_set = a->acc_set;
+  la->rows = a->rows; la->stats = a->stats; la->traj_stats = a->traj_stats;
+  return 0;
+}
+}  // namespace xt
+
+extern "C" {
+
+int xt_grads_finish_plan_ex(xt_grad_entry* entries, int32_t n, uint32_t select, uint32_t early, int32_t form,
+                            int32_t max_partials, int32_t* npartials_out, int32_t* grid_out) {
+  if (npartials_out) *npartials_out = 0;
+  if (grid_out) *grid_out = 0;
+  XT_REQUIRE(form >= 0 && form <= 3, "xt_grads_finish_plan_ex: form %d outside [0, 3]", form);
+  xt::GradTable tab;
+  if (int rc = xt::grad_table_of(entries, n, &tab, "xt_grads_finish_plan_ex")) return rc;
+  xt::GradsFinishPlan plan;
+  if (int rc = xt::plan_grads_finish(&tab, max_partials, form, /*has_counter*/ true, /*scatter*/ false, select, early, &plan))
+    return rc;
+  xt::plan_into(tab, entries);
+  if (npartials_out) *npartials_out = plan.npartials;
+  if (grid_out) *grid_out = plan.grid;
+  return 0;
+}
+
+int xt_grads_finish_ex(xt_grad_entry* entries, int32_t n, uint32_t select, uint32_t early, const xt_finish_args* a,
+                       void* stream, int32_t* form_out, int32_t* npartials_out) {
+  if (form_out) *form_out = -1;
+  if (npartials_out) *npartials_out = 0;
+  XT_REQUIRE(a && a->partial && a->max_partials > 0, "xt_grads_finish_ex: null argument");
+  XT_REQUIRE(a->form >= 0 && a->form <= 3, "xt_grads_finish_ex: form %d outside [0, 3]", a->form);
+  xt::GradTable tab;
+  if (int rc = xt::grad_table_of(entries, n, &tab, "xt_grads_finish_ex")) return rc;
+  xt::FinalizeArgs fin;
+  memset(&fin, 0, sizeof(fin));
+  fin.enable = a->form; fin.counter = a->counter; fin.clip_norm = a->clip_norm; fin.grad_scale = a->grad_scale;
+  fin.lr = a->lr; fin.beta1 = a->beta1; fin.beta2 = a->beta2; fin.state = a->state; fin.lr_dev = a->lr_dev;
+  if (int rc = xt::loss_args_of(a, &fin.loss, "xt_grads_finish_ex")) return rc;
+  if (a->form == 0) memset(&fin.loss, 0, sizeof(fin.loss));      // (partials only: nobody reduces a loss)
+  XT_REQUIRE(a->form == 0 || (a->state && a->clip_norm > 0.f), "xt_grads_finish_ex: form %d needs state and a clip norm", a->form);
+  XT_REQUIRE(a->form != 1 || a->counter, "xt_grads_finish_ex: the last-block finalize form needs the ticket counter");
+  if (a->form == 3) {
+    XT_REQUIRE(a->params && a->m && a->v && a->grads_base &&
+               (((uintptr_t)a->params | (uintptr_t)a->m | (uintptr_t)a->v | (uintptr_t)a->grads_base) & 15) == 0,
+               "xt_grads_finish_ex: the fused tail needs params / m / v / grads_base, 16-byte aligned");
+    fin.ap.params = a->params; fin.ap.m = a->m; fin.ap.v = a->v; fin.ap.grads = a->grads_base; fin.ap.eps = a->eps;
+    for (int i = 0; i < tab.n; ++i) {
+      const long long off = (long long)(tab.e[i].dst - a->grads_base);
+      XT_REQUIRE(off >= 0 && off % 4 == 0, "xt_grads_finish_ex: entry %d lies before grads_base or off its float4 grid", i);
+    }
+  }
+  // every refusal of the requested form first (host only), then the residency question, which asks the device
+  xt::GradsFinishPlan plan;
+  if (int rc = xt::plan_grads_finish(&tab, a->max_partials, a->form, a->counter != nullptr, false, select, early, &plan))
+    return rc;
+  if (a->form == 3) fin.enable = xt::grads_finish_fused_form(&tab, a->stats != nullptr);
+  int nb = 0;
+  if (int rc = xt::launch_grads_finish(&tab, a->partial, a->max_partials, &nb, a->form ? &fin : nullptr, xt::as_stream(stream),
+                                       select, early, nullptr))
+    return rc;
+  xt::plan_into(tab, entries);
+  if (form_out) *form_out = fin.enable;
+  if (npartials_out) *npartials_out = nb;
+  return 0;
+}
+
+int xt_optim_clip_ex(int32_t opt_type, float* param, const float* grad, float* m, float* v, int64_t count, float lr,
+                     const float* lr_dev, float beta1, float beta2, float eps, float* state, const float* partial,
+                     int32_t nblocks, float clip_norm, float grad_scale, double* stats, void* stream) {
+  XT_REQUIRE(param && grad && m && v && state && partial && count > 0 && nblocks > 0 && clip_norm > 0.f,
+             "xt_optim_clip_ex: bad arguments");
+  XT_REQUIRE((((uintptr_t)stats) & 7) == 0, "xt_optim_clip_ex: stats not 8-byte aligned");
+  if (opt_type == XT_OPT_RMSPROP_CENTERED)
+    return xt::launch_rmsprop_clip(param, grad, m, v, count, lr, beta1, eps, state, partial, nblocks, clip_norm, grad_scale,
+                                   xt::as_stream(stream), lr_dev, nullptr, 0, stats);
+  XT_REQUIRE(opt_type == XT_OPT_ADAM, "xt_optim_clip_ex: unknown opt_type %d", opt_type);
+  return xt::launch_adam_clip(param, grad, m, v, count, beta1, beta2, eps, state, partial, nblocks, clip_norm, grad_scale,
+                              xt::as_stream(stream), nullptr, 0, nullptr, stats);
+}
+
+int xt_norm_finalize_ex(const float* partial, int32_t nblocks, const xt_finish_args* a, void* stream) {
+  XT_REQUIRE(partial && nblocks > 0 && a && a->state && a->clip_norm > 0.f, "xt_norm_finalize_ex: bad arguments");
+  xt::LossArgs la;
+  if (int rc = xt::loss_args_of(a, &la, "xt_norm_finalize_ex")) return rc;
+  return xt::launch_norm_finalize(partial, nblocks, a->clip_norm, a->grad_scale, a->lr, a->beta1, a->beta2, 1, a->state, &la,
+                                  xt::as_stream(stream), a->lr_dev);
 }
 
 }  // extern "C"

@@ -96,6 +96,24 @@ class ActCfg(Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("call", ctypes.c_uint64), ("row0", c_int64), ("want_noise", c_int32)]
 
 
+class GradEntry(Structure):
+    """xt_grad_entry of include/xt_mi355x.h: one parameter block of the gradient-reduction launch (zl / nblk / pblk0: out)"""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("count", c_int32), ("nslab", c_int32), ("stride", c_int64),
+                ("pre", c_int32), ("zl", c_int32), ("nblk", c_int32), ("pblk0", c_int32)]
+
+
+class FinishArgs(Structure):
+    """xt_finish_args of include/xt_mi355x.h"""
+    _fields_ = [("form", c_int32), ("clip_norm", c_float), ("grad_scale", c_float), ("lr", c_float), ("beta1", c_float),
+                ("beta2", c_float), ("eps", c_float), ("lr_dev", c_void_p), ("state", c_void_p), ("partial", c_void_p),
+                ("max_partials", c_int32), ("counter", c_void_p), ("params", c_void_p), ("m", c_void_p), ("v", c_void_p),
+                ("grads_base", c_void_p), ("terms", c_void_p), ("B", c_int32), ("ent_coef", c_float),
+                ("critic_coef", c_float), ("inv_b", c_float), ("out", c_void_p), ("acc", c_void_p), ("rows", c_void_p),
+                ("stats", c_void_p), ("traj_loss", c_void_p), ("n_traj", c_int32), ("acc_set", c_int32),
+                ("traj_stats", c_void_p)]
+
+
+FINISH_COUNTER_WORDS = 32 * 66      # uint32 words of the ticket / barrier scratch of xt_finish_args.counter
 OPT_TYPE = {"adam": 0, "rmsprop": 1}
 XCHG_OVERLAP = 1         # XT_XCHG_OVERLAP
 DIRECT_HANDLE_BYTES = 64  # XT_DIRECT_HANDLE_BYTES
@@ -229,6 +247,13 @@ SIGNATURES = {
     "xt_dqn_loss": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_double, _P, _P, _P, _P,
                               _P, _P, _P, _P]),
     "xt_net_dqn_step": (c_int32, [_P, _P, POINTER(DqnCfg), _P, _P, c_int64, c_int64, _P, c_int32, _P, _P, _P, _P, _P, _P]),
+    "xt_grads_finish_plan_ex": (c_int32, [POINTER(GradEntry), c_int32, ctypes.c_uint32, ctypes.c_uint32, c_int32, c_int32,
+                                          POINTER(c_int32), POINTER(c_int32)]),
+    "xt_grads_finish_ex": (c_int32, [POINTER(GradEntry), c_int32, ctypes.c_uint32, ctypes.c_uint32, POINTER(FinishArgs), _P,
+                                     POINTER(c_int32), POINTER(c_int32)]),
+    "xt_optim_clip_ex": (c_int32, [c_int32, _P, _P, _P, _P, c_int64, c_float, _P, c_float, c_float, c_float, _P, _P, c_int32,
+                                   c_float, c_float, _P, _P]),
+    "xt_norm_finalize_ex": (c_int32, [_P, c_int32, POINTER(FinishArgs), _P]),
 }
 
 
