@@ -1114,6 +1114,71 @@ int xt_net_dqn_step(xt_net* net, xt_net* target_net, const xt_dqn_cfg* cfg, cons
                     int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, const int32_t* action,
                     const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream);
 
+/* ------------------------------------------------------------------ DQN: prioritised replay (appended under ABI 12)
+ * xt/algorithm/prioritized_replay_buffer_muzero.py::PrioritizedReplayBuffer on xt/algorithm/segment_tree.py, kept on the
+ * device: a sum tree (neutral element 0) and a min tree (neutral element +inf) of 2 * cap2 float64 nodes each, cap2 the
+ * smallest power of two >= the ring's capacity; node i = op(node 2i, node 2i + 1), leaf cap2 + slot belongs to ring slot
+ * `slot` (the reference's _next_idx is the ring's write position).  max_prio: one float64 on the device, 1.0 at the
+ * start.  Every entry enqueues ONE workgroup on `stream` and never synchronises; the levels are walked with a barrier
+ * between them, so a node is recomputed from final children and the trees are bit for bit what the reference's
+ * sequential __setitem__ calls leave.
+ *
+ * xt_per_add: leaves [first, first + count) <- pow(*max_prio, alpha) in both trees (*max_prio read on the device), then
+ * their ancestors.  A message that wraps the ring is two calls.  256 threads stride over each level's node range. */
+int xt_per_add(double* sum, double* min, int64_t cap2, const double* max_prio, int64_t first, int64_t count, double alpha,
+               void* stream);
+
+/* PrioritizedReplayBuffer.sample(B, beta) on `size` stored transitions, one thread per sample (B <= 1024):
+ *     p_total = v[L1] + (v[L2] + (... + v[Lk]))   over the maximal left subtrees on the way down to leaf size - 2 (the
+ *               reference's sum(0, size - 1) leaves the LAST stored slot outside the mass range: kept)
+ *     every   = p_total / B;   mass_b = u_b * every + b * every          (two roundings per product and sum, no fma)
+ *     idx_b   = find_prefixsum_idx(mass_b): at each level left iff sum[2i] > mass, else mass -= sum[2i] and right
+ *     p_min   = max(min[1] / sum[1], 1e-5);   max_w = (p_min * size) ** (-beta)
+ *     w_b     = (leaf[idx_b] / sum[1] * size) ** (-beta) / max_w
+ * u float64 [B] on the device (the caller's uniform draws in [0, 1)); slots_out int32 [B]; weights_out float64 [B].
+ * A descent that ends at a leaf >= size is clamped to size - 1 (the reference raises an IndexError there).  size < 2 is
+ * refused: the reference recurses without end. */
+int xt_per_sample(const double* sum, const double* min, int64_t cap2, int64_t size, const double* u, int32_t B, double beta,
+                  int32_t* slots_out, double* weights_out, void* stream);
+
+/* PrioritizedReplayBuffer.update_priorities(slots, |delta| + eps), one thread per sample (B <= 1024):
+ * priority_b = (double)|delta[b * delta_stride]| + eps; leaf slots[b] <- priority_b ** alpha in both trees -- of equal
+ * slots the largest b wins, as the reference's batch order leaves it (resolved in LDS before the leaf stores) --
+ * *max_prio = max(*max_prio, every priority_b), then the ancestors.  delta float32 with a stride in elements (2 reads
+ * terms[b].x of xt_dqn_loss in place); a slot outside [0, cap2) is not stored through.  eps > 0. */
+int xt_per_update(double* sum, double* min, int64_t cap2, double* max_prio, const int32_t* slots, const float* delta,
+                  int64_t delta_stride, int32_t B, double eps, double alpha, void* stream);
+
+/* xt_dqn_loss with importance weights (Keras train_on_batch(..., sample_weight=w) with 'mse'): weights float64 [B] on the
+ * device, each rounded once to float32;  L = sum_b w_b delta_b^2 / (B A),  g_b = 2 w_b delta_b / (B A);  out[1], out[2],
+ * y, astar, maxq and the scratch terms (delta_b, maxq_b) at out + 4 are unweighted.  weights == NULL is xt_dqn_loss bit
+ * for bit (xt_dqn_loss calls this entry with NULL). */
+int xt_dqn_loss_w(const float* logits, const float* value, const float* t_logits, const float* t_value,
+                  const float* o_logits, const float* o_value, int32_t B, int32_t A, int32_t dueling, const int32_t* slots,
+                  const int32_t* action, const double* reward, const uint8_t* done, double gamma, float* dlogits,
+                  float* dvalue, float* out, float* y, int32_t* astar, float* maxq, float* acc, const double* weights,
+                  void* stream);
+
+/* One prioritised DQN.train up to the gradient, in ONE call that never synchronises.  After the refusals of
+ * xt_net_dqn_step (the same ones, data parallelism included) it enqueues, in order: xt_per_sample on `size` stored
+ * transitions into cfg->slots / cfg->weights; the chain of xt_net_dqn_step on those slots with the weighted head
+ * (xt_dqn_loss_w); xt_per_update on the TD errors the head left.  size <= capacity <= cap2. */
+typedef struct xt_per_cfg {
+  double* sum;                  /* sum tree [2 * cap2]                                                      */
+  double* min;                  /* min tree [2 * cap2]                                                      */
+  int64_t cap2;
+  double* max_prio;             /* the running maximum priority (one float64)                               */
+  const double* u;              /* [B] uniform draws in [0, 1)                                              */
+  int32_t* slots;               /* scratch [B]: the sampled ring slots                                      */
+  double* weights;              /* scratch [B]: their importance weights                                    */
+  float* terms_out;             /* may be NULL; [2 * B]: copy of (delta_b, maxq_b) the update read          */
+  double alpha, beta, eps;
+} xt_per_cfg;
+int xt_net_dqn_step_per(xt_net* net, xt_net* target_net, const xt_dqn_cfg* cfg, const xt_per_cfg* per, const void* cur_ring,
+                        const void* next_ring, int64_t row_bytes, int64_t capacity, int64_t size, int32_t B,
+                        const int32_t* action, const double* reward, const uint8_t* done, float* loss_out, float* loss_acc,
+                        void* stream);
+
 /* ------------------------------------------------------------------ the step tail stand-alone (appended under ABI 12)
  * The gradient-reduction launch and the optimiser launches every xt_net_*_step ends in, on given buffers, for kernel
  * tests (tests/test_gpu_optim_branch.py).  Each entry fills the argument structs the step fills and calls the step's own

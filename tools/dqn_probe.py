@@ -2,12 +2,16 @@
 
     python tools/dqn_probe.py [--windows 5] [--trains 200] [--capacity 4096] [--out profiles/dqn_step.md]
 
-Three things are timed at DqnCnn 84x84x4, A = 4, B = 32, each as a host clock around ``--trains`` calls that ends in a
+Four things are timed at DqnCnn 84x84x4, A = 4, B = 32, each as a host clock around ``--trains`` calls that ends in a
 device synchronise, after a warm-up, in ``--windows`` windows taken in turn (so that drift of the box hits all alike):
 
 * ``DQN.train()`` as the learner loop calls it (sample, slot upload, ``xt_net_dqn_step``, ``xt_adam_keras``, the loss read
   back as a float -- one synchronisation per train), without and with ``double_dqn``;
 * the same train without the read-back (``DqnModel.train_replay`` on pre-uploaded slots: what the device is given to do);
+* each of the above with ``prioritized_replay`` (``xt_net_dqn_step_per``: two more launches per train, the sample in
+  front and the priority update behind; the draws of ``random.random()`` go up instead of the slots);
+* one ``prepare_data`` of a 20-row message without and with ``prioritized_replay`` (``xt_per_add`` per written span), each
+  call followed by a device synchronise;
 * ``keras_impala_step`` + ``adam_keras`` on 32 rows of ``netspec.impala_cnn`` (the same trunk and heads, one network, no
   gather), enqueue only.
 
@@ -29,12 +33,12 @@ if ROOT not in sys.path:
 B, A_DIM, DIM = 32, 4, 84
 
 
-def build_dqn(double, capacity):
+def build_dqn(double, capacity, per=False):
     from xingtian_amd.algorithm import alg_builder
     info = {"actor": {"model_name": "DqnCnn", "type": "learner", "state_dim": [DIM, DIM, 4], "action_dim": A_DIM,
                       "model_config": {"LR": 0.00015, "SEED": 0}}}
     cfg = {"instance_num": 1, "agent_num": 1, "prepare_times_per_train": 4, "BUFFER_SIZE": capacity, "BATCH_SIZE": B,
-           "TARGET_UPDATE_FREQ": 1000, "double_dqn": double}
+           "TARGET_UPDATE_FREQ": 1000, "double_dqn": double, "prioritized_replay": per}
     alg = alg_builder("DQN", info, cfg)
     rng = np.random.default_rng(1)
     for _ in range(capacity // 512):
@@ -61,6 +65,8 @@ def main():
     random.seed(0)
     algs = {False: build_dqn(False, args.capacity), True: build_dqn(True, args.capacity)}
     slots = {d: torch.tensor(a.buff.sample(B), dtype=torch.int32).cuda() for d, a in algs.items()}
+    pers = {False: build_dqn(False, args.capacity, True), True: build_dqn(True, args.capacity, True)}
+    draws = torch.tensor([random.random() for _ in range(B)], dtype=torch.float64).cuda()
     rng = np.random.default_rng(2)
     net = HipActorCritic(netspec.impala_cnn((DIM, DIM, 4), A_DIM), max_batch=B, seed=0)
     up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
@@ -78,8 +84,30 @@ def main():
         alg = algs[double]
         return lambda: alg.actor.train_replay(alg.target_actor, alg.buff, slots[double], dqn_mod.GAMMA, double)
 
-    cases = [("DQN.train (loss read back)", algs[False].train), ("DQN.train, double_dqn (loss read back)", algs[True].train),
-             ("dqn step + adam, enqueue only", replay(False)), ("dqn step + adam, double_dqn, enqueue only", replay(True)),
+    def replay_per(double):
+        alg = pers[double]
+        return lambda: alg.actor.train_replay_per(alg.target_actor, alg.buff, draws, alg.per_beta(), dqn_mod.GAMMA, double)
+
+    msg_rng = np.random.default_rng(3)
+    msg = {"cur_state": msg_rng.integers(0, 256, (20, DIM, DIM, 4), dtype=np.uint8),
+           "next_state": msg_rng.integers(0, 256, (20, DIM, DIM, 4), dtype=np.uint8),
+           "action": msg_rng.integers(0, A_DIM, 20), "reward": msg_rng.choice([-1.0, 0.0, 1.0], 20),
+           "done": msg_rng.random(20) < 0.02}
+
+    def ingest(alg):
+        def fn():
+            alg.prepare_data(msg)
+            torch.cuda.synchronize()
+        return fn
+
+    cases = [("DQN.train (loss read back)", algs[False].train), ("DQN.train, PER (loss read back)", pers[False].train),
+             ("DQN.train, double_dqn (loss read back)", algs[True].train),
+             ("DQN.train, PER, double_dqn (loss read back)", pers[True].train),
+             ("dqn step + adam, enqueue only", replay(False)), ("dqn step + adam, PER, enqueue only", replay_per(False)),
+             ("dqn step + adam, double_dqn, enqueue only", replay(True)),
+             ("dqn step + adam, PER, double_dqn, enqueue only", replay_per(True)),
+             ("prepare_data, 20 rows, synchronised", ingest(algs[False])),
+             ("prepare_data, 20 rows, PER, synchronised", ingest(pers[False])),
              ("keras_impala_step + adam_keras, 32 rows, enqueue only", impala_step)]
     for _, fn in cases:
         for _ in range(20):

@@ -14,6 +14,11 @@ device-to-device copy of the flat parameter buffer.
 
 A model without the device step (anything that only implements the reference's ``predict`` / ``train(states, y_t)``)
 is driven the reference's way on the host (``_train_host``), with ``td_targets`` as the arithmetic.
+
+``alg_config.prioritized_replay`` (off unless asked for) swaps the uniform draw for proportional prioritised replay
+(xt/algorithm/prioritized_replay_buffer_muzero.py, the baselines form): ``PrioritizedDeviceReplay`` keeps the sum tree,
+the min tree and the running maximum priority next to the rings, a train uploads its ``random.random()`` draws and ONE C
+call (``xt_net_dqn_step_per``) samples, weights the head and writes the new priorities back.  It needs the device step.
 """
 import random
 
@@ -105,6 +110,55 @@ class DeviceReplay(object):
         return self.slots_of(random.sample(range(self._size), int(k)))
 
 
+class PrioritizedDeviceReplay(DeviceReplay):
+    """``DeviceReplay`` plus the two segment trees of ``PrioritizedReplayBuffer(capacity, alpha)`` on the device: float64
+    ``sum_tree`` / ``min_tree`` [2 * cap2] (cap2: the smallest power of two >= capacity; leaf ``cap2 + slot`` is ring slot
+    ``slot``, the reference's ``_next_idx`` being the ring's write position) and ``max_prio`` [1], 1.0 at the start.  Every
+    slot a message writes takes the priority ``max_prio ** alpha`` (``xt_per_add``, one call per contiguous span).  The
+    trees are allocated with the rings; sampling and the priority update belong to the train (``xt_net_dqn_step_per``)."""
+
+    def __init__(self, capacity, device, to_rows=None, alpha=0.6, eps=1e-6):
+        super().__init__(capacity, device, to_rows)
+        if not float(alpha) >= 0.0 or not float(eps) > 0.0:
+            raise ValueError("PrioritizedDeviceReplay: alpha = {} must be >= 0 and eps = {} > 0".format(alpha, eps))
+        self.alpha, self.eps = float(alpha), float(eps)
+        self.cap2 = 1
+        while self.cap2 < self.capacity:
+            self.cap2 *= 2
+        self.sum_tree = self.min_tree = self.max_prio = None
+
+    def _allocate(self, state_rows):
+        if self.device.type != "cuda":
+            raise NotImplementedError("PrioritizedDeviceReplay: the trees live on the GPU; there is no host form")
+        tree_bytes = 2 * 2 * self.cap2 * 8
+        free, _ = torch.cuda.mem_get_info(self.device)
+        row_bytes = int(np.prod(tuple(state_rows.shape[1:]), dtype=np.int64)) * state_rows.element_size()
+        need = self.capacity * (2 * row_bytes + 4 + 8 + 1) + tree_bytes
+        if need > free:
+            raise RuntimeError("PrioritizedDeviceReplay: the rings of {} transitions and the two priority trees need {} bytes "
+                               "of device memory ({} bytes per state row, {} bytes of trees), {} bytes are free -- lower "
+                               "BUFFER_SIZE".format(self.capacity, need, row_bytes, tree_bytes, free))
+        super()._allocate(state_rows)
+        self.bytes += tree_bytes
+        self.sum_tree = torch.zeros(2 * self.cap2, dtype=torch.float64, device=self.device)
+        self.min_tree = torch.full((2 * self.cap2,), float("inf"), dtype=torch.float64, device=self.device)
+        self.max_prio = torch.ones(1, dtype=torch.float64, device=self.device)
+
+    def add(self, cur_state, next_state, action, reward, done):
+        n = len(done)
+        if n == 0:
+            return
+        m = min(n, self.capacity)
+        w = (self.head + self._size + n - m) % self.capacity        # where DeviceReplay.add starts to write
+        super().add(cur_state, next_state, action, reward, done)
+        from xingtian_amd import lib as L
+        first = min(m, self.capacity - w)
+        for start, count in ((w, first), (0, m - first)):
+            if count > 0:
+                L.check(L.load().xt_per_add(L.ptr(self.sum_tree), L.ptr(self.min_tree), self.cap2, L.ptr(self.max_prio),
+                                            start, count, self.alpha, L.stream_ptr()), "xt_per_add")
+
+
 @Registers.algorithm
 class DQN(Algorithm):
     def __init__(self, model_info, alg_config, **kwargs):
@@ -117,7 +171,25 @@ class DQN(Algorithm):
         self.double_dqn = alg_config.get("double_dqn", False)
         net = getattr(self.actor, "net", None)
         self.device_step = hasattr(self.actor, "train_replay") and not getattr(net, "inference_only", True)
-        if self.device_step:
+        self.prioritized = bool(alg_config.get("prioritized_replay", False))
+        if self.prioritized:
+            if not (self.device_step and hasattr(self.actor, "train_replay_per")):
+                raise NotImplementedError(
+                    "DQN: prioritized_replay needs a model with the device step (a learner DqnCnn / DqnMlp on the GPU): the "
+                    "priority trees live next to the device rings; {} has none".format(type(self.actor).__name__))
+            if int(BATCH_SIZE) > 1024:
+                raise ValueError("DQN: prioritized_replay samples with one thread per transition in one workgroup: "
+                                 "BATCH_SIZE = {} exceeds 1024".format(BATCH_SIZE))
+            self.per_beta0 = float(alg_config.get("prioritized_replay_beta0", 0.4))
+            self.per_beta_iters = alg_config.get("prioritized_replay_beta_iters", None)
+            if not 0.0 < self.per_beta0 <= 1.0:
+                raise ValueError("DQN: prioritized_replay_beta0 = {} outside (0, 1]".format(self.per_beta0))
+            if self.per_beta_iters is not None and int(self.per_beta_iters) < 1:
+                raise ValueError("DQN: prioritized_replay_beta_iters = {} must be positive or None".format(self.per_beta_iters))
+            self.buff = PrioritizedDeviceReplay(BUFFER_SIZE, net.device, net.to_device_obs,
+                                                alg_config.get("prioritized_replay_alpha", 0.6),
+                                                alg_config.get("prioritized_replay_eps", 1e-6))
+        elif self.device_step:
             self.buff = DeviceReplay(BUFFER_SIZE, net.device, net.to_device_obs)
         else:
             self.buff = DeviceReplay(BUFFER_SIZE)
@@ -127,7 +199,31 @@ class DQN(Algorithm):
                       train_data["done"])
 
     def train(self, **kwargs):
+        if self.prioritized:
+            return self._train_prioritized()
         return self.train_on_slots(self.buff.sample(min(self.buff.size(), BATCH_SIZE)))
+
+    def per_beta(self):
+        """the importance exponent of the next train: constant ``beta0``, or linear from ``beta0`` to 1.0 over
+        ``prioritized_replay_beta_iters`` trains (the baselines ``LinearSchedule``)"""
+        if self.per_beta_iters is None:
+            return self.per_beta0
+        frac = min(float(self.train_count) / float(int(self.per_beta_iters)), 1.0)
+        return self.per_beta0 + frac * (1.0 - self.per_beta0)
+
+    def _train_prioritized(self):
+        """One prioritised train: ``min(size, BATCH_SIZE)`` draws of ``random.random()`` go up, the device samples,
+        trains and writes the priorities back.  -> the loss as a float."""
+        size = self.buff.size()
+        if size < 2:
+            raise ValueError("DQN.train: prioritized replay cannot sample from {} stored transition(s): the mass range "
+                             "excludes the last stored slot, at least 2 are needed".format(size))
+        u = torch.tensor([random.random() for _ in range(min(size, BATCH_SIZE))], dtype=torch.float64).to(self.buff.device)
+        out = self.actor.train_replay_per(self.target_actor, self.buff, u, self.per_beta(), GAMMA, self.double_dqn)
+        self.train_count += 1
+        if self.train_count % TARGET_UPDATE_FREQ == 0:
+            self.update_target()
+        return float(out[0].item())
 
     def train_on_slots(self, slots):
         """One train on the given ring slots (``train`` draws them; tests inject them).  -> the loss as a float."""

@@ -41,7 +41,8 @@ __device__ __forceinline__ int dqn_argmax(const float* __restrict__ l, float s, 
   return best;
 }
 
-// One thread per sample: bootstrap action, TD target, d loss / d heads.  terms[b] = (delta_b, maxq_b).
+// One thread per sample: bootstrap action, TD target, d loss / d heads.  terms[b] = (delta_b, maxq_b).  weights (may be
+// NULL): the importance weight w_b of prioritised replay, rounded once to float32, scales g_b.
 __global__ __launch_bounds__(256) void dqn_loss_kernel(const float* __restrict__ logits, const float* __restrict__ value,
                                                        const float* __restrict__ t_logits, const float* __restrict__ t_value,
                                                        const float* __restrict__ o_logits, const float* __restrict__ o_value,
@@ -50,7 +51,8 @@ __global__ __launch_bounds__(256) void dqn_loss_kernel(const float* __restrict__
                                                        const uint8_t* __restrict__ done, double gamma,
                                                        float* __restrict__ dlogits, float* __restrict__ dvalue,
                                                        float2* __restrict__ terms, float* __restrict__ y_out,
-                                                       int32_t* __restrict__ astar_out, float* __restrict__ maxq_out) {
+                                                       int32_t* __restrict__ astar_out, float* __restrict__ maxq_out,
+                                                       const double* __restrict__ weights) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
   const bool du = dueling != 0;
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(256) void dqn_loss_kernel(const float* __restrict__
   const float* l = logits + (size_t)b * A;
   const float mean = du ? dqn_mean(l, A) : 0.f;
   const float delta = dqn_q(l, du ? value[b] : 0.f, mean, act, du) - y;
-  const float g = 2.f * delta / ((float)B * (float)A);
+  const float g = 2.f * (weights ? (float)weights[b] * delta : delta) / ((float)B * (float)A);
   const float inv_a = 1.f / (float)A;
   for (int a = 0; a < A; ++a) {
     const float hot = a == act ? 1.f : 0.f;
@@ -87,13 +89,16 @@ __global__ __launch_bounds__(256) void dqn_loss_kernel(const float* __restrict__
 }
 
 // fixed-order reduction of the per-sample terms by one block (double precision, LDS tree)
+// (weights, may be NULL: L = sum_b w_b delta_b^2 / (B A); the two means stay unweighted)
 __global__ __launch_bounds__(256) void dqn_loss_reduce_kernel(const float2* __restrict__ terms, int B, int A,
-                                                              float* __restrict__ out, float* __restrict__ acc) {
+                                                              float* __restrict__ out, float* __restrict__ acc,
+                                                              const double* __restrict__ weights) {
   __shared__ double sq[256], sa[256], sm[256];
   double q = 0.0, a = 0.0, m = 0.0;
   for (int b = threadIdx.x; b < B; b += 256) {
     const float d = terms[b].x;
-    q += (double)d * (double)d; a += (double)fabsf(d); m += (double)terms[b].y;
+    const double d2 = (double)d * (double)d;
+    q += weights ? (double)(float)weights[b] * d2 : d2; a += (double)fabsf(d); m += (double)terms[b].y;
   }
   sq[threadIdx.x] = q; sa[threadIdx.x] = a; sm[threadIdx.x] = m;
   __syncthreads();
@@ -131,10 +136,11 @@ int xt_replay_gather(const void* ring, int64_t row_bytes, int64_t capacity, cons
   return 0;
 }
 
-int xt_dqn_loss(const float* logits, const float* value, const float* t_logits, const float* t_value,
-                const float* o_logits, const float* o_value, int32_t B, int32_t A, int32_t dueling, const int32_t* slots,
-                const int32_t* action, const double* reward, const uint8_t* done, double gamma, float* dlogits,
-                float* dvalue, float* out, float* y, int32_t* astar, float* maxq, float* acc, void* stream) {
+int xt_dqn_loss_w(const float* logits, const float* value, const float* t_logits, const float* t_value,
+                  const float* o_logits, const float* o_value, int32_t B, int32_t A, int32_t dueling, const int32_t* slots,
+                  const int32_t* action, const double* reward, const uint8_t* done, double gamma, float* dlogits,
+                  float* dvalue, float* out, float* y, int32_t* astar, float* maxq, float* acc, const double* weights,
+                  void* stream) {
   XT_REQUIRE(logits && t_logits && action && reward && done && dlogits && dvalue && out, "xt_dqn_loss: null argument");
   XT_REQUIRE(!dueling || (value && t_value && (!o_logits || o_value)), "xt_dqn_loss: dueling needs the 1-wide heads");
   XT_REQUIRE(B > 0 && A > 0 && A <= 64, "xt_dqn_loss: bad sizes (B=%d A=%d; A <= 64)", B, A);
@@ -142,11 +148,19 @@ int xt_dqn_loss(const float* logits, const float* value, const float* t_logits, 
   hipStream_t st = xt::as_stream(stream);
   float2* terms = reinterpret_cast<float2*>(out + 4);       // out: >= 4 + 2*B floats
   hipLaunchKernelGGL(xt::dqn_loss_kernel, dim3((B + 255) / 256), dim3(256), 0, st, logits, value, t_logits, t_value, o_logits,
-                     o_value, B, A, dueling, slots, action, reward, done, gamma, dlogits, dvalue, terms, y, astar, maxq);
+                     o_value, B, A, dueling, slots, action, reward, done, gamma, dlogits, dvalue, terms, y, astar, maxq, weights);
   XT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(xt::dqn_loss_reduce_kernel, dim3(1), dim3(256), 0, st, terms, B, A, out, acc);
+  hipLaunchKernelGGL(xt::dqn_loss_reduce_kernel, dim3(1), dim3(256), 0, st, terms, B, A, out, acc, weights);
   XT_LAUNCH_CHECK();
   return 0;
+}
+
+int xt_dqn_loss(const float* logits, const float* value, const float* t_logits, const float* t_value,
+                const float* o_logits, const float* o_value, int32_t B, int32_t A, int32_t dueling, const int32_t* slots,
+                const int32_t* action, const double* reward, const uint8_t* done, double gamma, float* dlogits,
+                float* dvalue, float* out, float* y, int32_t* astar, float* maxq, float* acc, void* stream) {
+  return xt_dqn_loss_w(logits, value, t_logits, t_value, o_logits, o_value, B, A, dueling, slots, action, reward, done, gamma,
+                       dlogits, dvalue, out, y, astar, maxq, acc, nullptr, stream);
 }
 
 }  // extern "C"

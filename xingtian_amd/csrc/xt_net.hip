@@ -1711,26 +1711,45 @@ int xt_net_keras_impala_train(xt_net* n, const xt_keras_train_cfg* c, const void
   return 0;
 }
 
-int xt_net_dqn_step(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const void* cur_ring, const void* next_ring,
-                    int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, const int32_t* action,
-                    const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream) {
-  XT_REQUIRE(n && tn && c && cur_ring && next_ring && slots && action && reward && done, "xt_net_dqn_step: null argument");
-  XT_REQUIRE(c->cur_rows && c->next_rows && c->q_scratch, "xt_net_dqn_step: null scratch in cfg");
+}  // extern "C"
+
+namespace xt {
+
+// The chain of one DQN.train up to the gradient, shared by xt_net_dqn_step and xt_net_dqn_step_per (`who` names the
+// entry in refusals).  per (may be NULL): prioritised replay -- once every refusal has passed, xt_per_sample fills
+// per->slots / per->weights from `size` stored transitions, the chain runs on them with the weighted head, and
+// xt_per_update follows the loss; `slots` is then ignored.
+static int dqn_chain(const char* who, xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const void* cur_ring,
+                     const void* next_ring, int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B,
+                     const int32_t* action, const double* reward, const uint8_t* done, const xt_per_cfg* per, int64_t size,
+                     float* loss_out, float* loss_acc, void* stream) {
+  XT_REQUIRE(n && tn && c && cur_ring && next_ring && (slots || per) && action && reward && done, "%s: null argument", who);
+  XT_REQUIRE(c->cur_rows && c->next_rows && c->q_scratch, "%s: null scratch in cfg", who);
   XT_REQUIRE(n != tn && n->params && n->ws && tn->params && tn->ws && tn->params != n->params && tn->ws != n->ws,
-             "xt_net_dqn_step: the two nets must be bound to their own parameter buffers and workspaces");
+             "%s: the two nets must be bound to their own parameter buffers and workspaces", who);
   XT_REQUIRE(n->action_type == XT_ACTION_CATEGORICAL && tn->action_type == XT_ACTION_CATEGORICAL,
-             "xt_net_dqn_step: categorical heads only");
+             "%s: categorical heads only", who);
   XT_REQUIRE(!n->xchg && n->dp_world == 0 && !n->direct,
-             "xt_net_dqn_step: no data parallelism (a gradient exchange / data-parallel tail is installed)");
+             "%s: no data parallelism (a gradient exchange / data-parallel tail is installed)", who);
   XT_REQUIRE(tn->A == n->A && tn->feat == n->feat && tn->P == n->P && tn->layers.size() == n->layers.size() &&
                  tn->in_h == n->in_h && tn->in_w == n->in_w && tn->in_c == n->in_c && tn->xf.is_u8 == n->xf.is_u8,
-             "xt_net_dqn_step: target_net is not a net of the same description");
-  XT_REQUIRE(n->A <= 64, "xt_net_dqn_step: A = %d exceeds 64", n->A);
-  XT_REQUIRE(B > 0 && B <= n->maxB && B <= tn->maxB, "xt_net_dqn_step: batch %d outside (0,%d]", B,
+             "%s: target_net is not a net of the same description", who);
+  XT_REQUIRE(n->A <= 64, "%s: A = %d exceeds 64", who, n->A);
+  XT_REQUIRE(B > 0 && B <= n->maxB && B <= tn->maxB, "%s: batch %d outside (0,%d]", who, B,
              n->maxB < tn->maxB ? n->maxB : tn->maxB);
   const int64_t in_row = (int64_t)n->in_h * n->in_w * n->in_c * (n->xf.is_u8 ? 1 : 4);
-  XT_REQUIRE(row_bytes == in_row, "xt_net_dqn_step: row_bytes = %lld, the first layer reads rows of %lld bytes",
+  XT_REQUIRE(row_bytes == in_row, "%s: row_bytes = %lld, the first layer reads rows of %lld bytes", who,
              (long long)row_bytes, (long long)in_row);
+  const double* weights = nullptr;
+  if (per) {
+    XT_REQUIRE(per->sum && per->min && per->max_prio && per->u && per->slots && per->weights, "%s: null pointer in per cfg", who);
+    XT_REQUIRE(size <= capacity && capacity <= per->cap2, "%s: size = %lld, capacity = %lld, cap2 = %lld (size <= capacity <= cap2)",
+               who, (long long)size, (long long)capacity, (long long)per->cap2);
+    if (int rc = xt_per_sample(per->sum, per->min, per->cap2, size, per->u, B, per->beta, per->slots, per->weights, stream))
+      return rc;
+    slots = per->slots;
+    weights = per->weights;
+  }
   const int A = n->A;
   float* t_logits = c->q_scratch;
   float* t_value = t_logits + (int64_t)B * A;
@@ -1745,15 +1764,40 @@ int xt_net_dqn_step(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const void* cur_
   if (int rc = xt::net_forward(n, c->cur_rows, nullptr, B, true, st)) return rc;
   float* lo = n->ws + n->off_loss;
   float* rows = n->ws + n->off_terms;                       // per-row y | a* | maxq, maxB each
-  if (int rc = xt_dqn_loss(n->ws + n->off_logits, n->ws + n->off_value, t_logits, t_value, o_logits, o_value, B, A,
-                           c->dueling, slots, action, reward, done, c->gamma, n->ws + n->off_dlogits,
-                           n->ws + n->off_dvalue, lo, rows, reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB,
-                           loss_acc, stream))
+  if (int rc = xt_dqn_loss_w(n->ws + n->off_logits, n->ws + n->off_value, t_logits, t_value, o_logits, o_value, B, A,
+                             c->dueling, slots, action, reward, done, c->gamma, n->ws + n->off_dlogits,
+                             n->ws + n->off_dvalue, lo, rows, reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB,
+                             loss_acc, weights, stream))
     return rc;
   if (loss_out) XT_CHECK_HIP(hipMemcpyAsync(loss_out, lo, 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (int rc = xt::heads_dfeat(n, B, st)) return rc;
   if (int rc = xt::trunk_backward(n, c->cur_rows, nullptr, B, st)) return rc;
-  return xt::grads_finish(n, B, nullptr, st);
+  if (int rc = xt::grads_finish(n, B, nullptr, st)) return rc;
+  if (!per) return 0;
+  const float* delta = lo + 4;                              // terms[b].x of xt_dqn_loss
+  if (per->terms_out)
+    XT_CHECK_HIP(hipMemcpyAsync(per->terms_out, delta, 2 * sizeof(float) * B, hipMemcpyDeviceToDevice, st));
+  return xt_per_update(per->sum, per->min, per->cap2, per->max_prio, slots, delta, 2, B, per->eps, per->alpha, stream);
+}
+
+}  // namespace xt
+
+extern "C" {
+
+int xt_net_dqn_step(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const void* cur_ring, const void* next_ring,
+                    int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, const int32_t* action,
+                    const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream) {
+  return xt::dqn_chain("xt_net_dqn_step", n, tn, c, cur_ring, next_ring, row_bytes, capacity, slots, B, action, reward, done,
+                       nullptr, 0, loss_out, loss_acc, stream);
+}
+
+int xt_net_dqn_step_per(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_per_cfg* p, const void* cur_ring,
+                        const void* next_ring, int64_t row_bytes, int64_t capacity, int64_t size, int32_t B,
+                        const int32_t* action, const double* reward, const uint8_t* done, float* loss_out, float* loss_acc,
+                        void* stream) {
+  XT_REQUIRE(p, "xt_net_dqn_step_per: null per cfg");
+  return xt::dqn_chain("xt_net_dqn_step_per", n, tn, c, cur_ring, next_ring, row_bytes, capacity, nullptr, B, action, reward,
+                       done, p, size, loss_out, loss_acc, stream);
 }
 
 int xt_net_set_grad_exchange_ex(xt_net* net, xt_grad_exchange_fn fn, void* user, int32_t flags) {

@@ -91,6 +91,13 @@ class DqnCfg(Structure):
                 ("next_rows", c_void_p), ("q_scratch", c_void_p)]
 
 
+class PerCfg(Structure):
+    """xt_per_cfg of include/xt_mi355x.h"""
+    _fields_ = [("sum", c_void_p), ("min", c_void_p), ("cap2", c_int64), ("max_prio", c_void_p), ("u", c_void_p),
+                ("slots", c_void_p), ("weights", c_void_p), ("terms_out", c_void_p), ("alpha", c_double), ("beta", c_double),
+                ("eps", c_double)]
+
+
 class ActCfg(Structure):
     """xt_act_cfg of include/xt_mi355x.h: the generator's key and counter words of one ``xt_net_act`` call"""
     _fields_ = [("seed", ctypes.c_uint64), ("call", ctypes.c_uint64), ("row0", c_int64), ("want_noise", c_int32)]
@@ -247,6 +254,13 @@ SIGNATURES = {
     "xt_dqn_loss": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_double, _P, _P, _P, _P,
                               _P, _P, _P, _P]),
     "xt_net_dqn_step": (c_int32, [_P, _P, POINTER(DqnCfg), _P, _P, c_int64, c_int64, _P, c_int32, _P, _P, _P, _P, _P, _P]),
+    "xt_per_add": (c_int32, [_P, _P, c_int64, _P, c_int64, c_int64, c_double, _P]),
+    "xt_per_sample": (c_int32, [_P, _P, c_int64, c_int64, _P, c_int32, c_double, _P, _P, _P]),
+    "xt_per_update": (c_int32, [_P, _P, c_int64, _P, _P, _P, c_int64, c_int32, c_double, c_double, _P]),
+    "xt_dqn_loss_w": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_double, _P, _P, _P, _P,
+                                _P, _P, _P, _P, _P]),
+    "xt_net_dqn_step_per": (c_int32, [_P, _P, POINTER(DqnCfg), POINTER(PerCfg), _P, _P, c_int64, c_int64, c_int64, c_int32,
+                                      _P, _P, _P, _P, _P, _P]),
     "xt_grads_finish_plan_ex": (c_int32, [POINTER(GradEntry), c_int32, ctypes.c_uint32, ctypes.c_uint32, c_int32, c_int32,
                                           POINTER(c_int32), POINTER(c_int32)]),
     "xt_grads_finish_ex": (c_int32, [POINTER(GradEntry), c_int32, ctypes.c_uint32, ctypes.c_uint32, POINTER(FinishArgs), _P,

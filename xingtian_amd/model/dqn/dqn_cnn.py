@@ -87,6 +87,18 @@ class DqnModel(XTModel):
         self.iterations += 1
         return out
 
+    def train_replay_per(self, target, replay, u, beta, gamma, double_dqn):
+        """``train_replay`` on a ``PrioritizedDeviceReplay``: the minibatch is drawn on the device with the uniform draws
+        ``u`` (float64 device tensor [B]) and importance exponent ``beta``, and the replay's trees take the new TD errors
+        (``xt_net_dqn_step_per``), then tf.keras Adam.  Nothing synchronises.  -> the device tensor of ``train_replay``."""
+        self._require_learner()
+        out = self.net.dqn_step_per(target.net, replay.cur_state, replay.next_state, replay.size(), u, replay.action,
+                                    replay.reward, replay.done, gamma, self.dueling, double_dqn, replay.sum_tree,
+                                    replay.min_tree, replay.max_prio, replay.alpha, beta, replay.eps)
+        self.net.adam_keras(self.learning_rate, self.iterations, clipnorm=self.CLIPNORM)
+        self.iterations += 1
+        return out
+
     def copy_weights_from(self, other):
         """this network's parameters <- ``other``'s: one device-to-device copy of the flat buffer on a learner"""
         if getattr(self.net, "inference_only", False) or getattr(other.net, "inference_only", False):

@@ -829,29 +829,68 @@ class HipActorCritic(object):
         states, this net the states; the TD / MSE head reads ``action`` int32 / ``reward`` float64 / ``done`` uint8
         [capacity] through the same slots.  The gradient stays in ``self.grads`` for ``adam_keras``.  Returns the device
         tensor [loss, mean |TD error|, mean bootstrap Q]."""
+        cap, row_bytes, cfg = self._dqn_cfg("dqn_step", cur_ring, next_ring, {"slots": slots}, action, reward, done, gamma,
+                                            dueling, double_dqn)
+        L.check(self.lib.xt_net_dqn_step(self.handle, target.handle, ctypes.byref(cfg), L.ptr(cur_ring), L.ptr(next_ring),
+                                         row_bytes, cap, L.ptr(slots), int(slots.numel()), L.ptr(action), L.ptr(reward),
+                                         L.ptr(done), L.ptr(self.loss_out),
+                                         L.ptr(loss_acc) if loss_acc is not None else None, L.stream_ptr()),
+                "xt_net_dqn_step")
+        return self.loss_out
+
+    def _dqn_cfg(self, who, cur_ring, next_ring, batch, action, reward, done, gamma, dueling, double_dqn):
+        """-> (capacity, row_bytes, ``DqnCfg``) after the tensor checks ``dqn_step`` and ``dqn_step_per`` share; ``batch``:
+        the per-sample device tensors by name (int32 slots / float64 draws)"""
         cap = int(cur_ring.shape[0])
         row_bytes = cur_ring[0].numel() * cur_ring.element_size()
-        want = {"cur_ring": (cur_ring, None), "next_ring": (next_ring, cur_ring.dtype), "slots": (slots, torch.int32),
+        want = {"cur_ring": (cur_ring, None), "next_ring": (next_ring, cur_ring.dtype),
                 "action": (action, torch.int32), "reward": (reward, torch.float64), "done": (done, torch.uint8)}
+        want.update({k: (x, torch.int32 if k == "slots" else torch.float64) for k, x in batch.items()})
         for name, (x, dtype) in want.items():
             ok = x.is_cuda and x.is_contiguous() and (dtype is None or x.dtype == dtype)
-            if not (ok and (name == "slots" or x.shape[0] == cap)):
-                raise ValueError("dqn_step: {} must be a contiguous device tensor ({} rows)".format(name, cap))
+            if not (ok and (name in batch or x.shape[0] == cap)):
+                raise ValueError("{}: {} must be a contiguous device tensor ({} rows)".format(who, name, cap))
         if next_ring.shape != cur_ring.shape:
-            raise ValueError("dqn_step: the two state rings differ in shape")
-        b, a = int(slots.numel()), self.spec.action_dim
+            raise ValueError("{}: the two state rings differ in shape".format(who))
+        a = self.spec.action_dim
         if not hasattr(self, "_dqn_scratch"):
             mb = self.max_batch
             self._dqn_scratch = (torch.empty((mb, row_bytes), dtype=torch.uint8, device=self.device),
                                  torch.empty((mb, row_bytes), dtype=torch.uint8, device=self.device),
                                  torch.empty((2 * mb * (a + 1),), dtype=torch.float32, device=self.device))
         cur_rows, next_rows, q = self._dqn_scratch
-        cfg = L.DqnCfg(float(gamma), int(bool(dueling)), int(bool(double_dqn)), cur_rows.data_ptr(), next_rows.data_ptr(),
-                       q.data_ptr())
-        L.check(self.lib.xt_net_dqn_step(self.handle, target.handle, ctypes.byref(cfg), L.ptr(cur_ring), L.ptr(next_ring),
-                                         row_bytes, cap, L.ptr(slots), b, L.ptr(action), L.ptr(reward), L.ptr(done),
-                                         L.ptr(self.loss_out), L.ptr(loss_acc) if loss_acc is not None else None,
-                                         L.stream_ptr()), "xt_net_dqn_step")
+        return cap, row_bytes, L.DqnCfg(float(gamma), int(bool(dueling)), int(bool(double_dqn)), cur_rows.data_ptr(),
+                                        next_rows.data_ptr(), q.data_ptr())
+
+    def dqn_step_per(self, target, cur_ring, next_ring, size, u, action, reward, done, gamma, dueling, double_dqn,
+                     sum_tree, min_tree, max_prio, alpha, beta, eps, terms_out=None, loss_acc=None):
+        """``dqn_step`` with prioritised replay (C ABI ``xt_net_dqn_step_per``, never synchronises): the minibatch is
+        drawn on the device from the sum tree with the float64 uniform draws ``u`` [B] over the ``size`` stored
+        transitions, the head is weighted with the importance weights, and the sampled leaves of ``sum_tree`` /
+        ``min_tree`` (float64 [2 * cap2]) and ``max_prio`` (float64 [1]) take the new TD errors.  The sampled slots and
+        weights stay in ``self.per_slots`` / ``self.per_weights`` [max_batch]; ``terms_out`` (float32 [2 * B], optional)
+        receives (TD error, bootstrap Q) per sample.  Returns the device tensor of ``dqn_step``."""
+        cap, row_bytes, cfg = self._dqn_cfg("dqn_step_per", cur_ring, next_ring, {"u": u}, action, reward, done, gamma,
+                                            dueling, double_dqn)
+        cap2 = int(sum_tree.numel()) // 2
+        for name, x, n in (("sum_tree", sum_tree, 2 * cap2), ("min_tree", min_tree, 2 * cap2), ("max_prio", max_prio, 1)):
+            if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float64 and x.numel() == n):
+                raise ValueError("dqn_step_per: {} must be a contiguous float64 device tensor of {} elements".format(name, n))
+        b = int(u.numel())
+        if terms_out is not None and not (terms_out.is_cuda and terms_out.is_contiguous() and
+                                          terms_out.dtype == torch.float32 and terms_out.numel() >= 2 * b):
+            raise ValueError("dqn_step_per: terms_out must be a contiguous float32 device tensor of 2 * B elements")
+        if not hasattr(self, "per_slots"):
+            self.per_slots = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
+            self.per_weights = torch.zeros(self.max_batch, dtype=torch.float64, device=self.device)
+        per = L.PerCfg(sum_tree.data_ptr(), min_tree.data_ptr(), cap2, max_prio.data_ptr(), u.data_ptr(),
+                       self.per_slots.data_ptr(), self.per_weights.data_ptr(),
+                       terms_out.data_ptr() if terms_out is not None else None, float(alpha), float(beta), float(eps))
+        L.check(self.lib.xt_net_dqn_step_per(self.handle, target.handle, ctypes.byref(cfg), ctypes.byref(per),
+                                             L.ptr(cur_ring), L.ptr(next_ring), row_bytes, cap, int(size), b,
+                                             L.ptr(action), L.ptr(reward), L.ptr(done), L.ptr(self.loss_out),
+                                             L.ptr(loss_acc) if loss_acc is not None else None, L.stream_ptr()),
+                "xt_net_dqn_step_per")
         return self.loss_out
 
     def apply(self, lr, clip_norm, grad_scale=1.0):
