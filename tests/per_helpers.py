@@ -5,7 +5,9 @@ The restatement below is written from the semantics alone (DESIGN.md section 7, 
 floats -- IEEE float64, one rounding per operation, so it can be compared with the device bit for bit: two trees of
 ``2 * cap2`` nodes built bottom-up from the leaves, the right-nested prefix sum over leaves [0, N - 2], the stratified
 masses, the descent and the importance weights.  tests/golden/per_cases.npz holds what the executed reference computed
-for the same inputs (tools/gen_golden_per.py).
+for the same inputs (tools/gen_golden_per.py), tests/golden/per_cases_wide.npz the same for update batches of up to 1024
+rows.  ``build_trees_np`` is the same bottom-up construction level by level on numpy float64 arrays, for trees of
+2^19 leaves and more.
 """
 import ctypes
 import os
@@ -44,6 +46,23 @@ def build_trees(leaves_sum, leaves_min=None):
     s = build_tree(leaves_sum, lambda a, b: a + b)
     m = build_tree(min_leaves(leaves_sum) if leaves_min is None else leaves_min, min)
     m[0] = INF
+    return s, m
+
+
+def build_trees_np(leaves_sum, leaves_min=None):
+    """``build_trees`` on numpy float64 arrays, one level per step: the same additions and the same ``min`` (the right
+    operand only where it is strictly smaller), so the result equals the list builder's bit for bit"""
+    ls = np.asarray(leaves_sum, np.float64)
+    cap2 = len(ls)
+    s, m = np.zeros(2 * cap2, np.float64), np.full(2 * cap2, INF, np.float64)
+    s[cap2:] = ls
+    m[cap2:] = np.where(ls == 0.0, INF, ls) if leaves_min is None else np.asarray(leaves_min, np.float64)
+    lo = cap2 // 2
+    while lo >= 1:
+        s[lo:2 * lo] = s[2 * lo:4 * lo:2] + s[2 * lo + 1:4 * lo:2]
+        left, right = m[2 * lo:4 * lo:2], m[2 * lo + 1:4 * lo:2]
+        m[lo:2 * lo] = np.where(right < left, right, left)
+        lo //= 2
     return s, m
 
 
@@ -103,7 +122,7 @@ def spans_of_message(capacity, head, size, n):
 
 
 class Case(object):
-    """one recorded case of tests/golden/per_cases.npz"""
+    """one recorded case of tests/golden/per_cases.npz or per_cases_wide.npz"""
 
     def __init__(self, golden, name):
         g = lambda k: golden[name + "_" + k]
@@ -146,8 +165,8 @@ class Case(object):
         return leaves, max_prio
 
 
-def load_cases(golden_dir):
-    golden = np.load(os.path.join(golden_dir, "per_cases.npz"))
+def load_cases(golden_dir, fname="per_cases.npz"):
+    golden = np.load(os.path.join(golden_dir, fname))
     return {str(n): Case(golden, str(n)) for n in golden["names"]}
 
 
@@ -226,6 +245,20 @@ class GpuTrees(object):
         """-> (sum tree, min tree as lists of Python floats, max_prio)"""
         self.torch.cuda.synchronize()
         return self.sum.cpu().tolist(), self.min.cpu().tolist(), float(self.max_prio.item())
+
+
+    def read_np(self):
+        """-> (sum tree, min tree as float64 arrays, max_prio)"""
+        self.torch.cuda.synchronize()
+        return self.sum.cpu().numpy(), self.min.cpu().numpy(), float(self.max_prio.item())
+
+
+def assert_trees_follow_from_their_leaves_np(sum_tree, min_tree):
+    """``assert_trees_follow_from_their_leaves`` for trees read back as float64 arrays"""
+    cap2 = len(sum_tree) // 2
+    ref_s, ref_m = build_trees_np(sum_tree[cap2:], min_tree[cap2:])
+    assert np.array_equal(sum_tree[1:], ref_s[1:])
+    assert np.array_equal(min_tree[1:], ref_m[1:])
 
 
 def assert_trees_follow_from_their_leaves(sum_tree, min_tree):

@@ -5,17 +5,22 @@ loaded with importlib under stub ``xt`` / ``xt.algorithm`` packages (the pattern
 two files import nothing else of the reference).  Each case runs a script of messages (``add`` per transition, priority
 ``None``) and ``update_priorities`` batches on one buffer, then one ``sample(B, beta)`` under ``random.seed(7)``.
 
-Recorded per case ``<c>`` in tests/golden/per_cases.npz (data only; nothing at test time reads the reference):
+Two case tables, one file each: ``CASES`` -> tests/golden/per_cases.npz (batches of at most 256 rows on rings of at most
+1000), ``WIDE_CASES`` -> tests/golden/per_cases_wide.npz (update batches of 65 to 1024 rows: every workgroup size the
+update kernel launches between 64 and 1024 threads that these give, duplicates more than 255 rows apart).
+
+Recorded per case ``<c>`` (data only; nothing at test time reads the reference):
   <c>_cfg       float64 [5]: BUFFER_SIZE, N (stored transitions at the end), B, alpha, beta
   <c>_msg_lens  int64: the message lengths
   <c>_script    int64: k >= 0 -> message k is added, -1 -> the next update batch is applied
   <c>_upd_idx / <c>_upd_prio / <c>_upd_splits: all update batches concatenated, and where each one ends
   <c>_leaves    float64 [cap2]: the sum tree's leaves;  <c>_sum / <c>_min: both full trees [2 * cap2]
   <c>_max_prio  the final _max_priority
-  <c>_u         float64 [B]: the draws ``sample`` consumed (case c64_edge: replaced by 0.0 and 1 - 2**-53)
+  <c>_u         float64 [B]: the draws ``sample`` consumed (edge cases: the first three and the last replaced by 0.0 and
+                1 - 2**-53)
   <c>_p_total, <c>_idx [B], <c>_w [B]: what ``sample`` computed
 
-Usage:  python tools/gen_golden_per.py [reference root]
+Usage:  python tools/gen_golden_per.py [--table base|wide] [reference root]     (no --table: both files are rewritten)
 """
 import importlib.util
 import os
@@ -26,7 +31,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-OUT = os.path.join(ROOT, "tests", "golden", "per_cases.npz")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 SEED = 7
 
 # name: (BUFFER_SIZE, message lengths, B, alpha, beta, edge draws)
@@ -40,6 +45,14 @@ CASES = {
     "c37_beta1": (37, (20, 30), 33, 0.6, 1.0, False),
     "c64_edge": (64, (64, 10), 32, 0.6, 0.4, True),
 }
+
+WIDE_CASES = {
+    "w1000_b1024": (1000, (700, 650), 1024, 0.6, 0.4, False),  # batches of 700 / 952 / 1024 rows, duplicates in every one
+    "w330_b320": (330, (200, 250), 320, 0.6, 0.4, True),       # 200 / 320 / 30 rows; slot N - 1 drawn by 1 - 2**-53
+    "w140_b129": (140, (90, 40), 129, 1.0, 1.0, False),        # 90 / 129 / 3 rows; N < capacity
+    "w100_b65": (100, (100, 30), 65, 0.6, 0.4, False),         # 65 / 35 / 40 rows
+}
+TABLES = {"base": ("per_cases.npz", CASES), "wide": ("per_cases_wide.npz", WIDE_CASES)}
 
 
 def load_reference(ref):
@@ -59,8 +72,8 @@ def load_reference(ref):
     return mods[1].PrioritizedReplayBuffer
 
 
-def run_case(cls, name, out):
-    capacity, msg_lens, b, alpha, beta, edge = CASES[name]
+def run_case(cls, name, case, out):
+    capacity, msg_lens, b, alpha, beta, edge = case
     rng = np.random.default_rng(sum(map(ord, name)))
     buf = cls(capacity, alpha)
     script, idx_all, prio_all, splits, tag = [], [], [], [], 0
@@ -122,16 +135,22 @@ def run_case(cls, name, out):
 
 
 def main():
-    if len(sys.argv) > 1:
-        ref = sys.argv[1]
+    argv, tables = sys.argv[1:], sorted(TABLES)
+    if argv[:1] == ["--table"]:
+        tables, argv = [argv[1]], argv[2:]
+    if argv:
+        ref = argv[0]
     else:
         from oracle.gen_golden_alg import REF as ref
     cls = load_reference(ref)
-    out = {"names": np.array(sorted(CASES))}
-    for name in sorted(CASES):
-        run_case(cls, name, out)
-    np.savez_compressed(OUT, **out)
-    print("wrote", OUT, os.path.getsize(OUT), "bytes")
+    for table in tables:
+        fname, cases = TABLES[table]
+        out = {"names": np.array(sorted(cases))}
+        for name in sorted(cases):
+            run_case(cls, name, cases[name], out)
+        path = os.path.join(GOLDEN, fname)
+        np.savez_compressed(path, **out)
+        print("wrote", path, os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":
