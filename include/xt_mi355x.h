@@ -1250,6 +1250,34 @@ int xt_optim_clip_ex(int32_t opt_type, float* param, const float* grad, float* m
  * form / partial / counter / params are not read and the statistics are not kept. */
 int xt_norm_finalize_ex(const float* partial, int32_t nblocks, const xt_finish_args* a, void* stream);
 
+/* ------------------------------------------------------------------ what the last step did (appended under ABI 12)
+ * The shape-dependent decisions of the most recent xt_net_*_step / xt_net_forward on `net`, as the host recorded them
+ * while enqueueing: for tests (tests/test_gpu_net_zoo.py).  Host words only: no launch, no device memory is touched.
+ * out[0 .. XT_STEP_REPORT_NET_WORDS): the net's words, then XT_STEP_REPORT_LAYER_WORDS per layer, trunk 0 first; `cap`
+ * = words offered (refused when too few).
+ * Net: WORDS = words written; LAYERS; TRUNKS; FWD_FUSE12 / BWD_FUSE21 = 1 when the one-launch conv1 + conv2 forward /
+ * the first layer's weight gradient inside the second layer's backward launch was taken; HEAD_PATH =
+ * xt_net_last_head_path; TAIL_OVERLAP = the xt_tuning.tail_overlap bits the step honoured (0: refused or off);
+ * FINISH_FORM = form of the gradient-reduction launch (xt_finish_args.form; -1: none ran yet), FINISH_BLOCKS = its
+ * squared-norm partial slots; PARTIAL_FLOATS = capacity of a split-K partial region; MAX_NORM_PARTIALS = capacity of
+ * the squared-norm scratch; HEAD_CHUNKS = slabs of the head weight gradients.
+ * Layer: KSPLIT = split-K partial slabs the last forward LEFT in the layer's own region (1: none -- a layer that was not
+ * offered the deferral finishes its split itself and reports 1), DEFERRED = 1 when they were left for the fused head; MSPLIT = weight-gradient slabs of the last backward, SLAB_CAP = slabs the region holds;
+ * MASK_VALID = 1 when the last forward wrote the relu sign mask; PREACT = 1 when the layer keeps its pre-activation
+ * (swish / gelu); NPRE = squared-norm partials the last backward launch pre-reduced; TRUNK. */
+enum {
+  XT_STEP_REPORT_WORDS = 0, XT_STEP_REPORT_LAYERS = 1, XT_STEP_REPORT_TRUNKS = 2, XT_STEP_REPORT_FWD_FUSE12 = 3,
+  XT_STEP_REPORT_BWD_FUSE21 = 4, XT_STEP_REPORT_HEAD_PATH = 5, XT_STEP_REPORT_TAIL_OVERLAP = 6,
+  XT_STEP_REPORT_FINISH_FORM = 7, XT_STEP_REPORT_FINISH_BLOCKS = 8, XT_STEP_REPORT_PARTIAL_FLOATS = 9,
+  XT_STEP_REPORT_MAX_NORM_PARTIALS = 10, XT_STEP_REPORT_HEAD_CHUNKS = 11, XT_STEP_REPORT_NET_WORDS = 12
+};
+enum {
+  XT_STEP_REPORT_L_KSPLIT = 0, XT_STEP_REPORT_L_DEFERRED = 1, XT_STEP_REPORT_L_MSPLIT = 2, XT_STEP_REPORT_L_SLAB_CAP = 3,
+  XT_STEP_REPORT_L_MASK_VALID = 4, XT_STEP_REPORT_L_PREACT = 5, XT_STEP_REPORT_L_NPRE = 6, XT_STEP_REPORT_L_TRUNK = 7,
+  XT_STEP_REPORT_LAYER_WORDS = 8
+};
+int xt_net_last_step_report(const xt_net* net, int32_t* out, int32_t cap);
+
 #ifdef __cplusplus
 }
 #endif

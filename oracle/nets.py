@@ -107,8 +107,8 @@ def ppo_cnn_spec(state_dim, action_dim, hidden_sizes=(512,), act="relu", vf_shar
     """Layer lists for ``get_cnn_backbone`` xt/model/model_utils.py:49-80."""
     trunks = []
     for prefix in (["shared"] if vf_share else ["pi", "v"]):
-        convs, flat = _conv_trunk(prefix + "_conv_layer_{}", state_dim, ppo_cnn_filters(state_dim),
-                                  act, ["valid"] * 3)
+        filters = ppo_cnn_filters(state_dim)      # (the inferred architectures have one to four layers)
+        convs, flat = _conv_trunk(prefix + "_conv_layer_{}", state_dim, filters, act, ["valid"] * len(filters))
         mlps, feat = _mlp_trunk(prefix, flat, hidden_sizes, act)
         trunks.append(convs + mlps)
     return dict(trunks=trunks, feat=feat, action_dim=action_dim, pi_name="pi_latent",

@@ -30,6 +30,14 @@ def test_cabi_library_loads_and_exports_every_header_symbol():
         assert name in lib.SIGNATURES, "no ctypes prototype for " + name
     assert handle.xt_abi_version() == lib.ABI_VERSION == 12
     assert handle.xt_build_arch() == b"gfx950"
+    # the step report: the header's word enumerators are the positions of lib.STEP_REPORT_NET / STEP_REPORT_LAYER
+    assert "xt_net_last_step_report" in declared
+    words = {k: int(v) for k, v in re.findall(r"\bXT_STEP_REPORT_([A-Z0-9_]+) = (\d+)", header)}
+    assert words.pop("NET_WORDS") == len(lib.STEP_REPORT_NET) and words.pop("LAYER_WORDS") == len(lib.STEP_REPORT_LAYER)
+    assert {k: v for k, v in words.items() if not k.startswith("L_")} == {k: i for i, k in enumerate(lib.STEP_REPORT_NET)}
+    assert {k[2:]: v for k, v in words.items() if k.startswith("L_")} == {k: i for i, k in enumerate(lib.STEP_REPORT_LAYER)}
+    common = open(os.path.join(ROOT, "xingtian_amd", "csrc", "xt_common.h")).read()
+    assert int(re.search(r"kMaxGradEntries = (\d+);", common).group(1)) - 3 == lib.MAX_TRUNK_LAYERS
     # the binary carries the digest of the sources it was compiled from: a stale prebuilt .so next to newer kernel
     # sources is caught here (and profile artefacts are tagged with THIS digest, not with the tree's)
     assert lib.built_sources_sha() == lib.kernel_sources_sha(), "libxt_mi355x.so is stale: rebuild (make -C xingtian_amd/csrc)"

@@ -244,9 +244,11 @@ struct GradEntry {
   int pblk0;            // slot of the entry's first squared-norm partial (position in the full table's block order: the same
                         // whether the table is reduced by one launch or by two partial ones)
 };
+constexpr int kMaxGradEntries = 12;      // trunk layers + pi head + v head (+ pi_logstd, DiagGaussian)
+constexpr int kMaxTrunkLayers = kMaxGradEntries - 3;      // xt_net_create refuses a net beyond it, whatever its action type
 struct GradTable {
   int n;
-  GradEntry e[12];
+  GradEntry e[kMaxGradEntries];
 };
 
 struct PpoHeadArgs {

@@ -52,6 +52,7 @@ struct Layer {
   int64_t mask_off;            // relu sign mask of this layer's output (one word per position), else -1
   int mask_valid;              // the last forward of this layer wrote the mask
   int64_t z_off;               // pre-activation of this layer (swish / gelu: act_needs_preact), else -1
+  int last_deferred = 0;       // the last forward left this layer's split-K partials un-finished (xt_net_last_step_report)
 };
 
 static inline int64_t align4(int64_t x) { return (x + 3) & ~int64_t(3); }
@@ -137,6 +138,8 @@ struct xt_net {
   float* trows = nullptr;
   int last_head_path = 0;
   int gauss_fused = 0;                // xt_net_set_gauss_fused: a DiagGaussian step inside the envelope takes the fused head launch
+  // xt_net_last_step_report: what the most recent forward / backward / tail decided (host words, read by nothing else)
+  int last_fuse12 = 0, last_fuse21 = 0, last_tail_mode = 0, last_finish_form = -1;
   // xt_net_set_impala_stats: the caller's running sums and per-trajectory rows [itraj_max][XT_IMPALA_TRAJ_STATS_FLOATS] (both
   // null: off)
   double* istats = nullptr;
@@ -242,12 +245,14 @@ static int net_forward(xt_net* n, const void* obs, const int32_t* idx, int B, bo
   for (int tr = 0; tr < n->n_trunks; ++tr) {
     const void* x = obs;
     const int l0 = n->t_begin[tr];
+    if (tr == 0) n->last_fuse12 = 0;
     for (int l = l0; l < n->t_end[tr]; ++l) {
       Layer& L = n->layers[l];
       const bool first = (l == n->t_begin[tr]);
       const bool defer = defer_last && (l == n->t_end[tr] - 1) && L.part_off >= 0 && L.z_off < 0;
       L.last_ksplit = 1;
       L.mask_valid = 0;
+      L.last_deferred = 0;
       if (!first) { if (int rc = join_pending_update(n, st)) return rc; }
       if (first && tuning().fwd_fuse12 > 0 && B <= tuning().fwd_fuse12 && l + 2 < n->t_end[tr] && L.z_off < 0 &&
           L.mask_off < 0 && n->layers[l + 1].z_off < 0 && n->layers[l + 1].mask_off < 0) {
@@ -261,6 +266,8 @@ static int net_forward(xt_net* n, const void* obs, const int32_t* idx, int B, bo
         if (rc == 0) {
           L2.last_ksplit = 1;
           L2.mask_valid = 0;
+          L2.last_deferred = 0;
+          n->last_fuse12 = 1;
           x = n->ws + L2.act_off;
           ++l;
           continue;
@@ -277,6 +284,7 @@ static int net_forward(xt_net* n, const void* obs, const int32_t* idx, int B, bo
         continue;
       }
       if (int rc = layer_forward(n, L, &L.g, first, B, x, idx, n->ws + L.act_off, defer, st)) return rc;
+      L.last_deferred = (defer && L.last_ksplit > 1) ? 1 : 0;
       x = n->ws + L.act_off;
     }
   }
@@ -334,6 +342,7 @@ static int trunk_backward(xt_net* n, const void* obs, const int32_t* idx, int B,
   int fused21 = 0;      // the launch of a trunk's second layer also wrote its first layer's weight-gradient slabs
   const bool pre_ok = tuning().finalize_ticket == 0;      // (the last-block finalize form reads one partial per block)
   for (auto& L : n->layers) L.last_npre = 0;
+  n->last_fuse21 = 0;
   for (int tr = 0; tr < n->n_trunks; ++tr)
     for (int l = n->t_end[tr] - 1; l >= n->t_begin[tr]; --l) {
       const bool first = (l == n->t_begin[tr]);
@@ -372,10 +381,16 @@ static int trunk_backward(xt_net* n, const void* obs, const int32_t* idx, int B,
       if (pre_ok && l == (int)n->layers.size() - 1) c.sq_partials = n->ws + n->off_norm;
       c.npre_out = &L.last_npre;
       if (int rc = launch_bwd_layer(c)) return rc;
+      if (fused21) n->last_fuse21 = 1;
       if (!first_done && after_first) { if (int rc = after_first->fn(after_first->arg)) return rc; }
       first_done = true;
     }
   return 0;
+}
+
+// Entries of the gradient table of grads_finish: one per trunk layer, the pi head, the v head and -- DiagGaussian -- pi_logstd
+static inline int grad_table_entries(const xt_net* n) {
+  return (int)n->layers.size() + 2 + (n->action_type == XT_ACTION_DIAG_GAUSSIAN ? 1 : 0);
 }
 
 // ONE kernel: every slab reduction (trunk layers + heads) + the squared-norm partials
@@ -389,7 +404,9 @@ static int grads_finish(xt_net* n, int B, const FinalizeArgs* fin, hipStream_t s
   GradTable tab;
   tab.n = 0;
   unsigned first_bucket = 0;      // entries of part 1
-  XT_REQUIRE(n->layers.size() + 3 <= 12, "xt_net: too many layers for the gradient table");
+  // (xt_net_create has refused a net whose table does not fit: this is the same count, asserted)
+  XT_REQUIRE(grad_table_entries(n) <= kMaxGradEntries, "xt_net: %d gradient-table entries > %d", grad_table_entries(n),
+             kMaxGradEntries);
   const size_t l_last = n->layers.size() - 1;
   for (size_t li = 0; li < n->layers.size(); ++li) {
     Layer& L = n->layers[li];
@@ -435,6 +452,7 @@ static int grads_finish(xt_net* n, int B, const FinalizeArgs* fin, hipStream_t s
     }
     fin = &f2;
   }
+  if (part != 1) n->last_finish_form = fin ? fin->enable : 0;
   return launch_grads_finish(&tab, n->ws + n->off_norm, kMaxNormPartials, &n->norm_blocks, fin, st, select, first_bucket, dpf);
 }
 
@@ -726,6 +744,7 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
                    },
                    &ovl};
   const int tov = (apply == 1) ? tail_overlap_mode(n) : 0;
+  n->last_tail_mode = tov;
   TailFork tfk{n, B, st, false};
   AfterFirstBwd tf{tail_fork_first_bucket, &tfk};
   if (int rc = trunk_backward(n, obs, idx, B, st, apply == 2 ? &af : (tov & 1) ? &tf : nullptr)) return rc;
@@ -855,6 +874,7 @@ static int impala_step(xt_net* n, const xt_impala_cfg* c, const void* obs, int n
     if (int rc = heads_dfeat(n, nfr, st)) return rc;
   }
   const int tov = (apply == 1 && c->opt_type == XT_OPT_ADAM) ? tail_overlap_mode(n) : 0;
+  n->last_tail_mode = tov;
   TailFork tfk{n, nfr, st, false};
   AfterFirstBwd tf{tail_fork_first_bucket, &tfk};
   if (int rc = trunk_backward(n, obs, nullptr, nfr, st, (tov & 1) ? &tf : nullptr)) return rc;
@@ -951,6 +971,37 @@ int xt_net_create(const xt_net_desc* d, int32_t max_batch, xt_net** out) {
   XT_REQUIRE(d && out && max_batch > 0, "xt_net_create: bad arguments");
   XT_REQUIRE(d->n_trunks == 1 || d->n_trunks == 2, "xt_net_create: n_trunks must be 1 or 2");
   XT_REQUIRE(d->n_layers >= d->n_trunks, "xt_net_create: every trunk needs at least one layer");
+  // Everything a step of this net would refuse is refused here: no update is ever enqueued for a net that cannot finish it.
+  {
+    // the gradient table of the step's reduction launch: one entry per trunk layer + pi head + v head (+ pi_logstd)
+    // (the pi_logstd slot is reserved for every net: the limit does not depend on the action type)
+    XT_REQUIRE(d->n_layers <= xt::kMaxTrunkLayers,
+               "xt_net_create: %d trunk layers (both trunks counted) exceed the limit of %d: the gradient table holds %d "
+               "entries, three of them the pi head, the v head and pi_logstd", d->n_layers, xt::kMaxTrunkLayers,
+               xt::kMaxGradEntries);
+    XT_REQUIRE(d->feat > 0 && d->action_dim > 0, "xt_net_create: feat = %d, action_dim = %d (both must be positive)", d->feat,
+               d->action_dim);
+    int depth[2] = {0, 0};
+    for (int i = 0; i < d->n_layers; ++i) {
+      const xt_conv_geom& g = d->layers[i].g;
+      XT_REQUIRE(g.H > 0 && g.W > 0 && g.C > 0 && g.KH > 0 && g.KW > 0 && g.S > 0 && g.OH > 0 && g.OW > 0 && g.N > 0,
+                 "xt_net_create: layer %d is empty (input %dx%dx%d, kernel %dx%d stride %d, output %dx%dx%d): every "
+                 "dimension must be at least 1", i, g.H, g.W, g.C, g.KH, g.KW, g.S, g.OH, g.OW, g.N);
+      if (d->layers[i].trunk >= 0 && d->layers[i].trunk < 2) depth[d->layers[i].trunk]++;
+    }
+    if (d->n_trunks == 2 && depth[0] > 0 && depth[1] > 0) {
+      // the step's fused head finishes both trunks' last layers in one launch and requires them in the same split-K
+      // state; the heads read `feat` features of either: unshared trunks are two copies of one layer stack
+      bool same = depth[0] == depth[1];
+      for (int i = 0; same && i < depth[0]; ++i) {
+        const xt_conv_geom &a = d->layers[i].g, &b = d->layers[depth[0] + i].g;
+        same = a.H == b.H && a.W == b.W && a.C == b.C && a.KH == b.KH && a.KW == b.KW && a.S == b.S && a.PT == b.PT &&
+               a.PL == b.PL && a.OH == b.OH && a.OW == b.OW && a.N == b.N && a.act == b.act;
+      }
+      XT_REQUIRE(same, "xt_net_create: the pi and v trunks differ (%d and %d layers): unshared trunks must be two copies of "
+                       "the same layer stack (limit: equal depth and equal layer geometry)", depth[0], depth[1]);
+    }
+  }
   xt_net* n = new xt_net();
   n->n_trunks = d->n_trunks; n->feat = d->feat; n->A = d->action_dim;
   n->pi_off = d->pi_off; n->v_off = d->v_off; n->P = d->n_params; n->xf = d->xf;
@@ -1985,6 +2036,38 @@ int xt_net_time_layer(xt_net* n, int32_t layer, int32_t which, const void* obs, 
                             n->ws + Lp.dact_off, st);
   };
   return xt::time_reps(one, n, &call, reps, ms_out, xt::as_stream(stream));
+}
+
+int xt_net_last_step_report(const xt_net* n, int32_t* out, int32_t cap) {
+  XT_REQUIRE(n && out, "xt_net_last_step_report: null argument");
+  const int need = XT_STEP_REPORT_NET_WORDS + XT_STEP_REPORT_LAYER_WORDS * (int)n->layers.size();
+  XT_REQUIRE(cap >= need, "xt_net_last_step_report: %d words offered, the report of %d layers takes %d", cap,
+             (int)n->layers.size(), need);
+  out[XT_STEP_REPORT_WORDS] = need;
+  out[XT_STEP_REPORT_LAYERS] = (int32_t)n->layers.size();
+  out[XT_STEP_REPORT_TRUNKS] = n->n_trunks;
+  out[XT_STEP_REPORT_FWD_FUSE12] = n->last_fuse12;
+  out[XT_STEP_REPORT_BWD_FUSE21] = n->last_fuse21;
+  out[XT_STEP_REPORT_HEAD_PATH] = n->last_head_path;
+  out[XT_STEP_REPORT_TAIL_OVERLAP] = n->last_tail_mode;
+  out[XT_STEP_REPORT_FINISH_FORM] = n->last_finish_form;
+  out[XT_STEP_REPORT_FINISH_BLOCKS] = n->norm_blocks;
+  out[XT_STEP_REPORT_PARTIAL_FLOATS] = (int32_t)n->partial_floats;
+  out[XT_STEP_REPORT_MAX_NORM_PARTIALS] = xt::kMaxNormPartials;
+  out[XT_STEP_REPORT_HEAD_CHUNKS] = n->head_chunks;
+  for (size_t l = 0; l < n->layers.size(); ++l) {
+    const xt::Layer& L = n->layers[l];
+    int32_t* o = out + XT_STEP_REPORT_NET_WORDS + XT_STEP_REPORT_LAYER_WORDS * (int)l;
+    o[XT_STEP_REPORT_L_KSPLIT] = L.last_ksplit;
+    o[XT_STEP_REPORT_L_DEFERRED] = L.last_deferred;
+    o[XT_STEP_REPORT_L_MSPLIT] = L.last_msplit;
+    o[XT_STEP_REPORT_L_SLAB_CAP] = L.slab_cap;
+    o[XT_STEP_REPORT_L_MASK_VALID] = L.mask_valid;
+    o[XT_STEP_REPORT_L_PREACT] = L.z_off >= 0 ? 1 : 0;
+    o[XT_STEP_REPORT_L_NPRE] = L.last_npre;
+    o[XT_STEP_REPORT_L_TRUNK] = L.trunk;
+  }
+  return 0;
 }
 
 }  // extern "C"

@@ -268,7 +268,13 @@ SIGNATURES = {
     "xt_optim_clip_ex": (c_int32, [c_int32, _P, _P, _P, _P, c_int64, c_float, _P, c_float, c_float, c_float, _P, _P, c_int32,
                                    c_float, c_float, _P, _P]),
     "xt_norm_finalize_ex": (c_int32, [_P, c_int32, POINTER(FinishArgs), _P]),
+    "xt_net_last_step_report": (c_int32, [_P, POINTER(c_int32), c_int32]),
 }
+# XT_STEP_REPORT_<name> / XT_STEP_REPORT_L_<name> of include/xt_mi355x.h: word of every net / layer fact
+STEP_REPORT_NET = ("WORDS", "LAYERS", "TRUNKS", "FWD_FUSE12", "BWD_FUSE21", "HEAD_PATH", "TAIL_OVERLAP", "FINISH_FORM",
+                   "FINISH_BLOCKS", "PARTIAL_FLOATS", "MAX_NORM_PARTIALS", "HEAD_CHUNKS")
+STEP_REPORT_LAYER = ("KSPLIT", "DEFERRED", "MSPLIT", "SLAB_CAP", "MASK_VALID", "PREACT", "NPRE", "TRUNK")
+MAX_TRUNK_LAYERS = 9      # kMaxTrunkLayers: trunk layers of one net, both trunks counted (xt_net_create refuses more)
 
 
 def dp_error_text(bits):
@@ -320,6 +326,19 @@ def set_tuning(**knobs):
         setattr(t, k, int(v))
     check(lib.xt_tuning_set(ctypes.byref(t)), "xt_tuning_set")
     return old
+
+
+def step_report(handle):
+    """``xt_net_last_step_report`` of a net handle -> dict of the net's facts (lower-case names of ``STEP_REPORT_NET``) with
+    ``layer`` = list of per-layer dicts (``STEP_REPORT_LAYER``).  Host words only: nothing is launched."""
+    cap = len(STEP_REPORT_NET) + len(STEP_REPORT_LAYER) * 64
+    buf = (c_int32 * cap)()
+    check(load().xt_net_last_step_report(handle, buf, cap), "xt_net_last_step_report")
+    out = {k.lower(): int(buf[i]) for i, k in enumerate(STEP_REPORT_NET)}
+    nl, lw = len(STEP_REPORT_NET), len(STEP_REPORT_LAYER)
+    out["layer"] = [{k.lower(): int(buf[nl + lw * l + i]) for i, k in enumerate(STEP_REPORT_LAYER)}
+                    for l in range(out["layers"])]
+    return out
 
 
 def check(rc, what=""):

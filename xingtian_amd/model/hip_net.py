@@ -52,11 +52,48 @@ class _MailboxDone(object):
         return self.net.lib.xt_net_io_publish_wait(self.net.handle, self.seq, 0) == 0
 
 
+def net_desc(spec):
+    """``NetSpec`` -> (layer array, ``NetDesc``) of the C ABI; the array must outlive the description"""
+    lay_arr = (L.LayerDesc * len(spec.layers))()
+    for i, lay in enumerate(spec.layers):
+        g = lay_arr[i].g
+        g.H, g.W, g.C, g.KH, g.KW, g.S = lay.H, lay.W, lay.C, lay.KH, lay.KW, lay.S
+        g.PT, g.PL, g.OH, g.OW, g.N, g.act = lay.PT, lay.PL, lay.OH, lay.OW, lay.N, L.ACT[lay.act]
+        lay_arr[i].param_off = lay.param_off
+        lay_arr[i].trunk = lay.trunk
+    d = L.NetDesc()
+    d.n_layers, d.layers, d.n_trunks = len(spec.layers), lay_arr, spec.n_trunks
+    d.feat, d.action_dim, d.pi_off, d.v_off, d.n_params = spec.feat, spec.action_dim, spec.pi_off, spec.v_off, spec.n_flat
+    d.xf = L.InputXform(*spec.input_xform)
+    d.in_h, d.in_w, d.in_c = spec.layers[0].H, spec.layers[0].W, spec.layers[0].C      # (C: as the kernels read it, padded)
+    d.action_type = L.ACTION_TYPE[getattr(spec, "action_type", "Categorical")]
+    d.logstd_off = getattr(spec, "logstd_off", 0)
+    return lay_arr, d
+
+
+def create_net(spec, max_batch):
+    """C ABI ``xt_net_create`` (host code, no device call) -> (layer array, description, handle).  A network outside the
+    library's envelope -- more than ``lib.MAX_TRUNK_LAYERS`` trunk layers, an empty layer, unequal unshared
+    trunks -- is a ``ValueError`` carrying the library's message, raised before anything is allocated or enqueued."""
+    lib = L.load()
+    lay_arr, d = net_desc(spec)
+    h = ctypes.c_void_p()
+    rc = lib.xt_net_create(ctypes.byref(d), int(max_batch), ctypes.byref(h))
+    if rc != 0:
+        msg = lib.xt_last_error()
+        raise ValueError("xingtian_amd: this network cannot be built (xt_net_create, rc={}): {}".format(
+            rc, msg.decode() if msg else "?"))
+    return lay_arr, d, h
+
+
 class HipActorCritic(object):
     def __init__(self, spec, max_batch, device="cuda:0", seed=None, init="glorot"):
-        L.require_gpu()
         self.lib = L.load()
         self.spec, self.max_batch = spec, int(max_batch)
+        # host code only: a description the library cannot serve is a ValueError here, with or without a GPU
+        self._lay_arr, self._desc, self.handle = create_net(spec, self.max_batch)
+        h = self.handle
+        L.require_gpu()
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         n = spec.n_flat
@@ -71,25 +108,6 @@ class HipActorCritic(object):
         self.loss_acc = torch.zeros(8, dtype=torch.float32, device=self.device)
         self.loss_out = torch.zeros(8, dtype=torch.float32, device=self.device)
 
-        lay_arr = (L.LayerDesc * len(spec.layers))()
-        for i, lay in enumerate(spec.layers):
-            g = lay_arr[i].g
-            g.H, g.W, g.C, g.KH, g.KW, g.S = lay.H, lay.W, lay.C, lay.KH, lay.KW, lay.S
-            g.PT, g.PL, g.OH, g.OW, g.N, g.act = lay.PT, lay.PL, lay.OH, lay.OW, lay.N, L.ACT[lay.act]
-            lay_arr[i].param_off = lay.param_off
-            lay_arr[i].trunk = lay.trunk
-        self._lay_arr = lay_arr
-        d = L.NetDesc()
-        d.n_layers, d.layers, d.n_trunks = len(spec.layers), lay_arr, spec.n_trunks
-        d.feat, d.action_dim, d.pi_off, d.v_off, d.n_params = spec.feat, spec.action_dim, spec.pi_off, spec.v_off, n
-        d.xf = L.InputXform(*spec.input_xform)
-        d.in_h, d.in_w, d.in_c = spec.layers[0].H, spec.layers[0].W, spec.layers[0].C      # (C: as the kernels read it, padded)
-        d.action_type = L.ACTION_TYPE[getattr(spec, "action_type", "Categorical")]
-        d.logstd_off = getattr(spec, "logstd_off", 0)
-        self._desc = d
-        h = ctypes.c_void_p()
-        L.check(self.lib.xt_net_create(ctypes.byref(d), self.max_batch, ctypes.byref(h)), "xt_net_create")
-        self.handle = h
         ws_bytes = self.lib.xt_net_workspace_bytes(h)
         self.workspace = torch.empty(ws_bytes // 4, dtype=torch.float32, device=self.device)
         L.check(self.lib.xt_net_bind(h, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.adam_m), L.ptr(self.adam_v),
@@ -484,6 +502,11 @@ class HipActorCritic(object):
     def last_head_path(self):
         """the head / loss kernel the most recent PPO or IMPALA step launched (C ABI ``xt_net_last_head_path``; diagnostic)"""
         return int(self.lib.xt_net_last_head_path(self.handle))
+
+    def last_step_report(self):
+        """what the most recent step decided from the net's shapes (C ABI ``xt_net_last_step_report``, ``lib.step_report``;
+        host words only, diagnostic)"""
+        return L.step_report(self.handle)
 
     gauss_fused_on = False
 

@@ -90,6 +90,12 @@ def _conv(name, h, w, c, cout, k, s, padding, act, trunk):
     lay.OH, lay.PT = conv_out(h, k, s, padding)
     lay.OW, lay.PL = conv_out(w, k, s, padding)
     lay.N, lay.act, lay.trunk = cout, act, trunk
+    if lay.OH < 1 or lay.OW < 1:
+        # the reference's inferred architecture halves a SIZE COUNTER per 5x5/2 layer, not the VALID output size
+        # (model_utils.py:150-176): for some images (20x20, 40x40) it ends in a 3x3 kernel on a 2x2 map, which TensorFlow
+        # refuses too ("Negative dimension size")
+        raise ValueError("layer {}: a {}x{} kernel does not fit its {}x{} input (limit: every layer output must be at "
+                         "least 1x1; no default architecture serves this obs shape)".format(name, k, k, h, w))
     lay.kernel_shape = (k, k, c, cout)
     lay.store_shape = (k, k, cpad, cout) if cpad != c else None
     if cpad != c and padding == "valid" and k == h == w:
