@@ -473,7 +473,11 @@ int xt_net_ppo_step(xt_net* net, const xt_ppo_cfg* cfg, const void* obs, const i
  * permutations (the reference's np.random.shuffle, injected).  loss_acc (4 floats): [0] receives the
  * SUM of minibatch losses, [1] the number of minibatches, [2] data-parallel error bits (0 = none; ABI >= 11).  use_graph != 0
  * captures the whole call into a hipGraph on first use and replays it afterwards
- * (pointers and sizes must then stay the same between calls). */
+ * (pointers and sizes must then stay the same between calls).  The graph is looked up under a key that holds every
+ * argument, every cfg field (floats by their exact bits) and the net-level switches that change the enqueued work
+ * (training statistics, xt_net_set_gauss_fused, the data-parallel settings): a call that differs in any of them captures
+ * its own graph, up to 8 per net (xt_net_graph_cache_info).  NOT part of the key: the process-wide xt_tuning knobs --
+ * they stay "set before creating networks"; a graph captured under other knobs is replayed as it was captured. */
 int xt_net_ppo_train(xt_net* net, const xt_ppo_cfg* cfg, const void* obs, int32_t n,
                      const int32_t* perm, const void* action, const float* old_logp,
                      const double* adv, const float* old_v, const double* target_v,
@@ -714,7 +718,9 @@ int xt_net_impala_step(xt_net* net, const xt_impala_cfg* cfg, const void* obs, i
  * a hipGraph on first use and replays it while pointers and sizes repeat (a small cache of graphs is kept, so that
  * alternating ingest buffer sets do not re-capture).  A gradient-exchange hook (xt_net_set_grad_exchange) makes every
  * chunk data parallel: local gradient -> exchange (SUM; the loss is a sum, grad_scale = 1) -> norm of the exchanged
- * gradient -> clip + the configured optimiser (Adam or centred RMSProp, lr_steps honoured; ABI >= 9). */
+ * gradient -> clip + the configured optimiser (Adam or centred RMSProp, lr_steps honoured; ABI >= 9).  The graph key
+ * holds every argument, every cfg field (floats by their exact bits) and the v-trace statistics switch; as for
+ * xt_net_ppo_train the process-wide xt_tuning knobs are NOT part of it and stay "set before creating networks". */
 int xt_net_impala_train(xt_net* net, const xt_impala_cfg* cfg, const void* obs, int32_t n, int32_t batch_size,
                         const float* bp_logits, const int32_t* action, const uint8_t* done, const float* reward,
                         const float* lr_steps, float* loss_acc, int32_t use_graph, void* stream);
@@ -1277,6 +1283,18 @@ enum {
   XT_STEP_REPORT_LAYER_WORDS = 8
 };
 int xt_net_last_step_report(const xt_net* net, int32_t* out, int32_t cap);
+
+/* What the hipGraph cache of xt_net_ppo_train / xt_net_impala_train(_io) has done on this net so far (appended under ABI
+ * 12; diagnostic, for tests/test_gpu_train_entry.py).  Host words only: no launch, no device memory is touched.  `cap` =
+ * words offered (refused below XT_GRAPH_CACHE_WORDS).  CAPTURES = calls that captured and instantiated a graph (a call
+ * whose enqueue refused inside the capture is not one), LAUNCHES = graph launches (every use_graph call that succeeded),
+ * EVICTIONS = graphs given up for a new key while all slots were taken (the least recently used one goes); these three
+ * count over the net's lifetime.  LIVE_SLOTS = graphs held now (at most 8): xt_net_bind destroys them all. */
+enum {
+  XT_GRAPH_CACHE_CAPTURES = 0, XT_GRAPH_CACHE_LAUNCHES = 1, XT_GRAPH_CACHE_EVICTIONS = 2, XT_GRAPH_CACHE_LIVE_SLOTS = 3,
+  XT_GRAPH_CACHE_WORDS = 4
+};
+int xt_net_graph_cache_info(const xt_net* net, int32_t* out, int32_t cap);
 
 #ifdef __cplusplus
 }

@@ -108,6 +108,7 @@ struct xt_net {
   struct GraphSlot { std::string key; hipGraphExec_t exec = nullptr; unsigned long long used = 0; };
   GraphSlot gslots[8];
   unsigned long long gclock = 0;
+  int32_t gcaptures = 0, glaunches = 0, gevictions = 0;   // xt_net_graph_cache_info: counted in graph_run, never reset
   hipStream_t cap_stream = nullptr;   // capture happens on our own stream: the legacy null stream cannot be captured
   // xt_train_io.tail_in_graph: the 64-byte page-locked mailbox between the learner thread and the train's two tail kernels
   // (host side / the same block through the device's address space), the sequence number of the last train that used it, and
@@ -456,13 +457,19 @@ static int grads_finish(xt_net* n, int B, const FinalizeArgs* fin, hipStream_t s
   return launch_grads_finish(&tab, n->ws + n->off_norm, kMaxNormPartials, &n->norm_blocks, fin, st, select, first_bucket, dpf);
 }
 
-// loss_acc = [sum, count, data-parallel error bits, -].  TWO 8-byte memsets, the second only for a data-parallel net: ONE
-// 16-byte hipMemsetAsync captured into a hipGraph wrote garbage (a pointer-looking 64-bit word) into bytes 8..15 on every
-// REPLAY on this stack (ROCm 7.0 runtime of PyTorch 2.10; measured round 6, tools/dbg_acc.py) -- the 8-byte node has been
-// replayed correctly since round 1
+// loss_acc = [sum, count, data-parallel error bits, -]: the first two floats, all four for a data-parallel net.  No memset
+// node: ONE 16-byte hipMemsetAsync captured into a hipGraph wrote garbage (a pointer-looking 64-bit word) into bytes 8..15 on
+// every REPLAY on this stack (ROCm 7.0 runtime of PyTorch 2.10; measured round 6, tools/dbg_acc.py), and the 8-byte nodes that
+// replaced it are not safe either: a captured memset node REPLAYED after an eager hipMemsetAsync of the
+// same process had run in between left the same garbage word in both floats (tests/test_gpu_train_entry.py: eager A, graph
+// A, eager B, graph B, graph A; a replay right behind its capture, all the older tests did, is fine).  So the clear is a
+// kernel, as the statistics' is (launch_train_stats_clear): its arguments are captured by value.
+__global__ void __launch_bounds__(64) loss_acc_clear_kernel(float* __restrict__ acc, int count) {
+  if ((int)threadIdx.x < count) acc[threadIdx.x] = 0.f;
+}
 static int clear_loss_acc(const xt_net* n, float* loss_acc, hipStream_t st) {
-  XT_CHECK_HIP(hipMemsetAsync(loss_acc, 0, 2 * sizeof(float), st));
-  if (n->dp_world >= 1) XT_CHECK_HIP(hipMemsetAsync(loss_acc + 2, 0, 2 * sizeof(float), st));
+  hipLaunchKernelGGL(loss_acc_clear_kernel, dim3(1), dim3(64), 0, st, loss_acc, n->dp_world >= 1 ? 4 : 2);
+  XT_LAUNCH_CHECK();
   return 0;
 }
 
@@ -778,33 +785,39 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
   return launch_train_stats_reduce(&la, st);
 }
 
-// Replay the hipGraph cached under `key`, capturing `enqueue` (on the net's private stream) on a miss.
+// Replay the hipGraph cached under `key`, capturing `enqueue` (on the net's private stream) on a miss.  A slot is taken
+// (and the least recently used graph given up) only once the capture has been instantiated: an enqueue that refuses inside
+// the capture ends it and leaves the cache as it was.
 template <typename F>
 static int graph_run(xt_net* net, const char* key, hipStream_t st, F enqueue) {
   xt_net::GraphSlot* slot = nullptr;
   for (auto& g : net->gslots) if (g.exec && g.key == key) slot = &g;
   if (!slot) {
-    slot = &net->gslots[0];
-    for (auto& g : net->gslots) {
-      if (!g.exec) { slot = &g; break; }
-      if (g.used < slot->used) slot = &g;
-    }
-    if (slot->exec) { hipGraphExecDestroy(slot->exec); slot->exec = nullptr; slot->key.clear(); }
     hipGraph_t graph = nullptr;
     if (!net->cap_stream) XT_CHECK_HIP(hipStreamCreateWithFlags(&net->cap_stream, hipStreamNonBlocking));
     hipStream_t cs = net->cap_stream;
     XT_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed));
     int rc = enqueue(cs);
     hipError_t e = hipStreamEndCapture(cs, &graph);
-    if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
+    if (rc) { if (graph) hipGraphDestroy(graph); if (e != hipSuccess) (void)hipGetLastError(); return rc; }
     XT_CHECK_HIP(e);
-    e = hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0);
+    hipGraphExec_t exec = nullptr;
+    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     hipGraphDestroy(graph);
     XT_CHECK_HIP(e);
+    slot = &net->gslots[0];
+    for (auto& g : net->gslots) {
+      if (!g.exec) { slot = &g; break; }
+      if (g.used < slot->used) slot = &g;
+    }
+    if (slot->exec) { hipGraphExecDestroy(slot->exec); ++net->gevictions; }
+    slot->exec = exec;
     slot->key = key;
+    ++net->gcaptures;
   }
   slot->used = ++net->gclock;
   XT_CHECK_HIP(hipGraphLaunch(slot->exec, st));
+  ++net->glaunches;
   return 0;
 }
 
@@ -1247,8 +1260,9 @@ int xt_net_ppo_train(xt_net* net, const xt_ppo_cfg* c, const void* obs, int32_t 
   (void)xt::tail_overlap_mode(net);      // (creates the side stream outside of any capture)
   if (!use_graph)
     return ppo_train_enqueue(net, c, obs, n, perm, action, old_logp, adv, old_v, target_v, loss_acc, st);
-  char key[640];
-  snprintf(key, sizeof(key), "P%d.%d.%d.%d.%d.%g.%p|%p|%p|%p|%d|%p|%p|%p|%p|%p|%p|%p|%g|%g|%g|%g|%g|%g|%g|%g|%g|%d|%d|%g|%d|%p|%p|%d",
+  // every float as its exact hexadecimal form (%a): "%g" keeps six digits, and two step sizes one ulp apart shared a graph
+  char key[1024];
+  snprintf(key, sizeof(key), "P%d.%d.%d.%d.%d.%a.%p|%p|%p|%p|%d|%p|%p|%p|%p|%p|%p|%p|%a|%a|%a|%a|%a|%a|%a|%a|%a|%d|%d|%a|%d|%p|%p|%d",
            net->xchg_flags, c->shard_rank, c->shard_world, net->dp_rank, net->dp_world, net->dp_loss_scale, (void*)net->direct,
            (void*)net->xchg, net->xchg_user, obs, n,
            (const void*)perm, (const void*)action, (const void*)old_logp, (const void*)adv, (const void*)old_v,
@@ -1484,8 +1498,8 @@ static int impala_train_run(xt_net* net, const xt_impala_cfg* c, const void* obs
     return (io_tail && !fold) ? xt::io_tail_enqueue(net, loss_acc, io_tail, cs) : 0;
   };
   if (!use_graph) return enqueue(st);
-  char key[640];
-  snprintf(key, sizeof(key), "I%d.%d.%d.%d.%p|%p|%p|%p|%d|%d|%p|%p|%p|%p|%p|%p|%g|%g|%g|%g|%g|%g|%d|%g|%d|%g|%g|%p|%d|%p|%p",
+  char key[1024];      // (floats as %a: see xt_net_ppo_train)
+  snprintf(key, sizeof(key), "I%d.%d.%d.%d.%p|%p|%p|%p|%d|%d|%p|%p|%p|%p|%p|%p|%a|%a|%a|%a|%a|%a|%d|%a|%d|%a|%a|%p|%d|%p|%p",
            c->shard_rank, c->shard_world, net->dp_rank, net->dp_world, (void*)net->direct, (void*)net->xchg, net->xchg_user, obs, n, batch_size, (const void*)bp_logits, (const void*)action,
            (const void*)done, (const void*)reward, (const void*)lr_steps, (void*)loss_acc, c->lr, c->beta1, c->beta2,
            c->eps, c->grad_norm_clip, c->gamma, c->sample_batch_step, c->grad_scale, c->opt_type, c->rms_decay, c->rms_eps,
@@ -1759,6 +1773,19 @@ int xt_net_keras_impala_train(xt_net* n, const xt_keras_train_cfg* c, const void
                                c->beta1, c->beta2, c->eps, c->adam_scratch, stream))
       return rc;
   }
+  return 0;
+}
+
+int xt_net_graph_cache_info(const xt_net* n, int32_t* out, int32_t cap) {
+  XT_REQUIRE(n && out, "xt_net_graph_cache_info: null argument");
+  XT_REQUIRE(cap >= XT_GRAPH_CACHE_WORDS, "xt_net_graph_cache_info: %d words offered, the report takes %d", cap,
+             XT_GRAPH_CACHE_WORDS);
+  int live = 0;
+  for (const auto& g : n->gslots) live += g.exec ? 1 : 0;
+  out[XT_GRAPH_CACHE_CAPTURES] = n->gcaptures;
+  out[XT_GRAPH_CACHE_LAUNCHES] = n->glaunches;
+  out[XT_GRAPH_CACHE_EVICTIONS] = n->gevictions;
+  out[XT_GRAPH_CACHE_LIVE_SLOTS] = live;
   return 0;
 }
 

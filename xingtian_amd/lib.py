@@ -269,7 +269,11 @@ SIGNATURES = {
                                    c_float, c_float, _P, _P]),
     "xt_norm_finalize_ex": (c_int32, [_P, c_int32, POINTER(FinishArgs), _P]),
     "xt_net_last_step_report": (c_int32, [_P, POINTER(c_int32), c_int32]),
+    "xt_net_graph_cache_info": (c_int32, [_P, POINTER(c_int32), c_int32]),
 }
+# XT_GRAPH_CACHE_<name> of include/xt_mi355x.h: word of every counter of xt_net_graph_cache_info
+GRAPH_CACHE_WORDS = ("CAPTURES", "LAUNCHES", "EVICTIONS", "LIVE_SLOTS")
+GRAPH_CACHE_SLOTS = 8     # graphs one net holds (xt_net.hip: gslots)
 # XT_STEP_REPORT_<name> / XT_STEP_REPORT_L_<name> of include/xt_mi355x.h: word of every net / layer fact
 STEP_REPORT_NET = ("WORDS", "LAYERS", "TRUNKS", "FWD_FUSE12", "BWD_FUSE21", "HEAD_PATH", "TAIL_OVERLAP", "FINISH_FORM",
                    "FINISH_BLOCKS", "PARTIAL_FLOATS", "MAX_NORM_PARTIALS", "HEAD_CHUNKS")
@@ -339,6 +343,13 @@ def step_report(handle):
     out["layer"] = [{k.lower(): int(buf[nl + lw * l + i]) for i, k in enumerate(STEP_REPORT_LAYER)}
                     for l in range(out["layers"])]
     return out
+
+
+def graph_cache_info(handle):
+    """``xt_net_graph_cache_info`` of a net handle -> dict(captures, launches, evictions, live_slots).  Host words only."""
+    buf = (c_int32 * len(GRAPH_CACHE_WORDS))()
+    check(load().xt_net_graph_cache_info(handle, buf, len(GRAPH_CACHE_WORDS)), "xt_net_graph_cache_info")
+    return {k.lower(): int(buf[i]) for i, k in enumerate(GRAPH_CACHE_WORDS)}
 
 
 def check(rc, what=""):

@@ -508,6 +508,11 @@ class HipActorCritic(object):
         host words only, diagnostic)"""
         return L.step_report(self.handle)
 
+    def graph_cache_info(self):
+        """captures / launches / evictions / live slots of the net's update-graph cache (C ABI ``xt_net_graph_cache_info``,
+        ``lib.graph_cache_info``; host words only, diagnostic)"""
+        return L.graph_cache_info(self.handle)
+
     gauss_fused_on = False
 
     def set_gauss_fused(self, on=True):
