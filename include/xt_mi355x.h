@@ -1185,6 +1185,57 @@ int xt_net_dqn_step_per(xt_net* net, xt_net* target_net, const xt_dqn_cfg* cfg, 
                         const int32_t* action, const double* reward, const uint8_t* done, float* loss_out, float* loss_acc,
                         void* stream);
 
+/* ------------------------------------------------------------------ DQN: n-step returns (appended under ABI 12)
+ * The learner holds every message's rows in time order in the rings, so the m-step target of a sampled row is formed on
+ * the device inside the next-state gather.  follow int32 [capacity]: follow[s] = the number of rows that come after slot s
+ * in the message that wrote it (a negative value counts as 0).  For a start slot s (all float64; the product is rounded,
+ * then the sum: no fma):
+ *     R = reward[s]; g = gamma; j = s; k = 0
+ *     while k < n - 1 and k < follow[s] and not done[j]:  k += 1; j = (s + k) % capacity; R = R + g * reward[j]; g = g * gamma
+ *     boot_slot = j; reward_n = R; disc_n = g; done_n = done[j]; action_n = action[s]
+ *     y = done_n ? (float)R : (float)(R + disc_n * (double)maxq)                 (maxq from next_ring[boot_slot])
+ * n = 1 is (s, reward[s], gamma, done[s]): the one-step target bit for bit.  A walk that reaches the end of its message
+ * stops there (a shorter target); rows behind s in its message are newer than s, so a live row only walks live rows.
+ *
+ * xt_replay_gather_nstep: xt_replay_gather (same grid, same refusals) with the walk in front: dst[b] =
+ * next_ring[boot_slot_b], and the five labels of sample b go to boot_slots / action_n / reward_n / disc_n / done_n [B].
+ * 1 <= n <= 256; action / reward / done / follow: the label rings [capacity].  A start slot outside [0, capacity) reads
+ * nothing: a zero row, boot_slot = slot, action_n = 0, reward_n = 0, disc_n = gamma, done_n = 1. */
+int xt_replay_gather_nstep(const void* next_ring, int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B,
+                           const int32_t* action, const double* reward, const uint8_t* done, const int32_t* follow,
+                           int32_t n, double gamma, void* dst, int32_t* boot_slots, int32_t* action_n, double* reward_n,
+                           double* disc_n, uint8_t* done_n, void* stream);
+
+/* xt_dqn_loss_w with a per-sample discount: disc float64 [B] on the device (indexed by the sample, never through slots)
+ * takes gamma's place, y_b = done ? (float)r : (float)(r + disc[b] * (double)maxq).  disc == NULL is xt_dqn_loss_w bit
+ * for bit (xt_dqn_loss_w calls this entry with NULL). */
+int xt_dqn_loss_n(const float* logits, const float* value, const float* t_logits, const float* t_value,
+                  const float* o_logits, const float* o_value, int32_t B, int32_t A, int32_t dueling, const int32_t* slots,
+                  const int32_t* action, const double* reward, const uint8_t* done, double gamma, float* dlogits,
+                  float* dvalue, float* out, float* y, int32_t* astar, float* maxq, float* acc, const double* weights,
+                  const double* disc, void* stream);
+
+/* One DQN.train with n-step targets up to the gradient, uniform (per == NULL: `slots` int32 [B] on the device) or
+ * prioritised (per set: `slots` is ignored, `size` stored transitions are sampled), in ONE call that never synchronises.
+ * The refusals of xt_net_dqn_step(_per) in their order, then 1 <= ns->n <= 256 and non-null pointers in ns; then the chain
+ * of xt_net_dqn_step(_per) with two changes: the first gather is xt_replay_gather_nstep, so both next-state forwards run
+ * on the boot rows, and the head (xt_dqn_loss_n) reads the dense labels the gather left with disc = ns->disc_n.  The state
+ * rows are gathered by the start slots and xt_per_update writes the new priorities to the start slots.  The launches
+ * are those of the one-step chain in number; ns->n == 1 gives its loss, gradient and trees bit for bit. */
+typedef struct xt_nstep_cfg {
+  int32_t n;                    /* steps of the return, 1 <= n <= 256                                       */
+  const int32_t* follow;        /* ring [capacity]: rows behind each slot in its message                    */
+  int32_t* boot_slots;          /* scratch [B]: the slot whose next state bootstraps sample b               */
+  int32_t* action_n;            /* scratch [B]: action[start slot]                                          */
+  double* reward_n;             /* scratch [B]: the discounted reward sum                                   */
+  double* disc_n;               /* scratch [B]: gamma ** (rows walked + 1)                                  */
+  uint8_t* done_n;              /* scratch [B]: done[boot slot]                                             */
+} xt_nstep_cfg;
+int xt_net_dqn_step_n(xt_net* net, xt_net* target_net, const xt_dqn_cfg* cfg, const xt_nstep_cfg* ns,
+                      const xt_per_cfg* per, const void* cur_ring, const void* next_ring, int64_t row_bytes,
+                      int64_t capacity, int64_t size, const int32_t* slots, int32_t B, const int32_t* action,
+                      const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream);
+
 /* ------------------------------------------------------------------ the step tail stand-alone (appended under ABI 12)
  * The gradient-reduction launch and the optimiser launches every xt_net_*_step ends in, on given buffers, for kernel
  * tests (tests/test_gpu_optim_branch.py).  Each entry fills the argument structs the step fills and calls the step's own

@@ -10,6 +10,8 @@ device synchronise, after a warm-up, in ``--windows`` windows taken in turn (so 
 * the same train without the read-back (``DqnModel.train_replay`` on pre-uploaded slots: what the device is given to do);
 * each of the above with ``prioritized_replay`` (``xt_net_dqn_step_per``: two more launches per train, the sample in
   front and the priority update behind; the draws of ``random.random()`` go up instead of the slots);
+* the uniform and the prioritised train with ``n_step: 3`` (``xt_net_dqn_step_n``: the same launches, the walk over the
+  rows that follow each sampled row rides in the next-state gather), as ``DQN.train`` and enqueue only;
 * one ``prepare_data`` of a 20-row message without and with ``prioritized_replay`` (``xt_per_add`` per written span), each
   call followed by a device synchronise;
 * ``keras_impala_step`` + ``adam_keras`` on 32 rows of ``netspec.impala_cnn`` (the same trunk and heads, one network, no
@@ -33,12 +35,14 @@ if ROOT not in sys.path:
 B, A_DIM, DIM = 32, 4, 84
 
 
-def build_dqn(double, capacity, per=False):
+def build_dqn(double, capacity, per=False, n_step=1):
     from xingtian_amd.algorithm import alg_builder
     info = {"actor": {"model_name": "DqnCnn", "type": "learner", "state_dim": [DIM, DIM, 4], "action_dim": A_DIM,
                       "model_config": {"LR": 0.00015, "SEED": 0}}}
     cfg = {"instance_num": 1, "agent_num": 1, "prepare_times_per_train": 4, "BUFFER_SIZE": capacity, "BATCH_SIZE": B,
            "TARGET_UPDATE_FREQ": 1000, "double_dqn": double, "prioritized_replay": per}
+    if n_step != 1:
+        cfg["n_step"] = n_step
     alg = alg_builder("DQN", info, cfg)
     rng = np.random.default_rng(1)
     for _ in range(capacity // 512):
@@ -66,6 +70,8 @@ def main():
     algs = {False: build_dqn(False, args.capacity), True: build_dqn(True, args.capacity)}
     slots = {d: torch.tensor(a.buff.sample(B), dtype=torch.int32).cuda() for d, a in algs.items()}
     pers = {False: build_dqn(False, args.capacity, True), True: build_dqn(True, args.capacity, True)}
+    nstep, nstep_per = build_dqn(False, args.capacity, False, 3), build_dqn(False, args.capacity, True, 3)
+    nstep_slots = torch.tensor(nstep.buff.sample(B), dtype=torch.int32).cuda()
     draws = torch.tensor([random.random() for _ in range(B)], dtype=torch.float64).cuda()
     rng = np.random.default_rng(2)
     net = HipActorCritic(netspec.impala_cnn((DIM, DIM, 4), A_DIM), max_batch=B, seed=0)
@@ -88,6 +94,13 @@ def main():
         alg = pers[double]
         return lambda: alg.actor.train_replay_per(alg.target_actor, alg.buff, draws, alg.per_beta(), dqn_mod.GAMMA, double)
 
+    def replay_nstep():
+        return nstep.actor.train_replay(nstep.target_actor, nstep.buff, nstep_slots, dqn_mod.GAMMA, False)
+
+    def replay_nstep_per():
+        return nstep_per.actor.train_replay_per(nstep_per.target_actor, nstep_per.buff, draws, nstep_per.per_beta(),
+                                                dqn_mod.GAMMA, False)
+
     msg_rng = np.random.default_rng(3)
     msg = {"cur_state": msg_rng.integers(0, 256, (20, DIM, DIM, 4), dtype=np.uint8),
            "next_state": msg_rng.integers(0, 256, (20, DIM, DIM, 4), dtype=np.uint8),
@@ -101,9 +114,13 @@ def main():
         return fn
 
     cases = [("DQN.train (loss read back)", algs[False].train), ("DQN.train, PER (loss read back)", pers[False].train),
+             ("DQN.train, n_step 3 (loss read back)", nstep.train),
+             ("DQN.train, PER, n_step 3 (loss read back)", nstep_per.train),
              ("DQN.train, double_dqn (loss read back)", algs[True].train),
              ("DQN.train, PER, double_dqn (loss read back)", pers[True].train),
              ("dqn step + adam, enqueue only", replay(False)), ("dqn step + adam, PER, enqueue only", replay_per(False)),
+             ("dqn step + adam, n_step 3, enqueue only", replay_nstep),
+             ("dqn step + adam, PER, n_step 3, enqueue only", replay_nstep_per),
              ("dqn step + adam, double_dqn, enqueue only", replay(True)),
              ("dqn step + adam, PER, double_dqn, enqueue only", replay_per(True)),
              ("prepare_data, 20 rows, synchronised", ingest(algs[False])),

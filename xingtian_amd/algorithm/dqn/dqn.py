@@ -19,6 +19,11 @@ is driven the reference's way on the host (``_train_host``), with ``td_targets``
 (xt/algorithm/prioritized_replay_buffer_muzero.py, the baselines form): ``PrioritizedDeviceReplay`` keeps the sum tree,
 the min tree and the running maximum priority next to the rings, a train uploads its ``random.random()`` draws and ONE C
 call (``xt_net_dqn_step_per``) samples, weights the head and writes the new priorities back.  It needs the device step.
+
+``alg_config.n_step`` (1 unless asked for) trains on n-step returns: the reference's agents send one-step transitions, but
+a message holds consecutive steps of one agent and ``DeviceReplay.add`` writes it to contiguous slots, so the rows that
+follow a sampled row are next to it in the rings.  A sixth ring, ``follow``, says how many rows come after each slot in
+its message; ``nstep_targets`` is the definition, ``xt_net_dqn_step_n`` evaluates it inside the next-state gather.
 """
 import random
 
@@ -35,20 +40,59 @@ def td_targets(reward, done, maxq, gamma):
     scalar, ``gamma * maxq`` promotes the float32 Q value to float64, and storing into the float32 prediction rounds
     once.  ``done`` is truthiness."""
     r = np.asarray(reward, np.float64).reshape(-1)
-    boot = r + float(gamma) * np.asarray(maxq, np.float32).reshape(-1).astype(np.float64)
+    g = np.asarray(gamma, np.float64)                  # a scalar, or the per-sample discount of n-step targets
+    boot = r + (g.reshape(-1) if g.ndim else float(g)) * np.asarray(maxq, np.float32).reshape(-1).astype(np.float64)
     return np.where(np.asarray(done).reshape(-1).astype(bool), r, boot).astype(np.float32)
+
+
+def nstep_targets(slots, follow, action, reward, done, gamma, n, capacity):
+    """The n-step walk of every start slot in ``slots`` over the label rings (host arrays of ``capacity`` entries), in
+    Python floats (IEEE float64, one rounding per operation):
+
+        R = reward[s]; g = gamma; j = s; k = 0
+        while k < n - 1 and k < follow[s] and not done[j]:
+            k += 1; j = (s + k) % capacity; R = R + g * reward[j]; g = g * gamma
+
+    -> (boot_slot int32, action_n int32, reward_n float64, disc_n float64, done_n uint8), one entry per start slot:
+    ``j``, ``action[s]``, ``R``, ``g``, ``done[j]``.  ``y = done_n ? R : R + disc_n * max Q(next_state[boot_slot])``.
+    n = 1 is ``(s, action[s], reward[s], gamma, done[s])``.  ``follow[s]`` is the number of rows behind ``s`` in its
+    message (negative: 0), so a walk ends with its message.  A start slot outside [0, capacity) reads nothing:
+    ``(s, 0, 0.0, gamma, 1)``."""
+    n, cap, gamma = int(n), int(capacity), float(gamma)
+    if not 1 <= n <= 256:
+        raise ValueError("nstep_targets: n = {} outside [1, 256]".format(n))
+    out = ([], [], [], [], [])
+    for s in (int(x) for x in np.asarray(slots).reshape(-1)):
+        if not 0 <= s < cap:
+            row = (s, 0, 0.0, gamma, 1)
+        else:
+            R, g, j, k = float(reward[s]), gamma, s, 0
+            while k < n - 1 and k < int(follow[s]) and not done[j]:
+                k += 1
+                j = (s + k) % cap
+                prod = g * float(reward[j])
+                R = R + prod
+                g = g * gamma
+            row = (j, int(action[s]), R, g, int(done[j]))
+        for col, x in zip(out, row):
+            col.append(x)
+    return tuple(np.asarray(col, dt) for col, dt in zip(out, (np.int32, np.int32, np.float64, np.float64, np.uint8)))
 
 
 class DeviceReplay(object):
     """``ReplayBuffer`` (a ``deque(maxlen=capacity)`` of transitions) as five rings on ``device``: ``cur_state`` /
     ``next_state`` [capacity, ...] in the form the first layer reads (``to_rows``: ``HipActorCritic.to_device_obs``),
     ``action`` int32, ``reward`` float64, ``done`` uint8 [capacity].  Logical index i (0 = oldest) lives in slot
-    ``(head + i) % capacity``.  The rings are allocated at the first ``add``."""
+    ``(head + i) % capacity``.  The rings are allocated at the first ``add``.  ``n_step`` > 1 adds a sixth ring, ``follow``
+    int32 [capacity]: the number of rows that come after the slot in the message that wrote it."""
 
-    def __init__(self, capacity, device="cpu", to_rows=None):
+    def __init__(self, capacity, device="cpu", to_rows=None, n_step=1):
         if int(capacity) < 1:
             raise ValueError("DeviceReplay: capacity must be positive, got {}".format(capacity))
         self.capacity, self.device = int(capacity), torch.device(device)
+        self.n_step = int(n_step)
+        self.follow = None
+        self._label_bytes = 4 + 8 + 1 + (4 if self.n_step > 1 else 0)
         self._to_rows = to_rows
         self.head = self._size = 0
         self.cur_state = self.next_state = self.action = self.reward = self.done = None
@@ -64,7 +108,7 @@ class DeviceReplay(object):
     def _allocate(self, state_rows):
         row_shape, dtype = tuple(state_rows.shape[1:]), state_rows.dtype
         row_bytes = int(np.prod(row_shape, dtype=np.int64)) * state_rows.element_size()
-        need = self.capacity * (2 * row_bytes + 4 + 8 + 1)
+        need = self.capacity * (2 * row_bytes + self._label_bytes)
         if self.device.type == "cuda":
             free, _ = torch.cuda.mem_get_info(self.device)
             if need > free:
@@ -74,6 +118,8 @@ class DeviceReplay(object):
         new = lambda shape, dt: torch.empty((self.capacity,) + shape, dtype=dt, device=self.device)
         self.cur_state, self.next_state = new(row_shape, dtype), new(row_shape, dtype)
         self.action, self.reward, self.done = new((), torch.int32), new((), torch.float64), new((), torch.uint8)
+        if self.n_step > 1:
+            self.follow = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
         self.bytes = need
 
     def add(self, cur_state, next_state, action, reward, done):
@@ -92,7 +138,11 @@ class DeviceReplay(object):
         m, cap = n - skip, self.capacity
         w = (self.head + self._size + skip) % cap
         first = min(m, cap - w)
-        for ring, rows in zip((self.cur_state, self.next_state, self.action, self.reward, self.done), cols):
+        rings = [self.cur_state, self.next_state, self.action, self.reward, self.done]
+        if self.follow is not None:                     # m - 1, m - 2, ... 0 over the rows kept
+            rings.append(self.follow)
+            cols.append(torch.arange(m - 1, -1, -1, dtype=torch.int32).to(self.device))
+        for ring, rows in zip(rings, cols):
             ring[w:w + first] = rows[:first]
             if m > first:
                 ring[:m - first] = rows[first:]
@@ -117,8 +167,8 @@ class PrioritizedDeviceReplay(DeviceReplay):
     slot a message writes takes the priority ``max_prio ** alpha`` (``xt_per_add``, one call per contiguous span).  The
     trees are allocated with the rings; sampling and the priority update belong to the train (``xt_net_dqn_step_per``)."""
 
-    def __init__(self, capacity, device, to_rows=None, alpha=0.6, eps=1e-6):
-        super().__init__(capacity, device, to_rows)
+    def __init__(self, capacity, device, to_rows=None, alpha=0.6, eps=1e-6, n_step=1):
+        super().__init__(capacity, device, to_rows, n_step)
         if not float(alpha) >= 0.0 or not float(eps) > 0.0:
             raise ValueError("PrioritizedDeviceReplay: alpha = {} must be >= 0 and eps = {} > 0".format(alpha, eps))
         self.alpha, self.eps = float(alpha), float(eps)
@@ -133,7 +183,7 @@ class PrioritizedDeviceReplay(DeviceReplay):
         tree_bytes = 2 * 2 * self.cap2 * 8
         free, _ = torch.cuda.mem_get_info(self.device)
         row_bytes = int(np.prod(tuple(state_rows.shape[1:]), dtype=np.int64)) * state_rows.element_size()
-        need = self.capacity * (2 * row_bytes + 4 + 8 + 1) + tree_bytes
+        need = self.capacity * (2 * row_bytes + self._label_bytes) + tree_bytes
         if need > free:
             raise RuntimeError("PrioritizedDeviceReplay: the rings of {} transitions and the two priority trees need {} bytes "
                                "of device memory ({} bytes per state row, {} bytes of trees), {} bytes are free -- lower "
@@ -172,6 +222,10 @@ class DQN(Algorithm):
         net = getattr(self.actor, "net", None)
         self.device_step = hasattr(self.actor, "train_replay") and not getattr(net, "inference_only", True)
         self.prioritized = bool(alg_config.get("prioritized_replay", False))
+        n_step = alg_config.get("n_step", 1)
+        if isinstance(n_step, bool) or not isinstance(n_step, (int, np.integer)) or not 1 <= n_step <= 256:
+            raise ValueError("DQN: n_step = {!r} must be an integer in [1, 256]".format(n_step))
+        self.n_step = int(n_step)
         if self.prioritized:
             if not (self.device_step and hasattr(self.actor, "train_replay_per")):
                 raise NotImplementedError(
@@ -188,11 +242,11 @@ class DQN(Algorithm):
                 raise ValueError("DQN: prioritized_replay_beta_iters = {} must be positive or None".format(self.per_beta_iters))
             self.buff = PrioritizedDeviceReplay(BUFFER_SIZE, net.device, net.to_device_obs,
                                                 alg_config.get("prioritized_replay_alpha", 0.6),
-                                                alg_config.get("prioritized_replay_eps", 1e-6))
+                                                alg_config.get("prioritized_replay_eps", 1e-6), self.n_step)
         elif self.device_step:
-            self.buff = DeviceReplay(BUFFER_SIZE, net.device, net.to_device_obs)
+            self.buff = DeviceReplay(BUFFER_SIZE, net.device, net.to_device_obs, self.n_step)
         else:
-            self.buff = DeviceReplay(BUFFER_SIZE)
+            self.buff = DeviceReplay(BUFFER_SIZE, n_step=self.n_step)
 
     def prepare_data(self, train_data, **kwargs):
         self.buff.add(train_data["cur_state"], train_data["next_state"], train_data["action"], train_data["reward"],
@@ -237,13 +291,20 @@ class DQN(Algorithm):
         return self._train_host(slots)
 
     def _train_host(self, slots):
-        at = lambda ring: ring[torch.as_tensor(slots, dtype=torch.int64)].cpu().numpy()
-        states, new_states = at(self.buff.cur_state), at(self.buff.next_state)
+        at = lambda ring, idx=slots: ring[torch.as_tensor(idx, dtype=torch.int64)].cpu().numpy()
+        if self.n_step > 1:                             # the labels of the walk; the next states of the boot slots
+            host = lambda ring: ring.cpu().numpy()
+            boot, action, reward, gamma, done = nstep_targets(
+                slots, host(self.buff.follow), host(self.buff.action), host(self.buff.reward), host(self.buff.done), GAMMA,
+                self.n_step, self.buff.capacity)
+        else:
+            boot, action, reward, gamma, done = slots, at(self.buff.action), at(self.buff.reward), GAMMA, at(self.buff.done)
+        states, new_states = at(self.buff.cur_state), at(self.buff.next_state, boot)
         y_t = self.actor.predict(states)
         target_q = self.target_actor.predict(new_states)
         pick = np.argmax(self.actor.predict(new_states) if self.double_dqn else target_q, 1)
         rows = np.arange(len(slots))
-        y_t[rows, at(self.buff.action)] = td_targets(at(self.buff.reward), at(self.buff.done), target_q[rows, pick], GAMMA)
+        y_t[rows, action] = td_targets(reward, done, target_q[rows, pick], gamma)
         loss = self.actor.train(states, y_t)
         self.train_count += 1
         if self.train_count % TARGET_UPDATE_FREQ == 0:

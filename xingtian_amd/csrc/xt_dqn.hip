@@ -21,6 +21,71 @@ __global__ __launch_bounds__(256) void replay_gather_kernel(const uint4* __restr
   dst[b * nvec + v] = x;
 }
 
+// replay_gather_kernel with the n-step walk of DESIGN.md section 7 in front: the workgroup's start slot s = slots[b] is walked
+// over the rows that follow it in its message -- R = reward[s]; g = gamma; while k < n - 1, k < follow[s] and not
+// done[s + k]: ++k, R = R + g * reward[s + k] (product rounded, then sum rounded), g = g * gamma -- and the row copied is
+// ring[(s + k) % capacity].  The at most n <= 256 reward / done entries the walk can touch are loaded by one thread each
+// (one memory round trip whatever n is), thread 0 walks them in LDS and hands the boot slot to the others through LDS.
+// Every workgroup of a row repeats the walk (7 for an 84x84x4 frame); those with blockIdx.x == 0 store the labels
+// boot_slots / action_n / reward_n / disc_n / done_n [B].  All indices are taken modulo capacity.  A start slot outside
+// [0, capacity) reads nothing: zero row, labels (slot, 0, 0, gamma, 1).
+__global__ __launch_bounds__(256) void replay_gather_nstep_kernel(
+    const uint4* __restrict__ ring, long long nvec, long long capacity, const int32_t* __restrict__ slots,
+    const int32_t* __restrict__ action, const double* __restrict__ reward, const uint8_t* __restrict__ done,
+    const int32_t* __restrict__ follow, int n, double gamma, uint4* __restrict__ dst, int32_t* __restrict__ boot_slots,
+    int32_t* __restrict__ action_n, double* __restrict__ reward_n, double* __restrict__ disc_n,
+    uint8_t* __restrict__ done_n) {
+  __shared__ double s_reward[256];
+  __shared__ uint8_t s_done[256];
+  __shared__ long long s_boot;
+  const int t = threadIdx.x;
+  const long long b = blockIdx.y;
+  const long long slot = slots[b];
+  const bool live = slot >= 0 && slot < capacity;
+  int steps = 0;                                    // rows behind the start row the walk may reach
+  if (live) {
+    const int f = follow[slot];
+    steps = f < n - 1 ? f : n - 1;
+    steps = steps < 0 ? 0 : steps;
+  }
+  if (live && t <= steps) {
+    long long j = slot + t;
+    if (j >= capacity) j %= capacity;
+    s_reward[t] = reward[j];
+    s_done[t] = done[j];
+  }
+  __syncthreads();
+  if (t == 0) {
+    long long j = slot;
+    double R = 0.0, g = gamma;
+    int32_t act = 0;
+    uint8_t dn = 1;
+    if (live) {
+      int k = 0;
+      R = s_reward[0];
+      while (k < steps && !s_done[k]) {
+        ++k;
+        R = R + g * s_reward[k];
+        g = g * gamma;
+      }
+      j = slot + k;
+      if (j >= capacity) j %= capacity;
+      dn = s_done[k];
+      act = action[slot];
+    }
+    s_boot = j;
+    if (blockIdx.x == 0) {
+      boot_slots[b] = (int32_t)j; action_n[b] = act; reward_n[b] = R; disc_n[b] = g; done_n[b] = dn;
+    }
+  }
+  __syncthreads();
+  const long long v = (long long)blockIdx.x * 256 + t;
+  if (v >= nvec) return;
+  uint4 x = make_uint4(0u, 0u, 0u, 0u);
+  if (live) x = ring[s_boot * nvec + v];
+  dst[b * nvec + v] = x;
+}
+
 // Q of one row from the two heads: the [A] head as it is, or s + (l_a - mean_a l) with the 1-wide head s (dueling)
 __device__ __forceinline__ float dqn_mean(const float* __restrict__ l, int A) {
   float s = 0.f;
@@ -42,7 +107,8 @@ __device__ __forceinline__ int dqn_argmax(const float* __restrict__ l, float s, 
 }
 
 // One thread per sample: bootstrap action, TD target, d loss / d heads.  terms[b] = (delta_b, maxq_b).  weights (may be
-// NULL): the importance weight w_b of prioritised replay, rounded once to float32, scales g_b.
+// NULL): the importance weight w_b of prioritised replay, rounded once to float32, scales g_b.  disc (may be NULL): the
+// per-sample discount gamma^m of an m-step target, in gamma's place.
 __global__ __launch_bounds__(256) void dqn_loss_kernel(const float* __restrict__ logits, const float* __restrict__ value,
                                                        const float* __restrict__ t_logits, const float* __restrict__ t_value,
                                                        const float* __restrict__ o_logits, const float* __restrict__ o_value,
@@ -52,7 +118,8 @@ __global__ __launch_bounds__(256) void dqn_loss_kernel(const float* __restrict__
                                                        float* __restrict__ dlogits, float* __restrict__ dvalue,
                                                        float2* __restrict__ terms, float* __restrict__ y_out,
                                                        int32_t* __restrict__ astar_out, float* __restrict__ maxq_out,
-                                                       const double* __restrict__ weights) {
+                                                       const double* __restrict__ weights,
+                                                       const double* __restrict__ disc) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
   const bool du = dueling != 0;
@@ -69,7 +136,8 @@ __global__ __launch_bounds__(256) void dqn_loss_kernel(const float* __restrict__
   }
   const float maxq = dqn_q(tl, ts, tmean, astar, du);
   const double r = reward[row];
-  const float y = done[row] ? (float)r : (float)(r + gamma * (double)maxq);
+  const double gm = disc ? disc[b] : gamma;
+  const float y = done[row] ? (float)r : (float)(r + gm * (double)maxq);
   int act = action[row];
   act = act < 0 ? 0 : (act >= A ? A - 1 : act);    // (an action outside [0, A) never indexes outside the row)
   const float* l = logits + (size_t)b * A;
@@ -136,11 +204,35 @@ int xt_replay_gather(const void* ring, int64_t row_bytes, int64_t capacity, cons
   return 0;
 }
 
-int xt_dqn_loss_w(const float* logits, const float* value, const float* t_logits, const float* t_value,
+int xt_replay_gather_nstep(const void* next_ring, int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B,
+                           const int32_t* action, const double* reward, const uint8_t* done, const int32_t* follow,
+                           int32_t n, double gamma, void* dst, int32_t* boot_slots, int32_t* action_n, double* reward_n,
+                           double* disc_n, uint8_t* done_n, void* stream) {
+  XT_REQUIRE(next_ring && slots && dst && action && reward && done && follow, "xt_replay_gather_nstep: null argument");
+  XT_REQUIRE(boot_slots && action_n && reward_n && disc_n && done_n, "xt_replay_gather_nstep: null label output");
+  XT_REQUIRE(n >= 1 && n <= 256, "xt_replay_gather_nstep: n = %d outside [1, 256]", n);
+  XT_REQUIRE(row_bytes > 0 && row_bytes % 16 == 0,
+             "xt_replay_gather_nstep: row_bytes = %lld is not a positive multiple of 16 (rows are stored as the first layer "
+             "reads them: channel-padded images / feature-padded vectors)", (long long)row_bytes);
+  XT_REQUIRE(capacity > 0 && B > 0 && B <= 65535, "xt_replay_gather_nstep: bad sizes (capacity=%lld B=%d)",
+             (long long)capacity, B);
+  XT_REQUIRE((((uintptr_t)next_ring | (uintptr_t)dst) & 15) == 0,
+             "xt_replay_gather_nstep: ring and dst must be 16-byte aligned");
+  const long long nvec = row_bytes / 16;
+  XT_REQUIRE((nvec + 255) / 256 < (1ll << 31), "xt_replay_gather_nstep: row_bytes = %lld is too large", (long long)row_bytes);
+  hipLaunchKernelGGL(xt::replay_gather_nstep_kernel, dim3((unsigned)((nvec + 255) / 256), (unsigned)B), dim3(256), 0,
+                     xt::as_stream(stream), static_cast<const uint4*>(next_ring), nvec, (long long)capacity, slots, action,
+                     reward, done, follow, n, gamma, static_cast<uint4*>(dst), boot_slots, action_n, reward_n, disc_n,
+                     done_n);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+
+int xt_dqn_loss_n(const float* logits, const float* value, const float* t_logits, const float* t_value,
                   const float* o_logits, const float* o_value, int32_t B, int32_t A, int32_t dueling, const int32_t* slots,
                   const int32_t* action, const double* reward, const uint8_t* done, double gamma, float* dlogits,
                   float* dvalue, float* out, float* y, int32_t* astar, float* maxq, float* acc, const double* weights,
-                  void* stream) {
+                  const double* disc, void* stream) {
   XT_REQUIRE(logits && t_logits && action && reward && done && dlogits && dvalue && out, "xt_dqn_loss: null argument");
   XT_REQUIRE(!dueling || (value && t_value && (!o_logits || o_value)), "xt_dqn_loss: dueling needs the 1-wide heads");
   XT_REQUIRE(B > 0 && A > 0 && A <= 64, "xt_dqn_loss: bad sizes (B=%d A=%d; A <= 64)", B, A);
@@ -148,11 +240,21 @@ int xt_dqn_loss_w(const float* logits, const float* value, const float* t_logits
   hipStream_t st = xt::as_stream(stream);
   float2* terms = reinterpret_cast<float2*>(out + 4);       // out: >= 4 + 2*B floats
   hipLaunchKernelGGL(xt::dqn_loss_kernel, dim3((B + 255) / 256), dim3(256), 0, st, logits, value, t_logits, t_value, o_logits,
-                     o_value, B, A, dueling, slots, action, reward, done, gamma, dlogits, dvalue, terms, y, astar, maxq, weights);
+                     o_value, B, A, dueling, slots, action, reward, done, gamma, dlogits, dvalue, terms, y, astar, maxq, weights,
+                     disc);
   XT_LAUNCH_CHECK();
   hipLaunchKernelGGL(xt::dqn_loss_reduce_kernel, dim3(1), dim3(256), 0, st, terms, B, A, out, acc, weights);
   XT_LAUNCH_CHECK();
   return 0;
+}
+
+int xt_dqn_loss_w(const float* logits, const float* value, const float* t_logits, const float* t_value,
+                  const float* o_logits, const float* o_value, int32_t B, int32_t A, int32_t dueling, const int32_t* slots,
+                  const int32_t* action, const double* reward, const uint8_t* done, double gamma, float* dlogits,
+                  float* dvalue, float* out, float* y, int32_t* astar, float* maxq, float* acc, const double* weights,
+                  void* stream) {
+  return xt_dqn_loss_n(logits, value, t_logits, t_value, o_logits, o_value, B, A, dueling, slots, action, reward, done, gamma,
+                       dlogits, dvalue, out, y, astar, maxq, acc, weights, nullptr, stream);
 }
 
 int xt_dqn_loss(const float* logits, const float* value, const float* t_logits, const float* t_value,

@@ -1793,14 +1793,17 @@ int xt_net_graph_cache_info(const xt_net* n, int32_t* out, int32_t cap) {
 
 namespace xt {
 
-// The chain of one DQN.train up to the gradient, shared by xt_net_dqn_step and xt_net_dqn_step_per (`who` names the
-// entry in refusals).  per (may be NULL): prioritised replay -- once every refusal has passed, xt_per_sample fills
+// The chain of one DQN.train up to the gradient, shared by xt_net_dqn_step, xt_net_dqn_step_per and xt_net_dqn_step_n
+// (`who` names the entry in refusals).  per (may be NULL): prioritised replay -- once every refusal has passed, xt_per_sample fills
 // per->slots / per->weights from `size` stored transitions, the chain runs on them with the weighted head, and
-// xt_per_update follows the loss; `slots` is then ignored.
-static int dqn_chain(const char* who, xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const void* cur_ring,
-                     const void* next_ring, int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B,
-                     const int32_t* action, const double* reward, const uint8_t* done, const xt_per_cfg* per, int64_t size,
-                     float* loss_out, float* loss_acc, void* stream) {
+// xt_per_update follows the loss; `slots` is then ignored.  ns (may be NULL): n-step returns -- the first gather walks each
+// start slot to its boot slot and leaves the per-sample labels in ns' scratch (xt_replay_gather_nstep), both next-state
+// forwards run on the boot rows, and the head reads those dense labels with the per-sample discount; the state rows and the
+// new priorities stay those of the start slots.  The launches are the same in number either way.
+static int dqn_chain(const char* who, xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_nstep_cfg* ns,
+                     const void* cur_ring, const void* next_ring, int64_t row_bytes, int64_t capacity,
+                     const int32_t* slots, int32_t B, const int32_t* action, const double* reward, const uint8_t* done,
+                     const xt_per_cfg* per, int64_t size, float* loss_out, float* loss_acc, void* stream) {
   XT_REQUIRE(n && tn && c && cur_ring && next_ring && (slots || per) && action && reward && done, "%s: null argument", who);
   XT_REQUIRE(c->cur_rows && c->next_rows && c->q_scratch, "%s: null scratch in cfg", who);
   XT_REQUIRE(n != tn && n->params && n->ws && tn->params && tn->ws && tn->params != n->params && tn->ws != n->ws,
@@ -1818,6 +1821,12 @@ static int dqn_chain(const char* who, xt_net* n, xt_net* tn, const xt_dqn_cfg* c
   const int64_t in_row = (int64_t)n->in_h * n->in_w * n->in_c * (n->xf.is_u8 ? 1 : 4);
   XT_REQUIRE(row_bytes == in_row, "%s: row_bytes = %lld, the first layer reads rows of %lld bytes", who,
              (long long)row_bytes, (long long)in_row);
+  if (ns) {
+    XT_REQUIRE(ns->n >= 1 && ns->n <= 256, "%s: n = %d outside [1, 256]", who, ns->n);
+    XT_REQUIRE(ns->follow, "%s: null follow ring in nstep cfg", who);
+    XT_REQUIRE(ns->boot_slots && ns->action_n && ns->reward_n && ns->disc_n && ns->done_n,
+               "%s: null scratch in nstep cfg", who);
+  }
   const double* weights = nullptr;
   if (per) {
     XT_REQUIRE(per->sum && per->min && per->max_prio && per->u && per->slots && per->weights, "%s: null pointer in per cfg", who);
@@ -1834,7 +1843,14 @@ static int dqn_chain(const char* who, xt_net* n, xt_net* tn, const xt_dqn_cfg* c
   float* o_logits = c->double_dqn ? t_value + B : nullptr;
   float* o_value = c->double_dqn ? o_logits + (int64_t)B * A : nullptr;
   hipStream_t st = xt::as_stream(stream);
-  if (int rc = xt_replay_gather(next_ring, row_bytes, capacity, slots, B, c->next_rows, stream)) return rc;
+  if (ns) {
+    if (int rc = xt_replay_gather_nstep(next_ring, row_bytes, capacity, slots, B, action, reward, done, ns->follow, ns->n,
+                                        c->gamma, c->next_rows, ns->boot_slots, ns->action_n, ns->reward_n, ns->disc_n,
+                                        ns->done_n, stream))
+      return rc;
+  } else if (int rc = xt_replay_gather(next_ring, row_bytes, capacity, slots, B, c->next_rows, stream)) {
+    return rc;
+  }
   if (int rc = xt_net_forward(tn, c->next_rows, nullptr, B, t_logits, t_value, stream)) return rc;
   if (c->double_dqn)
     if (int rc = xt_net_forward(n, c->next_rows, nullptr, B, o_logits, o_value, stream)) return rc;
@@ -1842,10 +1858,12 @@ static int dqn_chain(const char* who, xt_net* n, xt_net* tn, const xt_dqn_cfg* c
   if (int rc = xt::net_forward(n, c->cur_rows, nullptr, B, true, st)) return rc;
   float* lo = n->ws + n->off_loss;
   float* rows = n->ws + n->off_terms;                       // per-row y | a* | maxq, maxB each
-  if (int rc = xt_dqn_loss_w(n->ws + n->off_logits, n->ws + n->off_value, t_logits, t_value, o_logits, o_value, B, A,
-                             c->dueling, slots, action, reward, done, c->gamma, n->ws + n->off_dlogits,
-                             n->ws + n->off_dvalue, lo, rows, reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB,
-                             loss_acc, weights, stream))
+  // (n-step: the labels are dense in the scratch the gather filled, in sample order)
+  if (int rc = xt_dqn_loss_n(n->ws + n->off_logits, n->ws + n->off_value, t_logits, t_value, o_logits, o_value, B, A,
+                             c->dueling, ns ? nullptr : slots, ns ? ns->action_n : action, ns ? ns->reward_n : reward,
+                             ns ? ns->done_n : done, c->gamma, n->ws + n->off_dlogits, n->ws + n->off_dvalue, lo, rows,
+                             reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB, loss_acc, weights,
+                             ns ? ns->disc_n : nullptr, stream))
     return rc;
   if (loss_out) XT_CHECK_HIP(hipMemcpyAsync(loss_out, lo, 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (int rc = xt::heads_dfeat(n, B, st)) return rc;
@@ -1865,8 +1883,8 @@ extern "C" {
 int xt_net_dqn_step(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const void* cur_ring, const void* next_ring,
                     int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, const int32_t* action,
                     const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream) {
-  return xt::dqn_chain("xt_net_dqn_step", n, tn, c, cur_ring, next_ring, row_bytes, capacity, slots, B, action, reward, done,
-                       nullptr, 0, loss_out, loss_acc, stream);
+  return xt::dqn_chain("xt_net_dqn_step", n, tn, c, nullptr, cur_ring, next_ring, row_bytes, capacity, slots, B, action,
+                       reward, done, nullptr, 0, loss_out, loss_acc, stream);
 }
 
 int xt_net_dqn_step_per(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_per_cfg* p, const void* cur_ring,
@@ -1874,8 +1892,17 @@ int xt_net_dqn_step_per(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_per
                         const int32_t* action, const double* reward, const uint8_t* done, float* loss_out, float* loss_acc,
                         void* stream) {
   XT_REQUIRE(p, "xt_net_dqn_step_per: null per cfg");
-  return xt::dqn_chain("xt_net_dqn_step_per", n, tn, c, cur_ring, next_ring, row_bytes, capacity, nullptr, B, action, reward,
-                       done, p, size, loss_out, loss_acc, stream);
+  return xt::dqn_chain("xt_net_dqn_step_per", n, tn, c, nullptr, cur_ring, next_ring, row_bytes, capacity, nullptr, B, action,
+                       reward, done, p, size, loss_out, loss_acc, stream);
+}
+
+int xt_net_dqn_step_n(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_nstep_cfg* ns, const xt_per_cfg* p,
+                      const void* cur_ring, const void* next_ring, int64_t row_bytes, int64_t capacity, int64_t size,
+                      const int32_t* slots, int32_t B, const int32_t* action, const double* reward, const uint8_t* done,
+                      float* loss_out, float* loss_acc, void* stream) {
+  XT_REQUIRE(ns, "xt_net_dqn_step_n: null nstep cfg");
+  return xt::dqn_chain("xt_net_dqn_step_n", n, tn, c, ns, cur_ring, next_ring, row_bytes, capacity, p ? nullptr : slots, B,
+                       action, reward, done, p, size, loss_out, loss_acc, stream);
 }
 
 int xt_net_set_grad_exchange_ex(xt_net* net, xt_grad_exchange_fn fn, void* user, int32_t flags) {

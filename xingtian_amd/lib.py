@@ -98,6 +98,12 @@ class PerCfg(Structure):
                 ("eps", c_double)]
 
 
+class NstepCfg(Structure):
+    """xt_nstep_cfg of include/xt_mi355x.h"""
+    _fields_ = [("n", c_int32), ("follow", c_void_p), ("boot_slots", c_void_p), ("action_n", c_void_p),
+                ("reward_n", c_void_p), ("disc_n", c_void_p), ("done_n", c_void_p)]
+
+
 class ActCfg(Structure):
     """xt_act_cfg of include/xt_mi355x.h: the generator's key and counter words of one ``xt_net_act`` call"""
     _fields_ = [("seed", ctypes.c_uint64), ("call", ctypes.c_uint64), ("row0", c_int64), ("want_noise", c_int32)]
@@ -261,6 +267,12 @@ SIGNATURES = {
                                 _P, _P, _P, _P, _P]),
     "xt_net_dqn_step_per": (c_int32, [_P, _P, POINTER(DqnCfg), POINTER(PerCfg), _P, _P, c_int64, c_int64, c_int64, c_int32,
                                       _P, _P, _P, _P, _P, _P]),
+    "xt_replay_gather_nstep": (c_int32, [_P, c_int64, c_int64, _P, c_int32, _P, _P, _P, _P, c_int32, c_double, _P, _P, _P, _P,
+                                         _P, _P, _P]),
+    "xt_dqn_loss_n": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_double, _P, _P, _P, _P,
+                                _P, _P, _P, _P, _P, _P]),
+    "xt_net_dqn_step_n": (c_int32, [_P, _P, POINTER(DqnCfg), POINTER(NstepCfg), POINTER(PerCfg), _P, _P, c_int64, c_int64,
+                                    c_int64, _P, c_int32, _P, _P, _P, _P, _P, _P]),
     "xt_grads_finish_plan_ex": (c_int32, [POINTER(GradEntry), c_int32, ctypes.c_uint32, ctypes.c_uint32, c_int32, c_int32,
                                           POINTER(c_int32), POINTER(c_int32)]),
     "xt_grads_finish_ex": (c_int32, [POINTER(GradEntry), c_int32, ctypes.c_uint32, ctypes.c_uint32, POINTER(FinishArgs), _P,

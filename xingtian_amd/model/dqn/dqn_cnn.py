@@ -79,10 +79,15 @@ class DqnModel(XTModel):
     def train_replay(self, target, replay, slots, gamma, double_dqn):
         """One update on the minibatch ``slots`` (int32 device tensor) of the device rings ``replay``
         (``algorithm.dqn.DeviceReplay``): ``xt_net_dqn_step`` with ``target``'s network as the target net, then tf.keras
-        Adam.  Nothing synchronises.  -> the device tensor [loss, mean |TD error|, mean bootstrap Q]."""
+        Adam.  Nothing synchronises.  -> the device tensor [loss, mean |TD error|, mean bootstrap Q].  A replay with
+        ``n_step`` > 1 trains on n-step targets (``xt_net_dqn_step_n``)."""
         self._require_learner()
-        out = self.net.dqn_step(target.net, replay.cur_state, replay.next_state, slots, replay.action, replay.reward,
-                                replay.done, gamma, self.dueling, double_dqn)
+        if getattr(replay, "n_step", 1) > 1:
+            out = self.net.dqn_step_n(target.net, replay.cur_state, replay.next_state, slots, replay.action, replay.reward,
+                                      replay.done, replay.follow, replay.n_step, gamma, self.dueling, double_dqn)
+        else:
+            out = self.net.dqn_step(target.net, replay.cur_state, replay.next_state, slots, replay.action, replay.reward,
+                                    replay.done, gamma, self.dueling, double_dqn)
         self.net.adam_keras(self.learning_rate, self.iterations, clipnorm=self.CLIPNORM)
         self.iterations += 1
         return out
@@ -92,9 +97,15 @@ class DqnModel(XTModel):
         ``u`` (float64 device tensor [B]) and importance exponent ``beta``, and the replay's trees take the new TD errors
         (``xt_net_dqn_step_per``), then tf.keras Adam.  Nothing synchronises.  -> the device tensor of ``train_replay``."""
         self._require_learner()
-        out = self.net.dqn_step_per(target.net, replay.cur_state, replay.next_state, replay.size(), u, replay.action,
-                                    replay.reward, replay.done, gamma, self.dueling, double_dqn, replay.sum_tree,
-                                    replay.min_tree, replay.max_prio, replay.alpha, beta, replay.eps)
+        if getattr(replay, "n_step", 1) > 1:
+            per = dict(size=replay.size(), u=u, sum_tree=replay.sum_tree, min_tree=replay.min_tree,
+                       max_prio=replay.max_prio, alpha=replay.alpha, beta=beta, eps=replay.eps)
+            out = self.net.dqn_step_n(target.net, replay.cur_state, replay.next_state, None, replay.action, replay.reward,
+                                      replay.done, replay.follow, replay.n_step, gamma, self.dueling, double_dqn, per=per)
+        else:
+            out = self.net.dqn_step_per(target.net, replay.cur_state, replay.next_state, replay.size(), u, replay.action,
+                                        replay.reward, replay.done, gamma, self.dueling, double_dqn, replay.sum_tree,
+                                        replay.min_tree, replay.max_prio, replay.alpha, beta, replay.eps)
         self.net.adam_keras(self.learning_rate, self.iterations, clipnorm=self.CLIPNORM)
         self.iterations += 1
         return out

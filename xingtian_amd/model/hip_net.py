@@ -900,25 +900,63 @@ class HipActorCritic(object):
         receives (TD error, bootstrap Q) per sample.  Returns the device tensor of ``dqn_step``."""
         cap, row_bytes, cfg = self._dqn_cfg("dqn_step_per", cur_ring, next_ring, {"u": u}, action, reward, done, gamma,
                                             dueling, double_dqn)
-        cap2 = int(sum_tree.numel()) // 2
-        for name, x, n in (("sum_tree", sum_tree, 2 * cap2), ("min_tree", min_tree, 2 * cap2), ("max_prio", max_prio, 1)):
-            if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float64 and x.numel() == n):
-                raise ValueError("dqn_step_per: {} must be a contiguous float64 device tensor of {} elements".format(name, n))
-        b = int(u.numel())
-        if terms_out is not None and not (terms_out.is_cuda and terms_out.is_contiguous() and
-                                          terms_out.dtype == torch.float32 and terms_out.numel() >= 2 * b):
-            raise ValueError("dqn_step_per: terms_out must be a contiguous float32 device tensor of 2 * B elements")
-        if not hasattr(self, "per_slots"):
-            self.per_slots = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
-            self.per_weights = torch.zeros(self.max_batch, dtype=torch.float64, device=self.device)
-        per = L.PerCfg(sum_tree.data_ptr(), min_tree.data_ptr(), cap2, max_prio.data_ptr(), u.data_ptr(),
-                       self.per_slots.data_ptr(), self.per_weights.data_ptr(),
-                       terms_out.data_ptr() if terms_out is not None else None, float(alpha), float(beta), float(eps))
+        b, per = self._per_cfg("dqn_step_per", u, sum_tree, min_tree, max_prio, alpha, beta, eps, terms_out)
         L.check(self.lib.xt_net_dqn_step_per(self.handle, target.handle, ctypes.byref(cfg), ctypes.byref(per),
                                              L.ptr(cur_ring), L.ptr(next_ring), row_bytes, cap, int(size), b,
                                              L.ptr(action), L.ptr(reward), L.ptr(done), L.ptr(self.loss_out),
                                              L.ptr(loss_acc) if loss_acc is not None else None, L.stream_ptr()),
                 "xt_net_dqn_step_per")
+        return self.loss_out
+
+    def _per_cfg(self, who, u, sum_tree, min_tree, max_prio, alpha, beta, eps, terms_out=None):
+        """-> (B, ``PerCfg``) after the tensor checks of the prioritised steps; allocates ``per_slots`` / ``per_weights``"""
+        cap2 = int(sum_tree.numel()) // 2
+        for name, x, n in (("sum_tree", sum_tree, 2 * cap2), ("min_tree", min_tree, 2 * cap2), ("max_prio", max_prio, 1)):
+            if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float64 and x.numel() == n):
+                raise ValueError("{}: {} must be a contiguous float64 device tensor of {} elements".format(who, name, n))
+        b = int(u.numel())
+        if terms_out is not None and not (terms_out.is_cuda and terms_out.is_contiguous() and
+                                          terms_out.dtype == torch.float32 and terms_out.numel() >= 2 * b):
+            raise ValueError("{}: terms_out must be a contiguous float32 device tensor of 2 * B elements".format(who))
+        if not hasattr(self, "per_slots"):
+            self.per_slots = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
+            self.per_weights = torch.zeros(self.max_batch, dtype=torch.float64, device=self.device)
+        return b, L.PerCfg(sum_tree.data_ptr(), min_tree.data_ptr(), cap2, max_prio.data_ptr(), u.data_ptr(),
+                           self.per_slots.data_ptr(), self.per_weights.data_ptr(),
+                           terms_out.data_ptr() if terms_out is not None else None, float(alpha), float(beta), float(eps))
+
+    def dqn_step_n(self, target, cur_ring, next_ring, slots, action, reward, done, follow, n, gamma, dueling, double_dqn,
+                   per=None, loss_acc=None):
+        """``dqn_step`` / ``dqn_step_per`` on n-step targets (C ABI ``xt_net_dqn_step_n``, never synchronises): the
+        next-state gather walks every start slot over the up to ``n - 1`` rows that follow it in its message (``follow``
+        int32 [capacity]: how many there are), both next-state forwards run on the rows it arrives at, and the head reads
+        the discounted reward sum, ``gamma ** m`` and the last row's ``done``.  ``per`` None: uniform, ``slots`` int32
+        (device); else the keywords of ``dqn_step_per`` (size, u, sum_tree, min_tree, max_prio, alpha, beta, eps and
+        optionally terms_out) and ``slots`` is ignored: the new priorities go to the start slots.  The labels of the walk
+        stay in ``self.nstep_boot`` / ``nstep_action`` / ``nstep_reward`` / ``nstep_disc`` / ``nstep_done`` [max_batch].
+        Returns the device tensor of ``dqn_step``."""
+        batch = {"slots": slots} if per is None else {"u": per["u"]}
+        cap, row_bytes, cfg = self._dqn_cfg("dqn_step_n", cur_ring, next_ring, batch, action, reward, done, gamma, dueling,
+                                            double_dqn)
+        if not (follow.is_cuda and follow.is_contiguous() and follow.dtype == torch.int32 and follow.shape[0] == cap):
+            raise ValueError("dqn_step_n: follow must be a contiguous int32 device tensor ({} rows)".format(cap))
+        if per is None:
+            b, size, p_ref = int(slots.numel()), 0, None
+        else:
+            b, p = self._per_cfg("dqn_step_n", **{k: v for k, v in per.items() if k != "size"})
+            size, p_ref = int(per["size"]), ctypes.byref(p)
+        if not hasattr(self, "nstep_boot"):
+            new = lambda dt: torch.zeros(self.max_batch, dtype=dt, device=self.device)
+            self.nstep_boot, self.nstep_action = new(torch.int32), new(torch.int32)
+            self.nstep_reward, self.nstep_disc, self.nstep_done = new(torch.float64), new(torch.float64), new(torch.uint8)
+        ns = L.NstepCfg(int(n), follow.data_ptr(), self.nstep_boot.data_ptr(), self.nstep_action.data_ptr(),
+                        self.nstep_reward.data_ptr(), self.nstep_disc.data_ptr(), self.nstep_done.data_ptr())
+        L.check(self.lib.xt_net_dqn_step_n(self.handle, target.handle, ctypes.byref(cfg), ctypes.byref(ns), p_ref,
+                                           L.ptr(cur_ring), L.ptr(next_ring), row_bytes, cap, size,
+                                           L.ptr(slots) if per is None else None, b, L.ptr(action), L.ptr(reward),
+                                           L.ptr(done), L.ptr(self.loss_out),
+                                           L.ptr(loss_acc) if loss_acc is not None else None, L.stream_ptr()),
+                "xt_net_dqn_step_n")
         return self.loss_out
 
     def apply(self, lr, clip_norm, grad_scale=1.0):
