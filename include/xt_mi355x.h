@@ -1236,6 +1236,46 @@ int xt_net_dqn_step_n(xt_net* net, xt_net* target_net, const xt_dqn_cfg* cfg, co
                       int64_t capacity, int64_t size, const int32_t* slots, int32_t B, const int32_t* action,
                       const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream);
 
+/* ------------------------------------------------------------------ distributional (C51) Q head (appended under ABI 12)
+ * Bellemare et al. 2017: the Q head is A * N wide, column a * N + i is the logit of atom i of action a, and the TD target
+ * is a distribution projected onto the fixed support.  Definitions (host twins dist_support / dist_q /
+ * categorical_projection of xingtian_amd/algorithm/dqn/dqn.py):
+ *     delta = (v_max - v_min) / (N - 1), z_i = v_min + i * delta in float64; (float)z_i where float32 is used
+ *     dist_q(l) = (sum_i z_i e_i) / (sum_i e_i), e_i = expf(l_i - max l), float32
+ *     a* = first maximal index over a of dist_q of the picking logits (t_logits, or o_logits when given: double DQN)
+ *     p_j = softmax(t_logits[a*, :])_j in float32;  (R, g, dn) = (reward, disc ? disc[b] : gamma, done) of the sample
+ *     Tz_j = clamp(dn ? R : R + g * z_j, v_min, v_max);  b_j = (Tz_j - v_min) / delta              (float64)
+ *     m_i = (float) sum_{j ascending} (double)p_j * max(0, 1 - |b_j - i|)                 (float64, one rounding)
+ *     logq_i = (l_i - mx) - logf(sum_k expf(l_k - mx)) on the online logits l of the taken action (clamped into [0, A))
+ *     loss_b = -sum_i m_i logq_i;  L = sum_b w_b loss_b / B  (w_b = (float)weights[b], 1 without weights)
+ *     dlogits[b, act * N + i] = w_b (expf(logq_i) M_b - m_i) / B with M_b = sum_i m_i; every other entry 0; dvalue[b] = 0
+ * The projection is Algorithm 1 of the paper in gather form: equal to its l/u scatter whenever no b_j is an integer, and
+ * it keeps the mass the published pseudo-code drops when l == u.  No atomics: the result does not depend on thread order.
+ * logits / t_logits / o_logits [B, A * N]; labels through `slots` (int32 [B]) or dense (slots == NULL); out: 4 + 2 B floats,
+ * 8-byte aligned: out[0] = L, out[1] = sum_b loss_b / B, out[2] = sum_b dist_q_target(a*_b) / B and from out + 4 the
+ * terms (loss_b, dist_q_target(a*_b)), where xt_per_update reads its |x|.  astar / maxq [B] / m [B, N] / acc / weights /
+ * disc may be NULL.  Two launches.  Refused: atoms outside [2, 256], A outside [1, 64], v_min >= v_max or not finite. */
+int xt_dqn_loss_dist(const float* logits, const float* t_logits, const float* o_logits, int32_t B, int32_t A, int32_t atoms,
+                     double v_min, double v_max, const int32_t* slots, const int32_t* action, const double* reward,
+                     const uint8_t* done, double gamma, float* dlogits, float* dvalue, float* out, int32_t* astar,
+                     float* maxq, float* m, float* acc, const double* weights, const double* disc, void* stream);
+/* Marks a net (per net, opt-in) as carrying a distributional head of `atoms` atoms on [v_min, v_max]: its action_dim is
+ * actions * atoms.  atoms == 1 clears the mark.  Refused: atoms outside [1, 256], bounds as above, a width that is no
+ * multiple of atoms, a DiagGaussian net.  A marked net is refused by xt_net_dqn_step / _per / _n. */
+int xt_net_set_dist(xt_net* net, int32_t atoms, double v_min, double v_max);
+/* The two head kernels of a marked net (on by default, re-armed by every xt_net_set_dist): heads_fwd_wide_kernel (one
+ * thread per output column instead of one wave reduction per output) for every forward of the net, and in
+ * xt_net_dqn_step_dist d(features) summed over the taken action's atoms only (bit-identical to the full sum).  on == 0:
+ * the kernels of an unmarked net, for same-run comparisons.  Refused on an unmarked net. */
+int xt_net_set_dist_wide(xt_net* net, int32_t on);
+/* xt_net_dqn_step_n's chain (ns == NULL: one-step targets; per == NULL: uniform, `slots`) with xt_dqn_loss_dist as the
+ * head, same launches in number.  Both nets must carry equal marks; cfg->dueling must be 0; actions <= 64; cfg->q_scratch
+ * holds 2 * B * (actions * atoms + 1) floats.  With per, the new priority of a start slot is loss_b + eps. */
+int xt_net_dqn_step_dist(xt_net* net, xt_net* target_net, const xt_dqn_cfg* cfg, const xt_nstep_cfg* ns,
+                         const xt_per_cfg* per, const void* cur_ring, const void* next_ring, int64_t row_bytes,
+                         int64_t capacity, int64_t size, const int32_t* slots, int32_t B, const int32_t* action,
+                         const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream);
+
 /* ------------------------------------------------------------------ the step tail stand-alone (appended under ABI 12)
  * The gradient-reduction launch and the optimiser launches every xt_net_*_step ends in, on given buffers, for kernel
  * tests (tests/test_gpu_optim_branch.py).  Each entry fills the argument structs the step fills and calls the step's own

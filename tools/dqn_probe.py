@@ -1,6 +1,6 @@
 """Time of one ``DQN.train`` at breakout_dqn's shape, beside a Keras-IMPALA step of the same trunk.
 
-    python tools/dqn_probe.py [--windows 5] [--trains 200] [--capacity 4096] [--out profiles/dqn_step.md]
+    python tools/dqn_probe.py [--windows 5] [--trains 200] [--capacity 4096] [--atoms 51] [--out profiles/dqn_step.md]
 
 Four things are timed at DqnCnn 84x84x4, A = 4, B = 32, each as a host clock around ``--trains`` calls that ends in a
 device synchronise, after a warm-up, in ``--windows`` windows taken in turn (so that drift of the box hits all alike):
@@ -12,6 +12,10 @@ device synchronise, after a warm-up, in ``--windows`` windows taken in turn (so 
   front and the priority update behind; the draws of ``random.random()`` go up instead of the slots);
 * the uniform and the prioritised train with ``n_step: 3`` (``xt_net_dqn_step_n``: the same launches, the walk over the
   rows that follow each sampled row rides in the next-state gather), as ``DQN.train`` and enqueue only;
+* with ``--atoms N`` (0: none) the distributional train (``model_config.atoms``, ``xt_net_dqn_step_dist``: the Q head is
+  4 * N wide) with and without ``prioritized_replay``, ``double_dqn`` and ``n_step: 3``, as ``DQN.train`` and enqueue
+  only, once on the head kernels of a marked net (wide forward, taken-action d(features)) and once, "generic", on the
+  head kernels every other net runs (``set_dist_wide(False)``);
 * one ``prepare_data`` of a 20-row message without and with ``prioritized_replay`` (``xt_per_add`` per written span), each
   call followed by a device synchronise;
 * ``keras_impala_step`` + ``adam_keras`` on 32 rows of ``netspec.impala_cnn`` (the same trunk and heads, one network, no
@@ -35,10 +39,12 @@ if ROOT not in sys.path:
 B, A_DIM, DIM = 32, 4, 84
 
 
-def build_dqn(double, capacity, per=False, n_step=1):
+def build_dqn(double, capacity, per=False, n_step=1, atoms=1):
     from xingtian_amd.algorithm import alg_builder
     info = {"actor": {"model_name": "DqnCnn", "type": "learner", "state_dim": [DIM, DIM, 4], "action_dim": A_DIM,
                       "model_config": {"LR": 0.00015, "SEED": 0}}}
+    if atoms > 1:
+        info["actor"]["model_config"]["atoms"] = atoms
     cfg = {"instance_num": 1, "agent_num": 1, "prepare_times_per_train": 4, "BUFFER_SIZE": capacity, "BATCH_SIZE": B,
            "TARGET_UPDATE_FREQ": 1000, "double_dqn": double, "prioritized_replay": per}
     if n_step != 1:
@@ -59,6 +65,7 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--trains", type=int, default=200)
     ap.add_argument("--capacity", type=int, default=4096)
+    ap.add_argument("--atoms", type=int, default=0)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -126,6 +133,36 @@ def main():
              ("prepare_data, 20 rows, synchronised", ingest(algs[False])),
              ("prepare_data, 20 rows, PER, synchronised", ingest(pers[False])),
              ("keras_impala_step + adam_keras, 32 rows, enqueue only", impala_step)]
+    if args.atoms > 1:
+        # the distributional arms share ONE algorithm per (PER, n_step) -- double_dqn is an argument of the train and the
+        # kernel selection a switch of the two nets -- so four more rings, not sixteen
+        dist = {(per, n): build_dqn(False, args.capacity, per, n, args.atoms) for per in (False, True) for n in (1, 3)}
+        dist_slots = torch.tensor(dist[(False, 1)].buff.sample(B), dtype=torch.int32).cuda()
+
+        def dist_case(per, n, double, wide, read_back):
+            alg = dist[(per, n)]
+
+            def fn():
+                alg.double_dqn = double
+                for net in (alg.actor.net, alg.target_actor.net):
+                    net.set_dist_wide(wide)
+                if read_back:
+                    return alg.train()
+                if per:
+                    return alg.actor.train_replay_per(alg.target_actor, alg.buff, draws, alg.per_beta(), dqn_mod.GAMMA, double)
+                return alg.actor.train_replay(alg.target_actor, alg.buff, dist_slots, dqn_mod.GAMMA, double)
+            return fn
+        extra = []
+        for read_back in (True, False):
+            for wide in (True, False):
+                for per, n, double in ((False, 1, False), (True, 1, False), (False, 3, False), (True, 3, False),
+                                       (False, 1, True), (True, 1, True), (False, 3, True), (True, 3, True)):
+                    name = "{}, atoms {}{}{}{}{}{}".format(
+                        "DQN.train" if read_back else "dqn step + adam", args.atoms, ", PER" if per else "",
+                        ", n_step 3" if n == 3 else "", ", double_dqn" if double else "", "" if wide else ", generic head kernels",
+                        " (loss read back)" if read_back else ", enqueue only")
+                    extra.append((name, dist_case(per, n, double, wide, read_back)))
+        cases = cases[:12] + extra + cases[12:]
     for _, fn in cases:
         for _ in range(20):
             fn()

@@ -24,6 +24,12 @@ call (``xt_net_dqn_step_per``) samples, weights the head and writes the new prio
 a message holds consecutive steps of one agent and ``DeviceReplay.add`` writes it to contiguous slots, so the rows that
 follow a sampled row are next to it in the rings.  A sixth ring, ``follow``, says how many rows come after each slot in
 its message; ``nstep_targets`` is the definition, ``xt_net_dqn_step_n`` evaluates it inside the next-state gather.
+
+``model_config.atoms`` > 1 on the actor makes the pair distributional (C51): the train is ``xt_net_dqn_step_dist``, whose
+head projects the target distribution of the bootstrap action onto the support and takes the cross-entropy of the taken
+action's distribution (``dist_support`` / ``dist_q`` / ``categorical_projection`` are the host definitions).  It composes
+with ``double_dqn``, ``prioritized_replay`` (the new priority is the sample's loss + eps) and ``n_step``, and like
+prioritised replay it needs the device step.
 """
 import random
 
@@ -32,6 +38,7 @@ import torch
 
 from xingtian_amd.algorithm.algorithm import Algorithm
 from xingtian_amd.algorithm.dqn.default_config import BATCH_SIZE, BUFFER_SIZE, GAMMA, TARGET_UPDATE_FREQ
+from xingtian_amd.model.dqn.dqn_cnn import categorical_projection, dist_q, dist_support  # noqa: F401
 from xingtian_amd.register import Registers, import_config
 
 
@@ -221,6 +228,12 @@ class DQN(Algorithm):
         self.double_dqn = alg_config.get("double_dqn", False)
         net = getattr(self.actor, "net", None)
         self.device_step = hasattr(self.actor, "train_replay") and not getattr(net, "inference_only", True)
+        self.atoms = int(getattr(self.actor, "atoms", 1))
+        if self.atoms > 1 and not self.device_step:
+            raise NotImplementedError(
+                "DQN: a distributional actor (atoms = {}) needs a model with the device step (a learner DqnCnn / DqnMlp on "
+                "the GPU): the target distribution is projected on the device, where the target network's output is; {} "
+                "has none".format(self.atoms, type(self.actor).__name__))
         self.prioritized = bool(alg_config.get("prioritized_replay", False))
         n_step = alg_config.get("n_step", 1)
         if isinstance(n_step, bool) or not isinstance(n_step, (int, np.integer)) or not 1 <= n_step <= 256:

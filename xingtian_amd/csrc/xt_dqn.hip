@@ -2,6 +2,8 @@
 // (xt/algorithm/dqn/dqn.py:61-103 + `model.compile(loss='mse')` of xt/model/dqn/dqn_cnn.py, dqn_mlp.py).
 // Both kernels are bandwidth- and latency-trivial (a minibatch is 32 rows); what matters is 64-bit addressing into a
 // ring of several GB, 16-byte accesses and a fixed reduction order.
+#include <cmath>
+
 #include "xt_common.h"
 
 namespace xt {
@@ -183,9 +185,185 @@ __global__ __launch_bounds__(256) void dqn_loss_reduce_kernel(const float2* __re
   }
 }
 
+// ---------------------------------------------------------------- distributional (C51) head, DESIGN.md section 7
+__device__ __forceinline__ float dist_wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float dist_wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// the float32 atom z_i = (float)(v_min + i * delta), product and sum rounded separately in float64
+__device__ __forceinline__ double dist_atom(double v_min, double delta, int i) { return v_min + (double)i * delta; }
+
+// dist_q of one action's N logits by the whole wave (lanes stride the atoms; every lane returns the same bits):
+// mx = max l, e_i = expf(l_i - mx), Q = (sum z_i e_i) / (sum e_i).  *mx_out / *se_out: mx and sum e_i.
+__device__ __forceinline__ float dist_q_wave(const float* __restrict__ l, int N, double v_min, double delta, int lane,
+                                             float* mx_out, float* se_out) {
+  float mx = -INFINITY;
+  for (int i = lane; i < N; i += 64) mx = fmaxf(mx, l[i]);
+  mx = dist_wave_max(mx);
+  float se = 0.f, sz = 0.f;
+  for (int i = lane; i < N; i += 64) {
+    const float e = expf(l[i] - mx);
+    se += e;
+    sz += (float)dist_atom(v_min, delta, i) * e;
+  }
+  se = dist_wave_sum(se);
+  sz = dist_wave_sum(sz);
+  *mx_out = mx; *se_out = se;
+  return sz / se;
+}
+
+// One wavefront per sample (grid B, 64 threads), lanes stride the atoms (up to 4 per lane at N = 256).  In order:
+// dist_q of every action of the picking logits (o_logits, else t_logits) and a* = the first maximal one; p_j = softmax of
+// the target logits of a* and b_j = (clamp(dn ? R : R + g z_j) - v_min) / delta into LDS as float64; every lane forms its
+// m_i = (float) sum_j p_j max(0, 1 - |b_j - i|) over ascending j (a gather: no atomics, no dependence on thread order);
+// then the log-softmax of the taken action's online logits, loss_b = -sum_i m_i logq_i, the gradient row
+// w_b (q_i M_b - m_i) / B with exact zeros in every other column, dvalue = 0 and terms[b] = (loss_b, dist_q_target(a*)).
+__global__ __launch_bounds__(64) void dqn_loss_dist_kernel(const float* __restrict__ logits, const float* __restrict__ t_logits,
+                                                           const float* __restrict__ o_logits, int B, int A, int N,
+                                                           double v_min, double v_max, const int32_t* __restrict__ slots,
+                                                           const int32_t* __restrict__ action,
+                                                           const double* __restrict__ reward, const uint8_t* __restrict__ done,
+                                                           double gamma, float* __restrict__ dlogits,
+                                                           float* __restrict__ dvalue, float2* __restrict__ terms,
+                                                           int32_t* __restrict__ astar_out, float* __restrict__ maxq_out,
+                                                           float* __restrict__ m_out, const double* __restrict__ weights,
+                                                           const double* __restrict__ disc) {
+  __shared__ double s_p[256], s_b[256];
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const double delta = (v_max - v_min) / (double)(N - 1);
+  const size_t W = (size_t)A * N;
+  const long long row = slots ? (long long)slots[b] : (long long)b;
+  const float* tl = t_logits + (size_t)b * W;
+  const float* pl = o_logits ? o_logits + (size_t)b * W : tl;
+  float mx, se;
+  int astar = 0;
+  float qb = dist_q_wave(pl, N, v_min, delta, lane, &mx, &se);
+  for (int a = 1; a < A; ++a) {
+    const float q = dist_q_wave(pl + (size_t)a * N, N, v_min, delta, lane, &mx, &se);
+    if (q > qb) { qb = q; astar = a; }
+  }
+  // (the wave sums leave the same bits in every lane, so a* is uniform)
+  const float* ts = tl + (size_t)astar * N;
+  const float qstar = dist_q_wave(ts, N, v_min, delta, lane, &mx, &se);
+  const double R = reward[row];
+  const double g = disc ? disc[b] : gamma;
+  const bool dn = done[row] != 0;
+  for (int j = lane; j < N; j += 64) {
+    const double z = dist_atom(v_min, delta, j);
+    double tz = dn ? R : R + g * z;
+    tz = tz < v_min ? v_min : (tz > v_max ? v_max : tz);
+    s_p[j] = (double)(expf(ts[j] - mx) / se);
+    s_b[j] = (tz - v_min) / delta;
+  }
+  __syncthreads();
+  int act = action[row];
+  act = act < 0 ? 0 : (act >= A ? A - 1 : act);    // (an action outside [0, A) never indexes outside the row)
+  const float* l = logits + (size_t)b * W + (size_t)act * N;
+  float lmx = -INFINITY;
+  for (int i = lane; i < N; i += 64) lmx = fmaxf(lmx, l[i]);
+  lmx = dist_wave_max(lmx);
+  float lse = 0.f;
+  for (int i = lane; i < N; i += 64) lse += expf(l[i] - lmx);
+  lse = logf(dist_wave_sum(lse));
+  float m[4], lq[4];
+  float loss = 0.f, mass = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = lane + 64 * k;
+    m[k] = 0.f; lq[k] = 0.f;
+    if (i < N) {
+      double s = 0.0;
+      const double di = (double)i;
+      for (int j = 0; j < N; ++j) {
+        const double w = 1.0 - fabs(s_b[j] - di);
+        s += s_p[j] * (w > 0.0 ? w : 0.0);
+      }
+      m[k] = (float)s;
+      lq[k] = (l[i] - lmx) - lse;
+      loss += m[k] * lq[k];
+      mass += m[k];
+      if (m_out) m_out[(size_t)b * N + i] = m[k];
+    }
+  }
+  loss = -dist_wave_sum(loss);
+  mass = dist_wave_sum(mass);
+  const float fb = (float)B;
+  float* dl = dlogits + (size_t)b * W;
+  const size_t c0 = (size_t)act * N;
+  for (size_t c = lane; c < W; c += 64)
+    if (c < c0 || c >= c0 + N) dl[c] = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = lane + 64 * k;
+    if (i < N) {
+      const float d = expf(lq[k]) * mass - m[k];
+      dl[c0 + i] = (weights ? (float)weights[b] * d : d) / fb;
+    }
+  }
+  if (lane == 0) {
+    dvalue[b] = 0.f;
+    terms[b] = make_float2(loss, qstar);
+    if (astar_out) astar_out[b] = astar;
+    if (maxq_out) maxq_out[b] = qstar;
+  }
+}
+
+// dqn_loss_reduce_kernel for the distributional head: terms[b] = (loss_b, dist_q_target(a*_b));
+// out[0] = sum_b w_b loss_b / B, out[1] = sum_b loss_b / B, out[2] = sum_b terms[b].y / B (same one-block float64 tree)
+__global__ __launch_bounds__(256) void dqn_dist_reduce_kernel(const float2* __restrict__ terms, int B, float* __restrict__ out,
+                                                              float* __restrict__ acc, const double* __restrict__ weights) {
+  __shared__ double sq[256], sa[256], sm[256];
+  double q = 0.0, a = 0.0, m = 0.0;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const double d = (double)terms[b].x;
+    q += weights ? (double)(float)weights[b] * d : d; a += d; m += (double)terms[b].y;
+  }
+  sq[threadIdx.x] = q; sa[threadIdx.x] = a; sm[threadIdx.x] = m;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      sq[threadIdx.x] += sq[threadIdx.x + o]; sa[threadIdx.x] += sa[threadIdx.x + o]; sm[threadIdx.x] += sm[threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float l = (float)(sq[0] / (double)B);
+    out[0] = l; out[1] = (float)(sa[0] / (double)B); out[2] = (float)(sm[0] / (double)B);
+    if (acc) { acc[0] += l; acc[1] += 1.f; }
+  }
+}
+
 }  // namespace xt
 
 extern "C" {
+
+int xt_dqn_loss_dist(const float* logits, const float* t_logits, const float* o_logits, int32_t B, int32_t A, int32_t atoms,
+                     double v_min, double v_max, const int32_t* slots, const int32_t* action, const double* reward,
+                     const uint8_t* done, double gamma, float* dlogits, float* dvalue, float* out, int32_t* astar,
+                     float* maxq, float* m, float* acc, const double* weights, const double* disc, void* stream) {
+  XT_REQUIRE(logits && t_logits && action && reward && done && dlogits && dvalue && out, "xt_dqn_loss_dist: null argument");
+  XT_REQUIRE(atoms >= 2 && atoms <= 256, "xt_dqn_loss_dist: atoms = %d outside [2, 256]", atoms);
+  XT_REQUIRE(B > 0 && A >= 1 && A <= 64, "xt_dqn_loss_dist: bad sizes (B=%d A=%d; 1 <= A <= 64)", B, A);
+  XT_REQUIRE(std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max,
+             "xt_dqn_loss_dist: the support needs finite v_min < v_max (got %g, %g)", v_min, v_max);
+  XT_REQUIRE(((uintptr_t)out & 7) == 0, "xt_dqn_loss_dist: out must be 8-byte aligned");
+  hipStream_t st = xt::as_stream(stream);
+  float2* terms = reinterpret_cast<float2*>(out + 4);       // out: >= 4 + 2*B floats
+  hipLaunchKernelGGL(xt::dqn_loss_dist_kernel, dim3(B), dim3(64), 0, st, logits, t_logits, o_logits, B, A, atoms, v_min, v_max,
+                     slots, action, reward, done, gamma, dlogits, dvalue, terms, astar, maxq, m, weights, disc);
+  XT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(xt::dqn_dist_reduce_kernel, dim3(1), dim3(256), 0, st, terms, B, out, acc, weights);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
 
 int xt_replay_gather(const void* ring, int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, void* dst,
                      void* stream) {

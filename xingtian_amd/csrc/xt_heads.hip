@@ -41,6 +41,45 @@ __global__ __launch_bounds__(256) void heads_fwd_kernel(const float* __restrict_
   if (lane == 0) value[b] = s + bv[0];
 }
 
+// The forward of a wide head on a shared trunk (a distributional Q head is actions * atoms wide: 204 for Breakout): one
+// thread per output column (columns 0 .. A-1 of the [F, A] head, column A = the 1-wide head), four samples per block.  The
+// features of the four samples go through LDS in tiles of 256 and are read as broadcasts; the weights are read once per
+// block, coalesced along the output axis; every output accumulates over f in ascending order.  Grid (ceil((A+1)/256),
+// ceil(B/4)).
+__global__ __launch_bounds__(256) void heads_fwd_wide_kernel(const float* __restrict__ feat, int B, int F, int A,
+                                                             const float* __restrict__ wpi, const float* __restrict__ bpi,
+                                                             const float* __restrict__ wv, const float* __restrict__ bv,
+                                                             float* __restrict__ logits, float* __restrict__ value) {
+  __shared__ float sf[4][256];
+  const int t = threadIdx.x;
+  const int col = blockIdx.x * 256 + t;
+  const int b0 = blockIdx.y * 4;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int f0 = 0; f0 < F; f0 += 256) {
+    const int nf = F - f0 < 256 ? F - f0 : 256;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sf[r][t] = (b0 + r < B && t < nf) ? feat[(size_t)(b0 + r) * F + f0 + t] : 0.f;
+    __syncthreads();
+    if (col <= A) {
+#pragma unroll 8
+      for (int f = 0; f < nf; ++f) {       // (unrolled: eight weight loads in flight; the order of accumulation is unchanged)
+        const float w = col < A ? wpi[(size_t)(f0 + f) * A + col] : wv[f0 + f];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = fmaf(sf[r][f], w, acc[r]);
+      }
+    }
+  }
+  if (col > A) return;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int b = b0 + r;
+    if (b >= B) break;
+    if (col < A) logits[(size_t)b * A + col] = acc[r] + bpi[col];
+    else value[b] = acc[r] + bv[0];
+  }
+}
+
 // ---------------------------------------------------------------- PPO loss
 // one thread per sample (A is tiny); tf_dist.py:103-113 + model/ppo/__init__.py:4-25
 // STATS (xt_net_set_train_stats): also rows[b] = {old_logp - logp, (!in_rng) + 2 * (!in_v), tv, tv - v}, one 16-byte store
@@ -355,6 +394,30 @@ __global__ __launch_bounds__(256) void heads_dfeat_kernel(const float* __restric
     df_pi[e] = s * act_grad(f_pi[e], act_prev);
     df_v[e] = sv * act_grad(f_v[e], act_prev);
   }
+}
+
+// heads_dfeat_kernel (shared trunk) behind the distributional head, whose gradient row is zero outside the N columns of
+// the taken action: the sum runs over those columns only.  The skipped terms are fmaf(0, w, s) = s, so the result is the
+// full sum's bit for bit.  The taken action is read as dqn_loss_dist_kernel reads it (through slots, clamped into [0, A/N)).
+__global__ __launch_bounds__(256) void heads_dfeat_dist_kernel(const float* __restrict__ f_pi, int B, int F, int A, int N,
+                                                               const float* __restrict__ wpi, const float* __restrict__ wv,
+                                                               const float* __restrict__ dlogits,
+                                                               const float* __restrict__ dvalue,
+                                                               const int32_t* __restrict__ slots,
+                                                               const int32_t* __restrict__ action, int act_prev,
+                                                               float* __restrict__ df_pi) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= B * F) return;
+  const int b = e / F, f = e - b * F;
+  int act = action[slots ? (long long)slots[b] : (long long)b];
+  const int actions = A / N;
+  act = act < 0 ? 0 : (act >= actions ? actions - 1 : act);
+  const float* dl = dlogits + (size_t)b * A + (size_t)act * N;
+  const float* w = wpi + (size_t)f * A + (size_t)act * N;
+  float s = 0.f;
+  for (int i = 0; i < N; ++i) s = fmaf(dl[i], w[i], s);
+  const float sv = dvalue[b] * wv[f];
+  df_pi[e] = (s + sv) * act_grad(f_pi[e], act_prev);
 }
 
 // head weight gradients: block = 64 features x 4 batch groups; outputs in chunks of 8
@@ -831,6 +894,25 @@ int launch_heads_dfeat(const float* f_pi, const float* f_v, int B, int F, int A,
   const int shared = (f_pi == f_v) ? 1 : 0;
   hipLaunchKernelGGL(heads_dfeat_kernel, dim3((B * F + 255) / 256), dim3(256), 0, st, f_pi, f_v, B, F, A, wpi, wv,
                      dlogits, dvalue, act_prev, shared, df_pi, df_v);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_heads_fwd_wide(const float* feat, int B, int F, int A, const float* wpi, const float* bpi, const float* wv,
+                          const float* bv, float* logits, float* value, hipStream_t st) {
+  XT_REQUIRE(B > 0 && F > 0 && A > 0 && (B + 3) / 4 <= 65535, "heads_fwd_wide: bad sizes (B=%d F=%d A=%d)", B, F, A);
+  hipLaunchKernelGGL(heads_fwd_wide_kernel, dim3((A + 1 + 255) / 256, (B + 3) / 4), dim3(256), 0, st, feat, B, F, A, wpi, bpi,
+                     wv, bv, logits, value);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_heads_dfeat_dist(const float* f_pi, int B, int F, int A, int N, const float* wpi, const float* wv,
+                            const float* dlogits, const float* dvalue, const int32_t* slots, const int32_t* action,
+                            int act_prev, float* df_pi, hipStream_t st) {
+  XT_REQUIRE(N >= 1 && A % N == 0 && action, "heads_dfeat_dist: bad arguments (A=%d N=%d)", A, N);
+  hipLaunchKernelGGL(heads_dfeat_dist_kernel, dim3((B * F + 255) / 256), dim3(256), 0, st, f_pi, B, F, A, N, wpi, wv, dlogits,
+                     dvalue, slots, action, act_prev, df_pi);
   XT_LAUNCH_CHECK();
   return 0;
 }
@@ -2068,7 +2150,8 @@ int xt_heads_wgrad_partial_ex(const float* f_pi, const float* f_v, int32_t B, in
                               const float* dlogits, const float* dvalue, float* slab_pi, int64_t stride_pi,
                               float* slab_v, int64_t stride_v, int32_t* nchunk_out, void* stream) {
   if (nchunk_out) *nchunk_out = 0;
-  XT_REQUIRE(B > 0 && F > 0 && A > 0 && A < 256, "xt_heads_wgrad_partial_ex: bad sizes (B=%d F=%d A=%d)", B, F, A);
+  XT_REQUIRE(B > 0 && F > 0 && A > 0 && (int64_t)F * A + A < (1ll << 31),
+             "xt_heads_wgrad_partial_ex: bad sizes (B=%d F=%d A=%d)", B, F, A);
   XT_REQUIRE(stride_pi >= (int64_t)F * A + A && stride_v >= (int64_t)F + 1,
              "xt_heads_wgrad_partial_ex: slab strides %lld / %lld below F*A+A / F+1", (long long)stride_pi,
              (long long)stride_v);

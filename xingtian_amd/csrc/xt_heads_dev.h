@@ -55,8 +55,10 @@ __device__ __forceinline__ void heads_wgrad_partial_body(const HeadWgArgs& h, co
     }
     __syncthreads();
   }
-  if (bx == 0 && (int)threadIdx.x <= A) {
-    const int a = threadIdx.x;
+  // bias sums: one thread per output, strided by the block (both callers launch 256 threads), so a head wider than the
+  // block (a distributional Q head is actions * atoms wide) is covered; below 256 outputs each thread makes one trip
+  if (bx != 0) return;
+  for (int a = threadIdx.x; a <= A; a += 256) {
     float s = 0.f;
     for (int r = 0; r < 8; ++r) {
       const int b = b0 + r;

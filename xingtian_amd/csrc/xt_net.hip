@@ -3,6 +3,7 @@
 // stream, optionally captured once into a hipGraph and replayed (a B=320 step is ~20
 // short kernels; the reference pays a feed_dict H2D + session dispatch per minibatch).
 #include <atomic>
+#include <cmath>
 #include <chrono>
 #include <thread>
 #include <mutex>
@@ -139,6 +140,10 @@ struct xt_net {
   float* trows = nullptr;
   int last_head_path = 0;
   int gauss_fused = 0;                // xt_net_set_gauss_fused: a DiagGaussian step inside the envelope takes the fused head launch
+  // xt_net_set_dist: atoms of a distributional Q head (0: a scalar one; A is then actions * atoms wide) and its support
+  int dist_atoms = 0;
+  double dist_vmin = 0.0, dist_vmax = 0.0;
+  int dist_wide = 0;                  // xt_net_set_dist_wide: the wide-head forward and the taken-action d(features)
   // xt_net_last_step_report: what the most recent forward / backward / tail decided (host words, read by nothing else)
   int last_fuse12 = 0, last_fuse21 = 0, last_tail_mode = 0, last_finish_form = -1;
   // xt_net_set_impala_stats: the caller's running sums and per-trajectory rows [itraj_max][XT_IMPALA_TRAJ_STATS_FLOATS] (both
@@ -220,11 +225,19 @@ static Heads heads_of(xt_net* n) {
 }
 static int heads_forward(xt_net* n, int B, hipStream_t st) {
   const Heads h = heads_of(n);
+  if (n->dist_atoms && n->dist_wide && h.f_pi == h.f_v)   // (only a net marked distributional: no other net changes kernels)
+    return launch_heads_fwd_wide(h.f_pi, B, h.F, h.A, h.wpi, h.bpi, h.wv, h.bv, n->ws + n->off_logits, n->ws + n->off_value, st);
   return xt_heads_fwd(h.f_pi, h.f_v, B, h.F, h.A, h.wpi, h.bpi, h.wv, h.bv, n->ws + n->off_logits, n->ws + n->off_value, st);
 }
 // (launch_heads_dfeat reads the features only for the activation derivative: the pre-activation where one is kept)
-static int heads_dfeat(xt_net* n, int B, hipStream_t st) {
+// (dist_action: the action labels of the distributional step, read through dist_slots when set -- the gradient row is zero
+// outside the taken action's atoms, and a marked net sums over those only)
+static int heads_dfeat(xt_net* n, int B, hipStream_t st, const int32_t* dist_slots = nullptr,
+                       const int32_t* dist_action = nullptr) {
   const Heads h = heads_of(n);
+  if (dist_action && n->dist_atoms && n->dist_wide && h.fd_pi == h.fd_v)
+    return launch_heads_dfeat_dist(h.fd_pi, B, h.F, h.A, n->dist_atoms, h.wpi, h.wv, n->ws + n->off_dlogits,
+                                   n->ws + n->off_dvalue, dist_slots, dist_action, h.Lp->g.act, n->ws + h.Lp->dact_off, st);
   return launch_heads_dfeat(h.fd_pi, h.fd_v, B, h.F, h.A, h.wpi, h.wv, n->ws + n->off_dlogits, n->ws + n->off_dvalue,
                             h.Lp->g.act, n->ws + h.Lp->dact_off, n->ws + h.Lv->dact_off, st);
 }
@@ -1793,14 +1806,17 @@ int xt_net_graph_cache_info(const xt_net* n, int32_t* out, int32_t cap) {
 
 namespace xt {
 
-// The chain of one DQN.train up to the gradient, shared by xt_net_dqn_step, xt_net_dqn_step_per and xt_net_dqn_step_n
+// The chain of one DQN.train up to the gradient, shared by xt_net_dqn_step, xt_net_dqn_step_per, xt_net_dqn_step_n and
+// xt_net_dqn_step_dist
 // (`who` names the entry in refusals).  per (may be NULL): prioritised replay -- once every refusal has passed, xt_per_sample fills
 // per->slots / per->weights from `size` stored transitions, the chain runs on them with the weighted head, and
 // xt_per_update follows the loss; `slots` is then ignored.  ns (may be NULL): n-step returns -- the first gather walks each
 // start slot to its boot slot and leaves the per-sample labels in ns' scratch (xt_replay_gather_nstep), both next-state
 // forwards run on the boot rows, and the head reads those dense labels with the per-sample discount; the state rows and the
-// new priorities stay those of the start slots.  The launches are the same in number either way.
-static int dqn_chain(const char* who, xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_nstep_cfg* ns,
+// new priorities stay those of the start slots.  The launches are the same in number either way.  dist: both nets carry
+// the mark of xt_net_set_dist and the head is xt_dqn_loss_dist on their actions * atoms wide logits (two launches, as
+// xt_dqn_loss_n); a net with the mark is refused by the scalar entries.
+static int dqn_chain(const char* who, bool dist, xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_nstep_cfg* ns,
                      const void* cur_ring, const void* next_ring, int64_t row_bytes, int64_t capacity,
                      const int32_t* slots, int32_t B, const int32_t* action, const double* reward, const uint8_t* done,
                      const xt_per_cfg* per, int64_t size, float* loss_out, float* loss_acc, void* stream) {
@@ -1815,7 +1831,20 @@ static int dqn_chain(const char* who, xt_net* n, xt_net* tn, const xt_dqn_cfg* c
   XT_REQUIRE(tn->A == n->A && tn->feat == n->feat && tn->P == n->P && tn->layers.size() == n->layers.size() &&
                  tn->in_h == n->in_h && tn->in_w == n->in_w && tn->in_c == n->in_c && tn->xf.is_u8 == n->xf.is_u8,
              "%s: target_net is not a net of the same description", who);
-  XT_REQUIRE(n->A <= 64, "%s: A = %d exceeds 64", who, n->A);
+  int atoms = 1;
+  if (dist) {
+    XT_REQUIRE(n->dist_atoms >= 2 && tn->dist_atoms == n->dist_atoms && tn->dist_vmin == n->dist_vmin &&
+                   tn->dist_vmax == n->dist_vmax,
+               "%s: both nets must be marked distributional with the same atoms and bounds (xt_net_set_dist: net %d atoms "
+               "[%g, %g], target_net %d atoms [%g, %g])", who, n->dist_atoms, n->dist_vmin, n->dist_vmax, tn->dist_atoms,
+               tn->dist_vmin, tn->dist_vmax);
+    atoms = n->dist_atoms;
+    XT_REQUIRE(!c->dueling, "%s: no dueling stream with a distributional head (it would have to be %d wide)", who, atoms);
+  } else {
+    XT_REQUIRE(n->dist_atoms == 0 && tn->dist_atoms == 0,
+               "%s: the net is marked distributional (xt_net_set_dist): its step is xt_net_dqn_step_dist", who);
+  }
+  XT_REQUIRE(n->A / atoms <= 64, "%s: A = %d exceeds 64", who, n->A / atoms);
   XT_REQUIRE(B > 0 && B <= n->maxB && B <= tn->maxB, "%s: batch %d outside (0,%d]", who, B,
              n->maxB < tn->maxB ? n->maxB : tn->maxB);
   const int64_t in_row = (int64_t)n->in_h * n->in_w * n->in_c * (n->xf.is_u8 ? 1 : 4);
@@ -1859,14 +1888,24 @@ static int dqn_chain(const char* who, xt_net* n, xt_net* tn, const xt_dqn_cfg* c
   float* lo = n->ws + n->off_loss;
   float* rows = n->ws + n->off_terms;                       // per-row y | a* | maxq, maxB each
   // (n-step: the labels are dense in the scratch the gather filled, in sample order)
-  if (int rc = xt_dqn_loss_n(n->ws + n->off_logits, n->ws + n->off_value, t_logits, t_value, o_logits, o_value, B, A,
+  if (dist) {
+    if (int rc = xt_dqn_loss_dist(n->ws + n->off_logits, t_logits, o_logits, B, A / atoms, atoms, n->dist_vmin, n->dist_vmax,
+                                  ns ? nullptr : slots, ns ? ns->action_n : action, ns ? ns->reward_n : reward,
+                                  ns ? ns->done_n : done, c->gamma, n->ws + n->off_dlogits, n->ws + n->off_dvalue, lo,
+                                  reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB, nullptr, loss_acc, weights,
+                                  ns ? ns->disc_n : nullptr, stream))
+      return rc;
+  } else if (int rc = xt_dqn_loss_n(n->ws + n->off_logits, n->ws + n->off_value, t_logits, t_value, o_logits, o_value, B, A,
                              c->dueling, ns ? nullptr : slots, ns ? ns->action_n : action, ns ? ns->reward_n : reward,
                              ns ? ns->done_n : done, c->gamma, n->ws + n->off_dlogits, n->ws + n->off_dvalue, lo, rows,
                              reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB, loss_acc, weights,
-                             ns ? ns->disc_n : nullptr, stream))
+                             ns ? ns->disc_n : nullptr, stream)) {
     return rc;
+  }
   if (loss_out) XT_CHECK_HIP(hipMemcpyAsync(loss_out, lo, 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-  if (int rc = xt::heads_dfeat(n, B, st)) return rc;
+  if (int rc = xt::heads_dfeat(n, B, st, dist && !ns ? slots : nullptr,
+                               dist ? (ns ? ns->action_n : action) : nullptr))
+    return rc;
   if (int rc = xt::trunk_backward(n, c->cur_rows, nullptr, B, st)) return rc;
   if (int rc = xt::grads_finish(n, B, nullptr, st)) return rc;
   if (!per) return 0;
@@ -1883,7 +1922,7 @@ extern "C" {
 int xt_net_dqn_step(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const void* cur_ring, const void* next_ring,
                     int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, const int32_t* action,
                     const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream) {
-  return xt::dqn_chain("xt_net_dqn_step", n, tn, c, nullptr, cur_ring, next_ring, row_bytes, capacity, slots, B, action,
+  return xt::dqn_chain("xt_net_dqn_step", false, n, tn, c, nullptr, cur_ring, next_ring, row_bytes, capacity, slots, B, action,
                        reward, done, nullptr, 0, loss_out, loss_acc, stream);
 }
 
@@ -1892,7 +1931,7 @@ int xt_net_dqn_step_per(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_per
                         const int32_t* action, const double* reward, const uint8_t* done, float* loss_out, float* loss_acc,
                         void* stream) {
   XT_REQUIRE(p, "xt_net_dqn_step_per: null per cfg");
-  return xt::dqn_chain("xt_net_dqn_step_per", n, tn, c, nullptr, cur_ring, next_ring, row_bytes, capacity, nullptr, B, action,
+  return xt::dqn_chain("xt_net_dqn_step_per", false, n, tn, c, nullptr, cur_ring, next_ring, row_bytes, capacity, nullptr, B, action,
                        reward, done, p, size, loss_out, loss_acc, stream);
 }
 
@@ -1901,8 +1940,38 @@ int xt_net_dqn_step_n(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_nstep
                       const int32_t* slots, int32_t B, const int32_t* action, const double* reward, const uint8_t* done,
                       float* loss_out, float* loss_acc, void* stream) {
   XT_REQUIRE(ns, "xt_net_dqn_step_n: null nstep cfg");
-  return xt::dqn_chain("xt_net_dqn_step_n", n, tn, c, ns, cur_ring, next_ring, row_bytes, capacity, p ? nullptr : slots, B,
+  return xt::dqn_chain("xt_net_dqn_step_n", false, n, tn, c, ns, cur_ring, next_ring, row_bytes, capacity, p ? nullptr : slots, B,
                        action, reward, done, p, size, loss_out, loss_acc, stream);
+}
+
+int xt_net_dqn_step_dist(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_nstep_cfg* ns, const xt_per_cfg* p,
+                         const void* cur_ring, const void* next_ring, int64_t row_bytes, int64_t capacity, int64_t size,
+                         const int32_t* slots, int32_t B, const int32_t* action, const double* reward, const uint8_t* done,
+                         float* loss_out, float* loss_acc, void* stream) {
+  return xt::dqn_chain("xt_net_dqn_step_dist", true, n, tn, c, ns, cur_ring, next_ring, row_bytes, capacity,
+                       p ? nullptr : slots, B, action, reward, done, p, size, loss_out, loss_acc, stream);
+}
+
+int xt_net_set_dist(xt_net* net, int32_t atoms, double v_min, double v_max) {
+  XT_REQUIRE(net, "xt_net_set_dist: null net");
+  if (atoms == 1) {
+    net->dist_atoms = 0; net->dist_vmin = net->dist_vmax = 0.0; net->dist_wide = 0;
+    return 0;
+  }
+  XT_REQUIRE(atoms >= 2 && atoms <= 256, "xt_net_set_dist: atoms = %d outside [1, 256]", atoms);
+  XT_REQUIRE(std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max,
+             "xt_net_set_dist: the support needs finite v_min < v_max (got %g, %g)", v_min, v_max);
+  XT_REQUIRE(net->action_type == XT_ACTION_CATEGORICAL, "xt_net_set_dist: categorical heads only");
+  XT_REQUIRE(net->A % atoms == 0, "xt_net_set_dist: the head is %d wide, no multiple of atoms = %d", net->A, atoms);
+  net->dist_atoms = atoms; net->dist_vmin = v_min; net->dist_vmax = v_max; net->dist_wide = 1;
+  return 0;
+}
+
+int xt_net_set_dist_wide(xt_net* net, int32_t on) {
+  XT_REQUIRE(net, "xt_net_set_dist_wide: null net");
+  XT_REQUIRE(net->dist_atoms, "xt_net_set_dist_wide: the net is not marked distributional (xt_net_set_dist)");
+  net->dist_wide = on ? 1 : 0;
+  return 0;
 }
 
 int xt_net_set_grad_exchange_ex(xt_net* net, xt_grad_exchange_fn fn, void* user, int32_t flags) {

@@ -273,6 +273,12 @@ SIGNATURES = {
                                 _P, _P, _P, _P, _P, _P]),
     "xt_net_dqn_step_n": (c_int32, [_P, _P, POINTER(DqnCfg), POINTER(NstepCfg), POINTER(PerCfg), _P, _P, c_int64, c_int64,
                                     c_int64, _P, c_int32, _P, _P, _P, _P, _P, _P]),
+    "xt_dqn_loss_dist": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_double, c_double, _P, _P, _P, _P, c_double, _P, _P,
+                                   _P, _P, _P, _P, _P, _P, _P, _P]),
+    "xt_net_set_dist": (c_int32, [_P, c_int32, c_double, c_double]),
+    "xt_net_set_dist_wide": (c_int32, [_P, c_int32]),
+    "xt_net_dqn_step_dist": (c_int32, [_P, _P, POINTER(DqnCfg), POINTER(NstepCfg), POINTER(PerCfg), _P, _P, c_int64, c_int64,
+                                       c_int64, _P, c_int32, _P, _P, _P, _P, _P, _P]),
     "xt_grads_finish_plan_ex": (c_int32, [POINTER(GradEntry), c_int32, ctypes.c_uint32, ctypes.c_uint32, c_int32, c_int32,
                                           POINTER(c_int32), POINTER(c_int32)]),
     "xt_grads_finish_ex": (c_int32, [POINTER(GradEntry), c_int32, ctypes.c_uint32, ctypes.c_uint32, POINTER(FinishArgs), _P,

@@ -6,6 +6,12 @@ the A-wide stream ``l`` combine to Q_a = s + (l_a - mean_a l) -- compiled with `
 returns Q as float32 [N, A].  The update does not go through ``train(states, y_t)``: the algorithm keeps its replay
 store on the device and one C call (``xt_net_dqn_step``) forms the TD target and the gradient there
 (``train_replay``), so ``train`` is not provided.
+
+``model_config.atoms`` (1 unless asked for) with ``v_min`` / ``v_max`` (-10 / 10) makes the network distributional (C51,
+Bellemare et al. 2017): the Q head is A * atoms wide, column a * atoms + i being the logit of atom i of action a, and
+``predict`` returns the expectation of every action's softmax over the fixed support (``dist_q``).  The definitions
+below (``dist_support``, ``dist_q``, ``categorical_projection``) are the host twins of the head kernel
+``xt_dqn_loss_dist``: the same arithmetic in the same precision, and the tests' first reference.
 """
 import numpy as np
 
@@ -26,6 +32,66 @@ def dueling_q(logits, value, dueling):
     return np.asarray(value, np.float32).reshape(-1, 1) + (l - l.mean(axis=1, keepdims=True, dtype=np.float32))
 
 
+def dist_support(atoms, v_min, v_max):
+    """-> (z float64 [N], delta): delta = (v_max - v_min) / (N - 1), z_i = v_min + i * delta, both in float64 (product
+    rounded, then sum).  ``z.astype(float32)`` is used where float32 is used."""
+    n, v_min, v_max = int(atoms), np.float64(v_min), np.float64(v_max)
+    if n < 2 or not (np.isfinite(v_min) and np.isfinite(v_max) and v_min < v_max):
+        raise ValueError("dist_support: needs atoms >= 2 and finite v_min < v_max (got {}, {}, {})".format(atoms, v_min, v_max))
+    delta = (v_max - v_min) / np.float64(n - 1)
+    return v_min + np.arange(n, dtype=np.float64) * delta, delta
+
+
+def dist_q(logits, z):
+    """Expectation of softmax(l) over the support, float32, for logits [..., N] and the float64 support ``z`` [N]:
+    mx = max l; e_i = expf(l_i - mx); Q = (sum z_i e_i) / (sum e_i) with z_i rounded to float32.  -> float32 [...]"""
+    l = np.asarray(logits, np.float32)
+    e = np.exp(l - l.max(axis=-1, keepdims=True), dtype=np.float32)
+    zf = np.asarray(z, np.float64).astype(np.float32)
+    return ((zf * e).sum(axis=-1, dtype=np.float32) / e.sum(axis=-1, dtype=np.float32)).astype(np.float32)
+
+
+def categorical_projection(p, reward, disc, done, v_min, v_max):
+    """The target distribution of C51 projected onto the support (Algorithm 1 of the paper in gather form), float64 with
+    one rounding: for probabilities ``p`` [B, N] (float32) and per-sample labels (R, g, dn),
+
+        Tz_j = clip(dn ? R : R + g * z_j, v_min, v_max);  b_j = (Tz_j - v_min) / delta
+        m_i = (float32) sum_{j = 0..N-1, ascending} (float64)p_j * max(0, 1 - |b_j - i|)
+
+    It equals the published l = floor(b) / u = ceil(b) scatter whenever no b_j is an integer, and keeps the mass where
+    that pseudo-code drops it (l == u).  Nothing is scattered, so no order of evaluation enters.  -> m float32 [B, N]"""
+    p = np.asarray(p, np.float32)
+    b, n = p.shape
+    z, delta = dist_support(n, v_min, v_max)
+    r = np.asarray(reward, np.float64).reshape(b, 1)
+    g = np.broadcast_to(np.asarray(disc, np.float64).reshape(-1, 1), (b, 1))
+    dn = np.asarray(done).reshape(b, 1).astype(bool)
+    gz = g * z[None, :]
+    tz = np.clip(np.where(dn, r, r + gz), np.float64(v_min), np.float64(v_max))
+    bj = (tz - np.float64(v_min)) / delta
+    idx = np.arange(n, dtype=np.float64)
+    m = np.zeros((b, n), np.float64)
+    for j in range(n):                                  # ascending j: the kernel's order of summation
+        m = m + p[:, j:j + 1].astype(np.float64) * np.maximum(0.0, 1.0 - np.abs(bj[:, j:j + 1] - idx[None, :]))
+    return m.astype(np.float32)
+
+
+def dist_config(model_config, action_dim):
+    """-> (atoms, v_min, v_max) of a DQN ``model_config`` after the checks of the distributional keys"""
+    atoms = netspec.check_atoms(model_config.get("atoms", 1))
+    v_min, v_max = float(model_config.get("v_min", -10.0)), float(model_config.get("v_max", 10.0))
+    if atoms > 1:
+        if not (np.isfinite(v_min) and np.isfinite(v_max) and v_min < v_max):
+            raise ValueError("atoms = {}: the support needs finite v_min < v_max, got v_min = {}, v_max = {}".format(
+                atoms, v_min, v_max))
+        if bool(model_config.get("dueling", False)):
+            raise NotImplementedError("dueling with atoms = {}: the dueling stream is 1 wide, a distributional dueling "
+                                      "network needs an atoms-wide one; not provided".format(atoms))
+        if int(action_dim) > 64:
+            raise ValueError("atoms = {}: action_dim = {} exceeds 64 (the device step's limit)".format(atoms, action_dim))
+    return atoms, v_min, v_max
+
+
 def dqn_spec(model_info):
     """The ``NetSpec`` of a DQN model description (``model_para.actor`` of a YAML): ``DqnCnn`` / ``DqnMlp``."""
     cfg = model_info.get("model_config") or {}
@@ -33,11 +99,13 @@ def dqn_spec(model_info):
     if name == "DqnCnnPong":
         raise NotImplementedError(PONG_MESSAGE)
     if name == "DqnCnn":
-        return netspec.dqn_cnn(tuple(model_info["state_dim"]), model_info["action_dim"], dueling)
+        return netspec.dqn_cnn(tuple(model_info["state_dim"]), model_info["action_dim"], dueling,
+                               dist_config(cfg, model_info["action_dim"])[0])
     if name == "DqnMlp":
         from xingtian_amd.model.dqn import default_config as d
         return netspec.dqn_mlp(tuple(model_info["state_dim"]), model_info["action_dim"],
-                               cfg.get("HIDDEN_SIZE", d.HIDDEN_SIZE), cfg.get("NUM_LAYERS", d.NUM_LAYERS), dueling)
+                               cfg.get("HIDDEN_SIZE", d.HIDDEN_SIZE), cfg.get("NUM_LAYERS", d.NUM_LAYERS), dueling,
+                               dist_config(cfg, model_info["action_dim"])[0])
     raise KeyError("no DQN model named {}".format(name))
 
 
@@ -49,6 +117,8 @@ class DqnModel(XTModel):
         self.state_dim, self.action_dim = model_info["state_dim"], model_info["action_dim"]
         self.learning_rate = learning_rate
         self.dueling = bool(model_config.get("dueling", False))
+        self.atoms, self.v_min, self.v_max = dist_config(model_config, self.action_dim)
+        self.support = dist_support(self.atoms, self.v_min, self.v_max)[0] if self.atoms > 1 else None
         self.seed = model_config.get("SEED")
         # the algorithm's minibatch (model_info["max_batch"], set by DQN) bounds the training step; predict walks larger
         # inputs in chunks
@@ -61,6 +131,8 @@ class DqnModel(XTModel):
 
     def create_model(self, model_info):
         self.net = build_net(model_info, self._spec(), self.max_batch, self.seed)
+        if self.atoms > 1 and not getattr(self.net, "inference_only", False):
+            self.net.set_dist(self.atoms, self.v_min, self.v_max)
         self.actor_var = self.net
         return True
 
@@ -72,17 +144,23 @@ class DqnModel(XTModel):
             self.iterations = int(arrays["keras_adam_iterations"])
 
     def predict(self, state):
-        """-> Q [N, A] (numpy float32)"""
+        """-> Q [N, A] (numpy float32); with ``atoms`` > 1 the expectation under every action's softmax (``dist_q``)"""
         logits, value = self.net.forward(np.asarray(state))
+        if self.atoms > 1:
+            return dist_q(as_numpy(logits).reshape(-1, self.action_dim, self.atoms), self.support)
         return dueling_q(as_numpy(logits), as_numpy(value), self.dueling)
 
     def train_replay(self, target, replay, slots, gamma, double_dqn):
         """One update on the minibatch ``slots`` (int32 device tensor) of the device rings ``replay``
         (``algorithm.dqn.DeviceReplay``): ``xt_net_dqn_step`` with ``target``'s network as the target net, then tf.keras
         Adam.  Nothing synchronises.  -> the device tensor [loss, mean |TD error|, mean bootstrap Q].  A replay with
-        ``n_step`` > 1 trains on n-step targets (``xt_net_dqn_step_n``)."""
+        ``n_step`` > 1 trains on n-step targets (``xt_net_dqn_step_n``).  A distributional model (``atoms`` > 1) takes
+        ``xt_net_dqn_step_dist`` either way; the tensor is then [loss, mean per-sample loss, mean bootstrap Q]."""
         self._require_learner()
-        if getattr(replay, "n_step", 1) > 1:
+        if self.atoms > 1:
+            out = self.net.dqn_step_dist(target.net, replay.cur_state, replay.next_state, slots, replay.action,
+                                         replay.reward, replay.done, gamma, double_dqn, **self._nstep_of(replay))
+        elif getattr(replay, "n_step", 1) > 1:
             out = self.net.dqn_step_n(target.net, replay.cur_state, replay.next_state, slots, replay.action, replay.reward,
                                       replay.done, replay.follow, replay.n_step, gamma, self.dueling, double_dqn)
         else:
@@ -97,9 +175,12 @@ class DqnModel(XTModel):
         ``u`` (float64 device tensor [B]) and importance exponent ``beta``, and the replay's trees take the new TD errors
         (``xt_net_dqn_step_per``), then tf.keras Adam.  Nothing synchronises.  -> the device tensor of ``train_replay``."""
         self._require_learner()
-        if getattr(replay, "n_step", 1) > 1:
-            per = dict(size=replay.size(), u=u, sum_tree=replay.sum_tree, min_tree=replay.min_tree,
-                       max_prio=replay.max_prio, alpha=replay.alpha, beta=beta, eps=replay.eps)
+        per = dict(size=replay.size(), u=u, sum_tree=replay.sum_tree, min_tree=replay.min_tree, max_prio=replay.max_prio,
+                   alpha=replay.alpha, beta=beta, eps=replay.eps)
+        if self.atoms > 1:
+            out = self.net.dqn_step_dist(target.net, replay.cur_state, replay.next_state, None, replay.action, replay.reward,
+                                         replay.done, gamma, double_dqn, per=per, **self._nstep_of(replay))
+        elif getattr(replay, "n_step", 1) > 1:
             out = self.net.dqn_step_n(target.net, replay.cur_state, replay.next_state, None, replay.action, replay.reward,
                                       replay.done, replay.follow, replay.n_step, gamma, self.dueling, double_dqn, per=per)
         else:
@@ -109,6 +190,13 @@ class DqnModel(XTModel):
         self.net.adam_keras(self.learning_rate, self.iterations, clipnorm=self.CLIPNORM)
         self.iterations += 1
         return out
+
+    @staticmethod
+    def _nstep_of(replay):
+        """the n-step keywords of ``dqn_step_dist`` for a replay store (none for one-step targets)"""
+        if getattr(replay, "n_step", 1) > 1:
+            return dict(follow=replay.follow, n=replay.n_step)
+        return {}
 
     def copy_weights_from(self, other):
         """this network's parameters <- ``other``'s: one device-to-device copy of the flat buffer on a learner"""
@@ -128,4 +216,4 @@ class DqnCnn(DqnModel):
         super().__init__(model_info, LR)
 
     def _spec(self):
-        return netspec.dqn_cnn(tuple(self.state_dim), self.action_dim, self.dueling)
+        return netspec.dqn_cnn(tuple(self.state_dim), self.action_dim, self.dueling, self.atoms)

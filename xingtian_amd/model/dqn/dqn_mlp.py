@@ -13,4 +13,5 @@ class DqnMlp(DqnModel):
         super().__init__(model_info, LR)
 
     def _spec(self):
-        return netspec.dqn_mlp(tuple(self.state_dim), self.action_dim, HIDDEN_SIZE, NUM_LAYERS, self.dueling)
+        return netspec.dqn_mlp(tuple(self.state_dim), self.action_dim, HIDDEN_SIZE, NUM_LAYERS, self.dueling,
+                               self.atoms)

@@ -880,7 +880,7 @@ class HipActorCritic(object):
                 raise ValueError("{}: {} must be a contiguous device tensor ({} rows)".format(who, name, cap))
         if next_ring.shape != cur_ring.shape:
             raise ValueError("{}: the two state rings differ in shape".format(who))
-        a = self.spec.action_dim
+        a = self.spec.action_dim                        # (the head's width: actions * atoms of a distributional spec)
         if not hasattr(self, "_dqn_scratch"):
             mb = self.max_batch
             self._dqn_scratch = (torch.empty((mb, row_bytes), dtype=torch.uint8, device=self.device),
@@ -938,19 +938,12 @@ class HipActorCritic(object):
         batch = {"slots": slots} if per is None else {"u": per["u"]}
         cap, row_bytes, cfg = self._dqn_cfg("dqn_step_n", cur_ring, next_ring, batch, action, reward, done, gamma, dueling,
                                             double_dqn)
-        if not (follow.is_cuda and follow.is_contiguous() and follow.dtype == torch.int32 and follow.shape[0] == cap):
-            raise ValueError("dqn_step_n: follow must be a contiguous int32 device tensor ({} rows)".format(cap))
         if per is None:
             b, size, p_ref = int(slots.numel()), 0, None
         else:
             b, p = self._per_cfg("dqn_step_n", **{k: v for k, v in per.items() if k != "size"})
             size, p_ref = int(per["size"]), ctypes.byref(p)
-        if not hasattr(self, "nstep_boot"):
-            new = lambda dt: torch.zeros(self.max_batch, dtype=dt, device=self.device)
-            self.nstep_boot, self.nstep_action = new(torch.int32), new(torch.int32)
-            self.nstep_reward, self.nstep_disc, self.nstep_done = new(torch.float64), new(torch.float64), new(torch.uint8)
-        ns = L.NstepCfg(int(n), follow.data_ptr(), self.nstep_boot.data_ptr(), self.nstep_action.data_ptr(),
-                        self.nstep_reward.data_ptr(), self.nstep_disc.data_ptr(), self.nstep_done.data_ptr())
+        ns = self._nstep_cfg("dqn_step_n", follow, n, cap)
         L.check(self.lib.xt_net_dqn_step_n(self.handle, target.handle, ctypes.byref(cfg), ctypes.byref(ns), p_ref,
                                            L.ptr(cur_ring), L.ptr(next_ring), row_bytes, cap, size,
                                            L.ptr(slots) if per is None else None, b, L.ptr(action), L.ptr(reward),
@@ -958,6 +951,55 @@ class HipActorCritic(object):
                                            L.ptr(loss_acc) if loss_acc is not None else None, L.stream_ptr()),
                 "xt_net_dqn_step_n")
         return self.loss_out
+
+    def set_dist(self, atoms, v_min, v_max):
+        """Mark the net as carrying a distributional Q head of ``atoms`` atoms on [v_min, v_max] (C ABI
+        ``xt_net_set_dist``; ``spec.action_dim`` is actions * atoms); ``atoms`` 1 clears the mark."""
+        L.check(self.lib.xt_net_set_dist(self.handle, int(atoms), float(v_min), float(v_max)), "xt_net_set_dist")
+        self.dist = (int(atoms), float(v_min), float(v_max)) if int(atoms) > 1 else None
+
+    def set_dist_wide(self, on):
+        """Switch a marked net between the wide-head kernels (the default) and those of an unmarked net (C ABI
+        ``xt_net_set_dist_wide``): for same-run comparisons and tests."""
+        L.check(self.lib.xt_net_set_dist_wide(self.handle, int(bool(on))), "xt_net_set_dist_wide")
+
+    def dqn_step_dist(self, target, cur_ring, next_ring, slots, action, reward, done, gamma, double_dqn, follow=None, n=1,
+                      per=None, loss_acc=None):
+        """``dqn_step`` / ``dqn_step_per`` / ``dqn_step_n`` of a distributional net (C ABI ``xt_net_dqn_step_dist``, never
+        synchronises): the same chain with the categorical projection and cross-entropy head ``xt_dqn_loss_dist``.  Both
+        nets carry the mark of ``set_dist``.  ``follow`` / ``n``: n-step targets as in ``dqn_step_n`` (absent: one step);
+        ``per``: the keywords of ``dqn_step_n``'s ``per`` (the new priority of a start slot is its loss + eps), ``slots``
+        is then ignored.  Returns the device tensor [loss, mean per-sample loss, mean bootstrap Q]."""
+        batch = {"slots": slots} if per is None else {"u": per["u"]}
+        cap, row_bytes, cfg = self._dqn_cfg("dqn_step_dist", cur_ring, next_ring, batch, action, reward, done, gamma, False,
+                                            double_dqn)
+        if per is None:
+            b, size, p_ref = int(slots.numel()), 0, None
+        else:
+            b, p = self._per_cfg("dqn_step_dist", **{k: v for k, v in per.items() if k != "size"})
+            size, p_ref = int(per["size"]), ctypes.byref(p)
+        ns_ref = None
+        if follow is not None:
+            ns = self._nstep_cfg("dqn_step_dist", follow, n, cap)
+            ns_ref = ctypes.byref(ns)
+        L.check(self.lib.xt_net_dqn_step_dist(self.handle, target.handle, ctypes.byref(cfg), ns_ref, p_ref, L.ptr(cur_ring),
+                                              L.ptr(next_ring), row_bytes, cap, size,
+                                              L.ptr(slots) if per is None else None, b, L.ptr(action), L.ptr(reward),
+                                              L.ptr(done), L.ptr(self.loss_out),
+                                              L.ptr(loss_acc) if loss_acc is not None else None, L.stream_ptr()),
+                "xt_net_dqn_step_dist")
+        return self.loss_out
+
+    def _nstep_cfg(self, who, follow, n, cap):
+        """-> ``NstepCfg`` after the check of ``follow``; allocates the label scratch ``nstep_*`` [max_batch]"""
+        if not (follow.is_cuda and follow.is_contiguous() and follow.dtype == torch.int32 and follow.shape[0] == cap):
+            raise ValueError("{}: follow must be a contiguous int32 device tensor ({} rows)".format(who, cap))
+        if not hasattr(self, "nstep_boot"):
+            new = lambda dt: torch.zeros(self.max_batch, dtype=dt, device=self.device)
+            self.nstep_boot, self.nstep_action = new(torch.int32), new(torch.int32)
+            self.nstep_reward, self.nstep_disc, self.nstep_done = new(torch.float64), new(torch.float64), new(torch.uint8)
+        return L.NstepCfg(int(n), follow.data_ptr(), self.nstep_boot.data_ptr(), self.nstep_action.data_ptr(),
+                          self.nstep_reward.data_ptr(), self.nstep_disc.data_ptr(), self.nstep_done.data_ptr())
 
     def apply(self, lr, clip_norm, grad_scale=1.0):
         self.touch()
