@@ -10,12 +10,9 @@ sampling and the priority write-back on the host (tests/per_helpers.py holds the
 Every twin takes ``bug``: a deliberately wrong variant of one detail.  The comparisons the GPU tests assert with must
 reject each of them for at least one case of the tables (tests/test_cpu_dqn_coverage.py).
 """
-import ctypes
-
 import numpy as np
 
 import dqn_helpers as H
-import per_helpers as P
 
 F = np.float32
 LOSS_BUGS = ("last_max", "gamma_f32", "w_f64", "w_by_slot", "no_clamp", "div_b")
@@ -118,7 +115,7 @@ def loss_ref64(d, dueling, double, gamma, weighted, slots=None):
              f64(d["o_logits"]) if double else None, f64(d["o_value"]) if double else None]
     labels = (np.clip(d["action"][lab], 0, a - 1), d["reward"][lab], d["done"][lab], gamma, dueling)
     plain = H.dqn_loss_ref(*heads, *labels)
-    return (P.dqn_loss_ref_w(d["w"], *heads, *labels) if weighted else plain), plain
+    return (H.dqn_loss_ref(*heads, *labels, d["w"]) if weighted else plain), plain
 
 
 BITWISE_KEYS = ("astar", "maxq", "y", "terms", "dlogits", "dvalue")
@@ -165,32 +162,8 @@ def within(errs):
     return all(e <= bar for e, bar in errs.values())
 
 
-PAD = 3                                    # rows (and 2 * PAD + 1 floats of ``out``) behind what the launch owns
-
-
-def gpu_dqn_loss_w(d, dueling, double, gamma, weighted, slots=None):
-    """-> (rc, dict of host arrays [B + PAD, ...], ``out`` [4 + 2B + 2 PAD + 1]): xt_dqn_loss_w on host inputs; every
-    output starts as NaN / -1, also behind the B rows"""
-    import torch
-    from xingtian_amd import lib as L
-    dev = torch.device("cuda:0")
-    up = lambda x, dt: None if x is None else torch.from_numpy(np.ascontiguousarray(x, dtype=dt)).to(dev)
-    b, a = d["logits"].shape
-    t = dict(logits=up(d["logits"], np.float32), value=up(d["value"], np.float32), tl=up(d["t_logits"], np.float32),
-             tv=up(d["t_value"], np.float32), ol=up(d["o_logits"] if double else None, np.float32),
-             ov=up(d["o_value"] if double else None, np.float32), action=up(d["action"], np.int32),
-             reward=up(d["reward"], np.float64), done=up(d["done"], np.uint8), slots=up(slots, np.int32),
-             w=up(d["w"] if weighted else None, np.float64))
-    nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
-    out = dict(dlogits=nan(b + PAD, a), dvalue=nan(b + PAD), out=nan(4 + 2 * b + 2 * PAD + 1), y=nan(b + PAD),
-               maxq=nan(b + PAD), astar=torch.full((b + PAD,), -1, dtype=torch.int32, device=dev))
-    rc = L.load().xt_dqn_loss_w(L.ptr(t["logits"]), L.ptr(t["value"]), L.ptr(t["tl"]), L.ptr(t["tv"]), L.ptr(t["ol"]),
-                                L.ptr(t["ov"]), b, a, int(dueling), L.ptr(t["slots"]), L.ptr(t["action"]),
-                                L.ptr(t["reward"]), L.ptr(t["done"]), ctypes.c_double(gamma), L.ptr(out["dlogits"]),
-                                L.ptr(out["dvalue"]), L.ptr(out["out"]), L.ptr(out["y"]), L.ptr(out["astar"]),
-                                L.ptr(out["maxq"]), None, L.ptr(t["w"]), L.stream_ptr())
-    torch.cuda.synchronize()
-    return rc, {k: v.cpu().numpy() for k, v in out.items()}
+PAD = 3                                    # rows (and 2 * PAD + 1 floats of ``out``) behind what the launch owns (``pad``
+                                           # of ``dqn_helpers.gpu_dqn_loss``)
 
 
 # ----------------------------------------------------------------------------------------------- trees

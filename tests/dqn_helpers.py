@@ -21,8 +21,12 @@ def q_from_heads(logits, value, dueling):
     return np.asarray(value).reshape(-1, 1) + (logits - logits.mean(axis=1, keepdims=True))
 
 
-def dqn_loss_ref(logits, value, t_logits, t_value, o_logits, o_value, action, reward, done, gamma, dueling):
-    """TD target and 'mse' head in the dtype of ``logits``.  o_logits None: plain DQN, else double DQN.
+def dqn_loss_ref(logits, value, t_logits, t_value, o_logits, o_value, action, reward, done, gamma, dueling, weights=None,
+                 disc=None):
+    """TD target and 'mse' head in the dtype of ``logits``.  o_logits None: plain DQN, else double DQN.  ``weights`` [B]:
+    Keras ``sample_weight`` (L = sum_b w_b delta_b^2 / (B A), the head gradients scaled by w_b; the means of |delta| and
+    of the bootstrap value stay unweighted).  ``disc`` [B]: a per-sample discount in gamma's place.  The weighted
+    arithmetic runs in the kernel's order, g = 2 w delta / (B A); a weight of one changes no bit.
     -> dict(astar, maxq, y, delta, loss, abs_td, mean_maxq, dlogits [B,A], dvalue [B])"""
     dt = logits.dtype.type
     b, a = logits.shape
@@ -32,18 +36,20 @@ def dqn_loss_ref(logits, value, t_logits, t_value, o_logits, o_value, action, re
     astar = np.argmax(pick, axis=1)                    # first maximal index
     maxq = qt[rows, astar]
     r = np.asarray(reward, np.float64).reshape(b)
-    y = np.where(np.asarray(done).reshape(b).astype(bool), r, r + float(gamma) * maxq.astype(np.float64)).astype(dt)
+    gm = float(gamma) if disc is None else np.asarray(disc, np.float64).reshape(b)
+    y = np.where(np.asarray(done).reshape(b).astype(bool), r, r + gm * maxq.astype(np.float64)).astype(dt)
     act = np.asarray(action).reshape(b).astype(np.int64)
     q = q_from_heads(logits, value, dueling)
     delta = q[rows, act] - y
-    g = dt(2.0) * delta / dt(b * a)
+    w = np.ones(b, logits.dtype) if weights is None else np.asarray(weights, logits.dtype).reshape(b)
+    g = dt(2.0) * w * delta / dt(b * a)
     hot = np.zeros((b, a), logits.dtype)
     hot[rows, act] = 1
     if dueling:
         dlogits, dvalue = g[:, None] * (hot - dt(1.0) / dt(a)), g.copy()
     else:
         dlogits, dvalue = g[:, None] * hot, np.zeros(b, logits.dtype)
-    return dict(astar=astar, maxq=maxq, y=y, delta=delta, loss=(delta * delta).sum() / dt(b * a),
+    return dict(astar=astar, maxq=maxq, y=y, delta=delta, loss=(w * delta * delta).sum() / dt(b * a),
                 abs_td=np.abs(delta).mean(), mean_maxq=maxq.mean(), dlogits=dlogits, dvalue=dvalue)
 
 
@@ -93,12 +99,15 @@ class DqnOracle(object):
         self.dueling, self.double, self.gamma = dueling, double, gamma
         self.opt = nets.AdamKeras(self.net.params, lr, clipnorm)
 
-    def step(self, states, next_states, action, reward, done, apply=True):
+    def step(self, states, next_states, action, reward, done, weights=None, disc=None, apply=True):
+        """``weights`` / ``disc``: as ``dqn_loss_ref`` takes them (with ``disc``, ``next_states`` are the
+        rows of the boot slots and the labels those of the walk)"""
         tl, tv = self.target.forward(next_states)
         ol, ov = self.net.forward(next_states) if self.double else (None, None)
         lg, v = self.net.forward(states)
         flat = lambda x: None if x is None else x.reshape(-1)
-        out = dqn_loss_ref(lg, flat(v), tl, flat(tv), ol, flat(ov), action, reward, done, self.gamma, self.dueling)
+        out = dqn_loss_ref(lg, flat(v), tl, flat(tv), ol, flat(ov), action, reward, done, self.gamma, self.dueling, weights,
+                           disc)
         out["grads"] = self.net.backward(out["dlogits"], out["dvalue"].reshape(-1, 1))
         if apply:
             self.opt.apply(self.net.params, out["grads"])
@@ -126,9 +135,11 @@ def gpu_replay_gather(ring, slots, b=None, row_bytes=None, capacity=None):
     return rc, dst
 
 
-def gpu_dqn_loss(logits, value, t_logits, t_value, o_logits, o_value, action, reward, done, gamma, dueling, slots=None,
-                 b=None, a=None, acc=None):
-    """-> (rc, dict of host arrays): xt_dqn_loss on host inputs; outputs start as NaN / -1 sentinels"""
+def gpu_dqn_loss(logits, value, t_logits, t_value, o_logits, o_value, action, reward, done, gamma, dueling,
+                 entry="xt_dqn_loss", slots=None, weights=None, disc=None, b=None, a=None, acc=None, pad=0):
+    """-> (rc, dict of host arrays): the scalar head ``entry`` (xt_dqn_loss / xt_dqn_loss_w / xt_dqn_loss_n) on host
+    inputs; ``weights`` / ``disc`` go to the entries that take them (None: NULL).  The outputs start as NaN / -1
+    sentinels and carry ``pad`` more rows (``out``: 2 * pad + 1 more floats) than the launch owns."""
     import torch
     from xingtian_amd import lib as L
     dev = torch.device("cuda:0")
@@ -138,14 +149,17 @@ def gpu_dqn_loss(logits, value, t_logits, t_value, o_logits, o_value, action, re
     d = dict(logits=up(logits, np.float32), value=up(value, np.float32), tl=up(t_logits, np.float32),
              tv=up(t_value, np.float32), ol=up(o_logits, np.float32), ov=up(o_value, np.float32),
              action=up(action, np.int32), reward=up(reward, np.float64), done=up(done, np.uint8),
-             slots=up(slots, np.int32))
+             slots=up(slots, np.int32), w=up(weights, np.float64), disc=up(disc, np.float64))
     nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
-    out = dict(dlogits=nan(rb, ra), dvalue=nan(rb), out=nan(4 + 2 * rb), y=nan(rb), maxq=nan(rb),
-               astar=torch.full((rb,), -1, dtype=torch.int32, device=dev))
-    rc = L.load().xt_dqn_loss(L.ptr(d["logits"]), L.ptr(d["value"]), L.ptr(d["tl"]), L.ptr(d["tv"]), L.ptr(d["ol"]),
-                              L.ptr(d["ov"]), b, a, int(dueling), L.ptr(d["slots"]), L.ptr(d["action"]),
-                              L.ptr(d["reward"]), L.ptr(d["done"]), ctypes.c_double(gamma), L.ptr(out["dlogits"]),
-                              L.ptr(out["dvalue"]), L.ptr(out["out"]), L.ptr(out["y"]), L.ptr(out["astar"]),
-                              L.ptr(out["maxq"]), L.ptr(acc), L.stream_ptr())
+    n = rb + pad
+    out = dict(dlogits=nan(n, ra), dvalue=nan(n), out=nan(4 + 2 * n + (1 if pad else 0)), y=nan(n), maxq=nan(n),
+               astar=torch.full((n,), -1, dtype=torch.int32, device=dev))
+    more = {"xt_dqn_loss": (), "xt_dqn_loss_w": (L.ptr(d["w"]),), "xt_dqn_loss_n": (L.ptr(d["w"]), L.ptr(d["disc"]))}[entry]
+    assert (weights is None or len(more) >= 1) and (disc is None or len(more) == 2), entry
+    rc = getattr(L.load(), entry)(L.ptr(d["logits"]), L.ptr(d["value"]), L.ptr(d["tl"]), L.ptr(d["tv"]), L.ptr(d["ol"]),
+                                  L.ptr(d["ov"]), b, a, int(dueling), L.ptr(d["slots"]), L.ptr(d["action"]),
+                                  L.ptr(d["reward"]), L.ptr(d["done"]), ctypes.c_double(gamma), L.ptr(out["dlogits"]),
+                                  L.ptr(out["dvalue"]), L.ptr(out["out"]), L.ptr(out["y"]), L.ptr(out["astar"]),
+                                  L.ptr(out["maxq"]), L.ptr(acc), *more, L.stream_ptr())
     torch.cuda.synchronize()
     return rc, {k: v.cpu().numpy() for k, v in out.items()}

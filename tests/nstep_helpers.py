@@ -13,8 +13,6 @@ import collections
 
 import numpy as np
 
-import dqn_helpers as H
-
 GAMMA = 0.99
 CAUSES = ("full", "done_start", "done_mid", "message_end")
 
@@ -141,48 +139,6 @@ def cause_counts(capacities=(7, 50), steps=(2, 3, 5), seed=11):
     return c
 
 
-# ----------------------------------------------------------------------------------------------- float64 head / step
-def dqn_loss_ref_n(disc, weights, logits, value, t_logits, t_value, o_logits, o_value, action, reward, done, dueling):
-    """``dqn_helpers.dqn_loss_ref`` with a per-sample discount ``disc`` [B] in gamma's place and, with ``weights`` not None,
-    Keras ``sample_weight`` (``per_helpers.dqn_loss_ref_w``)"""
-    dt = logits.dtype.type
-    b, a = logits.shape
-    rows = np.arange(b)
-    qt = H.q_from_heads(t_logits, t_value, dueling)
-    pick = qt if o_logits is None else H.q_from_heads(o_logits, o_value, dueling)
-    astar = np.argmax(pick, axis=1)
-    maxq = qt[rows, astar]
-    r = np.asarray(reward, np.float64).reshape(b)
-    y = np.where(np.asarray(done).reshape(b).astype(bool), r,
-                 r + np.asarray(disc, np.float64).reshape(b) * maxq.astype(np.float64)).astype(dt)
-    act = np.asarray(action).reshape(b).astype(np.int64)
-    delta = H.q_from_heads(logits, value, dueling)[rows, act] - y
-    w = np.ones(b, logits.dtype) if weights is None else np.asarray(weights, logits.dtype).reshape(b)
-    g = dt(2.0) * w * delta / dt(b * a)
-    hot = np.zeros((b, a), logits.dtype)
-    hot[rows, act] = 1
-    if dueling:
-        dlogits, dvalue = g[:, None] * (hot - dt(1.0) / dt(a)), g.copy()
-    else:
-        dlogits, dvalue = g[:, None] * hot, np.zeros(b, logits.dtype)
-    return dict(astar=astar, maxq=maxq, y=y, delta=delta, loss=(w * delta * delta).sum() / dt(b * a),
-                abs_td=np.abs(delta).mean(), mean_maxq=maxq.mean(), dlogits=dlogits, dvalue=dvalue)
-
-
-def oracle_step_n(orc, disc, weights, states, next_states, action, reward, done, apply=False):
-    """``DqnOracle.step`` with the per-sample discount (and importance weights, or None): ``next_states`` are the rows
-    of the boot slots, ``action`` / ``reward`` / ``done`` the labels of the walk"""
-    tl, tv = orc.target.forward(next_states)
-    ol, ov = orc.net.forward(next_states) if orc.double else (None, None)
-    lg, v = orc.net.forward(states)
-    flat = lambda x: None if x is None else x.reshape(-1)
-    out = dqn_loss_ref_n(disc, weights, lg, flat(v), tl, flat(tv), ol, flat(ov), action, reward, done, orc.dueling)
-    out["grads"] = orc.net.backward(out["dlogits"], out["dvalue"].reshape(-1, 1))
-    if apply:
-        orc.opt.apply(orc.net.params, out["grads"])
-    return out
-
-
 # ----------------------------------------------------------------------------------------------- C entries (GPU)
 def gpu_gather_nstep(replay, slots, n, gamma=GAMMA, follow="ring", labels=True, b=None):
     """-> (rc, dst, dict of the five label tensors): xt_replay_gather_nstep on a filled ``DeviceReplay``; ``dst`` starts
@@ -207,30 +163,6 @@ def gpu_gather_nstep(replay, slots, n, gamma=GAMMA, follow="ring", labels=True, 
                                          L.stream_ptr())
     torch.cuda.synchronize()
     return rc, dst, lab
-
-
-def gpu_dqn_loss_n(logits, value, t_logits, t_value, o_logits, o_value, action, reward, done, gamma, dueling, weights, disc):
-    """-> (rc, dict of device tensors): xt_dqn_loss_n on host inputs (``weights`` / ``disc`` None: NULL); outputs start as
-    NaN / -1"""
-    import torch
-    from xingtian_amd import lib as L
-    dev = torch.device("cuda:0")
-    up = lambda x, dt: None if x is None else torch.from_numpy(np.ascontiguousarray(x, dtype=dt)).to(dev)
-    b, a = logits.shape
-    d = dict(logits=up(logits, np.float32), value=up(value, np.float32), tl=up(t_logits, np.float32),
-             tv=up(t_value, np.float32), ol=up(o_logits, np.float32), ov=up(o_value, np.float32),
-             action=up(action, np.int32), reward=up(reward, np.float64), done=up(done, np.uint8),
-             w=up(weights, np.float64), disc=up(disc, np.float64))
-    nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
-    out = dict(dlogits=nan(b, a), dvalue=nan(b), out=nan(4 + 2 * b), y=nan(b), maxq=nan(b),
-               astar=torch.full((b,), -1, dtype=torch.int32, device=dev))
-    rc = L.load().xt_dqn_loss_n(L.ptr(d["logits"]), L.ptr(d["value"]), L.ptr(d["tl"]), L.ptr(d["tv"]), L.ptr(d["ol"]),
-                                L.ptr(d["ov"]), b, a, int(dueling), None, L.ptr(d["action"]), L.ptr(d["reward"]),
-                                L.ptr(d["done"]), ctypes.c_double(gamma), L.ptr(out["dlogits"]), L.ptr(out["dvalue"]),
-                                L.ptr(out["out"]), L.ptr(out["y"]), L.ptr(out["astar"]), L.ptr(out["maxq"]), None,
-                                L.ptr(d["w"]), L.ptr(d["disc"]), L.stream_ptr())
-    torch.cuda.synchronize()
-    return rc, out
 
 
 class CountingLib(object):

@@ -14,8 +14,6 @@ import os
 
 import numpy as np
 
-import dqn_helpers as H
-
 INF = float("inf")
 
 
@@ -176,30 +174,6 @@ def rel_err(got, ref):
     return float((np.abs(got - ref) / np.abs(ref)).max())
 
 
-# ----------------------------------------------------------------------------------------------- weighted loss
-def dqn_loss_ref_w(weights, *args, **kwargs):
-    """``dqn_helpers.dqn_loss_ref`` under Keras ``sample_weight``: L = sum_b w_b delta_b^2 / (B A), the head gradients
-    scaled by w_b; the means of |delta| and of the bootstrap value stay unweighted"""
-    out = H.dqn_loss_ref(*args, **kwargs)
-    w = np.asarray(weights, out["delta"].dtype).reshape(-1)
-    b, a = out["dlogits"].shape
-    out["loss"] = (w * out["delta"] * out["delta"]).sum() / out["delta"].dtype.type(b * a)
-    out["dlogits"] = out["dlogits"] * w[:, None]
-    out["dvalue"] = out["dvalue"] * w
-    return out
-
-
-def oracle_step_w(orc, weights, states, next_states, action, reward, done):
-    """``DqnOracle.step(apply=False)`` with importance weights"""
-    tl, tv = orc.target.forward(next_states)
-    ol, ov = orc.net.forward(next_states) if orc.double else (None, None)
-    lg, v = orc.net.forward(states)
-    flat = lambda x: None if x is None else x.reshape(-1)
-    out = dqn_loss_ref_w(weights, lg, flat(v), tl, flat(tv), ol, flat(ov), action, reward, done, orc.gamma, orc.dueling)
-    out["grads"] = orc.net.backward(out["dlogits"], out["dvalue"].reshape(-1, 1))
-    return out
-
-
 # ----------------------------------------------------------------------------------------------- C entries (GPU)
 class GpuTrees(object):
     """sum / min trees and max_prio on cuda:0 with thin callers of xt_per_add / xt_per_update / xt_per_sample"""
@@ -267,26 +241,3 @@ def assert_trees_follow_from_their_leaves(sum_tree, min_tree):
     ref_s, ref_m = build_trees(sum_tree[cap2:], min_tree[cap2:])
     assert sum_tree[1:] == ref_s[1:]
     assert min_tree[1:] == ref_m[1:]
-
-
-def gpu_dqn_loss_w(logits, value, t_logits, t_value, o_logits, o_value, action, reward, done, gamma, dueling, weights):
-    """-> (rc, dict of device tensors): xt_dqn_loss_w on host inputs (``weights`` None: NULL); outputs start as NaN / -1"""
-    import torch
-    from xingtian_amd import lib as L
-    dev = torch.device("cuda:0")
-    up = lambda x, dt: None if x is None else torch.from_numpy(np.ascontiguousarray(x, dtype=dt)).to(dev)
-    b, a = logits.shape
-    d = dict(logits=up(logits, np.float32), value=up(value, np.float32), tl=up(t_logits, np.float32),
-             tv=up(t_value, np.float32), ol=up(o_logits, np.float32), ov=up(o_value, np.float32),
-             action=up(action, np.int32), reward=up(reward, np.float64), done=up(done, np.uint8),
-             w=up(weights, np.float64))
-    nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
-    out = dict(dlogits=nan(b, a), dvalue=nan(b), out=nan(4 + 2 * b), y=nan(b), maxq=nan(b),
-               astar=torch.full((b,), -1, dtype=torch.int32, device=dev))
-    rc = L.load().xt_dqn_loss_w(L.ptr(d["logits"]), L.ptr(d["value"]), L.ptr(d["tl"]), L.ptr(d["tv"]), L.ptr(d["ol"]),
-                                L.ptr(d["ov"]), b, a, int(dueling), None, L.ptr(d["action"]), L.ptr(d["reward"]),
-                                L.ptr(d["done"]), ctypes.c_double(gamma), L.ptr(out["dlogits"]), L.ptr(out["dvalue"]),
-                                L.ptr(out["out"]), L.ptr(out["y"]), L.ptr(out["astar"]), L.ptr(out["maxq"]), None,
-                                L.ptr(d["w"]), L.stream_ptr())
-    torch.cuda.synchronize()
-    return rc, out

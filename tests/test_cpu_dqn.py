@@ -330,3 +330,23 @@ def test_abi_header_signatures_and_exported_symbols_agree_for_the_new_entries():
         names += [n.strip(" *") for n in decl.split(None, 1)[1].split(",")]
     assert names == [n for n, _ in L.DqnCfg._fields_]
     assert ctypes.sizeof(L.DqnCfg) == 8 + 4 + 4 + 3 * 8
+
+
+# ------------------------------------------------------------------------------------------------ the one reference head
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("dueling,double", [(False, False), (True, True)])
+def test_dqn_loss_ref_without_weights_and_discounts_is_the_unit_weight_scalar_gamma_form_bit_for_bit(dtype, dueling, double):
+    """``weights=None`` is a weight of one and ``disc=None`` is gamma in every row: a product with one is exact, so the
+    weighted, per-sample-discount arithmetic of the single reference leaves the plain head's bits alone"""
+    for seed in range(8):
+        rng = np.random.default_rng(seed)
+        b, a = int(rng.integers(1, 40)), int(rng.integers(1, 19))
+        f = lambda *s: rng.standard_normal(s).astype(dtype)
+        heads = [f(b, a), f(b), f(b, a) * 2, f(b), f(b, a) * 2 if double else None, f(b) if double else None]
+        labels = (rng.integers(0, a, b), rng.standard_normal(b), rng.random(b) < 0.3, 0.99, dueling)
+        plain = H.dqn_loss_ref(*heads, *labels)
+        unit = H.dqn_loss_ref(*heads, *labels, np.ones(b), np.full(b, 0.99))
+        for k, v in plain.items():
+            assert np.asarray(v).dtype == np.asarray(unit[k]).dtype and np.asarray(v).tobytes() == np.asarray(unit[k]).tobytes(), k
+        weighted = H.dqn_loss_ref(*heads, *labels, rng.uniform(0.05, 1.0, b))
+        assert np.array_equal(weighted["delta"], plain["delta"]) and weighted["abs_td"] == plain["abs_td"]

@@ -224,8 +224,8 @@ def test_wide_heads_forward_and_every_gradient_tensor_against_float64(L, a, n, b
     # 32 float32 products per logit: the error is at most 32 * 2^-24 = 2e-6 of sum |f w|, itself a few times the largest logit
     assert logits.shape == (b, a * n) and H.rel_max(logits, ref["logits"]) <= 1e-5
     net.grads.fill_(float("nan"))
-    out = net.dqn_step_dist(target, ring.cur_state, ring.next_state, torch.from_numpy(slots).cuda(), ring.action,
-                            ring.reward, ring.done, GAMMA, True)
+    out = net.dqn_step(target, ring.cur_state, ring.next_state, torch.from_numpy(slots).cuda(), ring.action,
+                       ring.reward, ring.done, GAMMA, False, True, dist=True)
     torch.cuda.synchronize()
     grads = net.grads_dict()
     for k, g in grads.items():
@@ -306,8 +306,8 @@ def test_net_dqn_step_dist_against_float64(L, kind, variant, wide):
                             h(ring.done)[s])
     boot_of = lambda s: labels(s)[0]
     p_pick = p_on if double else p_tg
-    kw = dict(follow=ring.follow, n=n_step) if n_step > 1 else {}
-    args = (ring.action, ring.reward, ring.done, GAMMA, double)
+    kw = dict(follow=ring.follow, n=n_step, dist=True) if n_step > 1 else dict(dist=True)
+    args = (ring.action, ring.reward, ring.done, GAMMA, False, double)
     ok = _ok_slots(kind, a_dim, atoms, ospec, p_on, p_pick, "online" if double else "target", boot_of)
     assert len(ok) >= b
     if prioritised:
@@ -322,14 +322,14 @@ def test_net_dqn_step_dist_against_float64(L, kind, variant, wide):
         terms = torch.full((2 * b,), float("nan"), dtype=torch.float32, device="cuda")
         per = dict(size=CAP, u=up(u), sum_tree=t.sum, min_tree=t.min, max_prio=t.max_prio, alpha=alpha, beta=beta, eps=EPS,
                    terms_out=terms)
-        out = net.dqn_step_dist(target, ring.cur_state, ring.next_state, None, *args, per=per, **kw)
+        out = net.dqn_step(target, ring.cur_state, ring.next_state, None, *args, per=per, **kw)
         torch.cuda.synchronize()
         _, ref_slots, ref_w = P.sample(s0, m0, CAP, u.tolist(), beta)
         slots, w = net.per_slots[:b].cpu().numpy(), net.per_weights[:b].cpu().numpy()
         assert slots.tolist() == ref_slots and P.rel_err(w, ref_w) <= 1e-12
     else:
         slots, w = rng.permutation(ok)[:b], None
-        out = net.dqn_step_dist(target, ring.cur_state, ring.next_state, up(slots), *args, **kw)
+        out = net.dqn_step(target, ring.cur_state, ring.next_state, up(slots), *args, **kw)
         torch.cuda.synchronize()
     boot, act, rew, disc, done = labels(slots)
     if n_step > 1:                                            # the five labels the gather left: the host's, bit for bit
@@ -374,10 +374,10 @@ def test_net_dqn_step_dist_refusals_and_the_scalar_entries_on_a_marked_net(L):
         net.dqn_step(target, *args, False, False)
     target.set_dist(51, V_MIN, 20.0)
     with pytest.raises(RuntimeError, match="same atoms and bounds"):
-        net.dqn_step_dist(target, *args, False)
+        net.dqn_step(target, *args, False, False, dist=True)
     target.set_dist(1, 0.0, 0.0)
     with pytest.raises(RuntimeError, match="same atoms and bounds"):
-        net.dqn_step_dist(target, *args, False)
+        net.dqn_step(target, *args, False, False, dist=True)
     with pytest.raises(RuntimeError, match="no multiple of atoms"):
         target.set_dist(50, V_MIN, V_MAX)
     with pytest.raises(RuntimeError, match="finite v_min < v_max"):
@@ -387,7 +387,7 @@ def test_net_dqn_step_dist_refusals_and_the_scalar_entries_on_a_marked_net(L):
     torch.cuda.synchronize()
     assert not bool(net.grads.any())                          # nothing was launched
     target.set_dist(51, V_MIN, V_MAX)
-    net.dqn_step_dist(target, *args, False)
+    net.dqn_step(target, *args, False, False, dist=True)
     torch.cuda.synchronize()
     assert bool(net.grads.any())
 

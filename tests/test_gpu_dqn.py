@@ -266,6 +266,82 @@ def test_net_dqn_step_refusals(L):
     assert "data parallelism" in str(info.value)
 
 
+DQN_ENTRIES = ("xt_net_dqn_step", "xt_net_dqn_step_per", "xt_net_dqn_step_n", "xt_net_dqn_step_dist")
+
+
+def _dispatch_case(per, follow, dist):
+    """-> (net with a counting lib, positional arguments of ``dqn_step`` up to double_dqn, its keywords, trees or None):
+    DqnMlp state 4, hidden 32, A = 2 (atoms 3 if ``dist``), ring capacity 50, B = 4"""
+    import nstep_helpers as N
+    import per_helpers as P
+    from xingtian_amd.model import netspec
+    from xingtian_amd.model.hip_net import HipActorCritic
+    cap, b, a_dim, atoms = 50, 4, 2, 3
+    spec = netspec.dqn_mlp((4,), a_dim, 32, 1, False, atoms if dist else 1)
+    net, target = HipActorCritic(spec, max_batch=b, seed=0), HipActorCritic(spec, max_batch=b, seed=1)
+    if dist:
+        net.set_dist(atoms, -10.0, 10.0)
+        target.set_dist(atoms, -10.0, 10.0)
+    rng = np.random.default_rng(4 * per + 2 * follow + dist)
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    cur, nxt = net.to_device_obs(_states("mlp", rng, cap)), net.to_device_obs(_states("mlp", rng, cap))
+    labels = (up(rng.integers(0, a_dim, cap).astype(np.int32)), up(rng.standard_normal(cap)),
+              up((rng.random(cap) < 0.1).astype(np.uint8)))
+    kw, t = dict(dist=dist), None
+    if follow:                                                           # messages of five rows
+        kw.update(follow=up((4 - np.arange(cap) % 5).astype(np.int32)), n=3)
+    if per:
+        t = P.GpuTrees(cap, 0.6)
+        assert t.add(0, cap) == 0
+        kw.update(per=dict(size=cap, u=up(rng.random(b)), sum_tree=t.sum, min_tree=t.min, max_prio=t.max_prio, alpha=0.6,
+                           beta=0.4, eps=1e-6))
+    slots = None if per else up(rng.permutation(cap)[:b].astype(np.int32))
+    net.lib = N.CountingLib(net.lib)
+    net.grads.zero_()
+    return net, (target, cur, nxt, slots, *labels, GAMMA, False, False), kw, t
+
+
+@pytest.mark.parametrize("dist", [False, True])
+@pytest.mark.parametrize("follow", [False, True])
+@pytest.mark.parametrize("per", [False, True])
+def test_net_dqn_step_reaches_the_entry_its_arguments_name(L, per, follow, dist):
+    """the dispatch table of ``HipActorCritic.dqn_step``: dist, else follow, else per, else the plain entry"""
+    net, args, kw, _ = _dispatch_case(per, follow, dist)
+    out = net.dqn_step(*args, **kw)
+    torch.cuda.synchronize()
+    want = DQN_ENTRIES[3 if dist else 2 if follow else 1 if per else 0]
+    assert {e: net.lib.calls[e] for e in DQN_ENTRIES} == {e: int(e == want) for e in DQN_ENTRIES}
+    assert out is net.loss_out and bool(torch.isfinite(out).all())
+    assert bool(net.grads.any())
+    assert hasattr(net, "nstep_boot") == follow and hasattr(net, "per_slots") == per
+
+
+@pytest.mark.parametrize("name", ["dqn_step_per", "dqn_step_n", "dqn_step_dist"])
+def test_net_dqn_step_earlier_names_forward_to_it(L, name):
+    """``dqn_step_per`` / ``dqn_step_n`` / ``dqn_step_dist`` with their old argument order are ``dqn_step``: the same C
+    entry and, for the two that move no priority tree here, the same bits in ``loss_out`` and the gradient"""
+    per, follow, dist = name == "dqn_step_per", name == "dqn_step_n", name == "dqn_step_dist"
+    net, args, kw, t = _dispatch_case(per, follow, dist)
+    first = net.dqn_step(*args, **kw).clone()
+    grads = net.grads.clone()
+    net.grads.zero_()
+    target, cur, nxt, slots, action, reward, done = args[:7]
+    if per:
+        again = net.dqn_step_per(target, cur, nxt, 50, kw["per"]["u"], action, reward, done, GAMMA, False, False, t.sum, t.min,
+                                 t.max_prio, 0.6, 0.4, 1e-6)
+    elif follow:
+        again = net.dqn_step_n(target, cur, nxt, slots, action, reward, done, kw["follow"], 3, GAMMA, False, False)
+    else:
+        again = net.dqn_step_dist(target, cur, nxt, slots, action, reward, done, GAMMA, False)
+    torch.cuda.synchronize()
+    want = "xt_net_" + name
+    assert {e: net.lib.calls[e] for e in DQN_ENTRIES} == {e: 2 * int(e == want) for e in DQN_ENTRIES}
+    assert again is net.loss_out and bool(torch.isfinite(again).all()) and bool(net.grads.any())
+    if not per:
+        assert torch.equal(again.view(torch.int32), first.view(torch.int32))
+        assert torch.equal(net.grads.view(torch.int32), grads.view(torch.int32))
+
+
 # ------------------------------------------------------------------------------------------------ alg_builder("DQN")
 def _messages(kind, rng, a_dim, n_msg=3, rows=20):
     msgs = []

@@ -221,7 +221,9 @@ def test_dqn_loss_w_launch_shapes_against_the_float32_twin_and_float64(L, c):
     d, slots = loss_data(c)
     b, a = c.b, c.a
     assert c.blocks == (b + 255) // 256
-    rc, got = B.gpu_dqn_loss_w(d, c.dueling, c.double, GAMMA, c.weighted, slots)
+    rc, got = H.gpu_dqn_loss(d["logits"], d["value"], d["t_logits"], d["t_value"], d["o_logits"] if c.double else None,
+                             d["o_value"] if c.double else None, d["action"], d["reward"], d["done"], GAMMA, c.dueling,
+                             entry="xt_dqn_loss_w", slots=slots, weights=d["w"] if c.weighted else None, pad=B.PAD)
     assert rc == 0
     # what the launch does not own keeps its sentinels: the rows behind B, out[3], out behind the terms
     for k in ("dlogits", "dvalue", "y", "maxq"):
@@ -474,8 +476,10 @@ def test_net_dqn_steps_at_320_rows_against_float64(L, c):
     s0, m0, max0 = t.read()
     u = d["u"]
     terms = torch.full((2 * b,), float("nan"), dtype=torch.float32, device="cuda")
-    out = net.dqn_step_per(target, net.to_device_obs(cur), net.to_device_obs(nxt), cap, up(u), up(action), up(reward),
-                           up(done), GAMMA, c.dueling, c.double, t.sum, t.min, t.max_prio, alpha, beta, EPS, terms_out=terms)
+    per = dict(size=cap, u=up(u), sum_tree=t.sum, min_tree=t.min, max_prio=t.max_prio, alpha=alpha, beta=beta, eps=EPS,
+               terms_out=terms)
+    out = net.dqn_step(target, net.to_device_obs(cur), net.to_device_obs(nxt), None, up(action), up(reward), up(done),
+                       GAMMA, c.dueling, c.double, per=per)
     torch.cuda.synchronize()
     # the draw: the restatement on the tree as it was before the step
     _, ref_slots, ref_w = P.sample(s0, m0, cap, u.tolist(), beta)
@@ -483,7 +487,7 @@ def test_net_dqn_steps_at_320_rows_against_float64(L, c):
     assert slots.tolist() == ref_slots and P.rel_err(w, ref_w) <= 1e-12
     assert len(set(ref_slots)) < b                                         # equal slots within the batch
     batch = (cur[slots], nxt[slots], action[slots], reward[slots], done[slots])
-    ref, ref32 = P.oracle_step_w(orc, w, *batch), P.oracle_step_w(orc32, w, *batch)
+    ref, ref32 = orc.step(*batch, w, apply=False), orc32.step(*batch, w, apply=False)
     _assert_step(c, float(out.cpu().numpy()[0]), net.grads_dict(), ref, ref32, spec, ospec)
     delta = terms.cpu().numpy()[0::2]
     assert H.rel_max(delta, ref["delta"]) <= 1e-5

@@ -134,13 +134,12 @@ def _heads(d, double):
 def test_dqn_loss_n_against_float64_and_its_two_bit_twins(L, b, a, dueling, double, weighted):
     d = _loss_inputs(b, a, 100 * b + a + 2 * dueling + double)
     w = d["w"] if weighted else None
-    rc, got_t = N.gpu_dqn_loss_n(*_heads(d, double), dueling, w, d["disc"])
+    rc, got = H.gpu_dqn_loss(*_heads(d, double), dueling, entry="xt_dqn_loss_n", weights=w, disc=d["disc"])
     assert rc == 0
-    got = {k: v.cpu().numpy() for k, v in got_t.items()}
     f64 = lambda x: None if x is None else np.asarray(x, np.float64)
     heads = [f64(x) for x in _heads(d, double)[:6]]
-    ref = N.dqn_loss_ref_n(d["disc"], w, *heads, d["action"], d["reward"], d["done"], dueling)
-    flat = N.dqn_loss_ref_n(np.full(b, GAMMA), w, *heads, d["action"], d["reward"], d["done"], dueling)
+    ref = H.dqn_loss_ref(*heads, d["action"], d["reward"], d["done"], GAMMA, dueling, w, d["disc"])
+    flat = H.dqn_loss_ref(*heads, d["action"], d["reward"], d["done"], GAMMA, dueling, w, np.full(b, GAMMA))
     out = got["out"]
     print("dqn_loss_n: loss", out[0], ref["loss"], "| dlogits", H.rel_max(got["dlogits"], ref["dlogits"]),
           "| maxq", H.rel_max(got["maxq"], ref["maxq"]))
@@ -159,13 +158,13 @@ def test_dqn_loss_n_against_float64_and_its_two_bit_twins(L, b, a, dueling, doub
     else:
         assert not got["dvalue"].any()
     # disc == NULL is xt_dqn_loss_w; disc filled with gamma is the scalar-gamma call: bit for bit
-    rc0, plain = P.gpu_dqn_loss_w(*_heads(d, double), dueling, w)
-    rc1, null = N.gpu_dqn_loss_n(*_heads(d, double), dueling, w, None)
-    rc2, filled = N.gpu_dqn_loss_n(*_heads(d, double), dueling, w, np.full(b, GAMMA))
+    rc0, plain = H.gpu_dqn_loss(*_heads(d, double), dueling, entry="xt_dqn_loss_w", weights=w)
+    rc1, null = H.gpu_dqn_loss(*_heads(d, double), dueling, entry="xt_dqn_loss_n", weights=w)
+    rc2, filled = H.gpu_dqn_loss(*_heads(d, double), dueling, entry="xt_dqn_loss_n", weights=w, disc=np.full(b, GAMMA))
     assert rc0 == 0 and rc1 == 0 and rc2 == 0
     for k, v in plain.items():
-        assert torch.equal(_bits(null[k]), _bits(v)), k                    # (out[3] is never written: NaN bits on both sides)
-        assert torch.equal(_bits(filled[k]), _bits(v)), k
+        assert null[k].tobytes() == v.tobytes(), k                         # (out[3] is never written: NaN bits on both sides)
+        assert filled[k].tobytes() == v.tobytes(), k
 
 
 # ------------------------------------------------------------------------------------------------ xt_net_dqn_step_n
@@ -276,7 +275,7 @@ def test_net_dqn_step_n_against_float64(L, kind, b, dueling, double, prioritised
     ring, store, cur, nxt = _filled_replay(kind, net, a_dim)
     rng = np.random.default_rng(b + 2 * dueling + double)
     up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    args = (ring.action, ring.reward, ring.done, ring.follow, n, GAMMA, dueling, double)
+    args = (ring.action, ring.reward, ring.done, GAMMA, dueling, double, ring.follow, n)
     if prioritised:
         t = _primed_trees(CAP, alpha, rng)
         s0, m0, max0 = t.read()
@@ -286,14 +285,14 @@ def test_net_dqn_step_n_against_float64(L, kind, b, dueling, double, prioritised
             return P.sample(s0, m0, CAP, u.tolist(), beta)[1], u
         _, u = _well_conditioned(kind, a_dim, draw)
         terms = torch.full((2 * b,), float("nan"), dtype=torch.float32, device="cuda")
-        out = net.dqn_step_n(target, ring.cur_state, ring.next_state, None, *args, per=_per_kw(t, up(u), alpha, beta, terms))
+        out = net.dqn_step(target, ring.cur_state, ring.next_state, None, *args, per=_per_kw(t, up(u), alpha, beta, terms))
         torch.cuda.synchronize()
         _, ref_slots, ref_w = P.sample(s0, m0, CAP, u.tolist(), beta)
         slots, w = net.per_slots[:b].cpu().numpy(), net.per_weights[:b].cpu().numpy()
         assert slots.tolist() == ref_slots and P.rel_err(w, ref_w) <= 1e-12
     else:
         slots, w = _well_conditioned(kind, a_dim, lambda: (rng.permutation(CAP)[:b].astype(np.int32), None))
-        out = net.dqn_step_n(target, ring.cur_state, ring.next_state, up(slots), *args)
+        out = net.dqn_step(target, ring.cur_state, ring.next_state, up(slots), *args)
         torch.cuda.synchronize()
     # the labels the gather left: the host's, bit for bit; the brute force agrees on boot slot, action and done
     boot, act_n, rew_n, disc_n, done_n = nstep_targets(slots, *N.host_rings(ring), GAMMA, n, CAP)
@@ -306,8 +305,8 @@ def test_net_dqn_step_n_against_float64(L, kind, b, dueling, double, prioritised
     assert (boot != slots).any() and len(set(disc_n.tolist())) > 1
     # loss and gradient: the float64 oracle on the start rows, the boot rows and those labels
     orc = H.DqnOracle(ospec, p_on, p_tg, dueling, double, GAMMA, lr=3e-4, dtype=np.float64)
-    ref = N.oracle_step_n(orc, disc_n, w, np.stack([cur[s] for s in slots]), np.stack([nxt[j] for j in boot]), act_n,
-                          rew_n, done_n)
+    ref = orc.step(np.stack([cur[s] for s in slots]), np.stack([nxt[j] for j in boot]), act_n, rew_n, done_n, w, disc_n,
+                   apply=False)
     _assert_step(float(out.cpu().numpy()[0]), net.grads_dict(), ref, spec, ospec)
     assert torch.equal(target.params, target_before) and not bool(target.grads.any())     # the target net is forward only
     if not prioritised:
@@ -346,7 +345,7 @@ def test_net_dqn_step_n_with_one_step_is_the_one_step_entries_bit_for_bit(L, kin
     out = net.dqn_step(target, *rings, slots, *labels, GAMMA, dueling, double).clone()
     grads = net.grads.clone()
     net.grads.zero_()
-    out_n = net.dqn_step_n(target, *rings, slots, *labels, ring.follow, 1, GAMMA, dueling, double).clone()
+    out_n = net.dqn_step(target, *rings, slots, *labels, GAMMA, dueling, double, ring.follow, 1).clone()
     torch.cuda.synchronize()
     assert torch.equal(_bits(out_n), _bits(out)) and torch.equal(_bits(net.grads), _bits(grads))
     assert bool(grads.any()) and torch.equal(net.nstep_boot[:b], slots)
@@ -354,11 +353,10 @@ def test_net_dqn_step_n_with_one_step_is_the_one_step_entries_bit_for_bit(L, kin
     u = torch.from_numpy(rng.random(b)).cuda()
     ta, tb = _primed_trees(CAP, 0.6, np.random.default_rng(1)), _primed_trees(CAP, 0.6, np.random.default_rng(1))
     assert torch.equal(ta.sum, tb.sum)
-    out = net.dqn_step_per(target, *rings, CAP, u, *labels, GAMMA, dueling, double, ta.sum, ta.min, ta.max_prio, 0.6, 0.4,
-                           EPS).clone()
+    out = net.dqn_step(target, *rings, None, *labels, GAMMA, dueling, double, per=_per_kw(ta, u)).clone()
     grads = net.grads.clone()
     net.grads.zero_()
-    out_n = net.dqn_step_n(target, *rings, None, *labels, ring.follow, 1, GAMMA, dueling, double, per=_per_kw(tb, u)).clone()
+    out_n = net.dqn_step(target, *rings, None, *labels, GAMMA, dueling, double, ring.follow, 1, per=_per_kw(tb, u)).clone()
     torch.cuda.synchronize()
     assert torch.equal(_bits(out_n), _bits(out)) and torch.equal(_bits(net.grads), _bits(grads))
     assert torch.equal(_bits(tb.sum), _bits(ta.sum)) and torch.equal(_bits(tb.min), _bits(ta.min))
@@ -375,8 +373,8 @@ def test_net_dqn_step_n_refusals_change_no_buffer(L):
     t = _primed_trees(CAP, 0.6, np.random.default_rng(0))
     u = torch.full((4,), 0.5, dtype=torch.float64, device="cuda")
     labels = (ring.action, ring.reward, ring.done)
-    net.dqn_step_n(target, ring.cur_state, ring.next_state, None, *labels, ring.follow, 3, GAMMA, False, False,
-                   per=_per_kw(t, u))                                       # allocates every scratch buffer; a good call
+    net.dqn_step(target, ring.cur_state, ring.next_state, None, *labels, GAMMA, False, False, ring.follow, 3,
+                 per=_per_kw(t, u))                                         # allocates every scratch buffer; a good call
     torch.cuda.synchronize()
     _, row_bytes, cfg = net._dqn_cfg("test", ring.cur_state, ring.next_state, {"slots": slots}, *labels, GAMMA, False, False)
     _, per = net._per_cfg("test", u, t.sum, t.min, t.max_prio, 0.6, 0.4, EPS)
@@ -410,7 +408,7 @@ def test_net_dqn_step_n_refusals_change_no_buffer(L):
         assert call(with_per=with_per) != 0
         assert "data parallelism" in L.load().xt_last_error().decode()
     with pytest.raises(RuntimeError) as info:
-        net.dqn_step_n(target, ring.cur_state, ring.next_state, slots, *labels, ring.follow, 3, GAMMA, False, False)
+        net.dqn_step(target, ring.cur_state, ring.next_state, slots, *labels, GAMMA, False, False, ring.follow, 3)
     assert "data parallelism" in str(info.value) and "xt_net_dqn_step_n" in str(info.value)
     torch.cuda.synchronize()
     for x, was in zip(watched, before):
@@ -491,11 +489,11 @@ def test_dqn_algorithm_with_n_step_four_trains_against_the_oracle(L, kind, dueli
         brute, _ = store.targets(slots.tolist(), 3)
         for got, want in zip((boot, act_n, rew_n, disc_n, done_n), brute):
             assert np.array_equal(got, want)
-        batch_args = (disc_n, w, np.stack([cur[s] for s in slots]), np.stack([nxt[j] for j in boot]), act_n, rew_n, done_n)
+        batch_args = (np.stack([cur[s] for s in slots]), np.stack([nxt[j] for j in boot]), act_n, rew_n, done_n, w, disc_n)
         if t == 1:
-            _assert_step(loss, net.grads_dict(), N.oracle_step_n(orc, *batch_args), spec, ospec)
-        ref = N.oracle_step_n(orc, *batch_args, apply=True)
-        N.oracle_step_n(orc32, *batch_args, apply=True)
+            _assert_step(loss, net.grads_dict(), orc.step(*batch_args, apply=False), spec, ospec)
+        ref = orc.step(*batch_args, apply=True)
+        orc32.step(*batch_args, apply=True)
         print("dqn n-step train", t, "loss", loss, float(ref["loss"]))
         assert abs(loss - ref["loss"]) <= 1e-4 * max(1.0, abs(ref["loss"])), (t, loss, ref["loss"])
         if t % 3 == 0:

@@ -190,12 +190,10 @@ def _heads(d, double):
 def test_dqn_loss_w_without_weights_is_xt_dqn_loss_bit_for_bit(L, b, a, dueling, double):
     d = _loss_inputs(b, a, 7 * b + a)
     rc0, plain = H.gpu_dqn_loss(*_heads(d, double), dueling)
-    rc1, got = P.gpu_dqn_loss_w(*_heads(d, double), dueling, None)
+    rc1, got = H.gpu_dqn_loss(*_heads(d, double), dueling, entry="xt_dqn_loss_w")
     assert rc0 == 0 and rc1 == 0
     for k, v in got.items():
-        want = torch.from_numpy(plain[k]).cuda()
-        bits = lambda x: x.view(torch.int32)
-        assert torch.equal(bits(v), bits(want)), k                         # (out[3] is never written: NaN bits on both sides)
+        assert v.tobytes() == plain[k].tobytes(), k                        # (out[3] is never written: NaN bits on both sides)
 
 
 @pytest.mark.parametrize("double", [False, True])
@@ -204,12 +202,11 @@ def test_dqn_loss_w_without_weights_is_xt_dqn_loss_bit_for_bit(L, b, a, dueling,
 @pytest.mark.parametrize("b", [5, 32])
 def test_dqn_loss_w_against_float64(L, b, a, dueling, double):
     d = _loss_inputs(b, a, 100 * b + a + 2 * dueling + double)
-    rc, got = P.gpu_dqn_loss_w(*_heads(d, double), dueling, d["w"])
+    rc, got = H.gpu_dqn_loss(*_heads(d, double), dueling, entry="xt_dqn_loss_w", weights=d["w"])
     assert rc == 0
-    got = {k: v.cpu().numpy() for k, v in got.items()}
     f64 = lambda x: None if x is None else np.asarray(x, np.float64)
     heads = [f64(x) for x in _heads(d, double)[:6]]
-    ref = P.dqn_loss_ref_w(d["w"], *heads, d["action"], d["reward"], d["done"], GAMMA, dueling)
+    ref = H.dqn_loss_ref(*heads, d["action"], d["reward"], d["done"], GAMMA, dueling, d["w"])
     plain = H.dqn_loss_ref(*heads, d["action"], d["reward"], d["done"], GAMMA, dueling)
     out = got["out"]
     print("dqn_loss_w: loss", out[0], ref["loss"], "| dlogits", H.rel_max(got["dlogits"], ref["dlogits"]))
@@ -285,8 +282,10 @@ def test_net_dqn_step_per_against_float64(L, kind, b, dueling, double):
     u = rng.random(b)
     up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
     terms = torch.full((2 * b,), float("nan"), dtype=torch.float32, device="cuda")
-    out = net.dqn_step_per(target, net.to_device_obs(cur), net.to_device_obs(nxt), size, up(u), up(action), up(reward),
-                           up(done), GAMMA, dueling, double, t.sum, t.min, t.max_prio, alpha, beta, EPS, terms_out=terms)
+    per = dict(size=size, u=up(u), sum_tree=t.sum, min_tree=t.min, max_prio=t.max_prio, alpha=alpha, beta=beta, eps=EPS,
+               terms_out=terms)
+    out = net.dqn_step(target, net.to_device_obs(cur), net.to_device_obs(nxt), None, up(action), up(reward), up(done),
+                       GAMMA, dueling, double, per=per)
     torch.cuda.synchronize()
     # the draw: the restatement on the tree as it was before the step
     _, ref_slots, ref_w = P.sample(s0, m0, size, u.tolist(), beta)
@@ -294,7 +293,7 @@ def test_net_dqn_step_per_against_float64(L, kind, b, dueling, double):
     assert slots.tolist() == ref_slots and P.rel_err(w, ref_w) <= 1e-12
     # loss and gradient on those slots with those weights
     orc = H.DqnOracle(ospec, p_on, p_tg, dueling, double, GAMMA, lr=3e-4, dtype=np.float64)
-    ref = P.oracle_step_w(orc, w, cur[slots], nxt[slots], action[slots], reward[slots], done[slots])
+    ref = orc.step(cur[slots], nxt[slots], action[slots], reward[slots], done[slots], w, apply=False)
     _assert_step(float(out.cpu().numpy()[0]), net.grads_dict(), ref, spec, ospec)
     delta = terms.cpu().numpy()[0::2]
     assert H.rel_max(delta, ref["delta"]) <= 1e-5
@@ -326,8 +325,8 @@ def test_net_dqn_step_per_refusals_are_the_uniform_step_s(L):
     t = _primed_trees(10, 10, 0.6, np.random.default_rng(0))
     before = t.read()
     u = torch.full((4,), 0.5, dtype=torch.float64, device="cuda")
-    step = lambda tgt, rg, uu, size=10: net.dqn_step_per(tgt, rg, rg, size, uu, *lab, GAMMA, False, False, t.sum, t.min,
-                                                         t.max_prio, 0.6, 0.4, EPS)
+    step = lambda tgt, rg, uu, size=10: net.dqn_step(tgt, rg, rg, None, *lab, GAMMA, False, False, per=dict(
+        size=size, u=uu, sum_tree=t.sum, min_tree=t.min, max_prio=t.max_prio, alpha=0.6, beta=0.4, eps=EPS))
     for tgt, rg, uu, word in ((net, ring, u, "own parameter buffers"), (other, ring, u, "same description"),
                               (target, ring, torch.full((9,), 0.5, dtype=torch.float64, device="cuda"), "batch"),
                               (target, torch.zeros((10, 8), dtype=torch.float32, device="cuda"), u, "row_bytes")):

@@ -30,6 +30,9 @@ head projects the target distribution of the bootstrap action onto the support a
 action's distribution (``dist_support`` / ``dist_q`` / ``categorical_projection`` are the host definitions).  It composes
 with ``double_dqn``, ``prioritized_replay`` (the new priority is the sample's loss + eps) and ``n_step``, and like
 prioritised replay it needs the device step.
+
+Every variant reaches its C entry through the model's ``train_replay`` / ``train_replay_per`` and one method of the net,
+``HipActorCritic.dqn_step``, whose keywords (``follow`` / ``n``, ``per``, ``dist``) choose the entry.
 """
 import random
 
@@ -287,9 +290,7 @@ class DQN(Algorithm):
                              "excludes the last stored slot, at least 2 are needed".format(size))
         u = torch.tensor([random.random() for _ in range(min(size, BATCH_SIZE))], dtype=torch.float64).to(self.buff.device)
         out = self.actor.train_replay_per(self.target_actor, self.buff, u, self.per_beta(), GAMMA, self.double_dqn)
-        self.train_count += 1
-        if self.train_count % TARGET_UPDATE_FREQ == 0:
-            self.update_target()
+        self._count_train()
         return float(out[0].item())
 
     def train_on_slots(self, slots):
@@ -297,11 +298,15 @@ class DQN(Algorithm):
         if self.device_step:
             d_slots = torch.tensor(slots, dtype=torch.int32).to(self.buff.device)
             out = self.actor.train_replay(self.target_actor, self.buff, d_slots, GAMMA, self.double_dqn)
-            self.train_count += 1
-            if self.train_count % TARGET_UPDATE_FREQ == 0:
-                self.update_target()
+            self._count_train()
             return float(out[0].item())
         return self._train_host(slots)
+
+    def _count_train(self):
+        """the tail of every train: count it and copy the weights to the target network every ``TARGET_UPDATE_FREQ``-th"""
+        self.train_count += 1
+        if self.train_count % TARGET_UPDATE_FREQ == 0:
+            self.update_target()
 
     def _train_host(self, slots):
         at = lambda ring, idx=slots: ring[torch.as_tensor(idx, dtype=torch.int64)].cpu().numpy()
@@ -319,9 +324,7 @@ class DQN(Algorithm):
         rows = np.arange(len(slots))
         y_t[rows, action] = td_targets(reward, done, target_q[rows, pick], gamma)
         loss = self.actor.train(states, y_t)
-        self.train_count += 1
-        if self.train_count % TARGET_UPDATE_FREQ == 0:
-            self.update_target()
+        self._count_train()
         return loss
 
     def update_target(self):

@@ -158,17 +158,25 @@ __global__ __launch_bounds__(256) void dqn_loss_kernel(const float* __restrict__
   if (maxq_out) maxq_out[b] = maxq;
 }
 
-// fixed-order reduction of the per-sample terms by one block (double precision, LDS tree)
-// (weights, may be NULL: L = sum_b w_b delta_b^2 / (B A); the two means stay unweighted)
+// fixed-order reduction of the per-sample terms by one block (double precision, LDS tree).  Scalar head (kDist false):
+// terms[b] = (delta_b, maxq_b); out = sum_b w_b delta_b^2 / (B A), sum_b |delta_b| / B, sum_b maxq_b / B.  Distributional
+// head (kDist true): terms[b] = (loss_b, dist_q_target(a*_b)); out = sum_b w_b loss_b / B, sum_b loss_b / B,
+// sum_b terms[b].y / B (A is not read).  weights may be NULL (w_b = 1); the two means stay unweighted.
+template <bool kDist>
 __global__ __launch_bounds__(256) void dqn_loss_reduce_kernel(const float2* __restrict__ terms, int B, int A,
                                                               float* __restrict__ out, float* __restrict__ acc,
                                                               const double* __restrict__ weights) {
   __shared__ double sq[256], sa[256], sm[256];
   double q = 0.0, a = 0.0, m = 0.0;
   for (int b = threadIdx.x; b < B; b += 256) {
-    const float d = terms[b].x;
-    const double d2 = (double)d * (double)d;
-    q += weights ? (double)(float)weights[b] * d2 : d2; a += (double)fabsf(d); m += (double)terms[b].y;
+    if constexpr (kDist) {
+      const double d = (double)terms[b].x;
+      q += weights ? (double)(float)weights[b] * d : d; a += d; m += (double)terms[b].y;
+    } else {
+      const float d = terms[b].x;
+      const double d2 = (double)d * (double)d;
+      q += weights ? (double)(float)weights[b] * d2 : d2; a += (double)fabsf(d); m += (double)terms[b].y;
+    }
   }
   sq[threadIdx.x] = q; sa[threadIdx.x] = a; sm[threadIdx.x] = m;
   __syncthreads();
@@ -179,7 +187,7 @@ __global__ __launch_bounds__(256) void dqn_loss_reduce_kernel(const float2* __re
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    const float l = (float)(sq[0] / ((double)B * (double)A));
+    const float l = (float)(sq[0] / (kDist ? (double)B : (double)B * (double)A));
     out[0] = l; out[1] = (float)(sa[0] / (double)B); out[2] = (float)(sm[0] / (double)B);
     if (acc) { acc[0] += l; acc[1] += 1.f; }
   }
@@ -316,29 +324,17 @@ __global__ __launch_bounds__(64) void dqn_loss_dist_kernel(const float* __restri
   }
 }
 
-// dqn_loss_reduce_kernel for the distributional head: terms[b] = (loss_b, dist_q_target(a*_b));
-// out[0] = sum_b w_b loss_b / B, out[1] = sum_b loss_b / B, out[2] = sum_b terms[b].y / B (same one-block float64 tree)
-__global__ __launch_bounds__(256) void dqn_dist_reduce_kernel(const float2* __restrict__ terms, int B, float* __restrict__ out,
-                                                              float* __restrict__ acc, const double* __restrict__ weights) {
-  __shared__ double sq[256], sa[256], sm[256];
-  double q = 0.0, a = 0.0, m = 0.0;
-  for (int b = threadIdx.x; b < B; b += 256) {
-    const double d = (double)terms[b].x;
-    q += weights ? (double)(float)weights[b] * d : d; a += d; m += (double)terms[b].y;
-  }
-  sq[threadIdx.x] = q; sa[threadIdx.x] = a; sm[threadIdx.x] = m;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      sq[threadIdx.x] += sq[threadIdx.x + o]; sa[threadIdx.x] += sa[threadIdx.x + o]; sm[threadIdx.x] += sm[threadIdx.x + o];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const float l = (float)(sq[0] / (double)B);
-    out[0] = l; out[1] = (float)(sa[0] / (double)B); out[2] = (float)(sm[0] / (double)B);
-    if (acc) { acc[0] += l; acc[1] += 1.f; }
-  }
+// The checks the two gather entries share (`who` names the entry in refusals); *nvec: 16-byte vectors per row
+static int replay_gather_check(const char* who, const void* ring, const void* dst, int64_t row_bytes, int64_t capacity,
+                               int32_t B, long long* nvec) {
+  XT_REQUIRE(row_bytes > 0 && row_bytes % 16 == 0,
+             "%s: row_bytes = %lld is not a positive multiple of 16 (rows are stored as the first layer reads them: "
+             "channel-padded images / feature-padded vectors)", who, (long long)row_bytes);
+  XT_REQUIRE(capacity > 0 && B > 0 && B <= 65535, "%s: bad sizes (capacity=%lld B=%d)", who, (long long)capacity, B);
+  XT_REQUIRE((((uintptr_t)ring | (uintptr_t)dst) & 15) == 0, "%s: ring and dst must be 16-byte aligned", who);
+  *nvec = row_bytes / 16;
+  XT_REQUIRE((*nvec + 255) / 256 < (1ll << 31), "%s: row_bytes = %lld is too large", who, (long long)row_bytes);
+  return 0;
 }
 
 }  // namespace xt
@@ -360,7 +356,7 @@ int xt_dqn_loss_dist(const float* logits, const float* t_logits, const float* o_
   hipLaunchKernelGGL(xt::dqn_loss_dist_kernel, dim3(B), dim3(64), 0, st, logits, t_logits, o_logits, B, A, atoms, v_min, v_max,
                      slots, action, reward, done, gamma, dlogits, dvalue, terms, astar, maxq, m, weights, disc);
   XT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(xt::dqn_dist_reduce_kernel, dim3(1), dim3(256), 0, st, terms, B, out, acc, weights);
+  hipLaunchKernelGGL(xt::dqn_loss_reduce_kernel<true>, dim3(1), dim3(256), 0, st, terms, B, A, out, acc, weights);
   XT_LAUNCH_CHECK();
   return 0;
 }
@@ -368,13 +364,8 @@ int xt_dqn_loss_dist(const float* logits, const float* t_logits, const float* o_
 int xt_replay_gather(const void* ring, int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, void* dst,
                      void* stream) {
   XT_REQUIRE(ring && slots && dst, "xt_replay_gather: null argument");
-  XT_REQUIRE(row_bytes > 0 && row_bytes % 16 == 0,
-             "xt_replay_gather: row_bytes = %lld is not a positive multiple of 16 (rows are stored as the first layer reads "
-             "them: channel-padded images / feature-padded vectors)", (long long)row_bytes);
-  XT_REQUIRE(capacity > 0 && B > 0 && B <= 65535, "xt_replay_gather: bad sizes (capacity=%lld B=%d)", (long long)capacity, B);
-  XT_REQUIRE((((uintptr_t)ring | (uintptr_t)dst) & 15) == 0, "xt_replay_gather: ring and dst must be 16-byte aligned");
-  const long long nvec = row_bytes / 16;
-  XT_REQUIRE((nvec + 255) / 256 < (1ll << 31), "xt_replay_gather: row_bytes = %lld is too large", (long long)row_bytes);
+  long long nvec;
+  if (int rc = xt::replay_gather_check("xt_replay_gather", ring, dst, row_bytes, capacity, B, &nvec)) return rc;
   hipLaunchKernelGGL(xt::replay_gather_kernel, dim3((unsigned)((nvec + 255) / 256), (unsigned)B), dim3(256), 0,
                      xt::as_stream(stream), static_cast<const uint4*>(ring), nvec, (long long)capacity, slots,
                      static_cast<uint4*>(dst));
@@ -389,15 +380,9 @@ int xt_replay_gather_nstep(const void* next_ring, int64_t row_bytes, int64_t cap
   XT_REQUIRE(next_ring && slots && dst && action && reward && done && follow, "xt_replay_gather_nstep: null argument");
   XT_REQUIRE(boot_slots && action_n && reward_n && disc_n && done_n, "xt_replay_gather_nstep: null label output");
   XT_REQUIRE(n >= 1 && n <= 256, "xt_replay_gather_nstep: n = %d outside [1, 256]", n);
-  XT_REQUIRE(row_bytes > 0 && row_bytes % 16 == 0,
-             "xt_replay_gather_nstep: row_bytes = %lld is not a positive multiple of 16 (rows are stored as the first layer "
-             "reads them: channel-padded images / feature-padded vectors)", (long long)row_bytes);
-  XT_REQUIRE(capacity > 0 && B > 0 && B <= 65535, "xt_replay_gather_nstep: bad sizes (capacity=%lld B=%d)",
-             (long long)capacity, B);
-  XT_REQUIRE((((uintptr_t)next_ring | (uintptr_t)dst) & 15) == 0,
-             "xt_replay_gather_nstep: ring and dst must be 16-byte aligned");
-  const long long nvec = row_bytes / 16;
-  XT_REQUIRE((nvec + 255) / 256 < (1ll << 31), "xt_replay_gather_nstep: row_bytes = %lld is too large", (long long)row_bytes);
+  long long nvec;
+  if (int rc = xt::replay_gather_check("xt_replay_gather_nstep", next_ring, dst, row_bytes, capacity, B, &nvec))
+    return rc;
   hipLaunchKernelGGL(xt::replay_gather_nstep_kernel, dim3((unsigned)((nvec + 255) / 256), (unsigned)B), dim3(256), 0,
                      xt::as_stream(stream), static_cast<const uint4*>(next_ring), nvec, (long long)capacity, slots, action,
                      reward, done, follow, n, gamma, static_cast<uint4*>(dst), boot_slots, action_n, reward_n, disc_n,
@@ -421,7 +406,7 @@ int xt_dqn_loss_n(const float* logits, const float* value, const float* t_logits
                      o_value, B, A, dueling, slots, action, reward, done, gamma, dlogits, dvalue, terms, y, astar, maxq, weights,
                      disc);
   XT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(xt::dqn_loss_reduce_kernel, dim3(1), dim3(256), 0, st, terms, B, A, out, acc, weights);
+  hipLaunchKernelGGL(xt::dqn_loss_reduce_kernel<false>, dim3(1), dim3(256), 0, st, terms, B, A, out, acc, weights);
   XT_LAUNCH_CHECK();
   return 0;
 }

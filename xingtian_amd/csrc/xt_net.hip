@@ -1806,113 +1806,138 @@ int xt_net_graph_cache_info(const xt_net* n, int32_t* out, int32_t cap) {
 
 namespace xt {
 
+// What the four DQN step entries hand to dqn_chain: first what every entry passes on as it came, in the order of the
+// entries' own parameters, then what differs between them (set by name)
+struct dqn_args {
+  const char* who;                                          // the entry, in refusals
+  const xt_dqn_cfg* c;
+  const void *cur_ring, *next_ring;
+  int64_t row_bytes, capacity;
+  int32_t B;
+  const int32_t* action;
+  const double* reward;
+  const uint8_t* done;
+  float *loss_out, *loss_acc;
+  void* stream;
+  bool dist = false;
+  const xt_nstep_cfg* ns = nullptr;
+  const xt_per_cfg* per = nullptr;
+  int64_t size = 0;
+  const int32_t* slots = nullptr;
+};
+
 // The chain of one DQN.train up to the gradient, shared by xt_net_dqn_step, xt_net_dqn_step_per, xt_net_dqn_step_n and
-// xt_net_dqn_step_dist
-// (`who` names the entry in refusals).  per (may be NULL): prioritised replay -- once every refusal has passed, xt_per_sample fills
-// per->slots / per->weights from `size` stored transitions, the chain runs on them with the weighted head, and
-// xt_per_update follows the loss; `slots` is then ignored.  ns (may be NULL): n-step returns -- the first gather walks each
-// start slot to its boot slot and leaves the per-sample labels in ns' scratch (xt_replay_gather_nstep), both next-state
-// forwards run on the boot rows, and the head reads those dense labels with the per-sample discount; the state rows and the
-// new priorities stay those of the start slots.  The launches are the same in number either way.  dist: both nets carry
-// the mark of xt_net_set_dist and the head is xt_dqn_loss_dist on their actions * atoms wide logits (two launches, as
-// xt_dqn_loss_n); a net with the mark is refused by the scalar entries.
-static int dqn_chain(const char* who, bool dist, xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_nstep_cfg* ns,
-                     const void* cur_ring, const void* next_ring, int64_t row_bytes, int64_t capacity,
-                     const int32_t* slots, int32_t B, const int32_t* action, const double* reward, const uint8_t* done,
-                     const xt_per_cfg* per, int64_t size, float* loss_out, float* loss_acc, void* stream) {
-  XT_REQUIRE(n && tn && c && cur_ring && next_ring && (slots || per) && action && reward && done, "%s: null argument", who);
-  XT_REQUIRE(c->cur_rows && c->next_rows && c->q_scratch, "%s: null scratch in cfg", who);
+// xt_net_dqn_step_dist (`who` names the entry in refusals).  per (may be NULL): prioritised replay -- once every refusal
+// has passed, xt_per_sample fills per->slots / per->weights from `size` stored transitions, the chain runs on them with
+// the weighted head, and xt_per_update follows the loss; `slots` is then ignored.  ns (may be NULL): n-step returns -- the
+// first gather walks each start slot to its boot slot and leaves the per-sample labels in ns' scratch
+// (xt_replay_gather_nstep), both next-state forwards run on the boot rows, and the head reads those dense labels with the
+// per-sample discount; the state rows and the new priorities stay those of the start slots.  The launches are the same in
+// number either way.  dist: both nets carry the mark of xt_net_set_dist and the head is xt_dqn_loss_dist on their
+// actions * atoms wide logits (two launches, as xt_dqn_loss_n); a net with the mark is refused by the scalar entries.
+static int dqn_chain(xt_net* n, xt_net* tn, const dqn_args& a) {
+  const xt_dqn_cfg* c = a.c;
+  const xt_nstep_cfg* ns = a.ns;
+  const xt_per_cfg* per = a.per;
+  const int32_t* slots = a.slots;                           // (prioritised: the sampled ones, below)
+  XT_REQUIRE(n && tn && c && a.cur_ring && a.next_ring && (slots || per) && a.action && a.reward && a.done,
+             "%s: null argument", a.who);
+  XT_REQUIRE(c->cur_rows && c->next_rows && c->q_scratch, "%s: null scratch in cfg", a.who);
   XT_REQUIRE(n != tn && n->params && n->ws && tn->params && tn->ws && tn->params != n->params && tn->ws != n->ws,
-             "%s: the two nets must be bound to their own parameter buffers and workspaces", who);
+             "%s: the two nets must be bound to their own parameter buffers and workspaces", a.who);
   XT_REQUIRE(n->action_type == XT_ACTION_CATEGORICAL && tn->action_type == XT_ACTION_CATEGORICAL,
-             "%s: categorical heads only", who);
+             "%s: categorical heads only", a.who);
   XT_REQUIRE(!n->xchg && n->dp_world == 0 && !n->direct,
-             "%s: no data parallelism (a gradient exchange / data-parallel tail is installed)", who);
+             "%s: no data parallelism (a gradient exchange / data-parallel tail is installed)", a.who);
   XT_REQUIRE(tn->A == n->A && tn->feat == n->feat && tn->P == n->P && tn->layers.size() == n->layers.size() &&
                  tn->in_h == n->in_h && tn->in_w == n->in_w && tn->in_c == n->in_c && tn->xf.is_u8 == n->xf.is_u8,
-             "%s: target_net is not a net of the same description", who);
+             "%s: target_net is not a net of the same description", a.who);
   int atoms = 1;
-  if (dist) {
+  if (a.dist) {
     XT_REQUIRE(n->dist_atoms >= 2 && tn->dist_atoms == n->dist_atoms && tn->dist_vmin == n->dist_vmin &&
                    tn->dist_vmax == n->dist_vmax,
                "%s: both nets must be marked distributional with the same atoms and bounds (xt_net_set_dist: net %d atoms "
-               "[%g, %g], target_net %d atoms [%g, %g])", who, n->dist_atoms, n->dist_vmin, n->dist_vmax, tn->dist_atoms,
+               "[%g, %g], target_net %d atoms [%g, %g])", a.who, n->dist_atoms, n->dist_vmin, n->dist_vmax, tn->dist_atoms,
                tn->dist_vmin, tn->dist_vmax);
     atoms = n->dist_atoms;
-    XT_REQUIRE(!c->dueling, "%s: no dueling stream with a distributional head (it would have to be %d wide)", who, atoms);
+    XT_REQUIRE(!c->dueling, "%s: no dueling stream with a distributional head (it would have to be %d wide)", a.who, atoms);
   } else {
     XT_REQUIRE(n->dist_atoms == 0 && tn->dist_atoms == 0,
-               "%s: the net is marked distributional (xt_net_set_dist): its step is xt_net_dqn_step_dist", who);
+               "%s: the net is marked distributional (xt_net_set_dist): its step is xt_net_dqn_step_dist", a.who);
   }
-  XT_REQUIRE(n->A / atoms <= 64, "%s: A = %d exceeds 64", who, n->A / atoms);
-  XT_REQUIRE(B > 0 && B <= n->maxB && B <= tn->maxB, "%s: batch %d outside (0,%d]", who, B,
+  XT_REQUIRE(n->A / atoms <= 64, "%s: A = %d exceeds 64", a.who, n->A / atoms);
+  XT_REQUIRE(a.B > 0 && a.B <= n->maxB && a.B <= tn->maxB, "%s: batch %d outside (0,%d]", a.who, a.B,
              n->maxB < tn->maxB ? n->maxB : tn->maxB);
   const int64_t in_row = (int64_t)n->in_h * n->in_w * n->in_c * (n->xf.is_u8 ? 1 : 4);
-  XT_REQUIRE(row_bytes == in_row, "%s: row_bytes = %lld, the first layer reads rows of %lld bytes", who,
-             (long long)row_bytes, (long long)in_row);
+  XT_REQUIRE(a.row_bytes == in_row, "%s: row_bytes = %lld, the first layer reads rows of %lld bytes", a.who,
+             (long long)a.row_bytes, (long long)in_row);
   if (ns) {
-    XT_REQUIRE(ns->n >= 1 && ns->n <= 256, "%s: n = %d outside [1, 256]", who, ns->n);
-    XT_REQUIRE(ns->follow, "%s: null follow ring in nstep cfg", who);
+    XT_REQUIRE(ns->n >= 1 && ns->n <= 256, "%s: n = %d outside [1, 256]", a.who, ns->n);
+    XT_REQUIRE(ns->follow, "%s: null follow ring in nstep cfg", a.who);
     XT_REQUIRE(ns->boot_slots && ns->action_n && ns->reward_n && ns->disc_n && ns->done_n,
-               "%s: null scratch in nstep cfg", who);
+               "%s: null scratch in nstep cfg", a.who);
   }
   const double* weights = nullptr;
   if (per) {
-    XT_REQUIRE(per->sum && per->min && per->max_prio && per->u && per->slots && per->weights, "%s: null pointer in per cfg", who);
-    XT_REQUIRE(size <= capacity && capacity <= per->cap2, "%s: size = %lld, capacity = %lld, cap2 = %lld (size <= capacity <= cap2)",
-               who, (long long)size, (long long)capacity, (long long)per->cap2);
-    if (int rc = xt_per_sample(per->sum, per->min, per->cap2, size, per->u, B, per->beta, per->slots, per->weights, stream))
+    XT_REQUIRE(per->sum && per->min && per->max_prio && per->u && per->slots && per->weights,
+               "%s: null pointer in per cfg", a.who);
+    XT_REQUIRE(a.size <= a.capacity && a.capacity <= per->cap2,
+               "%s: size = %lld, capacity = %lld, cap2 = %lld (size <= capacity <= cap2)", a.who, (long long)a.size,
+               (long long)a.capacity, (long long)per->cap2);
+    if (int rc = xt_per_sample(per->sum, per->min, per->cap2, a.size, per->u, a.B, per->beta, per->slots, per->weights,
+                               a.stream))
       return rc;
     slots = per->slots;
     weights = per->weights;
   }
   const int A = n->A;
   float* t_logits = c->q_scratch;
-  float* t_value = t_logits + (int64_t)B * A;
-  float* o_logits = c->double_dqn ? t_value + B : nullptr;
-  float* o_value = c->double_dqn ? o_logits + (int64_t)B * A : nullptr;
-  hipStream_t st = xt::as_stream(stream);
+  float* t_value = t_logits + (int64_t)a.B * A;
+  float* o_logits = c->double_dqn ? t_value + a.B : nullptr;
+  float* o_value = c->double_dqn ? o_logits + (int64_t)a.B * A : nullptr;
+  hipStream_t st = xt::as_stream(a.stream);
   if (ns) {
-    if (int rc = xt_replay_gather_nstep(next_ring, row_bytes, capacity, slots, B, action, reward, done, ns->follow, ns->n,
-                                        c->gamma, c->next_rows, ns->boot_slots, ns->action_n, ns->reward_n, ns->disc_n,
-                                        ns->done_n, stream))
+    if (int rc = xt_replay_gather_nstep(a.next_ring, a.row_bytes, a.capacity, slots, a.B, a.action, a.reward, a.done,
+                                        ns->follow, ns->n, c->gamma, c->next_rows, ns->boot_slots, ns->action_n,
+                                        ns->reward_n, ns->disc_n, ns->done_n, a.stream))
       return rc;
-  } else if (int rc = xt_replay_gather(next_ring, row_bytes, capacity, slots, B, c->next_rows, stream)) {
+  } else if (int rc = xt_replay_gather(a.next_ring, a.row_bytes, a.capacity, slots, a.B, c->next_rows, a.stream)) {
     return rc;
   }
-  if (int rc = xt_net_forward(tn, c->next_rows, nullptr, B, t_logits, t_value, stream)) return rc;
+  if (int rc = xt_net_forward(tn, c->next_rows, nullptr, a.B, t_logits, t_value, a.stream)) return rc;
   if (c->double_dqn)
-    if (int rc = xt_net_forward(n, c->next_rows, nullptr, B, o_logits, o_value, stream)) return rc;
-  if (int rc = xt_replay_gather(cur_ring, row_bytes, capacity, slots, B, c->cur_rows, stream)) return rc;
-  if (int rc = xt::net_forward(n, c->cur_rows, nullptr, B, true, st)) return rc;
+    if (int rc = xt_net_forward(n, c->next_rows, nullptr, a.B, o_logits, o_value, a.stream)) return rc;
+  if (int rc = xt_replay_gather(a.cur_ring, a.row_bytes, a.capacity, slots, a.B, c->cur_rows, a.stream)) return rc;
+  if (int rc = xt::net_forward(n, c->cur_rows, nullptr, a.B, true, st)) return rc;
   float* lo = n->ws + n->off_loss;
   float* rows = n->ws + n->off_terms;                       // per-row y | a* | maxq, maxB each
-  // (n-step: the labels are dense in the scratch the gather filled, in sample order)
-  if (dist) {
-    if (int rc = xt_dqn_loss_dist(n->ws + n->off_logits, t_logits, o_logits, B, A / atoms, atoms, n->dist_vmin, n->dist_vmax,
-                                  ns ? nullptr : slots, ns ? ns->action_n : action, ns ? ns->reward_n : reward,
-                                  ns ? ns->done_n : done, c->gamma, n->ws + n->off_dlogits, n->ws + n->off_dvalue, lo,
-                                  reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB, nullptr, loss_acc, weights,
-                                  ns ? ns->disc_n : nullptr, stream))
+  // the labels the head reads (n-step: dense in the scratch the gather filled, in sample order, so without slots)
+  const int32_t* l_slots = ns ? nullptr : slots;
+  const int32_t* l_action = ns ? ns->action_n : a.action;
+  const double* l_reward = ns ? ns->reward_n : a.reward;
+  const uint8_t* l_done = ns ? ns->done_n : a.done;
+  const double* l_disc = ns ? ns->disc_n : nullptr;
+  if (a.dist) {
+    if (int rc = xt_dqn_loss_dist(n->ws + n->off_logits, t_logits, o_logits, a.B, A / atoms, atoms, n->dist_vmin, n->dist_vmax,
+                                  l_slots, l_action, l_reward, l_done, c->gamma, n->ws + n->off_dlogits, n->ws + n->off_dvalue,
+                                  lo, reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB, nullptr, a.loss_acc,
+                                  weights, l_disc, a.stream))
       return rc;
-  } else if (int rc = xt_dqn_loss_n(n->ws + n->off_logits, n->ws + n->off_value, t_logits, t_value, o_logits, o_value, B, A,
-                             c->dueling, ns ? nullptr : slots, ns ? ns->action_n : action, ns ? ns->reward_n : reward,
-                             ns ? ns->done_n : done, c->gamma, n->ws + n->off_dlogits, n->ws + n->off_dvalue, lo, rows,
-                             reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB, loss_acc, weights,
-                             ns ? ns->disc_n : nullptr, stream)) {
+  } else if (int rc = xt_dqn_loss_n(n->ws + n->off_logits, n->ws + n->off_value, t_logits, t_value, o_logits, o_value, a.B, A,
+                                    c->dueling, l_slots, l_action, l_reward, l_done, c->gamma, n->ws + n->off_dlogits,
+                                    n->ws + n->off_dvalue, lo, rows, reinterpret_cast<int32_t*>(rows + n->maxB),
+                                    rows + 2 * n->maxB, a.loss_acc, weights, l_disc, a.stream)) {
     return rc;
   }
-  if (loss_out) XT_CHECK_HIP(hipMemcpyAsync(loss_out, lo, 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-  if (int rc = xt::heads_dfeat(n, B, st, dist && !ns ? slots : nullptr,
-                               dist ? (ns ? ns->action_n : action) : nullptr))
-    return rc;
-  if (int rc = xt::trunk_backward(n, c->cur_rows, nullptr, B, st)) return rc;
-  if (int rc = xt::grads_finish(n, B, nullptr, st)) return rc;
+  if (a.loss_out) XT_CHECK_HIP(hipMemcpyAsync(a.loss_out, lo, 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (int rc = xt::heads_dfeat(n, a.B, st, a.dist ? l_slots : nullptr, a.dist ? l_action : nullptr)) return rc;
+  if (int rc = xt::trunk_backward(n, c->cur_rows, nullptr, a.B, st)) return rc;
+  if (int rc = xt::grads_finish(n, a.B, nullptr, st)) return rc;
   if (!per) return 0;
   const float* delta = lo + 4;                              // terms[b].x of xt_dqn_loss
   if (per->terms_out)
-    XT_CHECK_HIP(hipMemcpyAsync(per->terms_out, delta, 2 * sizeof(float) * B, hipMemcpyDeviceToDevice, st));
-  return xt_per_update(per->sum, per->min, per->cap2, per->max_prio, slots, delta, 2, B, per->eps, per->alpha, stream);
+    XT_CHECK_HIP(hipMemcpyAsync(per->terms_out, delta, 2 * sizeof(float) * a.B, hipMemcpyDeviceToDevice, st));
+  return xt_per_update(per->sum, per->min, per->cap2, per->max_prio, slots, delta, 2, a.B, per->eps, per->alpha, a.stream);
 }
 
 }  // namespace xt
@@ -1922,8 +1947,10 @@ extern "C" {
 int xt_net_dqn_step(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const void* cur_ring, const void* next_ring,
                     int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, const int32_t* action,
                     const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream) {
-  return xt::dqn_chain("xt_net_dqn_step", false, n, tn, c, nullptr, cur_ring, next_ring, row_bytes, capacity, slots, B, action,
-                       reward, done, nullptr, 0, loss_out, loss_acc, stream);
+  xt::dqn_args a{"xt_net_dqn_step", c, cur_ring, next_ring, row_bytes, capacity, B, action, reward, done, loss_out,
+                  loss_acc, stream};
+  a.slots = slots;
+  return xt::dqn_chain(n, tn, a);
 }
 
 int xt_net_dqn_step_per(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_per_cfg* p, const void* cur_ring,
@@ -1931,8 +1958,10 @@ int xt_net_dqn_step_per(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_per
                         const int32_t* action, const double* reward, const uint8_t* done, float* loss_out, float* loss_acc,
                         void* stream) {
   XT_REQUIRE(p, "xt_net_dqn_step_per: null per cfg");
-  return xt::dqn_chain("xt_net_dqn_step_per", false, n, tn, c, nullptr, cur_ring, next_ring, row_bytes, capacity, nullptr, B, action,
-                       reward, done, p, size, loss_out, loss_acc, stream);
+  xt::dqn_args a{"xt_net_dqn_step_per", c, cur_ring, next_ring, row_bytes, capacity, B, action, reward, done, loss_out,
+                  loss_acc, stream};
+  a.per = p; a.size = size;
+  return xt::dqn_chain(n, tn, a);
 }
 
 int xt_net_dqn_step_n(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_nstep_cfg* ns, const xt_per_cfg* p,
@@ -1940,16 +1969,20 @@ int xt_net_dqn_step_n(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_nstep
                       const int32_t* slots, int32_t B, const int32_t* action, const double* reward, const uint8_t* done,
                       float* loss_out, float* loss_acc, void* stream) {
   XT_REQUIRE(ns, "xt_net_dqn_step_n: null nstep cfg");
-  return xt::dqn_chain("xt_net_dqn_step_n", false, n, tn, c, ns, cur_ring, next_ring, row_bytes, capacity, p ? nullptr : slots, B,
-                       action, reward, done, p, size, loss_out, loss_acc, stream);
+  xt::dqn_args a{"xt_net_dqn_step_n", c, cur_ring, next_ring, row_bytes, capacity, B, action, reward, done, loss_out,
+                  loss_acc, stream};
+  a.ns = ns; a.per = p; a.size = size; a.slots = p ? nullptr : slots;
+  return xt::dqn_chain(n, tn, a);
 }
 
 int xt_net_dqn_step_dist(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_nstep_cfg* ns, const xt_per_cfg* p,
                          const void* cur_ring, const void* next_ring, int64_t row_bytes, int64_t capacity, int64_t size,
                          const int32_t* slots, int32_t B, const int32_t* action, const double* reward, const uint8_t* done,
                          float* loss_out, float* loss_acc, void* stream) {
-  return xt::dqn_chain("xt_net_dqn_step_dist", true, n, tn, c, ns, cur_ring, next_ring, row_bytes, capacity,
-                       p ? nullptr : slots, B, action, reward, done, p, size, loss_out, loss_acc, stream);
+  xt::dqn_args a{"xt_net_dqn_step_dist", c, cur_ring, next_ring, row_bytes, capacity, B, action, reward, done, loss_out,
+                  loss_acc, stream};
+  a.dist = true; a.ns = ns; a.per = p; a.size = size; a.slots = p ? nullptr : slots;
+  return xt::dqn_chain(n, tn, a);
 }
 
 int xt_net_set_dist(xt_net* net, int32_t atoms, double v_min, double v_max) {

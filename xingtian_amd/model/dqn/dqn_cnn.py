@@ -5,7 +5,8 @@ the A-wide stream ``l`` combine to Q_a = s + (l_a - mean_a l) -- compiled with `
 (xt/model/dqn/dqn_cnn.py:45-61: ``clipnorm=10.``; xt/model/dqn/dqn_mlp.py:43-58: plain Adam).  ``predict(state)``
 returns Q as float32 [N, A].  The update does not go through ``train(states, y_t)``: the algorithm keeps its replay
 store on the device and one C call (``xt_net_dqn_step``) forms the TD target and the gradient there
-(``train_replay``), so ``train`` is not provided.
+(``train_replay``), so ``train`` is not provided.  ``train_replay`` and ``train_replay_per`` are one call of
+``HipActorCritic.dqn_step``, whose keywords (``follow`` / ``n``, ``per``, ``dist``) choose among the four C entries.
 
 ``model_config.atoms`` (1 unless asked for) with ``v_min`` / ``v_max`` (-10 / 10) makes the network distributional (C51,
 Bellemare et al. 2017): the Q head is A * atoms wide, column a * atoms + i being the logit of atom i of action a, and
@@ -156,47 +157,27 @@ class DqnModel(XTModel):
         Adam.  Nothing synchronises.  -> the device tensor [loss, mean |TD error|, mean bootstrap Q].  A replay with
         ``n_step`` > 1 trains on n-step targets (``xt_net_dqn_step_n``).  A distributional model (``atoms`` > 1) takes
         ``xt_net_dqn_step_dist`` either way; the tensor is then [loss, mean per-sample loss, mean bootstrap Q]."""
-        self._require_learner()
-        if self.atoms > 1:
-            out = self.net.dqn_step_dist(target.net, replay.cur_state, replay.next_state, slots, replay.action,
-                                         replay.reward, replay.done, gamma, double_dqn, **self._nstep_of(replay))
-        elif getattr(replay, "n_step", 1) > 1:
-            out = self.net.dqn_step_n(target.net, replay.cur_state, replay.next_state, slots, replay.action, replay.reward,
-                                      replay.done, replay.follow, replay.n_step, gamma, self.dueling, double_dqn)
-        else:
-            out = self.net.dqn_step(target.net, replay.cur_state, replay.next_state, slots, replay.action, replay.reward,
-                                    replay.done, gamma, self.dueling, double_dqn)
-        self.net.adam_keras(self.learning_rate, self.iterations, clipnorm=self.CLIPNORM)
-        self.iterations += 1
-        return out
+        return self._train_step(target, replay, slots, None, gamma, double_dqn)
 
     def train_replay_per(self, target, replay, u, beta, gamma, double_dqn):
         """``train_replay`` on a ``PrioritizedDeviceReplay``: the minibatch is drawn on the device with the uniform draws
         ``u`` (float64 device tensor [B]) and importance exponent ``beta``, and the replay's trees take the new TD errors
         (``xt_net_dqn_step_per``), then tf.keras Adam.  Nothing synchronises.  -> the device tensor of ``train_replay``."""
-        self._require_learner()
         per = dict(size=replay.size(), u=u, sum_tree=replay.sum_tree, min_tree=replay.min_tree, max_prio=replay.max_prio,
                    alpha=replay.alpha, beta=beta, eps=replay.eps)
-        if self.atoms > 1:
-            out = self.net.dqn_step_dist(target.net, replay.cur_state, replay.next_state, None, replay.action, replay.reward,
-                                         replay.done, gamma, double_dqn, per=per, **self._nstep_of(replay))
-        elif getattr(replay, "n_step", 1) > 1:
-            out = self.net.dqn_step_n(target.net, replay.cur_state, replay.next_state, None, replay.action, replay.reward,
-                                      replay.done, replay.follow, replay.n_step, gamma, self.dueling, double_dqn, per=per)
-        else:
-            out = self.net.dqn_step_per(target.net, replay.cur_state, replay.next_state, replay.size(), u, replay.action,
-                                        replay.reward, replay.done, gamma, self.dueling, double_dqn, replay.sum_tree,
-                                        replay.min_tree, replay.max_prio, replay.alpha, beta, replay.eps)
+        return self._train_step(target, replay, None, per, gamma, double_dqn)
+
+    def _train_step(self, target, replay, slots, per, gamma, double_dqn):
+        """``net.dqn_step`` with the keywords the replay store (n-step) and the model (distributional) ask for, then
+        tf.keras Adam"""
+        self._require_learner()
+        n = getattr(replay, "n_step", 1)
+        out = self.net.dqn_step(target.net, replay.cur_state, replay.next_state, slots, replay.action, replay.reward,
+                                replay.done, gamma, self.dueling, double_dqn, follow=replay.follow if n > 1 else None, n=n,
+                                per=per, dist=self.atoms > 1)
         self.net.adam_keras(self.learning_rate, self.iterations, clipnorm=self.CLIPNORM)
         self.iterations += 1
         return out
-
-    @staticmethod
-    def _nstep_of(replay):
-        """the n-step keywords of ``dqn_step_dist`` for a replay store (none for one-step targets)"""
-        if getattr(replay, "n_step", 1) > 1:
-            return dict(follow=replay.follow, n=replay.n_step)
-        return {}
 
     def copy_weights_from(self, other):
         """this network's parameters <- ``other``'s: one device-to-device copy of the flat buffer on a learner"""
