@@ -1276,6 +1276,52 @@ int xt_net_dqn_step_dist(xt_net* net, xt_net* target_net, const xt_dqn_cfg* cfg,
                          int64_t capacity, int64_t size, const int32_t* slots, int32_t B, const int32_t* action,
                          const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream);
 
+/* ------------------------------------------------------------------ quantile-regression (QR-DQN) Q head (appended under ABI 12)
+ * Dabney et al. 2018: the Q head is A * N wide, column a * N + i is quantile theta_i of action a at the midpoint tau_i;
+ * there is no support and there are no bounds.  Definitions (host twins quantile_midpoints / quant_q /
+ * quantile_huber of xingtian_amd/algorithm/dqn/dqn.py):
+ *     tau_i = (2 i + 1) / (2 N)                                                                    (float64)
+ *     quant_q(theta) = (float)((sum_{i ascending} (double)theta_i) / N)                            (one rounding)
+ *     a* = first maximal index over a of quant_q of the picking quantiles (t_logits, or o_logits when given: double DQN)
+ *     (R, g, dn) = (reward, disc ? disc[b] : gamma, done) of the sample
+ *     T_j = (float)(dn ? R : R + g * (double)theta'_j), theta' = t_logits[a*, :]       (float64, no fma, one rounding)
+ *     u_ij = T_j - theta_i in float32, theta = the online quantiles of the taken action (clamped into [0, A))
+ *     wt_ij = u_ij < 0 ? (float)(1 - tau_i) : (float)tau_i
+ *     H(u) = |u| <= kappa ? 0.5f u u : kappa (|u| - 0.5f kappa)                                    (float32)
+ *     r_i = (float)((sum_{j ascending} (double)(wt_ij * H(u_ij) / kappa)) / N)
+ *     g_i = (float)(-(sum_{j ascending} (double)(wt_ij * clamp(u_ij, -kappa, kappa) / kappa)) / N)
+ *     loss_b = sum_i r_i;  L = sum_b w_b loss_b / B  (w_b = (float)weights[b], 1 without weights)
+ *     dlogits[b, act * N + i] = w_b g_i / B; every other entry 0; dvalue[b] = 0
+ * kappa (used as a float32) must be finite and > 0: loss and gradient are then continuous in u, at 0 and at |u| = kappa;
+ * the pure |u| loss (kappa = 0) is not provided.  No atomics: the result does not depend on thread order.
+ * logits / t_logits / o_logits [B, A * N]; labels through `slots` (int32 [B]) or dense (slots == NULL); out: 4 + 2 B floats,
+ * 8-byte aligned: out[0] = L, out[1] = sum_b loss_b / B, out[2] = sum_b quant_q(theta'(a*_b)) / B and from out + 4 the
+ * terms (loss_b, quant_q(theta'(a*_b))), where xt_per_update reads its |x|.  astar / maxq [B] / acc / weights / disc may
+ * be NULL.  Two launches.  Refused: quantiles outside [2, 256], A outside [1, 64], kappa not finite or <= 0, a null
+ * required pointer, a misaligned out. */
+int xt_dqn_loss_quant(const float* logits, const float* t_logits, const float* o_logits, int32_t B, int32_t A,
+                      int32_t quantiles, double kappa, const int32_t* slots, const int32_t* action, const double* reward,
+                      const uint8_t* done, double gamma, float* dlogits, float* dvalue, float* out, int32_t* astar, float* maxq,
+                      float* acc, const double* weights, const double* disc, void* stream);
+/* The head a net is marked with: a net carries at most one mark, and both marks fill the same columns-per-action count. */
+#define XT_HEAD_SCALAR 0
+#define XT_HEAD_C51 1     /* xt_net_set_dist  */
+#define XT_HEAD_QUANT 2   /* xt_net_set_quant */
+/* Marks a net (per net, opt-in) as carrying a quantile head of `quantiles` quantiles with Huber threshold kappa: its
+ * action_dim is actions * quantiles.  quantiles == 1 clears the mark.  Refused: quantiles outside [1, 256], kappa as
+ * above, a width that is no multiple of quantiles, a DiagGaussian net, a net marked by xt_net_set_dist (as xt_net_set_dist
+ * refuses one marked here: clear the other mark first).  A quantile-marked net takes the two wide-head kernels of a
+ * C51-marked one (xt_net_set_dist_wide works on it) and is refused by xt_net_dqn_step / _per / _n / _dist. */
+int xt_net_set_quant(xt_net* net, int32_t quantiles, double kappa);
+/* xt_net_dqn_step_dist's chain with xt_dqn_loss_quant as the head, same launches in number.  Both nets must carry equal
+ * quantile marks; cfg->dueling must be 0; actions <= 64; cfg->q_scratch holds 2 * B * (actions * quantiles + 1) floats.  A
+ * C51-marked net is refused (its step is xt_net_dqn_step_dist).  With per, the new priority of a start slot is
+ * loss_b + eps. */
+int xt_net_dqn_step_quant(xt_net* net, xt_net* target_net, const xt_dqn_cfg* cfg, const xt_nstep_cfg* ns,
+                          const xt_per_cfg* per, const void* cur_ring, const void* next_ring, int64_t row_bytes,
+                          int64_t capacity, int64_t size, const int32_t* slots, int32_t B, const int32_t* action,
+                          const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream);
+
 /* ------------------------------------------------------------------ the step tail stand-alone (appended under ABI 12)
  * The gradient-reduction launch and the optimiser launches every xt_net_*_step ends in, on given buffers, for kernel
  * tests (tests/test_gpu_optim_branch.py).  Each entry fills the argument structs the step fills and calls the step's own

@@ -1,6 +1,7 @@
 """Time of one ``DQN.train`` at breakout_dqn's shape, beside a Keras-IMPALA step of the same trunk.
 
-    python tools/dqn_probe.py [--windows 5] [--trains 200] [--capacity 4096] [--atoms 51] [--out profiles/dqn_step.md]
+    python tools/dqn_probe.py [--windows 5] [--trains 200] [--capacity 4096] [--atoms 51] [--quantiles 51]
+                              [--model DqnCnn] [--out profiles/dqn_step.md]
 
 Four things are timed at DqnCnn 84x84x4, A = 4, B = 32, each as a host clock around ``--trains`` calls that ends in a
 device synchronise, after a warm-up, in ``--windows`` windows taken in turn (so that drift of the box hits all alike):
@@ -16,13 +17,17 @@ device synchronise, after a warm-up, in ``--windows`` windows taken in turn (so 
   4 * N wide) with and without ``prioritized_replay``, ``double_dqn`` and ``n_step: 3``, as ``DQN.train`` and enqueue
   only, once on the head kernels of a marked net (wide forward, taken-action d(features)) and once, "generic", on the
   head kernels every other net runs (``set_dist_wide(False)``);
+* with ``--quantiles N`` (0: none) the same arms for the quantile-regression train (``model_config.quantiles``,
+  ``xt_net_dqn_step_quant``: the head is again 4 * N wide), so that ``--atoms N --quantiles N`` compares the two
+  distributional heads at one width in one run;
 * one ``prepare_data`` of a 20-row message without and with ``prioritized_replay`` (``xt_per_add`` per written span), each
   call followed by a device synchronise;
 * ``keras_impala_step`` + ``adam_keras`` on 32 rows of ``netspec.impala_cnn`` (the same trunk and heads, one network, no
   gather), enqueue only.
 
 The ring holds ``--capacity`` transitions (a full breakout_dqn buffer is 22.6 GB; the gather reads 32 rows whatever the
-capacity is).  No threshold is attached to any of these numbers.  Needs a GPU.
+capacity is).  ``--model DqnMlp`` times the same trains on the CartPole network (state 4, Dense 128) instead, with the
+same A and B and without the IMPALA row.  No threshold is attached to any of these numbers.  Needs a GPU.
 """
 import argparse
 import os
@@ -37,14 +42,24 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 B, A_DIM, DIM = 32, 4, 84
+MODEL = {"name": "DqnCnn"}                  # --model: DqnCnn (84x84x4 uint8 frames) or DqnMlp (CartPole: 4 float32)
 
 
-def build_dqn(double, capacity, per=False, n_step=1, atoms=1):
+def _states(rng, n):
+    if MODEL["name"] == "DqnMlp":
+        return rng.standard_normal((n, 4)).astype(np.float32)
+    return rng.integers(0, 256, (n, DIM, DIM, 4), dtype=np.uint8)
+
+
+def build_dqn(double, capacity, per=False, n_step=1, atoms=1, quantiles=1):
     from xingtian_amd.algorithm import alg_builder
-    info = {"actor": {"model_name": "DqnCnn", "type": "learner", "state_dim": [DIM, DIM, 4], "action_dim": A_DIM,
+    info = {"actor": {"model_name": MODEL["name"], "type": "learner",
+                      "state_dim": [4] if MODEL["name"] == "DqnMlp" else [DIM, DIM, 4], "action_dim": A_DIM,
                       "model_config": {"LR": 0.00015, "SEED": 0}}}
     if atoms > 1:
         info["actor"]["model_config"]["atoms"] = atoms
+    if quantiles > 1:
+        info["actor"]["model_config"]["quantiles"] = quantiles
     cfg = {"instance_num": 1, "agent_num": 1, "prepare_times_per_train": 4, "BUFFER_SIZE": capacity, "BATCH_SIZE": B,
            "TARGET_UPDATE_FREQ": 1000, "double_dqn": double, "prioritized_replay": per}
     if n_step != 1:
@@ -53,8 +68,7 @@ def build_dqn(double, capacity, per=False, n_step=1, atoms=1):
     rng = np.random.default_rng(1)
     for _ in range(capacity // 512):
         n = 512
-        alg.prepare_data({"cur_state": rng.integers(0, 256, (n, DIM, DIM, 4), dtype=np.uint8),
-                          "next_state": rng.integers(0, 256, (n, DIM, DIM, 4), dtype=np.uint8),
+        alg.prepare_data({"cur_state": _states(rng, n), "next_state": _states(rng, n),
                           "action": rng.integers(0, A_DIM, n), "reward": rng.choice([-1.0, 0.0, 1.0], n),
                           "done": rng.random(n) < 0.02})
     return alg
@@ -66,8 +80,11 @@ def main():
     ap.add_argument("--trains", type=int, default=200)
     ap.add_argument("--capacity", type=int, default=4096)
     ap.add_argument("--atoms", type=int, default=0)
+    ap.add_argument("--quantiles", type=int, default=0)
+    ap.add_argument("--model", default="DqnCnn", choices=["DqnCnn", "DqnMlp"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    MODEL["name"] = args.model
     import torch
     from xingtian_amd.algorithm.dqn import dqn as dqn_mod
     from xingtian_amd.model import netspec
@@ -109,8 +126,7 @@ def main():
                                                 dqn_mod.GAMMA, False)
 
     msg_rng = np.random.default_rng(3)
-    msg = {"cur_state": msg_rng.integers(0, 256, (20, DIM, DIM, 4), dtype=np.uint8),
-           "next_state": msg_rng.integers(0, 256, (20, DIM, DIM, 4), dtype=np.uint8),
+    msg = {"cur_state": _states(msg_rng, 20), "next_state": _states(msg_rng, 20),
            "action": msg_rng.integers(0, A_DIM, 20), "reward": msg_rng.choice([-1.0, 0.0, 1.0], 20),
            "done": msg_rng.random(20) < 0.02}
 
@@ -133,13 +149,18 @@ def main():
              ("prepare_data, 20 rows, synchronised", ingest(algs[False])),
              ("prepare_data, 20 rows, PER, synchronised", ingest(pers[False])),
              ("keras_impala_step + adam_keras, 32 rows, enqueue only", impala_step)]
-    if args.atoms > 1:
+    if args.model == "DqnMlp":
+        cases = cases[:-1]                                  # (the IMPALA row is the CNN trunk's)
+    pos = 12                                                # the head arms go behind the twelve train rows
+    for key, count in (("atoms", args.atoms), ("quantiles", args.quantiles)):
+        if count <= 1:
+            continue
         # the distributional arms share ONE algorithm per (PER, n_step) -- double_dqn is an argument of the train and the
         # kernel selection a switch of the two nets -- so four more rings, not sixteen
-        dist = {(per, n): build_dqn(False, args.capacity, per, n, args.atoms) for per in (False, True) for n in (1, 3)}
+        dist = {(per, n): build_dqn(False, args.capacity, per, n, **{key: count}) for per in (False, True) for n in (1, 3)}
         dist_slots = torch.tensor(dist[(False, 1)].buff.sample(B), dtype=torch.int32).cuda()
 
-        def dist_case(per, n, double, wide, read_back):
+        def dist_case(per, n, double, wide, read_back, dist=dist, dist_slots=dist_slots):
             alg = dist[(per, n)]
 
             def fn():
@@ -157,12 +178,13 @@ def main():
             for wide in (True, False):
                 for per, n, double in ((False, 1, False), (True, 1, False), (False, 3, False), (True, 3, False),
                                        (False, 1, True), (True, 1, True), (False, 3, True), (True, 3, True)):
-                    name = "{}, atoms {}{}{}{}{}{}".format(
-                        "DQN.train" if read_back else "dqn step + adam", args.atoms, ", PER" if per else "",
+                    name = "{}, {} {}{}{}{}{}{}".format(
+                        "DQN.train" if read_back else "dqn step + adam", key, count, ", PER" if per else "",
                         ", n_step 3" if n == 3 else "", ", double_dqn" if double else "", "" if wide else ", generic head kernels",
                         " (loss read back)" if read_back else ", enqueue only")
                     extra.append((name, dist_case(per, n, double, wide, read_back)))
-        cases = cases[:12] + extra + cases[12:]
+        cases = cases[:pos] + extra + cases[pos:]
+        pos += len(extra)
     for _, fn in cases:
         for _ in range(20):
             fn()
@@ -176,7 +198,8 @@ def main():
                 fn()
             torch.cuda.synchronize()
             times[name].append(1e6 * (time.perf_counter() - t0) / args.trains)
-    lines = ["| what (DqnCnn 84x84x4, A = 4, B = 32) | us per call: median | min | max |", "|---|---|---|---|"]
+    lines = ["| what ({}, A = 4, B = 32) | us per call: median | min | max |".format(
+        "DqnCnn 84x84x4" if args.model == "DqnCnn" else "DqnMlp, state 4"), "|---|---|---|---|"]
     for name, _ in cases:
         t = sorted(times[name])
         lines.append("| {} | {:.1f} | {:.1f} | {:.1f} |".format(name, t[len(t) // 2], t[0], t[-1]))

@@ -31,8 +31,13 @@ action's distribution (``dist_support`` / ``dist_q`` / ``categorical_projection`
 with ``double_dqn``, ``prioritized_replay`` (the new priority is the sample's loss + eps) and ``n_step``, and like
 prioritised replay it needs the device step.
 
+``model_config.quantiles`` > 1 makes the pair quantile-regression (QR-DQN) instead: the train is
+``xt_net_dqn_step_quant``, whose head takes the pairwise quantile-Huber loss between the taken action's quantiles and the
+Bellman targets of the bootstrap action's (``quantile_midpoints`` / ``quant_q`` / ``quantile_huber`` are the host
+definitions).  There is no support to choose; it composes and is bound to the device step in the same way.
+
 Every variant reaches its C entry through the model's ``train_replay`` / ``train_replay_per`` and one method of the net,
-``HipActorCritic.dqn_step``, whose keywords (``follow`` / ``n``, ``per``, ``dist``) choose the entry.
+``HipActorCritic.dqn_step``, whose keywords (``follow`` / ``n``, ``per``, ``dist``, ``quant``) choose the entry.
 """
 import random
 
@@ -42,6 +47,7 @@ import torch
 from xingtian_amd.algorithm.algorithm import Algorithm
 from xingtian_amd.algorithm.dqn.default_config import BATCH_SIZE, BUFFER_SIZE, GAMMA, TARGET_UPDATE_FREQ
 from xingtian_amd.model.dqn.dqn_cnn import categorical_projection, dist_q, dist_support  # noqa: F401
+from xingtian_amd.model.dqn.dqn_cnn import quant_q, quantile_huber, quantile_midpoints  # noqa: F401
 from xingtian_amd.register import Registers, import_config
 
 
@@ -237,6 +243,12 @@ class DQN(Algorithm):
                 "DQN: a distributional actor (atoms = {}) needs a model with the device step (a learner DqnCnn / DqnMlp on "
                 "the GPU): the target distribution is projected on the device, where the target network's output is; {} "
                 "has none".format(self.atoms, type(self.actor).__name__))
+        self.quantiles = int(getattr(self.actor, "quantiles", 1))
+        if self.quantiles > 1 and not self.device_step:
+            raise NotImplementedError(
+                "DQN: a quantile actor (quantiles = {}) needs a model with the device step (a learner DqnCnn / DqnMlp on "
+                "the GPU): the quantile targets are formed on the device, where the target network's output is; {} "
+                "has none".format(self.quantiles, type(self.actor).__name__))
         self.prioritized = bool(alg_config.get("prioritized_replay", False))
         n_step = alg_config.get("n_step", 1)
         if isinstance(n_step, bool) or not isinstance(n_step, (int, np.integer)) or not 1 <= n_step <= 256:

@@ -324,6 +324,104 @@ __global__ __launch_bounds__(64) void dqn_loss_dist_kernel(const float* __restri
   }
 }
 
+// ---------------------------------------------------------------- quantile-regression (QR-DQN) head, DESIGN.md section 7
+// quant_q of one action's N quantiles by one thread: the float64 sum over ascending i, divided by N, rounded once
+__device__ __forceinline__ float quant_q_of(const float* __restrict__ th, int N) {
+  double s = 0.0;
+  for (int i = 0; i < N; ++i) s += (double)th[i];
+  return (float)(s / (double)N);
+}
+
+// One wavefront per sample (grid B, 64 threads), lanes stride the quantiles (up to 4 per lane at N = 256).  In order:
+// lane a < A forms quant_q of action a of the picking quantiles (o_logits, else t_logits) by its own ordered sum and a
+// butterfly picks a* = the first maximal one; the N targets T_j = (float)(dn ? R : R + g theta'_j) of the target net's
+// quantiles of a* go into LDS; every lane forms r_i and g_i of its quantiles of the taken action by the float64 sum over
+// ascending j (LDS broadcasts: no atomics, no dependence on thread order); loss_b = sum_i r_i by a wave reduction; then
+// the gradient row w_b g_i / B with exact zeros in every other column, dvalue = 0 and terms[b] = (loss_b, quant_q_target(a*)).
+__global__ __launch_bounds__(64) void dqn_loss_quant_kernel(const float* __restrict__ logits, const float* __restrict__ t_logits,
+                                                            const float* __restrict__ o_logits, int B, int A, int N,
+                                                            float kappa, const int32_t* __restrict__ slots,
+                                                            const int32_t* __restrict__ action,
+                                                            const double* __restrict__ reward, const uint8_t* __restrict__ done,
+                                                            double gamma, float* __restrict__ dlogits,
+                                                            float* __restrict__ dvalue, float2* __restrict__ terms,
+                                                            int32_t* __restrict__ astar_out, float* __restrict__ maxq_out,
+                                                            const double* __restrict__ weights,
+                                                            const double* __restrict__ disc) {
+  __shared__ float s_t[256];
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const size_t W = (size_t)A * N;
+  const long long row = slots ? (long long)slots[b] : (long long)b;
+  const float* tl = t_logits + (size_t)b * W;
+  const float* pl = o_logits ? o_logits + (size_t)b * W : tl;
+  // (A <= 64: one action per lane; a lane without one holds -inf under an index no action has)
+  float q = lane < A ? quant_q_of(pl + (size_t)lane * N, N) : -INFINITY;
+  float qb = q;
+  int astar = lane;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float qo = __shfl_xor(qb, o, 64);
+    const int io = __shfl_xor(astar, o, 64);
+    if (qo > qb || (qo == qb && io < astar)) { qb = qo; astar = io; }
+  }
+  astar = __shfl(astar, 0, 64);                    // (uniform whatever the quantiles hold)
+  astar = astar < A ? astar : A - 1;
+  const float* ts = tl + (size_t)astar * N;
+  const float qstar = o_logits ? quant_q_of(ts, N) : __shfl(q, astar, 64);
+  const double R = reward[row];
+  const double g = disc ? disc[b] : gamma;
+  const bool dn = done[row] != 0;
+  for (int j = lane; j < N; j += 64) s_t[j] = dn ? (float)R : (float)(R + g * (double)ts[j]);
+  __syncthreads();
+  int act = action[row];
+  act = act < 0 ? 0 : (act >= A ? A - 1 : act);    // (an action outside [0, A) never indexes outside the row)
+  const float* l = logits + (size_t)b * W + (size_t)act * N;
+  const double dN = (double)N;
+  float gr[4];
+  float loss = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = lane + 64 * k;
+    gr[k] = 0.f;
+    if (i < N) {
+      const float th = l[i];
+      const double tau = (double)(2 * i + 1) / (2.0 * dN);
+      const float w_neg = (float)(1.0 - tau), w_pos = (float)tau;
+      double sr = 0.0, sg = 0.0;
+      for (int j = 0; j < N; ++j) {
+        const float u = s_t[j] - th;
+        const float wt = u < 0.f ? w_neg : w_pos;
+        const float au = fabsf(u);
+        const float hub = au <= kappa ? 0.5f * u * u : kappa * (au - 0.5f * kappa);
+        const float cl = u < -kappa ? -kappa : (u > kappa ? kappa : u);
+        sr += (double)(wt * hub / kappa);
+        sg += (double)(wt * cl / kappa);
+      }
+      loss += (float)(sr / dN);
+      gr[k] = (float)(-sg / dN);
+    }
+  }
+  loss = dist_wave_sum(loss);
+  const float fb = (float)B;
+  float* dl = dlogits + (size_t)b * W;
+  const size_t c0 = (size_t)act * N;
+  for (size_t c = lane; c < W; c += 64)
+    if (c < c0 || c >= c0 + N) dl[c] = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = lane + 64 * k;
+    if (i < N) dl[c0 + i] = (weights ? (float)weights[b] * gr[k] : gr[k]) / fb;
+  }
+  if (lane == 0) {
+    dvalue[b] = 0.f;
+    terms[b] = make_float2(loss, qstar);
+    if (astar_out) astar_out[b] = astar;
+    if (maxq_out) maxq_out[b] = qstar;
+  }
+}
+
 // The checks the two gather entries share (`who` names the entry in refusals); *nvec: 16-byte vectors per row
 static int replay_gather_check(const char* who, const void* ring, const void* dst, int64_t row_bytes, int64_t capacity,
                                int32_t B, long long* nvec) {
@@ -355,6 +453,26 @@ int xt_dqn_loss_dist(const float* logits, const float* t_logits, const float* o_
   float2* terms = reinterpret_cast<float2*>(out + 4);       // out: >= 4 + 2*B floats
   hipLaunchKernelGGL(xt::dqn_loss_dist_kernel, dim3(B), dim3(64), 0, st, logits, t_logits, o_logits, B, A, atoms, v_min, v_max,
                      slots, action, reward, done, gamma, dlogits, dvalue, terms, astar, maxq, m, weights, disc);
+  XT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(xt::dqn_loss_reduce_kernel<true>, dim3(1), dim3(256), 0, st, terms, B, A, out, acc, weights);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+
+int xt_dqn_loss_quant(const float* logits, const float* t_logits, const float* o_logits, int32_t B, int32_t A,
+                      int32_t quantiles, double kappa, const int32_t* slots, const int32_t* action, const double* reward,
+                      const uint8_t* done, double gamma, float* dlogits, float* dvalue, float* out, int32_t* astar, float* maxq,
+                      float* acc, const double* weights, const double* disc, void* stream) {
+  XT_REQUIRE(logits && t_logits && action && reward && done && dlogits && dvalue && out, "xt_dqn_loss_quant: null argument");
+  XT_REQUIRE(quantiles >= 2 && quantiles <= 256, "xt_dqn_loss_quant: quantiles = %d outside [2, 256]", quantiles);
+  XT_REQUIRE(B > 0 && A >= 1 && A <= 64, "xt_dqn_loss_quant: bad sizes (B=%d A=%d; 1 <= A <= 64)", B, A);
+  XT_REQUIRE(std::isfinite(kappa) && (float)kappa > 0.f && std::isfinite((float)kappa),
+             "xt_dqn_loss_quant: kappa must be finite and > 0 as a float32 (got %g)", kappa);
+  XT_REQUIRE(((uintptr_t)out & 7) == 0, "xt_dqn_loss_quant: out must be 8-byte aligned");
+  hipStream_t st = xt::as_stream(stream);
+  float2* terms = reinterpret_cast<float2*>(out + 4);       // out: >= 4 + 2*B floats
+  hipLaunchKernelGGL(xt::dqn_loss_quant_kernel, dim3(B), dim3(64), 0, st, logits, t_logits, o_logits, B, A, quantiles,
+                     (float)kappa, slots, action, reward, done, gamma, dlogits, dvalue, terms, astar, maxq, weights, disc);
   XT_LAUNCH_CHECK();
   hipLaunchKernelGGL(xt::dqn_loss_reduce_kernel<true>, dim3(1), dim3(256), 0, st, terms, B, A, out, acc, weights);
   XT_LAUNCH_CHECK();

@@ -140,9 +140,13 @@ struct xt_net {
   float* trows = nullptr;
   int last_head_path = 0;
   int gauss_fused = 0;                // xt_net_set_gauss_fused: a DiagGaussian step inside the envelope takes the fused head launch
-  // xt_net_set_dist: atoms of a distributional Q head (0: a scalar one; A is then actions * atoms wide) and its support
-  int dist_atoms = 0;
+  // xt_net_set_dist / xt_net_set_quant: the mark of a distributional Q head (at most one of the two).  head_group: columns
+  // per action (atoms of a C51 head, quantiles of a QR-DQN one; 0: a scalar head -- A is actions * head_group wide);
+  // head_kind says which; then the C51 support and the quantile head's Huber threshold
+  int head_group = 0;
+  int head_kind = XT_HEAD_SCALAR;
   double dist_vmin = 0.0, dist_vmax = 0.0;
+  double quant_kappa = 0.0;
   int dist_wide = 0;                  // xt_net_set_dist_wide: the wide-head forward and the taken-action d(features)
   // xt_net_last_step_report: what the most recent forward / backward / tail decided (host words, read by nothing else)
   int last_fuse12 = 0, last_fuse21 = 0, last_tail_mode = 0, last_finish_form = -1;
@@ -225,7 +229,7 @@ static Heads heads_of(xt_net* n) {
 }
 static int heads_forward(xt_net* n, int B, hipStream_t st) {
   const Heads h = heads_of(n);
-  if (n->dist_atoms && n->dist_wide && h.f_pi == h.f_v)   // (only a net marked distributional: no other net changes kernels)
+  if (n->head_group && n->dist_wide && h.f_pi == h.f_v)   // (only a net marked distributional: no other net changes kernels)
     return launch_heads_fwd_wide(h.f_pi, B, h.F, h.A, h.wpi, h.bpi, h.wv, h.bv, n->ws + n->off_logits, n->ws + n->off_value, st);
   return xt_heads_fwd(h.f_pi, h.f_v, B, h.F, h.A, h.wpi, h.bpi, h.wv, h.bv, n->ws + n->off_logits, n->ws + n->off_value, st);
 }
@@ -235,8 +239,8 @@ static int heads_forward(xt_net* n, int B, hipStream_t st) {
 static int heads_dfeat(xt_net* n, int B, hipStream_t st, const int32_t* dist_slots = nullptr,
                        const int32_t* dist_action = nullptr) {
   const Heads h = heads_of(n);
-  if (dist_action && n->dist_atoms && n->dist_wide && h.fd_pi == h.fd_v)
-    return launch_heads_dfeat_dist(h.fd_pi, B, h.F, h.A, n->dist_atoms, h.wpi, h.wv, n->ws + n->off_dlogits,
+  if (dist_action && n->head_group && n->dist_wide && h.fd_pi == h.fd_v)
+    return launch_heads_dfeat_dist(h.fd_pi, B, h.F, h.A, n->head_group, h.wpi, h.wv, n->ws + n->off_dlogits,
                                    n->ws + n->off_dvalue, dist_slots, dist_action, h.Lp->g.act, n->ws + h.Lp->dact_off, st);
   return launch_heads_dfeat(h.fd_pi, h.fd_v, B, h.F, h.A, h.wpi, h.wv, n->ws + n->off_dlogits, n->ws + n->off_dvalue,
                             h.Lp->g.act, n->ws + h.Lp->dact_off, n->ws + h.Lv->dact_off, st);
@@ -1819,22 +1823,24 @@ struct dqn_args {
   const uint8_t* done;
   float *loss_out, *loss_acc;
   void* stream;
-  bool dist = false;
+  int head = XT_HEAD_SCALAR;                                // the head: XT_HEAD_SCALAR / _C51 / _QUANT
   const xt_nstep_cfg* ns = nullptr;
   const xt_per_cfg* per = nullptr;
   int64_t size = 0;
   const int32_t* slots = nullptr;
 };
 
-// The chain of one DQN.train up to the gradient, shared by xt_net_dqn_step, xt_net_dqn_step_per, xt_net_dqn_step_n and
-// xt_net_dqn_step_dist (`who` names the entry in refusals).  per (may be NULL): prioritised replay -- once every refusal
-// has passed, xt_per_sample fills per->slots / per->weights from `size` stored transitions, the chain runs on them with
-// the weighted head, and xt_per_update follows the loss; `slots` is then ignored.  ns (may be NULL): n-step returns -- the
+// The chain of one DQN.train up to the gradient, shared by xt_net_dqn_step, xt_net_dqn_step_per, xt_net_dqn_step_n,
+// xt_net_dqn_step_dist and xt_net_dqn_step_quant (`who` names the entry in refusals).  per (may be NULL): prioritised
+// replay -- once every refusal has passed, xt_per_sample fills per->slots / per->weights from `size` stored
+// transitions, the chain runs on them with the weighted head, and xt_per_update follows the loss; `slots` is then
+// ignored.  ns (may be NULL): n-step returns -- the
 // first gather walks each start slot to its boot slot and leaves the per-sample labels in ns' scratch
 // (xt_replay_gather_nstep), both next-state forwards run on the boot rows, and the head reads those dense labels with the
 // per-sample discount; the state rows and the new priorities stay those of the start slots.  The launches are the same in
-// number either way.  dist: both nets carry the mark of xt_net_set_dist and the head is xt_dqn_loss_dist on their
-// actions * atoms wide logits (two launches, as xt_dqn_loss_n); a net with the mark is refused by the scalar entries.
+// number either way.  head XT_HEAD_C51: both nets carry the mark of xt_net_set_dist and the head is xt_dqn_loss_dist on
+// their actions * atoms wide logits (two launches, as xt_dqn_loss_n); XT_HEAD_QUANT: the mark of xt_net_set_quant and
+// xt_dqn_loss_quant, likewise.  A net with a mark is refused by every entry but its own.
 static int dqn_chain(xt_net* n, xt_net* tn, const dqn_args& a) {
   const xt_dqn_cfg* c = a.c;
   const xt_nstep_cfg* ns = a.ns;
@@ -1852,18 +1858,30 @@ static int dqn_chain(xt_net* n, xt_net* tn, const dqn_args& a) {
   XT_REQUIRE(tn->A == n->A && tn->feat == n->feat && tn->P == n->P && tn->layers.size() == n->layers.size() &&
                  tn->in_h == n->in_h && tn->in_w == n->in_w && tn->in_c == n->in_c && tn->xf.is_u8 == n->xf.is_u8,
              "%s: target_net is not a net of the same description", a.who);
-  int atoms = 1;
-  if (a.dist) {
-    XT_REQUIRE(n->dist_atoms >= 2 && tn->dist_atoms == n->dist_atoms && tn->dist_vmin == n->dist_vmin &&
-                   tn->dist_vmax == n->dist_vmax,
-               "%s: both nets must be marked distributional with the same atoms and bounds (xt_net_set_dist: net %d atoms "
-               "[%g, %g], target_net %d atoms [%g, %g])", a.who, n->dist_atoms, n->dist_vmin, n->dist_vmax, tn->dist_atoms,
-               tn->dist_vmin, tn->dist_vmax);
-    atoms = n->dist_atoms;
-    XT_REQUIRE(!c->dueling, "%s: no dueling stream with a distributional head (it would have to be %d wide)", a.who, atoms);
-  } else {
-    XT_REQUIRE(n->dist_atoms == 0 && tn->dist_atoms == 0,
+  // a net with a mark goes to the entry of its mark and to no other; each refusal names that entry
+  for (const xt_net* m : {n, tn}) {
+    XT_REQUIRE(m->head_kind != XT_HEAD_C51 || a.head == XT_HEAD_C51,
                "%s: the net is marked distributional (xt_net_set_dist): its step is xt_net_dqn_step_dist", a.who);
+    XT_REQUIRE(m->head_kind != XT_HEAD_QUANT || a.head == XT_HEAD_QUANT,
+               "%s: the net is marked quantile (xt_net_set_quant): its step is xt_net_dqn_step_quant", a.who);
+  }
+  int atoms = 1;                                            // columns per action
+  if (a.head == XT_HEAD_C51) {
+    XT_REQUIRE(n->head_kind == XT_HEAD_C51 && tn->head_kind == XT_HEAD_C51 && n->head_group >= 2 &&
+                   tn->head_group == n->head_group && tn->dist_vmin == n->dist_vmin && tn->dist_vmax == n->dist_vmax,
+               "%s: both nets must be marked distributional with the same atoms and bounds (xt_net_set_dist: net %d atoms "
+               "[%g, %g], target_net %d atoms [%g, %g])", a.who, n->head_kind == XT_HEAD_C51 ? n->head_group : 0, n->dist_vmin,
+               n->dist_vmax, tn->head_kind == XT_HEAD_C51 ? tn->head_group : 0, tn->dist_vmin, tn->dist_vmax);
+    atoms = n->head_group;
+    XT_REQUIRE(!c->dueling, "%s: no dueling stream with a distributional head (it would have to be %d wide)", a.who, atoms);
+  } else if (a.head == XT_HEAD_QUANT) {
+    XT_REQUIRE(n->head_kind == XT_HEAD_QUANT && tn->head_kind == XT_HEAD_QUANT && n->head_group >= 2 &&
+                   tn->head_group == n->head_group && tn->quant_kappa == n->quant_kappa,
+               "%s: both nets must be marked quantile with the same quantiles and kappa (xt_net_set_quant: net %d quantiles "
+               "kappa %g, target_net %d quantiles kappa %g)", a.who, n->head_kind == XT_HEAD_QUANT ? n->head_group : 0,
+               n->quant_kappa, tn->head_kind == XT_HEAD_QUANT ? tn->head_group : 0, tn->quant_kappa);
+    atoms = n->head_group;
+    XT_REQUIRE(!c->dueling, "%s: no dueling stream with a quantile head (it would have to be %d wide)", a.who, atoms);
   }
   XT_REQUIRE(n->A / atoms <= 64, "%s: A = %d exceeds 64", a.who, n->A / atoms);
   XT_REQUIRE(a.B > 0 && a.B <= n->maxB && a.B <= tn->maxB, "%s: batch %d outside (0,%d]", a.who, a.B,
@@ -1917,7 +1935,14 @@ static int dqn_chain(xt_net* n, xt_net* tn, const dqn_args& a) {
   const double* l_reward = ns ? ns->reward_n : a.reward;
   const uint8_t* l_done = ns ? ns->done_n : a.done;
   const double* l_disc = ns ? ns->disc_n : nullptr;
-  if (a.dist) {
+  const bool grouped = a.head != XT_HEAD_SCALAR;
+  if (a.head == XT_HEAD_QUANT) {
+    if (int rc = xt_dqn_loss_quant(n->ws + n->off_logits, t_logits, o_logits, a.B, A / atoms, atoms, n->quant_kappa, l_slots,
+                                   l_action, l_reward, l_done, c->gamma, n->ws + n->off_dlogits, n->ws + n->off_dvalue, lo,
+                                   reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB, a.loss_acc, weights, l_disc,
+                                   a.stream))
+      return rc;
+  } else if (a.head == XT_HEAD_C51) {
     if (int rc = xt_dqn_loss_dist(n->ws + n->off_logits, t_logits, o_logits, a.B, A / atoms, atoms, n->dist_vmin, n->dist_vmax,
                                   l_slots, l_action, l_reward, l_done, c->gamma, n->ws + n->off_dlogits, n->ws + n->off_dvalue,
                                   lo, reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB, nullptr, a.loss_acc,
@@ -1930,7 +1955,7 @@ static int dqn_chain(xt_net* n, xt_net* tn, const dqn_args& a) {
     return rc;
   }
   if (a.loss_out) XT_CHECK_HIP(hipMemcpyAsync(a.loss_out, lo, 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-  if (int rc = xt::heads_dfeat(n, a.B, st, a.dist ? l_slots : nullptr, a.dist ? l_action : nullptr)) return rc;
+  if (int rc = xt::heads_dfeat(n, a.B, st, grouped ? l_slots : nullptr, grouped ? l_action : nullptr)) return rc;
   if (int rc = xt::trunk_backward(n, c->cur_rows, nullptr, a.B, st)) return rc;
   if (int rc = xt::grads_finish(n, a.B, nullptr, st)) return rc;
   if (!per) return 0;
@@ -1981,14 +2006,44 @@ int xt_net_dqn_step_dist(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_ns
                          float* loss_out, float* loss_acc, void* stream) {
   xt::dqn_args a{"xt_net_dqn_step_dist", c, cur_ring, next_ring, row_bytes, capacity, B, action, reward, done, loss_out,
                   loss_acc, stream};
-  a.dist = true; a.ns = ns; a.per = p; a.size = size; a.slots = p ? nullptr : slots;
+  a.head = XT_HEAD_C51; a.ns = ns; a.per = p; a.size = size; a.slots = p ? nullptr : slots;
   return xt::dqn_chain(n, tn, a);
+}
+
+int xt_net_dqn_step_quant(xt_net* n, xt_net* tn, const xt_dqn_cfg* c, const xt_nstep_cfg* ns, const xt_per_cfg* p,
+                          const void* cur_ring, const void* next_ring, int64_t row_bytes, int64_t capacity, int64_t size,
+                          const int32_t* slots, int32_t B, const int32_t* action, const double* reward, const uint8_t* done,
+                          float* loss_out, float* loss_acc, void* stream) {
+  xt::dqn_args a{"xt_net_dqn_step_quant", c, cur_ring, next_ring, row_bytes, capacity, B, action, reward, done, loss_out,
+                  loss_acc, stream};
+  a.head = XT_HEAD_QUANT; a.ns = ns; a.per = p; a.size = size; a.slots = p ? nullptr : slots;
+  return xt::dqn_chain(n, tn, a);
+}
+
+int xt_net_set_quant(xt_net* net, int32_t quantiles, double kappa) {
+  XT_REQUIRE(net, "xt_net_set_quant: null net");
+  XT_REQUIRE(net->head_kind != XT_HEAD_C51,
+             "xt_net_set_quant: the net is marked distributional (xt_net_set_dist): a net carries one mark, clear that one first");
+  if (quantiles == 1) {
+    net->head_group = 0; net->head_kind = XT_HEAD_SCALAR; net->quant_kappa = 0.0; net->dist_wide = 0;
+    return 0;
+  }
+  XT_REQUIRE(quantiles >= 2 && quantiles <= 256, "xt_net_set_quant: quantiles = %d outside [1, 256]", quantiles);
+  XT_REQUIRE(std::isfinite(kappa) && (float)kappa > 0.f && std::isfinite((float)kappa),
+             "xt_net_set_quant: kappa must be finite and > 0 as a float32 (got %g)", kappa);
+  XT_REQUIRE(net->action_type == XT_ACTION_CATEGORICAL, "xt_net_set_quant: categorical heads only");
+  XT_REQUIRE(net->A % quantiles == 0, "xt_net_set_quant: the head is %d wide, no multiple of quantiles = %d", net->A,
+             quantiles);
+  net->head_group = quantiles; net->head_kind = XT_HEAD_QUANT; net->quant_kappa = kappa; net->dist_wide = 1;
+  return 0;
 }
 
 int xt_net_set_dist(xt_net* net, int32_t atoms, double v_min, double v_max) {
   XT_REQUIRE(net, "xt_net_set_dist: null net");
+  XT_REQUIRE(net->head_kind != XT_HEAD_QUANT,
+             "xt_net_set_dist: the net is marked quantile (xt_net_set_quant): a net carries one mark, clear that one first");
   if (atoms == 1) {
-    net->dist_atoms = 0; net->dist_vmin = net->dist_vmax = 0.0; net->dist_wide = 0;
+    net->head_group = 0; net->head_kind = XT_HEAD_SCALAR; net->dist_vmin = net->dist_vmax = 0.0; net->dist_wide = 0;
     return 0;
   }
   XT_REQUIRE(atoms >= 2 && atoms <= 256, "xt_net_set_dist: atoms = %d outside [1, 256]", atoms);
@@ -1996,13 +2051,14 @@ int xt_net_set_dist(xt_net* net, int32_t atoms, double v_min, double v_max) {
              "xt_net_set_dist: the support needs finite v_min < v_max (got %g, %g)", v_min, v_max);
   XT_REQUIRE(net->action_type == XT_ACTION_CATEGORICAL, "xt_net_set_dist: categorical heads only");
   XT_REQUIRE(net->A % atoms == 0, "xt_net_set_dist: the head is %d wide, no multiple of atoms = %d", net->A, atoms);
-  net->dist_atoms = atoms; net->dist_vmin = v_min; net->dist_vmax = v_max; net->dist_wide = 1;
+  net->head_group = atoms; net->head_kind = XT_HEAD_C51; net->dist_vmin = v_min; net->dist_vmax = v_max; net->dist_wide = 1;
   return 0;
 }
 
 int xt_net_set_dist_wide(xt_net* net, int32_t on) {
   XT_REQUIRE(net, "xt_net_set_dist_wide: null net");
-  XT_REQUIRE(net->dist_atoms, "xt_net_set_dist_wide: the net is not marked distributional (xt_net_set_dist)");
+  XT_REQUIRE(net->head_group,
+             "xt_net_set_dist_wide: the net is not marked distributional (xt_net_set_dist) or quantile (xt_net_set_quant)");
   net->dist_wide = on ? 1 : 0;
   return 0;
 }

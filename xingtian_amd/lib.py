@@ -288,6 +288,11 @@ SIGNATURES = {
     "xt_norm_finalize_ex": (c_int32, [_P, c_int32, POINTER(FinishArgs), _P]),
     "xt_net_last_step_report": (c_int32, [_P, POINTER(c_int32), c_int32]),
     "xt_net_graph_cache_info": (c_int32, [_P, POINTER(c_int32), c_int32]),
+    "xt_dqn_loss_quant": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P, c_double, _P, _P, _P, _P,
+                                    _P, _P, _P, _P, _P]),
+    "xt_net_set_quant": (c_int32, [_P, c_int32, c_double]),
+    "xt_net_dqn_step_quant": (c_int32, [_P, _P, POINTER(DqnCfg), POINTER(NstepCfg), POINTER(PerCfg), _P, _P, c_int64, c_int64,
+                                        c_int64, _P, c_int32, _P, _P, _P, _P, _P, _P]),
 }
 # XT_GRAPH_CACHE_<name> of include/xt_mi355x.h: word of every counter of xt_net_graph_cache_info
 GRAPH_CACHE_WORDS = ("CAPTURES", "LAUNCHES", "EVICTIONS", "LIVE_SLOTS")

@@ -6,13 +6,20 @@ the A-wide stream ``l`` combine to Q_a = s + (l_a - mean_a l) -- compiled with `
 returns Q as float32 [N, A].  The update does not go through ``train(states, y_t)``: the algorithm keeps its replay
 store on the device and one C call (``xt_net_dqn_step``) forms the TD target and the gradient there
 (``train_replay``), so ``train`` is not provided.  ``train_replay`` and ``train_replay_per`` are one call of
-``HipActorCritic.dqn_step``, whose keywords (``follow`` / ``n``, ``per``, ``dist``) choose among the four C entries.
+``HipActorCritic.dqn_step``, whose keywords (``follow`` / ``n``, ``per``, ``dist``, ``quant``) choose among the five C
+entries.
 
 ``model_config.atoms`` (1 unless asked for) with ``v_min`` / ``v_max`` (-10 / 10) makes the network distributional (C51,
 Bellemare et al. 2017): the Q head is A * atoms wide, column a * atoms + i being the logit of atom i of action a, and
 ``predict`` returns the expectation of every action's softmax over the fixed support (``dist_q``).  The definitions
 below (``dist_support``, ``dist_q``, ``categorical_projection``) are the host twins of the head kernel
 ``xt_dqn_loss_dist``: the same arithmetic in the same precision, and the tests' first reference.
+
+``model_config.quantiles`` (1 unless asked for) with ``kappa`` (1.0) makes it a quantile-regression network instead
+(QR-DQN, Dabney et al. 2018): the Q head is A * quantiles wide, column a * quantiles + i being quantile i of action a at
+the midpoint tau_i = (2 i + 1) / (2 N); there is no support to choose.  ``predict`` returns the mean of every action's
+quantiles (``quant_q``).  ``quantile_midpoints``, ``quant_q`` and ``quantile_huber`` are the host twins of the head kernel
+``xt_dqn_loss_quant``.  A network is one or the other, never both.
 """
 import numpy as np
 
@@ -93,6 +100,80 @@ def dist_config(model_config, action_dim):
     return atoms, v_min, v_max
 
 
+def quantile_midpoints(quantiles):
+    """-> tau float64 [N]: tau_i = (2 i + 1) / (2 N)"""
+    n = int(quantiles)
+    if n < 1:
+        raise ValueError("quantile_midpoints: needs quantiles >= 1 (got {})".format(quantiles))
+    return (2.0 * np.arange(n, dtype=np.float64) + 1.0) / (2.0 * np.float64(n))
+
+
+def quant_q(theta):
+    """Mean of the quantiles [..., N] (float32): the float64 sum over ascending i, divided by N, rounded once.
+    -> float32 [...]"""
+    t = np.asarray(theta, np.float32)
+    s = np.zeros(t.shape[:-1], np.float64)
+    for i in range(t.shape[-1]):                        # ascending i: the kernel's order of summation
+        s = s + t[..., i].astype(np.float64)
+    return (s / np.float64(t.shape[-1])).astype(np.float32)
+
+
+def quantile_huber(theta, target_theta, reward, disc, done, kappa):
+    """The quantile-Huber loss of QR-DQN and its gradient, per sample, as the kernel forms them: for the online quantiles
+    ``theta`` [B, N] of the taken action, the target net's quantiles ``target_theta`` [B, N] of the bootstrap action
+    (float32) and per-sample labels (R, g, dn),
+
+        T_j = (float32)(dn ? R : R + g * (float64)theta'_j);  u_ij = T_j - theta_i   (float32)
+        wt_ij = u_ij < 0 ? (float32)(1 - tau_i) : (float32)tau_i
+        H(u) = |u| <= kappa ? 0.5 u u : kappa (|u| - 0.5 kappa)                      (float32)
+        r_i = (float32)((sum_{j ascending} (float64)(wt_ij * H(u_ij) / kappa)) / N)
+        g_i = (float32)(-(sum_{j ascending} (float64)(wt_ij * clip(u_ij, -kappa, kappa) / kappa)) / N)
+
+    -> (loss_b float32 [B] = sum_i r_i, g float32 [B, N] = d loss_b / d theta)"""
+    th, tt = np.asarray(theta, np.float32), np.asarray(target_theta, np.float32)
+    b, n = th.shape
+    k = np.float32(kappa)
+    if not (np.isfinite(k) and k > 0):
+        raise ValueError("quantile_huber: kappa must be finite and > 0 (got {})".format(kappa))
+    r = np.asarray(reward, np.float64).reshape(b, 1)
+    g = np.broadcast_to(np.asarray(disc, np.float64).reshape(-1, 1), (b, 1))
+    dn = np.asarray(done).reshape(b, 1).astype(bool)
+    gt = g * tt.astype(np.float64)
+    t = np.where(dn, r, r + gt).astype(np.float32)
+    tau = quantile_midpoints(n)
+    w_neg, w_pos = (1.0 - tau).astype(np.float32)[None, :], tau.astype(np.float32)[None, :]
+    half = np.float32(0.5)
+    sr, sg = np.zeros((b, n), np.float64), np.zeros((b, n), np.float64)
+    for j in range(n):                                  # ascending j: the kernel's order of summation
+        u = t[:, j:j + 1] - th
+        wt = np.where(u < 0, w_neg, w_pos)
+        au = np.abs(u)
+        hub = np.where(au <= k, half * u * u, k * (au - half * k))
+        sr = sr + (wt * hub / k).astype(np.float64)
+        sg = sg + (wt * np.clip(u, -k, k) / k).astype(np.float64)
+    r_i = (sr / np.float64(n)).astype(np.float32)
+    return r_i.sum(axis=1, dtype=np.float32), (-sg / np.float64(n)).astype(np.float32)
+
+
+def quant_config(model_config, action_dim):
+    """-> (quantiles, kappa) of a DQN ``model_config`` after the checks of the quantile keys"""
+    quantiles = netspec.check_quantiles(model_config.get("quantiles", 1))
+    kappa = float(model_config.get("kappa", 1.0))
+    if quantiles > 1:
+        if netspec.check_atoms(model_config.get("atoms", 1)) > 1:
+            raise ValueError("quantiles = {} together with atoms = {}: a Q head is quantile (QR-DQN) or categorical (C51), "
+                             "not both".format(quantiles, model_config["atoms"]))
+        if bool(model_config.get("dueling", False)):
+            raise NotImplementedError("dueling with quantiles = {}: the dueling stream is 1 wide, a quantile dueling "
+                                      "network needs a quantiles-wide one; not provided".format(quantiles))
+        if not (np.isfinite(np.float32(kappa)) and np.float32(kappa) > 0):
+            raise ValueError("quantiles = {}: kappa must be finite and > 0, got kappa = {} (the pure |u| loss, kappa = 0, "
+                             "is not provided)".format(quantiles, kappa))
+        if int(action_dim) > 64:
+            raise ValueError("quantiles = {}: action_dim = {} exceeds 64 (the device step's limit)".format(quantiles, action_dim))
+    return quantiles, kappa
+
+
 def dqn_spec(model_info):
     """The ``NetSpec`` of a DQN model description (``model_para.actor`` of a YAML): ``DqnCnn`` / ``DqnMlp``."""
     cfg = model_info.get("model_config") or {}
@@ -101,12 +182,12 @@ def dqn_spec(model_info):
         raise NotImplementedError(PONG_MESSAGE)
     if name == "DqnCnn":
         return netspec.dqn_cnn(tuple(model_info["state_dim"]), model_info["action_dim"], dueling,
-                               dist_config(cfg, model_info["action_dim"])[0])
+                               dist_config(cfg, model_info["action_dim"])[0], quant_config(cfg, model_info["action_dim"])[0])
     if name == "DqnMlp":
         from xingtian_amd.model.dqn import default_config as d
         return netspec.dqn_mlp(tuple(model_info["state_dim"]), model_info["action_dim"],
                                cfg.get("HIDDEN_SIZE", d.HIDDEN_SIZE), cfg.get("NUM_LAYERS", d.NUM_LAYERS), dueling,
-                               dist_config(cfg, model_info["action_dim"])[0])
+                               dist_config(cfg, model_info["action_dim"])[0], quant_config(cfg, model_info["action_dim"])[0])
     raise KeyError("no DQN model named {}".format(name))
 
 
@@ -120,6 +201,7 @@ class DqnModel(XTModel):
         self.dueling = bool(model_config.get("dueling", False))
         self.atoms, self.v_min, self.v_max = dist_config(model_config, self.action_dim)
         self.support = dist_support(self.atoms, self.v_min, self.v_max)[0] if self.atoms > 1 else None
+        self.quantiles, self.kappa = quant_config(model_config, self.action_dim)
         self.seed = model_config.get("SEED")
         # the algorithm's minibatch (model_info["max_batch"], set by DQN) bounds the training step; predict walks larger
         # inputs in chunks
@@ -134,6 +216,8 @@ class DqnModel(XTModel):
         self.net = build_net(model_info, self._spec(), self.max_batch, self.seed)
         if self.atoms > 1 and not getattr(self.net, "inference_only", False):
             self.net.set_dist(self.atoms, self.v_min, self.v_max)
+        if self.quantiles > 1 and not getattr(self.net, "inference_only", False):
+            self.net.set_quant(self.quantiles, self.kappa)
         self.actor_var = self.net
         return True
 
@@ -145,10 +229,13 @@ class DqnModel(XTModel):
             self.iterations = int(arrays["keras_adam_iterations"])
 
     def predict(self, state):
-        """-> Q [N, A] (numpy float32); with ``atoms`` > 1 the expectation under every action's softmax (``dist_q``)"""
+        """-> Q [N, A] (numpy float32); with ``atoms`` > 1 the expectation under every action's softmax (``dist_q``), with
+        ``quantiles`` > 1 the mean of every action's quantiles (``quant_q``)"""
         logits, value = self.net.forward(np.asarray(state))
         if self.atoms > 1:
             return dist_q(as_numpy(logits).reshape(-1, self.action_dim, self.atoms), self.support)
+        if self.quantiles > 1:
+            return quant_q(as_numpy(logits).reshape(-1, self.action_dim, self.quantiles))
         return dueling_q(as_numpy(logits), as_numpy(value), self.dueling)
 
     def train_replay(self, target, replay, slots, gamma, double_dqn):
@@ -156,7 +243,8 @@ class DqnModel(XTModel):
         (``algorithm.dqn.DeviceReplay``): ``xt_net_dqn_step`` with ``target``'s network as the target net, then tf.keras
         Adam.  Nothing synchronises.  -> the device tensor [loss, mean |TD error|, mean bootstrap Q].  A replay with
         ``n_step`` > 1 trains on n-step targets (``xt_net_dqn_step_n``).  A distributional model (``atoms`` > 1) takes
-        ``xt_net_dqn_step_dist`` either way; the tensor is then [loss, mean per-sample loss, mean bootstrap Q]."""
+        ``xt_net_dqn_step_dist`` either way, a quantile one (``quantiles`` > 1) ``xt_net_dqn_step_quant``; the tensor is
+        then [loss, mean per-sample loss, mean bootstrap Q]."""
         return self._train_step(target, replay, slots, None, gamma, double_dqn)
 
     def train_replay_per(self, target, replay, u, beta, gamma, double_dqn):
@@ -168,13 +256,13 @@ class DqnModel(XTModel):
         return self._train_step(target, replay, None, per, gamma, double_dqn)
 
     def _train_step(self, target, replay, slots, per, gamma, double_dqn):
-        """``net.dqn_step`` with the keywords the replay store (n-step) and the model (distributional) ask for, then
+        """``net.dqn_step`` with the keywords the replay store (n-step) and the model (distributional, quantile) ask for, then
         tf.keras Adam"""
         self._require_learner()
         n = getattr(replay, "n_step", 1)
         out = self.net.dqn_step(target.net, replay.cur_state, replay.next_state, slots, replay.action, replay.reward,
                                 replay.done, gamma, self.dueling, double_dqn, follow=replay.follow if n > 1 else None, n=n,
-                                per=per, dist=self.atoms > 1)
+                                per=per, dist=self.atoms > 1, quant=self.quantiles > 1)
         self.net.adam_keras(self.learning_rate, self.iterations, clipnorm=self.CLIPNORM)
         self.iterations += 1
         return out
@@ -197,4 +285,4 @@ class DqnCnn(DqnModel):
         super().__init__(model_info, LR)
 
     def _spec(self):
-        return netspec.dqn_cnn(tuple(self.state_dim), self.action_dim, self.dueling, self.atoms)
+        return netspec.dqn_cnn(tuple(self.state_dim), self.action_dim, self.dueling, self.atoms, self.quantiles)

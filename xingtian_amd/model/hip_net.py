@@ -850,7 +850,7 @@ class HipActorCritic(object):
         return out
 
     def dqn_step(self, target, cur_ring, next_ring, slots, action, reward, done, gamma, dueling, double_dqn,
-                 follow=None, n=1, per=None, dist=False, loss_acc=None):
+                 follow=None, n=1, per=None, dist=False, loss_acc=None, quant=False):
         """One ``DQN.train`` up to the gradient (never synchronises): the minibatch ``slots`` (int32, device) is gathered
         out of the device rings ``cur_ring`` / ``next_ring`` [capacity, ...] (rows as ``to_device_obs`` lays them out),
         ``target`` (a second ``HipActorCritic`` of the same spec) evaluates the next states, this net the states; the TD /
@@ -875,14 +875,18 @@ class HipActorCritic(object):
         nets carry the mark of ``set_dist``; no dueling); the new priority of a start slot is its loss + eps and the
         tensor returned is [loss, mean per-sample loss, mean bootstrap Q].
 
+        ``quant``: the quantile-Huber head ``xt_dqn_loss_quant`` of a quantile pair (both nets carry the mark of
+        ``set_quant``; no dueling), with the priorities and the returned tensor of ``dist``.
+
         The C entry follows from the arguments alone, the first row that applies:
 
+            quant                 xt_net_dqn_step_quant
             dist                  xt_net_dqn_step_dist
             follow is not None    xt_net_dqn_step_n
             per is not None       xt_net_dqn_step_per
             otherwise             xt_net_dqn_step
         """
-        who = "dqn_step" + ("_dist" if dist else "_n" if follow is not None else "_per" if per is not None else "")
+        who = "dqn_step" + ("_quant" if quant else "_dist" if dist else "_n" if follow is not None else "_per" if per is not None else "")
         cap, row_bytes, cfg = self._dqn_cfg(who, cur_ring, next_ring, {"slots": slots} if per is None else {"u": per["u"]},
                                             action, reward, done, gamma, dueling, double_dqn)
         if per is None:
@@ -902,12 +906,13 @@ class HipActorCritic(object):
             L.ptr(loss_acc) if loss_acc is not None else None, L.stream_ptr()), entry)
         return self.loss_out
 
-    # what each C entry takes besides the arguments all four share: (after the cfg, after the rings' capacity)
+    # what each C entry takes besides the arguments all five share: (after the cfg, after the rings' capacity)
     _DQN_ENTRY_ARGS = {
         "dqn_step": lambda ns, p, size, slots: ((), (slots,)),
         "dqn_step_per": lambda ns, p, size, slots: ((p,), (size,)),
         "dqn_step_n": lambda ns, p, size, slots: ((ns, p), (size, slots)),
         "dqn_step_dist": lambda ns, p, size, slots: ((ns, p), (size, slots)),
+        "dqn_step_quant": lambda ns, p, size, slots: ((ns, p), (size, slots)),
     }
 
     # The three names from before ``dqn_step`` took keywords, each forwarding with its old argument order.  Nothing in the
@@ -976,6 +981,13 @@ class HipActorCritic(object):
         ``xt_net_set_dist``; ``spec.action_dim`` is actions * atoms); ``atoms`` 1 clears the mark."""
         L.check(self.lib.xt_net_set_dist(self.handle, int(atoms), float(v_min), float(v_max)), "xt_net_set_dist")
         self.dist = (int(atoms), float(v_min), float(v_max)) if int(atoms) > 1 else None
+
+    def set_quant(self, quantiles, kappa):
+        """Mark the net as carrying a quantile (QR-DQN) Q head of ``quantiles`` quantiles with Huber threshold ``kappa`` (C
+        ABI ``xt_net_set_quant``; ``spec.action_dim`` is actions * quantiles); ``quantiles`` 1 clears the mark.  A net
+        carries one mark: ``set_dist`` and this refuse a net the other has marked."""
+        L.check(self.lib.xt_net_set_quant(self.handle, int(quantiles), float(kappa)), "xt_net_set_quant")
+        self.quant = (int(quantiles), float(kappa)) if int(quantiles) > 1 else None
 
     def set_dist_wide(self, on):
         """Switch a marked net between the wide-head kernels (the default) and those of an unmarked net (C ABI

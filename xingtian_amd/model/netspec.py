@@ -295,33 +295,48 @@ def check_atoms(atoms):
     return int(atoms)
 
 
-def _dqn_spec(layers, feat, action_dim, n_trunk_layers, dueling, xf, state_dim, atoms=1):
+def check_quantiles(quantiles):
+    """``quantiles`` of a DQN model as an int in [1, MAX_ATOMS] (1: the scalar Q head), else ValueError"""
+    if isinstance(quantiles, bool) or int(quantiles) != quantiles or not 1 <= int(quantiles) <= MAX_ATOMS:
+        raise ValueError("quantiles = {!r} must be an integer in [1, {}] (1: the scalar Q head)".format(quantiles, MAX_ATOMS))
+    return int(quantiles)
+
+
+def _dqn_spec(layers, feat, action_dim, n_trunk_layers, dueling, xf, state_dim, atoms=1, quantiles=1):
     """The Q head is the Keras layer after the trunk (dense_<n>), the dueling 1-wide stream the one after it.  ``atoms``
     > 1: the distributional head -- kernel (F, A * atoms), column a * atoms + i is atom i of action a; the spec's
-    ``action_dim`` is then the head's width A * atoms, ``n_actions`` is A and ``atoms`` the count."""
-    atoms = check_atoms(atoms)
+    ``action_dim`` is then the head's width A * atoms, ``n_actions`` is A and ``atoms`` the count.  ``quantiles`` > 1: the
+    quantile head, by the same width rule (column a * quantiles + i is quantile i of action a; ``quantiles`` the count);
+    a head is one or the other."""
+    atoms, quantiles = check_atoms(atoms), check_quantiles(quantiles)
+    if atoms > 1 and quantiles > 1:
+        raise ValueError("atoms = {} together with quantiles = {}: a Q head is categorical (C51) or quantile (QR-DQN), "
+                         "not both".format(atoms, quantiles))
     if atoms > 1 and dueling:
         raise NotImplementedError("dueling with atoms = {}: the dueling stream is 1 wide, a distributional dueling network "
                                   "needs an atoms-wide one; not provided".format(atoms))
-    width = int(action_dim) * atoms
+    if quantiles > 1 and dueling:
+        raise NotImplementedError("dueling with quantiles = {}: the dueling stream is 1 wide, a quantile dueling network "
+                                  "needs a quantiles-wide one; not provided".format(quantiles))
+    width = int(action_dim) * atoms * quantiles
     spec = NetSpec(layers, 1, feat, width, "dense_%d" % n_trunk_layers, "dense_%d" % (n_trunk_layers + 1),
                    (feat, width), xf, state_dim, hidden_v=not dueling)
-    spec.atoms, spec.n_actions = atoms, int(action_dim)
+    spec.atoms, spec.quantiles, spec.n_actions = atoms, quantiles, int(action_dim)
     return spec
 
 
-def dqn_cnn(state_dim, action_dim, dueling=False, atoms=1):
+def dqn_cnn(state_dim, action_dim, dueling=False, atoms=1, quantiles=1):
     """Keras ``DqnCnn`` (xt/model/dqn/dqn_cnn.py:45-59): the trunk of ``impala_cnn`` (Conv2D 32@8x8/4, 64@4x4/2, 64@3x3/1
     valid relu on uint8 / 255, Dense 256 relu), a linear Q head Dense(A) and, with ``dueling``, a 1-wide Dense stream:
     Q_a = s + (l_a - mean_a l).  Variable names are Keras' automatic ones of a first-built model: conv2d, conv2d_1,
-    conv2d_2, dense, the Q head dense_1, the 1-wide stream dense_2.  ``atoms`` > 1: see ``_dqn_spec``."""
+    conv2d_2, dense, the Q head dense_1, the 1-wide stream dense_2.  ``atoms`` / ``quantiles`` > 1: see ``_dqn_spec``."""
     trunk = impala_cnn(state_dim, action_dim).layers
-    return _dqn_spec(trunk, 256, action_dim, 1, dueling, (1, 0.0, 255.0), state_dim, atoms)
+    return _dqn_spec(trunk, 256, action_dim, 1, dueling, (1, 0.0, 255.0), state_dim, atoms, quantiles)
 
 
-def dqn_mlp(state_dim, action_dim, hidden_size=128, num_layers=1, dueling=False, atoms=1):
+def dqn_mlp(state_dim, action_dim, hidden_size=128, num_layers=1, dueling=False, atoms=1, quantiles=1):
     """Keras ``DqnMlp`` (xt/model/dqn/dqn_mlp.py:43-56): ``impala_mlp``'s trunk (dense ... dense_{L-1}), the Q head
-    dense_L and, with ``dueling``, the 1-wide stream dense_{L+1}.  ``atoms`` > 1: see ``_dqn_spec``."""
+    dense_L and, with ``dueling``, the 1-wide stream dense_{L+1}.  ``atoms`` / ``quantiles`` > 1: see ``_dqn_spec``."""
     trunk = impala_mlp(state_dim, action_dim, hidden_size, num_layers).layers
     return _dqn_spec(trunk, hidden_size, action_dim, int(num_layers), dueling, (0, 0.0, 1.0), (1, 1, int(state_dim[0])),
-                     atoms)
+                     atoms, quantiles)
