@@ -533,6 +533,14 @@ int32_t xt_net_last_head_path(const xt_net* net);
  * float32 results differ from the default's in the last bits.  Refused on a categorical net.  The flag is part of
  * xt_net_ppo_train's hipGraph key. */
 int xt_net_set_gauss_fused(xt_net* net, int32_t on);
+/* PpoCnn's first two layers in one forward launch (appended under ABI 12; per net, default ON).  on != 0: a trunk whose
+ * first layer is the uint8 8x8/4 VALID 4 -> 32 layer of the flat bf16x3 form, followed by a 4x4/2 VALID 32 -> 32 layer,
+ * neither keeping its pre-activation, runs conv12_u8_valid_fwd_flat_kernel for both when the batch is inside the
+ * kernel's envelope (the second layer's own forward would neither be split over K nor leave its four-wave-group form:
+ * 201 <= B <= 404 for 84x84 frames); every other forward keeps the two launches.  Both activations, the
+ * sign mask and everything downstream are bit for bit what the two launches give.  on == 0: always two launches.  The
+ * flag is part of the key of every cached hipGraph of the net. */
+int xt_net_set_fwd_fuse12_flat(xt_net* net, int32_t on);
 
 /* Gradient exchange hook of xt_net_ppo_train (ABI >= 4): the reference's learner is single-process
  * (its grad_communicate host averaging, xt/framework/trainer.py:89-92, is dead code); data parallelism is this
@@ -885,6 +893,16 @@ int xt_net_time_tail(xt_net* net, float lr, float clip_norm, int32_t reps, float
 int xt_layer_fwd_ex(const xt_conv_geom* g, const xt_input_xform* xf, int32_t B, const void* in, const int32_t* idx,
                     const float* w, const float* bias, float* y, float* partial, int32_t ksplit, void* stream,
                     uint32_t* relu_mask, int32_t* mask_written, int32_t* path_out);
+/* xt_layer_fwd of the uint8 first layer g0 and of the 4x4/2 VALID 32 -> 32 layer g1 behind it as ONE launch
+ * (conv12_u8_valid_fwd_flat_kernel, see xt_net_set_fwd_fuse12_flat; appended, the ABI version stays): act1 / relu_mask
+ * (may be null; written when g0's activation is relu) / act2 receive what the two xt_layer_fwd calls (ksplit 1) write,
+ * bit for bit.  rows_per_block: rows of g1's output (over all samples) per workgroup, 1..12; 0 = as the network splits
+ * them (evenly over 256 workgroups, more once that exceeds 12 rows each).  Refused when the layers, the batch or
+ * rows_per_block are outside the kernel's envelope. */
+int xt_conv12_valid_fwd(const xt_conv_geom* g0, const xt_input_xform* xf, const xt_conv_geom* g1, int32_t B,
+                        const void* in, const int32_t* idx, const float* w0, const float* b0, float* act1,
+                        uint32_t* relu_mask, const float* w1, const float* b1, float* act2, int32_t rows_per_block,
+                        void* stream);
 
 /* xt_layer_wgrad the way a network's update runs it (appended; the ABI version stays): the gradient is left in slabs
  * (no reduction inside the launcher) and the slab buffer has `slab_cap` slabs, which is what lets the uint8 first-layer

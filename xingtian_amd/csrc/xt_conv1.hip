@@ -464,6 +464,435 @@ int launch_conv1_fwd_bf16x3(const xt_conv_geom* g, const xt_input_xform* xf, int
   return 0;
 }
 
+// ================================================================================================================
+// conv1 -> conv2 of PpoCnn (uint8 8x8/4 VALID -> 4x4/2 VALID, 32 -> 32 channels) in ONE launch over row-aligned flat
+// tiles.  (sample, conv2 output row) is flattened into T = B * OH2 rows and every workgroup takes a contiguous run of
+// WHOLE rows (<= 12: <= 108 conv2 positions = four 32-row tiles), so the launch has equal workgroups, one per CU, like
+// the flat conv1 kernel -- the per-frame-stack fusions gave 320 stacks to 256 CUs (two rounds for 1.25 rounds of work).
+// A run touches at most three samples ("pieces"); a piece of n output rows needs the 2n + 2 conv1 rows 2 oy_first ..
+// 2 oy_last + 3, all of which the block computes itself: the two rows it shares with its neighbour are recomputed, not
+// exchanged, so no block reads what another block of the launch wrote (no flags, no atomics, nothing to wait on).
+//  1. conv1 over the block's <= 560 positions: conv_u8c4k8_fwd_flat_kernel's staging, weight split and MFMA loop (tile
+//     = wave + 8 slot; waves 0..2 walk a third tile when there are more than 16), every element the same sum.
+//  2. act1 and the relu sign mask go to memory for the positions the block OWNS (conv1 rows 2 oy, 2 oy + 1 of its rows
+//     oy, and the last two rows of a sample with oy = OH2 - 1), as the unfused kernel writes them; ALL computed positions
+//     go to LDS as three bf16 planes (split3_store's truncation split) laid out [plane][16-byte k quarter][position],
+//     the even and the odd columns of a conv1 row in separate runs: the 32 positions of a conv2 A operand (two columns
+//     apart) are then consecutive 16-byte slots.
+//  3. conv2 from the planes with the sums of igemm_fwd_kernel<128, 32, 4, 1, false, false, 4, true>: wave group ky
+//     (two waves, two row tiles each) walks kx = 0..3, two 16-channel chunks of mfma_bf16x6 per tap into one
+//     accumulator per tile; the groups are summed through LDS in the order 0, 1, 2, 3, then bias and activation.
+//     A lane's B operand is 8 consecutive k of ONE column: it loads and splits its own 16 weights per tap (all four
+//     taps are fetched before the conv1 epilogue), so the loop has no weight stage in LDS and no barrier.
+struct C12Args {
+  C1FwdArgs c1;        // y = act1, mask = its sign words, img_cap = LDS bytes of the bf16 image of the packed input rows
+  const float* w2;     // [16 * 32][32]
+  const float* b2;     // [32]
+  float* y2;           // [B * OH2 * OW2][32]
+  int OH2, OW2, act2;
+  int T, q, r;         // T rows; block b owns rows [b q + min(b, r), ... + q + (b < r)) clipped to T
+  int nps;             // 16-byte slots per (plane, k quarter) run of the act1 planes
+  int tab_off;         // LDS byte of the position table [positions] x {global position or -1, plane slot}
+};
+
+constexpr int kC12Pieces = 3, kC12MaxRows = 12, kC12Blocks = 256;
+constexpr int kC12TbufBytes = 8 * 32 * 36 * 4, kC12RedBytes = 4 * 128 * 36 * 4, kC12WplBytes = 16 * 3 * 64 * 16;
+
+// the pieces of the row run [row0, row1): n output rows from conv1 row clo on, first local position lbase; own_all: the
+// piece ends its sample, so its two last conv1 rows are the block's too
+__device__ __host__ __forceinline__ void c12_pieces(int row0, int row1, int OH2, int OW1, int (&n)[kC12Pieces],
+                                                    int (&clo)[kC12Pieces], int (&lbase)[kC12Pieces],
+                                                    int (&own_all)[kC12Pieces], int* npos) {
+  const int s0 = row0 / OH2;
+  int cum = 0;
+#pragma unroll
+  for (int i = 0; i < kC12Pieces; ++i) {
+    const int sb = (s0 + i) * OH2;
+    const int lo = (row0 > sb ? row0 : sb) - sb, hi = (row1 < sb + OH2 ? row1 : sb + OH2) - 1 - sb;
+    n[i] = hi >= lo ? hi - lo + 1 : 0;
+    clo[i] = 2 * lo;
+    own_all[i] = hi == OH2 - 1 ? 1 : 0;
+    lbase[i] = cum;
+    cum += n[i] > 0 ? (2 * n[i] + 2) * OW1 : 0;
+  }
+  *npos = cum;
+}
+#define XT_C12_SEL(a, i) ((i) == 2 ? (a)[2] : (i) == 1 ? (a)[1] : (a)[0])
+
+// the 16 half-kernel-row steps of conv_u8c4k8_fwd_flat_kernel for NTI tiles of one wave (same reads, same MFMA order)
+template <int NTI>
+__device__ __forceinline__ void c12_conv1_steps(const uint8_t* limg, const uint4* wpl, int lane, int Wrow,
+                                                const int* poff, f32x16* acc) {
+  constexpr int NS = 16;
+  uint4 wq[2][3], aq[2][NTI];
+  auto lds_fetch = [&](int s, uint4 (&w3)[3], uint4 (&a2)[NTI]) {
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) w3[pl] = wpl[(s * 3 + pl) * 64 + lane];
+    const int koff = 2 * ((s >> 1) * Wrow + (s & 1) * 16);
+#pragma unroll
+    for (int ti = 0; ti < NTI; ++ti) a2[ti] = *reinterpret_cast<const uint4*>(limg + poff[ti] + koff);
+  };
+  lds_fetch(0, wq[0], aq[0]);
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int cur = s & 1;
+    BF8 bp[3], av[NTI];
+    if (s + 1 < NS) lds_fetch(s + 1, wq[cur ^ 1], aq[cur ^ 1]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) { bp[pl].u[0] = wq[cur][pl].x; bp[pl].u[1] = wq[cur][pl].y; bp[pl].u[2] = wq[cur][pl].z; bp[pl].u[3] = wq[cur][pl].w; }
+#pragma unroll
+    for (int ti = 0; ti < NTI; ++ti) { av[ti].u[0] = aq[cur][ti].x; av[ti].u[1] = aq[cur][ti].y; av[ti].u[2] = aq[cur][ti].z; av[ti].u[3] = aq[cur][ti].w; }
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+      for (int ti = 0; ti < NTI; ++ti)
+        acc[ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[ti].v, bp[pl].v, acc[ti], 0, 0, 0);
+  }
+}
+
+__global__ __launch_bounds__(512) void conv12_u8_valid_fwd_flat_kernel(const C12Args a) {
+  constexpr int NW = 8, NT = 512, NP = kC12Pieces, WQ = 1024 / NT, U = 6, SL = 3;
+  extern __shared__ __attribute__((aligned(16))) uint8_t limg[];
+  const C1FwdArgs& p = a.c1;
+  const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int HWC = p.H * p.W * 4, Wrow = p.W * 4, OW1 = p.OW, OHOW1 = p.OH * p.OW, HW1 = (OW1 + 1) >> 1;
+  const int blk = blockIdx.x;
+  const int row0 = blk * a.q + min(blk, a.r), row1 = min(a.T, row0 + a.q + (blk < a.r ? 1 : 0));
+  const int s0 = row0 / a.OH2;
+  int pn[NP], clo[NP], lbase[NP], own_all[NP], npos;
+  c12_pieces(row0, row1, a.OH2, OW1, pn, clo, lbase, own_all, &npos);
+  uint4* wpl = reinterpret_cast<uint4*>(limg + p.img_cap);
+  int2* ptab = reinterpret_cast<int2*>(limg + a.tab_off);
+  XT_TL(0);
+  XT_TL_ROLE(45);
+  // ---- phase 1: conv1.  Every global load of the phase goes out first (weights, then the packed input rows).
+  float wv[WQ][8];
+  constexpr int nslots = 16 * 64;
+#pragma unroll
+  for (int q = 0; q < WQ; ++q) {
+    const int slot = t + NT * q;
+    const float* wl = p.w + (size_t)((slot >> 6) * 16 + 8 * ((slot & 63) >> 5)) * 32 + (slot & 31);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wv[q][j] = wl[j * 32];
+  }
+  int shift[NP];
+  {
+    int un[NP], srow[NP];
+    long long goff[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const int sc = min(s0 + i, p.B - 1);
+      srow[i] = p.idx ? p.idx[sc] : sc;
+    }
+    int ntot = 0;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      un[i] = 0; goff[i] = 0; shift[i] = 0;
+      if (pn[i] > 0) {
+        const int blo = p.S * clo[i] * Wrow, bhi = (p.S * (clo[i] + 2 * pn[i] + 1) + p.KH) * Wrow;
+        const int ul = blo >> 4;
+        un[i] = ((bhi + 15) >> 4) - ul;
+        goff[i] = (long long)srow[i] * (long long)HWC + (long long)ul * 16;
+        shift[i] = (ntot - ul) * 16;          // LDS byte (before the bf16 doubling) of the stack's byte o: shift + o
+      }
+      ntot += un[i];
+    }
+    for (int base = 0; base < ntot; base += NT * U) {
+      uint4 v[U];
+      int dst[U];
+#pragma unroll
+      for (int q = 0; q < U; ++q) {
+        int u = base + t + NT * q;
+        u = u < ntot ? u : 0;                 // (a spare slot stages unit 0 again: the same bytes)
+        long long go = goff[0];
+        int cum = 0;
+#pragma unroll
+        for (int j = 0; j + 1 < NP; ++j) {
+          cum += un[j];
+          if (u >= cum) go = goff[j + 1] - (long long)cum * 16;
+        }
+        v[q] = *reinterpret_cast<const uint4*>(p.in + go + (long long)u * 16);
+        dst[q] = u * 32;
+      }
+#pragma unroll
+      for (int q = 0; q < U; ++q) {
+        BF8 lo, hi;
+        lo.v = bytes_to_bf16x8(v[q].x, v[q].y);
+        hi.v = bytes_to_bf16x8(v[q].z, v[q].w);
+        *reinterpret_cast<uint4*>(limg + dst[q]) = make_uint4(lo.u[0], lo.u[1], lo.u[2], lo.u[3]);
+        *reinterpret_cast<uint4*>(limg + dst[q] + 16) = make_uint4(hi.u[0], hi.u[1], hi.u[2], hi.u[3]);
+      }
+    }
+  }
+  XT_TL(1);
+#pragma unroll
+  for (int q = 0; q < WQ; ++q) {
+    const int slot = t + NT * q;
+    BF8 b1, b2, b3;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float w0 = wv[q][2 * e], w1 = wv[q][2 * e + 1];
+      const float r0 = w0 - trunc_bf16(w0), r1 = w1 - trunc_bf16(w1);
+      const float q0 = r0 - trunc_bf16(r0), q1 = r1 - trunc_bf16(r1);
+      b1.u[e] = pack_hi16(w0, w1);
+      b2.u[e] = pack_hi16(r0, r1);
+      b3.u[e] = pack_hi16(q0, q1);
+    }
+    const int sidx = slot >> 6, ln = slot & 63;
+    wpl[(sidx * 3 + 0) * 64 + ln] = make_uint4(b1.u[0], b1.u[1], b1.u[2], b1.u[3]);
+    wpl[(sidx * 3 + 1) * 64 + ln] = make_uint4(b2.u[0], b2.u[1], b2.u[2], b2.u[3]);
+    wpl[(sidx * 3 + 2) * 64 + ln] = make_uint4(b3.u[0], b3.u[1], b3.u[2], b3.u[3]);
+  }
+  static_assert(nslots == NT * WQ, "conv12: one weight slot pass");
+  // position table: local position -> {global conv1 position if the block owns it, else -1; slot in a plane run}
+  for (int L = t; L < npos; L += NT) {
+    const int i = L >= lbase[2] ? 2 : L >= lbase[1] ? 1 : 0;
+    const int l = L - XT_C12_SEL(lbase, i), lr = l / OW1, x = l - lr * OW1;
+    const bool own = lr < 2 * XT_C12_SEL(pn, i) || XT_C12_SEL(own_all, i) != 0;
+    const int gpos = (s0 + i) * OHOW1 + (XT_C12_SEL(clo, i) + lr) * OW1 + x;
+    ptab[L] = make_int2(own ? gpos : -1, XT_C12_SEL(lbase, i) + lr * OW1 + (x & 1) * HW1 + (x >> 1));
+  }
+  const int il = lane & 31, h = lane >> 5;
+  const int ntiles = (npos + 31) >> 5;
+  int poff[SL];                              // LDS byte of this lane's 8 bf16 at step 0
+#pragma unroll
+  for (int ti = 0; ti < SL; ++ti) {
+    const int L = min((wave + NW * ti) * 32 + il, npos - 1);        // tail positions recompute the last valid one
+    const int i = L >= lbase[2] ? 2 : L >= lbase[1] ? 1 : 0;
+    const int l = L - XT_C12_SEL(lbase, i), lr = l / OW1, x = l - lr * OW1;
+    poff[ti] = 2 * (XT_C12_SEL(shift, i) + (p.S * (XT_C12_SEL(clo, i) + lr) * p.W + p.S * x) * 4 + 8 * h);
+  }
+  f32x16 acc[SL];
+#pragma unroll
+  for (int ti = 0; ti < SL; ++ti)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[ti][r] = 0.f;
+  const float bias = p.bias[il];
+  __syncthreads();
+  XT_TL(2);
+  c12_conv1_steps<2>(limg, wpl, lane, Wrow, poff, acc);
+  if (wave + 2 * NW < ntiles) c12_conv1_steps<1>(limg, wpl, lane, Wrow, poff + 2, acc + 2);
+  // conv2's weights of this wave group (kernel row ky = group), all four taps: lane (k half h, column il) of a chunk
+  // takes k = 16 chunk + 8 h .. + 7 of its column -- in flight while the epilogue below runs
+  const int grp = wave >> 1;
+  float w2v[4][2][8];
+#pragma unroll
+  for (int kx = 0; kx < 4; ++kx)
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch) {
+      const float* wl = a.w2 + (size_t)((grp * 4 + kx) * 32 + 16 * ch + 8 * h) * 32 + il;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) w2v[kx][ch][j] = wl[j * 32];
+    }
+  __syncthreads();                           // the image and conv1's weight planes are dead
+  XT_TL(3);
+  // ---- phase 2: act1 + sign mask of the owned positions to memory, every position into the bf16 planes
+  uint8_t* planes = limg;
+  const int qrun = a.nps * 16, prun = 4 * qrun;      // bytes of a k-quarter run / of a plane
+  float* tbuf = reinterpret_cast<float*>(limg + 3 * prun) + wave * (32 * 36);
+#pragma unroll
+  for (int ti = 0; ti < SL; ++ti) {
+    const int L0 = (wave + NW * ti) * 32;
+    if (L0 < npos) {
+      uint32_t mw = 0u;
+      if (p.act == XT_ACT_RELU) {
+#define XT_C12_RELU_ROW(r)                                                                                       \
+        {                                                                                                        \
+          constexpr int rw0 = ((r) & 3) + 8 * ((r) >> 2);                                                        \
+          const float z = fmaf(acc[ti][r], p.xs, bias);                                                          \
+          const unsigned long long bal = __ballot(z > 0.f);                                                      \
+          tbuf[(rw0 + 4 * h) * 36 + il] = z > 0.f ? z : 0.f;                                                     \
+          asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(mw) : "s"((uint32_t)bal), "n"(rw0));                 \
+          asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(mw) : "s"((uint32_t)(bal >> 32)), "n"(rw0 + 4));     \
+        }
+        XT_C12_RELU_ROW(0) XT_C12_RELU_ROW(1) XT_C12_RELU_ROW(2) XT_C12_RELU_ROW(3)
+        XT_C12_RELU_ROW(4) XT_C12_RELU_ROW(5) XT_C12_RELU_ROW(6) XT_C12_RELU_ROW(7)
+        XT_C12_RELU_ROW(8) XT_C12_RELU_ROW(9) XT_C12_RELU_ROW(10) XT_C12_RELU_ROW(11)
+        XT_C12_RELU_ROW(12) XT_C12_RELU_ROW(13) XT_C12_RELU_ROW(14) XT_C12_RELU_ROW(15)
+#undef XT_C12_RELU_ROW
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          tbuf[((r & 3) + 8 * (r >> 2) + 4 * h) * 36 + il] = act_apply(fmaf(acc[ti][r], p.xs, bias), p.act);
+      }
+      if (p.mask && lane < 32 && L0 + lane < npos) {
+        const int gpos = ptab[L0 + lane].x;
+        if (gpos >= 0) p.mask[gpos] = mw;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int row = q * 8 + (lane >> 3), cg = lane & 7;
+        const float4 v = *reinterpret_cast<const float4*>(&tbuf[row * 36 + cg * 4]);
+        if (L0 + row < npos) {
+          const int2 e = ptab[L0 + row];
+          if (e.x >= 0) store4_wt(p.y, (size_t)e.x * 32 + cg * 4, v);
+          split3_store(planes + (cg >> 1) * qrun + e.y * 16 + (cg & 1) * 8, prun, v);
+        }
+      }
+    }
+  }
+  __syncthreads();                           // the planes are complete
+  XT_TL(4);
+  // ---- phase 3: conv2 from the planes
+  const int n2 = (row1 - row0) * a.OW2;
+  int aoff[2];
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt) {
+    const int j = ((wave & 1) * 2 + tt) * 32 + il;
+    const int jc = j < n2 ? j : 0;           // rows past the block's positions read position 0 and are dropped below
+    const int rr = jc / a.OW2, ox = jc - rr * a.OW2;
+    const int smp = (row0 + rr) / a.OH2, oy = row0 + rr - smp * a.OH2, i = smp - s0;
+    aoff[tt] = (XT_C12_SEL(lbase, i) + (2 * oy - XT_C12_SEL(clo, i) + grp) * OW1 + ox) * 16 + h * qrun;
+  }
+  f32x16 acc2[2];
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc2[tt][r] = 0.f;
+#pragma unroll
+  for (int kx = 0; kx < 4; ++kx) {
+    bf16x8 bw[2][3], av[2][2][3];
+    const int koff = ((kx & 1) * HW1 + (kx >> 1)) * 16;
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+      for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+          av[tt][ch][pl] = *reinterpret_cast<const bf16x8*>(planes + pl * prun + ch * 2 * qrun + aoff[tt] + koff);
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch)
+      split3_regs(make_float4(w2v[kx][ch][0], w2v[kx][ch][1], w2v[kx][ch][2], w2v[kx][ch][3]),
+                  make_float4(w2v[kx][ch][4], w2v[kx][ch][5], w2v[kx][ch][6], w2v[kx][ch][7]), bw[ch]);
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt) acc2[tt] = mfma_bf16x6(av[tt][ch], bw[ch], acc2[tt]);
+  }
+  __syncthreads();                           // every plane read is done: the area becomes the combine buffer
+  constexpr int RS = 36;
+  float* red = reinterpret_cast<float*>(limg);
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = ((wave & 1) * 2 + tt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      red[(grp * 128 + row) * RS + il] = acc2[tt][r];
+    }
+  __syncthreads();
+  for (int e = t; e < 128 * 8; e += NT) {
+    const int row = e >> 3, c4 = (e & 7) * 4;
+    if (row >= n2) continue;
+    float4 s = *reinterpret_cast<const float4*>(&red[row * RS + c4]);
+#pragma unroll
+    for (int g = 1; g < 4; ++g) {            // groups in order: the unfused kernel's summation order
+      const float4 b = *reinterpret_cast<const float4*>(&red[(g * 128 + row) * RS + c4]);
+      s.x += b.x; s.y += b.y; s.z += b.z; s.w += b.w;
+    }
+    const float4 bb = *reinterpret_cast<const float4*>(a.b2 + c4);
+    store4_wt(a.y2, (size_t)(row0 * a.OW2 + row) * 32 + c4,
+              make_float4(act_apply(s.x + bb.x, a.act2), act_apply(s.y + bb.y, a.act2),
+                          act_apply(s.z + bb.z, a.act2), act_apply(s.w + bb.w, a.act2)));
+  }
+  XT_TL_DRAIN(5);
+}
+#undef XT_C12_SEL
+
+// The automatic split: the rows evenly over one block per CU; past 12 rows per block, over more blocks than CUs (B = 342 ..
+// 404 for 84x84 frames: 257 .. 303 blocks still beat the two launches by 4 to 7 us, profiles/fwd_fuse12_flat_ab.md).
+static int c12_auto_blocks(int T) {
+  const int one_per_cu = T < kC12Blocks ? T : kC12Blocks, by_rows = (T + kC12MaxRows - 1) / kC12MaxRows;
+  return one_per_cu > by_rows ? one_per_cu : by_rows;
+}
+
+// Is (conv1 g, conv2 g2) at batch B what conv12_u8_valid_fwd_flat_kernel computes, bit for bit what the two launches
+// would?  That pins the tuning knobs too: the first layer must take the flat bf16x3 form (it writes the sign mask) and the
+// second the four-group bf16x6 form (<= 256 blocks of 128 rows).  rows_per_block: 0 = the automatic split.
+bool conv12_valid_envelope(const xt_conv_geom* g, const xt_input_xform* xf, const xt_conv_geom* g2, int B, int rows_per_block) {
+#ifdef XT_NO_FWD12_FLAT
+  return false;
+#endif
+  const xt_tuning t = tuning();
+  if (!t.conv1_bf16x3 || !t.conv1_flat || t.conv1_waves == 4 || !t.bf16x6 || !t.fwd_tiled_valid || !t.fwd_two_groups ||
+      !t.fwd_four_groups || t.fwd_prefetch_all)
+    return false;
+  if (!xf || !xf->is_u8 || fabsf(xf->mean) >= 1e-4f || B < 1) return false;
+  if (g->C != 4 || g->KW != 8 || g->KH != 8 || g->N != 32 || g->PT != 0 || g->PL != 0) return false;
+  if ((g->OH - 1) * g->S + g->KH > g->H || (g->OW - 1) * g->S + g->KW > g->W) return false;
+  const int HWC = g->H * g->W * 4;
+  if (HWC % 16 != 0 || HWC > 64 * 1024 || (g->W * 4) % 8 != 0 || (g->S * 4) % 8 != 0) return false;
+  if (act_needs_preact(g->act) || act_needs_preact(g2->act)) return false;
+  if (g2->C != 32 || g2->N != 32 || g2->KH != 4 || g2->KW != 4 || g2->S != 2 || g2->PT != 0 || g2->PL != 0) return false;
+  if (g2->H != g->OH || g2->W != g->OW || g->OH != 2 * g2->OH + 2 || g->OW != 2 * g2->OW + 2) return false;
+  if ((long long)B * g->OH * g->OW * 32 * 4 >= (1ll << 31)) return false;      // store4_wt: 32-bit byte offsets
+  if (((long long)B * g2->OH * g2->OW + 127) / 128 > 256) return false;        // the unfused conv2 leaves the four-group form
+  const int T = B * g2->OH;
+  int R = rows_per_block;
+  if (R <= 0) {
+    const int nblk = c12_auto_blocks(T);
+    R = (T + nblk - 1) / nblk;
+  }
+  if (R > kC12MaxRows || R * g2->OW > 128 || (R + g2->OH - 2) / g2->OH + 1 > kC12Pieces) return false;
+  return true;
+}
+
+// returns 0 launched, 1 error, -1 outside the envelope (the caller then launches the two layers separately)
+int launch_conv12_valid_fwd(const xt_conv_geom* g, const xt_input_xform* xf, const xt_conv_geom* g2, int B, const void* in,
+                            const int32_t* idx, const float* w, const float* bias, float* y, uint32_t* relu_mask,
+                            const float* w2, const float* b2, float* y2, int rows_per_block, hipStream_t st,
+                            int* mask_written) {
+  if (mask_written) *mask_written = 0;
+  if (!conv12_valid_envelope(g, xf, g2, B, rows_per_block)) return -1;
+  C12Args a;
+  a.c1.in = static_cast<const uint8_t*>(in); a.c1.idx = idx; a.c1.w = w; a.c1.bias = bias; a.c1.y = y;
+  a.c1.B = B; a.c1.H = g->H; a.c1.W = g->W; a.c1.OH = g->OH; a.c1.OW = g->OW; a.c1.S = g->S; a.c1.KH = g->KH; a.c1.act = g->act;
+  a.c1.xs = 1.f / xf->std; a.c1.xb = 0.f;
+  a.c1.mask = (g->act == XT_ACT_RELU) ? relu_mask : nullptr;
+  a.w2 = w2; a.b2 = b2; a.y2 = y2; a.OH2 = g2->OH; a.OW2 = g2->OW; a.act2 = g2->act;
+  a.T = B * g2->OH;
+  int nblk;
+  if (rows_per_block > 0) { a.q = rows_per_block; a.r = 0; nblk = (a.T + a.q - 1) / a.q; }
+  else { nblk = c12_auto_blocks(a.T); a.q = a.T / nblk; a.r = a.T % nblk; }
+  // the largest block of the launch: packed input bytes and conv1 positions
+  int cap = 0, maxpos = 0;
+  const int Wrow = g->W * 4;
+  for (int b = 0; b < nblk; ++b) {
+    const int row0 = b * a.q + (b < a.r ? b : a.r);
+    int row1 = row0 + a.q + (b < a.r ? 1 : 0);
+    if (row1 > a.T) row1 = a.T;
+    int pn[kC12Pieces], clo[kC12Pieces], lbase[kC12Pieces], own_all[kC12Pieces], npos;
+    c12_pieces(row0, row1, g2->OH, g->OW, pn, clo, lbase, own_all, &npos);
+    int units = 0;
+    for (int i = 0; i < kC12Pieces; ++i)
+      if (pn[i] > 0) {
+        const int blo = g->S * clo[i] * Wrow, bhi = (g->S * (clo[i] + 2 * pn[i] + 1) + g->KH) * Wrow;
+        units += ((bhi + 15) >> 4) - (blo >> 4);
+      }
+    if (units * 16 > cap) cap = units * 16;
+    if (npos > maxpos) maxpos = npos;
+  }
+  if (maxpos > 3 * 8 * 32 || cap / 16 > 512 * 6) return -1;      // three tile slots per wave; one staging pass of 6 units per thread
+  a.c1.img_cap = 2 * cap;
+  a.nps = (maxpos + 7) / 8 * 8 + 4;         // == 4 (mod 8): consecutive k-quarter runs of a plane start 16 banks (mod 32) apart
+  size_t body = (size_t)a.c1.img_cap + kC12WplBytes;
+  if (body < (size_t)192 * a.nps + kC12TbufBytes) body = (size_t)192 * a.nps + kC12TbufBytes;
+  if (body < (size_t)kC12RedBytes) body = kC12RedBytes;
+  a.tab_off = (int)body;
+  const size_t fl = body + (size_t)maxpos * 8;
+  if (fl > 160 * 1024) return -1;
+  static PerDeviceOnce attr_once;
+  attr_once.run([] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv12_u8_valid_fwd_flat_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipGetLastError();
+  });
+  hipLaunchKernelGGL(conv12_u8_valid_fwd_flat_kernel, dim3(nblk), dim3(512), fl, st, a);
+  XT_LAUNCH_CHECK();
+  if (mask_written && a.c1.mask) *mask_written = 1;
+  return 0;
+}
+
 // ------------------------------------------------------------------ first-layer weight gradient
 // dW[k,n] = sum_pixels x[pixel,k] * dY[pixel,n]  (x uint8 -> exact bf16 A operand, dY split into 3 bf16 planes
 // as the B operand; the reduction index of v_mfma_f32_32x32x16_bf16 is 16 pixels per instruction).
@@ -1534,3 +1963,14 @@ int launch_conv1_wgrad_bf16x3(const xt_conv_geom* g, const xt_input_xform* xf, i
 }
 
 }  // namespace xt
+
+int xt_conv12_valid_fwd(const xt_conv_geom* g0, const xt_input_xform* xf, const xt_conv_geom* g1, int32_t B, const void* in,
+                        const int32_t* idx, const float* w0, const float* b0, float* act1, uint32_t* relu_mask,
+                        const float* w1, const float* b1, float* act2, int32_t rows_per_block, void* stream) {
+  XT_REQUIRE(g0 && g1 && in && w0 && b0 && act1 && w1 && b1 && act2 && B > 0, "xt_conv12_valid_fwd: null argument / bad batch");
+  const int rc = xt::launch_conv12_valid_fwd(g0, xf, g1, B, in, idx, w0, b0, act1, relu_mask, w1, b1, act2, rows_per_block,
+                                             xt::as_stream(stream), nullptr);
+  XT_REQUIRE(rc >= 0, "xt_conv12_valid_fwd: layers, batch %d or rows per block %d outside the fused kernel's envelope", B,
+             rows_per_block);
+  return rc;
+}

@@ -83,6 +83,15 @@ int launch_conv1_same_wgrad(const xt_conv_geom* g, const xt_input_xform* xf, int
 int launch_conv12_same_fwd(const xt_conv_geom* g, const xt_input_xform* xf, const xt_conv_geom* g2, int B,
                            const void* in, const int32_t* idx, const float* w, const float* bias, float* y,
                            const float* w2, const float* b2, float* y2, hipStream_t st);
+// PpoCnn's conv1 -> conv2 (8x8/4 -> 4x4/2, VALID) in one launch over row-aligned flat tiles, every output bit what the two
+// launches write (conv12_u8_valid_fwd_flat_kernel).  rows_per_block: 0 = the automatic split (<= 12 rows each, one block
+// per CU while that holds).
+bool conv12_valid_envelope(const xt_conv_geom* g, const xt_input_xform* xf, const xt_conv_geom* g2, int B,
+                           int rows_per_block);
+int launch_conv12_valid_fwd(const xt_conv_geom* g, const xt_input_xform* xf, const xt_conv_geom* g2, int B,
+                            const void* in, const int32_t* idx, const float* w, const float* bias, float* y,
+                            uint32_t* relu_mask, const float* w2, const float* b2, float* y2, int rows_per_block,
+                            hipStream_t st, int* mask_written);
 
 // ------------------------------------------------------------------ xt_heads.hip: heads and losses
 int launch_act_apply(const float* z, float* y, long long count, int act, hipStream_t st);

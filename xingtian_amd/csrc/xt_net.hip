@@ -140,6 +140,7 @@ struct xt_net {
   float* trows = nullptr;
   int last_head_path = 0;
   int gauss_fused = 0;                // xt_net_set_gauss_fused: a DiagGaussian step inside the envelope takes the fused head launch
+  int fwd_fuse12_flat = 1;            // xt_net_set_fwd_fuse12_flat: PpoCnn's conv1 -> conv2 forward as one launch inside its envelope
   // xt_net_set_dist / xt_net_set_quant: the mark of a distributional Q head (at most one of the two).  head_group: columns
   // per action (atoms of a C51 head, quantiles of a QR-DQN one; 0: a scalar head -- A is actions * head_group wide);
   // head_kind says which; then the C51 support and the quantile head's Huber threshold
@@ -286,6 +287,27 @@ static int net_forward(xt_net* n, const void* obs, const int32_t* idx, int B, bo
           L2.mask_valid = 0;
           L2.last_deferred = 0;
           n->last_fuse12 = 1;
+          x = n->ws + L2.act_off;
+          ++l;
+          continue;
+        }
+      }
+      if (first && n->fwd_fuse12_flat && l + 1 < n->t_end[tr] && L.z_off < 0 && n->layers[l + 1].z_off < 0 &&
+          fwd_split(n->layers[l + 1], B) == 1 && conv12_valid_envelope(&L.g, &n->xf, &n->layers[l + 1].g, B, 0)) {
+        // PpoCnn at a few hundred frames: conv1 -> conv2 in ONE launch over row-aligned flat tiles, every bit of both
+        // activations and of the sign mask what the two launches write (so it is on by default; last_fuse12 keeps meaning
+        // the ImpalaCnnOpt fusion above).  Only where the second layer's own forward would not be split over K: that sum
+        // has another order.  -1: no launch was made
+        Layer& L2 = n->layers[l + 1];
+        if (int rcj = join_pending_update(n, st)) return rcj;      // (the launch reads the second layer's weights too)
+        const int rc = launch_conv12_valid_fwd(&L.g, &n->xf, &L2.g, B, x, idx, w_of(n, L), b_of(n, L), n->ws + L.act_off,
+                                               L.mask_off >= 0 ? reinterpret_cast<uint32_t*>(n->ws + L.mask_off) : nullptr,
+                                               w_of(n, L2), b_of(n, L2), n->ws + L2.act_off, 0, st, &L.mask_valid);
+        if (rc > 0) return rc;
+        if (rc == 0) {
+          L2.last_ksplit = 1;
+          L2.mask_valid = 0;
+          L2.last_deferred = 0;
           x = n->ws + L2.act_off;
           ++l;
           continue;
@@ -806,7 +828,9 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
 // (and the least recently used graph given up) only once the capture has been instantiated: an enqueue that refuses inside
 // the capture ends it and leaves the cache as it was.
 template <typename F>
-static int graph_run(xt_net* net, const char* key, hipStream_t st, F enqueue) {
+static int graph_run(xt_net* net, const char* key_in, hipStream_t st, F enqueue) {
+  // every cached graph holds a forward: the fused / two-launch first layers never replay each other's graph
+  const std::string key = std::string(key_in) + (net->fwd_fuse12_flat ? "|F1" : "|F0");
   xt_net::GraphSlot* slot = nullptr;
   for (auto& g : net->gslots) if (g.exec && g.key == key) slot = &g;
   if (!slot) {
@@ -2104,6 +2128,12 @@ int xt_net_set_gauss_fused(xt_net* net, int32_t on) {
   XT_REQUIRE(net->action_type == XT_ACTION_DIAG_GAUSSIAN,
              "xt_net_set_gauss_fused: refused on a categorical net (its head is ppo_heads_fused_kernel already)");
   net->gauss_fused = on ? 1 : 0;
+  return 0;
+}
+
+int xt_net_set_fwd_fuse12_flat(xt_net* net, int32_t on) {
+  XT_REQUIRE(net, "xt_net_set_fwd_fuse12_flat: null net");
+  net->fwd_fuse12_flat = on ? 1 : 0;
   return 0;
 }
 

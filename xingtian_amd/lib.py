@@ -196,6 +196,9 @@ SIGNATURES = {
     "xt_net_set_train_stats": (c_int32, [_P, _P, _P]),
     "xt_net_last_head_path": (c_int32, [_P]),
     "xt_net_set_gauss_fused": (c_int32, [_P, c_int32]),
+    "xt_net_set_fwd_fuse12_flat": (c_int32, [_P, c_int32]),
+    "xt_conv12_valid_fwd": (c_int32, [POINTER(ConvGeom), POINTER(InputXform), POINTER(ConvGeom), c_int32, _P, _P, _P, _P, _P,
+                                      _P, _P, _P, _P, c_int32, _P]),
     "xt_net_set_impala_stats": (c_int32, [_P, _P, _P, c_int32]),
     "xt_impala_loss_stats": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P, _P,
                                        _P, _P, POINTER(c_int32)]),

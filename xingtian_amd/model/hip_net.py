@@ -522,6 +522,15 @@ class HipActorCritic(object):
         L.check(self.lib.xt_net_set_gauss_fused(self.handle, 1 if on else 0), "xt_net_set_gauss_fused")
         self.gauss_fused_on = bool(on)
 
+    fwd_fuse12_flat_on = True
+
+    def set_fwd_fuse12_flat(self, on=True):
+        """C ABI ``xt_net_set_fwd_fuse12_flat``: PpoCnn's conv1 -> conv2 forward as ONE launch
+        (``conv12_u8_valid_fwd_flat_kernel``) where the batch is inside the kernel's envelope, bit for bit the two
+        launches' results.  On by default; ``False`` keeps the two launches everywhere."""
+        L.check(self.lib.xt_net_set_fwd_fuse12_flat(self.handle, 1 if on else 0), "xt_net_set_fwd_fuse12_flat")
+        self.fwd_fuse12_flat_on = bool(on)
+
     # ------------------------------------------------------------------ per-train IMPALA v-trace diagnostics (opt-in)
     impala_stats_on = False
 
