@@ -1451,6 +1451,47 @@ enum {
 };
 int xt_net_graph_cache_info(const xt_net* net, int32_t* out, int32_t cap);
 
+/* ------------------------------------------------------------------ noisy layers (NoisyNet; appended under ABI 12)
+ * Factorised-Gaussian noisy Dense layers (Fortunato et al. 2018) beside the net, not inside it: the learner keeps a STORE
+ * of n_net floats in the net's own layout -- holding the means mu at the noisy layers' offsets -- followed by one sigma
+ * block per noisy layer, and binds the net (xt_net_bind) to a second buffer params_eff of n_net floats.  xt_noisy_compose
+ * writes the effective parameters there before the step, xt_noisy_grads forms the sigma gradients behind it; no layer
+ * kernel, step entry or optimiser knows about noise.
+ *
+ * xt_noisy_layer: the mean block [K, N] kernel + [N] bias at store[w_off ..), inside [0, n_net); the sigma block of the
+ * same form at store[sigma_off ..), at or behind n_net; the layer's vectors in `noise`: f_in [K] at noise_off, f_out [N]
+ * at noise_off + align4(K).  All three offsets are multiples of 4.  `index`: the layer's position among the model's
+ * noisy layers (counter word c1 of its draws), so that a table holding one layer draws what the whole table draws.
+ *
+ * Definitions (float32, no contraction), Philox4x32-10 keyed by seed (k0 low word, k1 high word):
+ *   element i of vector v (0: f_in, 1: f_out) of layer `index`:
+ *     block = philox(c0 = i >> 1, c1 = 2 * index + v, c2 = (uint32)call, c3 = stream_id)
+ *     u1, u2 = uniform(words 2 (i & 1), 2 (i & 1) + 1), uniform(w) = ((float)(w >> 9) + 0.5) * 2^-23
+ *     x = sqrtf(-2 logf(u1)) * cosf(6.283185307179586f * u2);  f = copysignf(sqrtf(fabsf(x)), x)
+ *   e[k, n] = f_in[k] * f_out[n];  W_eff[k, n] = mu[k, n] + sigma[k, n] * e[k, n];  b_eff[n] = mu_b[n] + sigma_b[n] * f_out[n]
+ *   g_sigma[k, n] = dW_eff[k, n] * e[k, n];  g_sigma_b[n] = db_eff[n] * f_out[n] */
+#define XT_NOISY_MAX_LAYERS 8
+typedef struct xt_noisy_layer {
+  int64_t w_off, sigma_off, noise_off;
+  int32_t K, N, index, reserved;
+} xt_noisy_layer;
+/* One launch: params_eff[0, n_net) = store[0, n_net) bit for bit, but W_eff / b_eff over the mean blocks of `layers`; every
+ * f_in / f_out drawn is stored in `noise` (the values used).  noise_in (may be NULL; laid out as `noise`): the vectors are
+ * taken from it instead of drawn, and copied to `noise`.  mean_only != 0: a plain copy, nothing is drawn, `noise` is not
+ * written.  Nothing outside params_eff[0, n_net) and the layers' vectors in `noise` is written.
+ * Refused: a null pointer, store == params_eff or either not 16-byte aligned, n_layers outside [1, XT_NOISY_MAX_LAYERS],
+ * n_net that is not a positive multiple of 4, a layer with K or N < 1 or (K + 1) * N >= 2^31, a misaligned or negative
+ * offset, a mean block that leaves [0, n_net), a sigma block in front of n_net, overlapping mean blocks, sigma blocks or
+ * noise ranges, stream_id or index negative. */
+int xt_noisy_compose(const xt_noisy_layer* layers, int32_t n_layers, const float* store, float* params_eff, int64_t n_net,
+                     float* noise, const float* noise_in, uint64_t seed, uint64_t call, int32_t stream_id,
+                     int32_t mean_only, void* stream);
+/* One launch behind the step's backward: grads[sigma_off ..) of every layer = g_sigma / g_sigma_b, from grads[w_off ..)
+ * (dW_eff, db_eff: what the backward left; not modified) and the vectors xt_noisy_compose stored in `noise`.  `grads` is
+ * laid out as the store.  Refused: what xt_noisy_compose refuses of a table, and a sigma block in front of the end of a
+ * mean block. */
+int xt_noisy_grads(const xt_noisy_layer* layers, int32_t n_layers, const float* noise, float* grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """Time of one ``DQN.train`` at breakout_dqn's shape, beside a Keras-IMPALA step of the same trunk.
 
-    python tools/dqn_probe.py [--windows 5] [--trains 200] [--capacity 4096] [--atoms 51] [--quantiles 51]
+    python tools/dqn_probe.py [--windows 5] [--trains 200] [--capacity 4096] [--atoms 51] [--quantiles 51] [--noisy]
                               [--model DqnCnn] [--out profiles/dqn_step.md]
 
 Four things are timed at DqnCnn 84x84x4, A = 4, B = 32, each as a host clock around ``--trains`` calls that ends in a
@@ -20,6 +20,9 @@ device synchronise, after a warm-up, in ``--windows`` windows taken in turn (so 
 * with ``--quantiles N`` (0: none) the same arms for the quantile-regression train (``model_config.quantiles``,
   ``xt_net_dqn_step_quant``: the head is again 4 * N wide), so that ``--atoms N --quantiles N`` compares the two
   distributional heads at one width in one run;
+* with ``--noisy`` the train of a noisy pair (``model_config.noisy``: ``xt_noisy_compose`` on both nets in front of the step,
+  ``xt_noisy_grads`` behind it) without and with ``double_dqn``, as ``DQN.train`` and enqueue only, beside the plain rows
+  of the same run, and the three added launches alone (enqueue only);
 * one ``prepare_data`` of a 20-row message without and with ``prioritized_replay`` (``xt_per_add`` per written span), each
   call followed by a device synchronise;
 * ``keras_impala_step`` + ``adam_keras`` on 32 rows of ``netspec.impala_cnn`` (the same trunk and heads, one network, no
@@ -51,7 +54,7 @@ def _states(rng, n):
     return rng.integers(0, 256, (n, DIM, DIM, 4), dtype=np.uint8)
 
 
-def build_dqn(double, capacity, per=False, n_step=1, atoms=1, quantiles=1):
+def build_dqn(double, capacity, per=False, n_step=1, atoms=1, quantiles=1, noisy=False):
     from xingtian_amd.algorithm import alg_builder
     info = {"actor": {"model_name": MODEL["name"], "type": "learner",
                       "state_dim": [4] if MODEL["name"] == "DqnMlp" else [DIM, DIM, 4], "action_dim": A_DIM,
@@ -60,6 +63,8 @@ def build_dqn(double, capacity, per=False, n_step=1, atoms=1, quantiles=1):
         info["actor"]["model_config"]["atoms"] = atoms
     if quantiles > 1:
         info["actor"]["model_config"]["quantiles"] = quantiles
+    if noisy:
+        info["actor"]["model_config"]["noisy"] = True
     cfg = {"instance_num": 1, "agent_num": 1, "prepare_times_per_train": 4, "BUFFER_SIZE": capacity, "BATCH_SIZE": B,
            "TARGET_UPDATE_FREQ": 1000, "double_dqn": double, "prioritized_replay": per}
     if n_step != 1:
@@ -81,6 +86,7 @@ def main():
     ap.add_argument("--capacity", type=int, default=4096)
     ap.add_argument("--atoms", type=int, default=0)
     ap.add_argument("--quantiles", type=int, default=0)
+    ap.add_argument("--noisy", action="store_true")
     ap.add_argument("--model", default="DqnCnn", choices=["DqnCnn", "DqnMlp"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -183,6 +189,27 @@ def main():
                         ", n_step 3" if n == 3 else "", ", double_dqn" if double else "", "" if wide else ", generic head kernels",
                         " (loss read back)" if read_back else ", enqueue only")
                     extra.append((name, dist_case(per, n, double, wide, read_back)))
+        cases = cases[:pos] + extra + cases[pos:]
+        pos += len(extra)
+    if args.noisy:
+        noisy = {d: build_dqn(d, args.capacity, noisy=True) for d in (False, True)}
+        noisy_slots = {d: torch.tensor(a.buff.sample(B), dtype=torch.int32).cuda() for d, a in noisy.items()}
+
+        def noisy_replay(double):
+            alg = noisy[double]
+            return lambda: alg.actor.train_replay(alg.target_actor, alg.buff, noisy_slots[double], dqn_mod.GAMMA, double)
+
+        def noisy_launches():
+            online, target = noisy[False].actor.net, noisy[False].target_actor.net
+            online.compose(state["it"], 0)
+            target.compose(state["it"], 1)
+            online.noisy_grads()
+
+        extra = [("DQN.train, noisy (loss read back)", noisy[False].train),
+                 ("DQN.train, noisy, double_dqn (loss read back)", noisy[True].train),
+                 ("dqn step + adam, noisy, enqueue only", noisy_replay(False)),
+                 ("dqn step + adam, noisy, double_dqn, enqueue only", noisy_replay(True)),
+                 ("compose online + compose target + noisy_grads alone, enqueue only", noisy_launches)]
         cases = cases[:pos] + extra + cases[pos:]
         pos += len(extra)
     for _, fn in cases:

@@ -36,6 +36,12 @@ prioritised replay it needs the device step.
 Bellman targets of the bootstrap action's (``quantile_midpoints`` / ``quant_q`` / ``quantile_huber`` are the host
 definitions).  There is no support to choose; it composes and is bound to the device step in the same way.
 
+``model_config.noisy`` gives the actor pair factorised-Gaussian noisy layers (NoisyNet): the last trunk layer, the Q head
+and the dueling stream run on ``W_eff = mu + sigma * (f_in f_out^T)``, composed on the device in front of every train
+(``xt_noisy_compose``, the online net on noise stream 0 and the target net on stream 1 of the call ``iterations``), with
+the sigma gradients formed behind it (``xt_noisy_grads``); it composes with everything above, because no step entry
+knows about it.  The target sync copies the whole store, means and sigmas.
+
 Every variant reaches its C entry through the model's ``train_replay`` / ``train_replay_per`` and one method of the net,
 ``HipActorCritic.dqn_step``, whose keywords (``follow`` / ``n``, ``per``, ``dist``, ``quant``) choose the entry.
 """

@@ -1598,22 +1598,8 @@ int launch_act_apply(const float* z, float* y, long long count, int act, hipStre
 
 namespace xt {
 // ---------------------------------------------------------------- acting heads (Model.predict on the device)
-// Philox4x32-10 (Salmon et al., SC'11), the standard constants.  Counter-based: a row's draw depends on
+// The generator is xt_common.h's Philox4x32-10.  Counter-based: a row's draw depends on
 // (seed, call, global row, action) only -- not on the chunking of the batch, the grid shape or the call history.
-struct Philox4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                                 uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return Philox4{c0, c1, c2, c3};
-}
-// word -> uniform in [2^-24, 1 - 2^-24]: every step is exact in fp32, so neither logarithm below sees 0 or 1
-__device__ __forceinline__ float philox_uniform(uint32_t w) { return ((float)(w >> 9) + 0.5f) * 0x1p-23f; }
 
 // Runs behind the trunk instead of heads_fwd_kernel: logits and value by heads_fwd_kernel's arithmetic (bit for bit),
 // then the action, its log-probability and the noise it was drawn with.  One wave per sample, four per block, lane a <->

@@ -109,6 +109,15 @@ class ActCfg(Structure):
     _fields_ = [("seed", ctypes.c_uint64), ("call", ctypes.c_uint64), ("row0", c_int64), ("want_noise", c_int32)]
 
 
+class NoisyLayer(Structure):
+    """xt_noisy_layer of include/xt_mi355x.h"""
+    _fields_ = [("w_off", c_int64), ("sigma_off", c_int64), ("noise_off", c_int64), ("K", c_int32), ("N", c_int32),
+                ("index", c_int32), ("reserved", c_int32)]
+
+
+NOISY_MAX_LAYERS = 8     # XT_NOISY_MAX_LAYERS
+
+
 class GradEntry(Structure):
     """xt_grad_entry of include/xt_mi355x.h: one parameter block of the gradient-reduction launch (zl / nblk / pblk0: out)"""
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("count", c_int32), ("nslab", c_int32), ("stride", c_int64),
@@ -296,6 +305,9 @@ SIGNATURES = {
     "xt_net_set_quant": (c_int32, [_P, c_int32, c_double]),
     "xt_net_dqn_step_quant": (c_int32, [_P, _P, POINTER(DqnCfg), POINTER(NstepCfg), POINTER(PerCfg), _P, _P, c_int64, c_int64,
                                         c_int64, _P, c_int32, _P, _P, _P, _P, _P, _P]),
+    "xt_noisy_compose": (c_int32, [POINTER(NoisyLayer), c_int32, _P, _P, c_int64, _P, _P, ctypes.c_uint64, ctypes.c_uint64,
+                                   c_int32, c_int32, _P]),
+    "xt_noisy_grads": (c_int32, [POINTER(NoisyLayer), c_int32, _P, _P, _P]),
 }
 # XT_GRAPH_CACHE_<name> of include/xt_mi355x.h: word of every counter of xt_net_graph_cache_info
 GRAPH_CACHE_WORDS = ("CAPTURES", "LAUNCHES", "EVICTIONS", "LIVE_SLOTS")

@@ -19,11 +19,21 @@ def initial_weights(spec, seed=None, baseline_norm_std=None):
     """Keras default initialisation of every variable of ``spec`` (glorot_uniform kernels, zero biases; Conv2D/Dense
     in xt/model/model_utils.py:86-96) and, for ImpalaCnnOpt's baseline, ``custom_norm_initializer(std)``
     (xt/model/model_utils.py:204-211).  One generator, fixed variable order -> the GPU learner and a CPU replica
-    built from the same seed start identical."""
+    built from the same seed start identical.  The noisy layers of a noisy spec (``netspec._add_noisy``) start as
+    Fortunato et al. 2018 section 3.2 (factorised) has it, ``p`` being the TF fan-in: mu kernel and mu bias drawn from
+    U(-1/sqrt(p), 1/sqrt(p)), both sigmas ``noisy_sigma0`` / sqrt(p) -- from the same generator, in ``spec.names`` order."""
     rng = np.random.default_rng(seed)
     w = OrderedDict()
+    noisy = {nl.name for nl in getattr(spec, "noisy_layers", ())}
     for name, (_, shape) in spec.names.items():
-        if name.endswith("/bias") or name == "pi_logstd":
+        layer, _, var = name.rpartition("/")
+        if layer in noisy:
+            p = np.float64(spec.names[layer + "/kernel"][1][0])
+            if var.startswith("sigma_"):
+                w[name] = np.full(shape, np.float32(np.float64(spec.noisy_sigma0) / np.sqrt(p)), np.float32)
+            else:
+                w[name] = rng.uniform(-1.0 / np.sqrt(p), 1.0 / np.sqrt(p), size=shape).astype(np.float32)
+        elif name.endswith("/bias") or name == "pi_logstd":
             w[name] = np.zeros(shape, np.float32)
         else:
             if len(shape) == 4:
@@ -102,14 +112,37 @@ class CpuActorCritic(object):
                 raise KeyError("update {} encounter error: shape {} vs {}".format(name, val.shape, shape))
             self.spec.var_view(self.params, name)[...] = val
 
+    # ------------------------------------------------------------------ noisy layers
+    noisy = None
+
+    def set_noisy(self, seed, sigma0, mean_only=False):
+        """``HipActorCritic.set_noisy`` on the replica: the key of the noise draws; every ``forward`` then composes the
+        effective parameters once, by the host definitions (``model.dqn.dqn_cnn.noisy_vectors`` / ``noisy_effective``) on
+        stream 2 and a call counter of the replica's own -- or, ``mean_only``, runs on the means alone."""
+        if not getattr(self.spec, "noisy_layers", None):
+            raise ValueError("set_noisy: the net's spec has no noisy layers (netspec.dqn_cnn / dqn_mlp with noisy=True)")
+        self.noisy = (int(seed) & 0xFFFFFFFFFFFFFFFF, float(sigma0))
+        self.noisy_mean_only, self.noisy_call = bool(mean_only), 0
+
+    def _forward_params(self):
+        """the flat parameters this ``forward`` runs on: ``self.params``, or a noisy spec's effective ones"""
+        if not getattr(self.spec, "noisy_layers", None):
+            return self.params
+        if self.noisy is None or self.noisy_mean_only:
+            return self.params[:self.spec.n_net]
+        from xingtian_amd.model.dqn.dqn_cnn import NOISY_STREAM_PREDICT, noisy_effective, noisy_vectors
+        noise = noisy_vectors(self.spec, self.noisy[0], self.noisy_call, NOISY_STREAM_PREDICT)
+        self.noisy_call += 1
+        return noisy_effective(self.spec, self.params, noise)
+
     def publish_weights(self, ring, ctr_info=None, lag=0):
         """hand the replica's weights to a ``transport.WeightsRing`` in the packed form the learner publishes"""
         return ring.publish_flat_host(self.params, self.spec, ctr_info)
 
     # ------------------------------------------------------------------ forward
-    def _layer(self, lay, x):
-        """x: [B, H, W, C] float32 -> [B, OH, OW, N]; Conv2D (VALID / TensorFlow's asymmetric SAME) or Dense."""
-        p = self.params
+    def _layer(self, lay, x, p):
+        """x: [B, H, W, C] float32 -> [B, OH, OW, N] on the flat parameters ``p``; Conv2D (VALID / TensorFlow's asymmetric
+        SAME) or Dense."""
         w = p[lay.param_off:lay.param_off + lay.K * lay.N].reshape(lay.K, lay.N)
         b = p[lay.param_off + lay.K * lay.N:lay.param_off + (lay.K + 1) * lay.N]
         bsz = x.shape[0]
@@ -130,6 +163,7 @@ class CpuActorCritic(object):
     def forward(self, obs):
         """obs [B, ...] -> (logits [B, A] (the mean for DiagGaussian), value [B]) as numpy float32."""
         spec = self.spec
+        p = self._forward_params()
         x0 = np.asarray(obs)
         is_u8, mean, std = spec.input_xform
         lay0 = spec.layers[0]
@@ -152,10 +186,10 @@ class CpuActorCritic(object):
                     continue
                 if lay.H == 1 and lay.W == 1 and x.shape[1:3] != (1, 1):
                     x = x.reshape(x.shape[0], 1, 1, -1)      # Flatten in (H, W, C) order
-                x = self._layer(lay, x)
+                x = self._layer(lay, x, p)
             feats.append(x.reshape(x.shape[0], -1))
         f_pi, f_v = feats[0], feats[-1]
-        p, f, a = self.params, spec.feat, spec.action_dim
+        f, a = spec.feat, spec.action_dim
         wpi = p[spec.pi_off:spec.pi_off + f * a].reshape(f, a)
         bpi = p[spec.pi_off + f * a:spec.pi_off + f * a + a]
         wv = p[spec.v_off:spec.v_off + f]

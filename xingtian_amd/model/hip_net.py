@@ -63,7 +63,9 @@ def net_desc(spec):
         lay_arr[i].trunk = lay.trunk
     d = L.NetDesc()
     d.n_layers, d.layers, d.n_trunks = len(spec.layers), lay_arr, spec.n_trunks
-    d.feat, d.action_dim, d.pi_off, d.v_off, d.n_params = spec.feat, spec.action_dim, spec.pi_off, spec.v_off, spec.n_flat
+    # (a noisy spec: the net sees the n_net floats of the effective parameters; the store behind them is the learner's)
+    d.feat, d.action_dim, d.pi_off, d.v_off = spec.feat, spec.action_dim, spec.pi_off, spec.v_off
+    d.n_params = getattr(spec, "n_net", spec.n_flat)
     d.xf = L.InputXform(*spec.input_xform)
     d.in_h, d.in_w, d.in_c = spec.layers[0].H, spec.layers[0].W, spec.layers[0].C      # (C: as the kernels read it, padded)
     d.action_type = L.ACTION_TYPE[getattr(spec, "action_type", "Categorical")]
@@ -110,7 +112,17 @@ class HipActorCritic(object):
 
         ws_bytes = self.lib.xt_net_workspace_bytes(h)
         self.workspace = torch.empty(ws_bytes // 4, dtype=torch.float32, device=self.device)
-        L.check(self.lib.xt_net_bind(h, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.adam_m), L.ptr(self.adam_v),
+        # a noisy spec (netspec._add_noisy): ``params`` / ``grads`` / the Adam slots are the STORE (means in the net's layout,
+        # the sigma blocks behind n_net) and the net is bound to ``params_eff``, the n_net effective parameters ``compose``
+        # writes; the backward leaves g_mu in grads[0, n_net).  A plain spec allocates nothing more.
+        self.params_eff = self.noise = None
+        if getattr(spec, "noisy_layers", None):
+            self.params_eff = torch.zeros(spec.n_net, dtype=torch.float32, device=self.device)
+            self.noise = torch.zeros(spec.noise_floats, dtype=torch.float32, device=self.device)
+            self._noisy_table = (L.NoisyLayer * len(spec.noisy_layers))(*[
+                L.NoisyLayer(nl.w_off, nl.sigma_off, nl.noise_off, nl.K, nl.N, nl.index, 0) for nl in spec.noisy_layers])
+        bound = self.params if self.params_eff is None else self.params_eff
+        L.check(self.lib.xt_net_bind(h, L.ptr(bound), L.ptr(self.grads), L.ptr(self.adam_m), L.ptr(self.adam_v),
                                      L.ptr(self.adam_state), L.ptr(self.workspace), ws_bytes), "xt_net_bind")
         L.check(self.lib.xt_adam_state_init(L.ptr(self.adam_state), L.stream_ptr()), "xt_adam_state_init")
         if init == "glorot":
@@ -997,6 +1009,34 @@ class HipActorCritic(object):
         carries one mark: ``set_dist`` and this refuse a net the other has marked."""
         L.check(self.lib.xt_net_set_quant(self.handle, int(quantiles), float(kappa)), "xt_net_set_quant")
         self.quant = (int(quantiles), float(kappa)) if int(quantiles) > 1 else None
+
+    def set_noisy(self, seed, sigma0):
+        """Give the noisy layers of the net's spec the 64-bit key ``seed`` of their noise draws; ``sigma0`` is the spec's
+        (what ``initial_weights`` started the sigmas from) and is only checked.  A plain spec is refused."""
+        if self.params_eff is None:
+            raise ValueError("set_noisy: the net's spec has no noisy layers (netspec.dqn_cnn / dqn_mlp with noisy=True)")
+        if float(sigma0) != self.spec.noisy_sigma0:
+            raise ValueError("set_noisy: sigma0 = {} differs from the spec's noisy_sigma0 = {}".format(
+                sigma0, self.spec.noisy_sigma0))
+        self.noisy = (int(seed) & 0xFFFFFFFFFFFFFFFF, float(sigma0))
+
+    def compose(self, call, stream_id, mean_only=False, noise_in=None):
+        """The effective parameters of the net for its next forward / step (C ABI ``xt_noisy_compose``, one launch, nothing
+        synchronises): W_eff = mu + sigma * (f_in f_out^T) over the noisy layers with the vectors of (seed, ``call``,
+        ``stream_id``), which stay in ``self.noise``; every other parameter is copied.  ``mean_only``: W_eff = mu.
+        ``noise_in`` (float32 device tensor laid out as ``self.noise``): the vectors are taken from it instead of drawn."""
+        if getattr(self, "noisy", None) is None:
+            raise ValueError("compose: the net has no noise key (call set_noisy first)")
+        L.check(self.lib.xt_noisy_compose(
+            self._noisy_table, len(self._noisy_table), L.ptr(self.params), L.ptr(self.params_eff), self.spec.n_net,
+            L.ptr(self.noise), L.ptr(noise_in), self.noisy[0], int(call) & 0xFFFFFFFFFFFFFFFF, int(stream_id),
+            1 if mean_only else 0, L.stream_ptr()), "xt_noisy_compose")
+
+    def noisy_grads(self):
+        """Behind a step: the sigma blocks of ``self.grads`` = dW_eff * e / db_eff * f_out, from grads[0, n_net) and the vectors
+        the last ``compose`` stored (C ABI ``xt_noisy_grads``, one launch)"""
+        L.check(self.lib.xt_noisy_grads(self._noisy_table, len(self._noisy_table), L.ptr(self.noise), L.ptr(self.grads),
+                                        L.stream_ptr()), "xt_noisy_grads")
 
     def set_dist_wide(self, on):
         """Switch a marked net between the wide-head kernels (the default) and those of an unmarked net (C ABI

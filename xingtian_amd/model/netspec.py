@@ -302,12 +302,70 @@ def check_quantiles(quantiles):
     return int(quantiles)
 
 
-def _dqn_spec(layers, feat, action_dim, n_trunk_layers, dueling, xf, state_dim, atoms=1, quantiles=1):
+def check_noisy(noisy, sigma0):
+    """``noisy`` / ``noisy_sigma0`` of a DQN model as (bool, float): ``noisy`` must be a bool, ``noisy_sigma0`` finite and
+    > 0, else ValueError"""
+    if not isinstance(noisy, bool):
+        raise ValueError("noisy = {!r} must be a bool".format(noisy))
+    try:
+        s0 = float(sigma0)
+    except (TypeError, ValueError):
+        raise ValueError("noisy_sigma0 = {!r} must be a finite number > 0".format(sigma0))
+    if isinstance(sigma0, bool) or not (s0 == s0 and abs(s0) != float("inf") and s0 > 0.0):
+        raise ValueError("noisy_sigma0 = {!r} must be a finite number > 0".format(sigma0))
+    return noisy, s0
+
+
+class NoisyLayer(object):
+    """One factorised-Gaussian noisy Dense block of a spec: ``name`` (the Keras layer), ``index`` (its position in the list
+    of noisy layers: counter word c1 of its draws is 2 * index + side), the mean block ``w_off`` ([K, N] kernel then [N]
+    bias, inside [0, n_net)), the sigma block ``sigma_off`` of the same form behind n_net, and ``noise_off``: where its
+    f_in [K] then f_out [N] live in the net's noise buffer (each vector starts on a 16-byte boundary)."""
+    __slots__ = ("name", "index", "w_off", "sigma_off", "noise_off", "K", "N")
+
+    @property
+    def f_in(self):
+        return slice(self.noise_off, self.noise_off + self.K)
+
+    @property
+    def f_out(self):
+        off = self.noise_off + ((self.K + 3) & ~3)
+        return slice(off, off + self.N)
+
+
+def _add_noisy(spec, sigma0, dueling):
+    """Make the last trunk layer, the Q head and (``dueling``) the 1-wide stream of a DQN spec noisy: today's layout
+    [0, n_flat) becomes [0, n_net) and holds the means under their names; ``<layer>/sigma_kernel`` / ``sigma_bias`` are
+    appended behind it, one 16-byte aligned [K, N] + [N] block per layer, and n_flat grows to the store's size."""
+    last = spec.layers[-1]
+    blocks = [(last.name, last.param_off, last.K, last.N), (spec.pi_name, spec.pi_off, spec.feat, spec.action_dim)]
+    if dueling:
+        blocks.append((spec.v_name, spec.v_off, spec.feat, 1))
+    spec.n_net, spec.noisy_sigma0, spec.noisy_layers = spec.n_flat, float(sigma0), []
+    off, noise_off = spec.n_flat, 0
+    for index, (name, w_off, k, n) in enumerate(blocks):
+        nl = NoisyLayer()
+        nl.name, nl.index, nl.w_off, nl.sigma_off, nl.noise_off, nl.K, nl.N = name, index, w_off, off, noise_off, k, n
+        spec.noisy_layers.append(nl)
+        shape = spec.names[name + "/kernel"][1]
+        spec.names[name + "/sigma_kernel"] = (off, shape)
+        if name + "/kernel" in spec.store_shape:        # a channel-padded block: the padded sigma rows are 0 and stay 0
+            spec.store_shape[name + "/sigma_kernel"] = spec.store_shape[name + "/kernel"]
+        spec.names[name + "/sigma_bias"] = (off + k * n, (n,))
+        off = (off + (k + 1) * n + 3) & ~3
+        noise_off += ((k + 3) & ~3) + ((n + 3) & ~3)
+    spec.n_flat, spec.noise_floats = off, noise_off
+    spec.n_params = sum(int(_prod(s)) for _, s in spec.names.values())
+
+
+def _dqn_spec(layers, feat, action_dim, n_trunk_layers, dueling, xf, state_dim, atoms=1, quantiles=1, noisy=False,
+              noisy_sigma0=0.5):
     """The Q head is the Keras layer after the trunk (dense_<n>), the dueling 1-wide stream the one after it.  ``atoms``
     > 1: the distributional head -- kernel (F, A * atoms), column a * atoms + i is atom i of action a; the spec's
     ``action_dim`` is then the head's width A * atoms, ``n_actions`` is A and ``atoms`` the count.  ``quantiles`` > 1: the
     quantile head, by the same width rule (column a * quantiles + i is quantile i of action a; ``quantiles`` the count);
-    a head is one or the other."""
+    a head is one or the other.  ``noisy``: see ``_add_noisy``; a spec without it is unchanged."""
+    noisy, noisy_sigma0 = check_noisy(noisy, noisy_sigma0)
     atoms, quantiles = check_atoms(atoms), check_quantiles(quantiles)
     if atoms > 1 and quantiles > 1:
         raise ValueError("atoms = {} together with quantiles = {}: a Q head is categorical (C51) or quantile (QR-DQN), "
@@ -322,21 +380,26 @@ def _dqn_spec(layers, feat, action_dim, n_trunk_layers, dueling, xf, state_dim, 
     spec = NetSpec(layers, 1, feat, width, "dense_%d" % n_trunk_layers, "dense_%d" % (n_trunk_layers + 1),
                    (feat, width), xf, state_dim, hidden_v=not dueling)
     spec.atoms, spec.quantiles, spec.n_actions = atoms, quantiles, int(action_dim)
+    if noisy:
+        _add_noisy(spec, noisy_sigma0, dueling)
     return spec
 
 
-def dqn_cnn(state_dim, action_dim, dueling=False, atoms=1, quantiles=1):
+def dqn_cnn(state_dim, action_dim, dueling=False, atoms=1, quantiles=1, noisy=False, noisy_sigma0=0.5):
     """Keras ``DqnCnn`` (xt/model/dqn/dqn_cnn.py:45-59): the trunk of ``impala_cnn`` (Conv2D 32@8x8/4, 64@4x4/2, 64@3x3/1
     valid relu on uint8 / 255, Dense 256 relu), a linear Q head Dense(A) and, with ``dueling``, a 1-wide Dense stream:
     Q_a = s + (l_a - mean_a l).  Variable names are Keras' automatic ones of a first-built model: conv2d, conv2d_1,
-    conv2d_2, dense, the Q head dense_1, the 1-wide stream dense_2.  ``atoms`` / ``quantiles`` > 1: see ``_dqn_spec``."""
+    conv2d_2, dense, the Q head dense_1, the 1-wide stream dense_2.  ``atoms`` / ``quantiles`` > 1 and ``noisy``: see
+    ``_dqn_spec``."""
     trunk = impala_cnn(state_dim, action_dim).layers
-    return _dqn_spec(trunk, 256, action_dim, 1, dueling, (1, 0.0, 255.0), state_dim, atoms, quantiles)
+    return _dqn_spec(trunk, 256, action_dim, 1, dueling, (1, 0.0, 255.0), state_dim, atoms, quantiles, noisy, noisy_sigma0)
 
 
-def dqn_mlp(state_dim, action_dim, hidden_size=128, num_layers=1, dueling=False, atoms=1, quantiles=1):
+def dqn_mlp(state_dim, action_dim, hidden_size=128, num_layers=1, dueling=False, atoms=1, quantiles=1, noisy=False,
+            noisy_sigma0=0.5):
     """Keras ``DqnMlp`` (xt/model/dqn/dqn_mlp.py:43-56): ``impala_mlp``'s trunk (dense ... dense_{L-1}), the Q head
-    dense_L and, with ``dueling``, the 1-wide stream dense_{L+1}.  ``atoms`` / ``quantiles`` > 1: see ``_dqn_spec``."""
+    dense_L and, with ``dueling``, the 1-wide stream dense_{L+1}.  ``atoms`` / ``quantiles`` > 1 and ``noisy``: see
+    ``_dqn_spec``."""
     trunk = impala_mlp(state_dim, action_dim, hidden_size, num_layers).layers
     return _dqn_spec(trunk, hidden_size, action_dim, int(num_layers), dueling, (0, 0.0, 1.0), (1, 1, int(state_dim[0])),
-                     atoms, quantiles)
+                     atoms, quantiles, noisy, noisy_sigma0)
