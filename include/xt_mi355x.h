@@ -1492,6 +1492,18 @@ int xt_noisy_compose(const xt_noisy_layer* layers, int32_t n_layers, const float
  * mean block. */
 int xt_noisy_grads(const xt_noisy_layer* layers, int32_t n_layers, const float* noise, float* grads, void* stream);
 
+/* The Dense instance of the fused backward launch (XT_BWD_PATH_PF_GENERIC of xt_layer_bwd; appended, the ABI version stays):
+ * process-wide, default 1.  on == 1: its weight-gradient blocks address the rows of the 1x1, stride-1, unpadded layer
+ * directly (row m at byte m * K * 4) instead of decoding them into an LDS table behind a barrier, and the blocks that own
+ * the bias gradient take the fp32 dy rows from memory next to their operands; its input-gradient blocks skip the tap
+ * decode of their loads (the layer has one tap); and the head weight-gradient tiles that ride in the launch share the
+ * workgroup slots the other blocks leave (a head block walks several tiles) instead of queueing behind each other.  dx,
+ * dW, db, the head slabs, the squared-norm partials and the reported path are bit for bit those of on == 0, which
+ * launches the instance as it was.  Returns the PREVIOUS value
+ * (0 or 1); anything but 0 or 1 is refused: returns 2, xt_last_error names the entry, nothing changes.  Set it before
+ * graphs are captured outside a net (a net's own cached hipGraphs carry it in their key). */
+int xt_bwd_dense_lean_set(int32_t on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -525,9 +525,15 @@ constexpr int wgrad_smem_floats() {
 // for the Dense layer's backward (18.04 -> 16.90 us: ten short steps, the co-resident input-gradient blocks get the pipe),
 // LOSES for the conv layers (more elements to split per step; conv3 also drops from three to two workgroups per CU) -- so
 // only the Dense instance of the fused backward selects it (xt_tuning.dense_wgrad_x6).
-template <int BI, int BJ, int WI, int WJ, bool U8, bool PADDED, bool PF4 = false, int WX6 = 0>
+// DL (xt_bwd_dense_lean_set; the host guarantees a 1x1, stride-1, unpadded, ungathered layer inside the `lean` bounds): row
+// m of the input starts at byte m * K * 4, so there is no row table, no decode and no barrier in front of the first loads
+// (timeline: 2.6 us of "rowtab + fetch issued" per block before), and the bias column sums of the bx == 0 blocks take the
+// fp32 dY straight from memory, in the four register stages of the operands, instead of adding the three bf16 planes back
+// up out of LDS (72 instructions per step of a loop that is issue-bound; the same values in the same order).
+template <int BI, int BJ, int WI, int WJ, bool U8, bool PADDED, bool PF4 = false, int WX6 = 0, bool DL = false>
 __device__ __forceinline__ void igemm_wgrad_body(const WgradArgs& p, const int bx, const int by, const int bz,
                                                  float* smem) {
+  static_assert(!DL || (PF4 && !U8 && !PADDED), "igemm_wgrad: the table-free form is the four-stage fp32 unpadded one");
   constexpr int TI = BI / (32 * WI), TJ = BJ / (32 * WJ);
   constexpr int SA = BI, SB = BJ;
   constexpr int CPRA = BI / 4, RPA = 256 / CPRA, NA = 32 / RPA;
@@ -550,10 +556,10 @@ __device__ __forceinline__ void igemm_wgrad_body(const WgradArgs& p, const int b
   const int ca = t % CPRA, rowa = t / CPRA;
   const int k = i0 + ca * 4;
   const bool kok = k < g.K;
-  const uint32_t ky = fdiv((uint32_t)k, g.d_kwc);
+  const uint32_t ky = DL ? 0u : fdiv((uint32_t)k, g.d_kwc);
   const uint32_t rr = (uint32_t)k - ky * (uint32_t)g.KWC;
-  const uint32_t kx = fdiv(rr, g.d_c);
-  const int koff = ((int)ky * g.W + (int)kx) * g.C + (int)(rr - kx * (uint32_t)g.C);
+  const uint32_t kx = DL ? 0u : fdiv(rr, g.d_c);
+  const int koff = ((int)ky * g.W + (int)kx) * g.C + (int)(rr - kx * (uint32_t)g.C);      // (DL: = k)
   const int cb = t % CPRB, rowb = t / CPRB;
   const int nb = j0 + cb * 4;
   const bool nok = nb < g.N;
@@ -578,10 +584,11 @@ __device__ __forceinline__ void igemm_wgrad_body(const WgradArgs& p, const int b
     const int nsteps = (sub_end - sub + 31) / 32;
     // "lean" loads (fp32 input, no row gather): see below
     constexpr bool LEAN_T = !U8;
-    const bool lean = LEAN_T && p.idx == nullptr && (long long)g.B * g.HWC * 4 < (1ll << 30) &&
-                      (long long)g.M * g.N * 4 < (1ll << 30);
+    const bool lean = DL || (LEAN_T && p.idx == nullptr && (long long)g.B * g.HWC * 4 < (1ll << 30) &&
+                             (long long)g.M * g.N * 4 < (1ll << 30));
     uint32_t* tab32 = reinterpret_cast<uint32_t*>(rowtab);
-    // ---- decode the rows of this sub-range once
+    // ---- decode the rows of this sub-range once (DL: nothing to decode, nothing to wait for)
+    if constexpr (!DL) {
     for (int r = t; r < nsteps * 32; r += 256) {
       int mr[1] = {sub + r < sub_end ? sub + r : g.M};
       long long base[1];
@@ -600,6 +607,7 @@ __device__ __forceinline__ void igemm_wgrad_body(const WgradArgs& p, const int b
       if (PADDED) rowxy[r] = (iy0[0] << 16) | (ix0[0] & 0xffff);
     }
     __syncthreads();
+    }
 
     struct Regs { Raw4<U8> a[NA]; float4 b[NB]; uint32_t ok; };
     auto fetch = [&](int s, Regs& R) {
@@ -645,8 +653,8 @@ __device__ __forceinline__ void igemm_wgrad_body(const WgradArgs& p, const int b
       for (int i = 0; i < NB; ++i)
         *reinterpret_cast<float4*>(&Bs[(rowb + RPB * i) * SB + cb * 4]) = sel4((R.ok >> (8 + i)) & 1u, R.b[i]);
     };
-    auto colsum = [&](const float* stage) {       // (stage base: A part first, then B)
-      if (do_bias) {
+    auto colsum = [&](const float* stage) {       // (stage base: A part first, then B; DL: from the register stages, below)
+      if (!DL && do_bias) {
         if constexpr (X6W) {      // the three planes add up to the fp32 value exactly: same sums, bit for bit
           const uint8_t* Bp = reinterpret_cast<const uint8_t*>(stage) + 3 * XL::PlaneA;
 #pragma unroll
@@ -706,11 +714,27 @@ __device__ __forceinline__ void igemm_wgrad_body(const WgradArgs& p, const int b
     //  * the LDS writes store the load registers as they are (no zero-selects);
     //  * one LDS read per step fetches all NA row offsets of the thread.
     if constexpr (LEAN_T) if (lean) {
-      const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(p.in, (uint32_t)g.B * (uint32_t)g.HWC * 4u);
-      const __amdgpu_buffer_rsrc_t rs_b = make_rsrc(p.dy, (uint32_t)g.M * (uint32_t)g.N * 4u);
+      // (DL: both descriptors end with the sub-range, a row past it reads as zeros without a comparison)
+      const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(p.in, DL ? (uint32_t)sub_end * (uint32_t)g.K * 4u : (uint32_t)g.B * (uint32_t)g.HWC * 4u);
+      const __amdgpu_buffer_rsrc_t rs_b = make_rsrc(p.dy, (uint32_t)(DL ? sub_end : g.M) * (uint32_t)g.N * 4u);
       const uint32_t koff4 = (kok || PADDED) ? (uint32_t)koff * 4u : 0x40000000u;   // (any row offset + 2^30 is out of range)
-      struct LRegs { float4 a[NA]; float4 b[NB]; };
+      struct LRegs { float4 a[NA]; float4 b[NB]; float c[DL ? 32 / RG : 1]; };
+      // DL: byte offsets of this thread's rows of step 0 (operands) and of its first bias row; a step adds a block-uniform term
+      const uint32_t dl_a = (uint32_t)(rowa * g.K) * 4u + koff4, dl_b = nok ? (uint32_t)(rowb * g.N + nb) * 4u : kOob;
+      const uint32_t dl_c = (j0 + bcol < g.N) ? (uint32_t)(brg * g.N + j0 + bcol) * 4u : kOob;
       auto lfetch = [&](int sf, LRegs& Rf) {
+        if constexpr (DL) {
+          const uint32_t m0 = (uint32_t)(sub + sf * 32);
+#pragma unroll
+          for (int i = 0; i < NA; ++i) Rf.a[i] = buf_load4(rs_a, dl_a + (m0 + RPA * i) * (uint32_t)g.K * 4u, 0);
+#pragma unroll
+          for (int i = 0; i < NB; ++i) Rf.b[i] = buf_load4(rs_b, dl_b + (m0 + RPB * i) * (uint32_t)g.N * 4u, 0);
+          if (do_bias) {      // rows brg + RG * q of the step, the order of colsum()
+#pragma unroll
+            for (int q = 0; q < 32 / RG; ++q) Rf.c[q] = buf_load1(rs_b, dl_c + (m0 + RG * q) * (uint32_t)g.N * 4u, 0);
+          }
+          return;
+        }
         uint32_t ro[NA];
         int rxy[NA];
         if constexpr (NA == 4) {
@@ -769,6 +793,10 @@ __device__ __forceinline__ void igemm_wgrad_body(const WgradArgs& p, const int b
             if (s + u < nsteps) {                                                   // block-uniform
               float* stage = smem + (u & 1) * BUF2;
               lstash(R[u], stage, stage + 32 * SA);
+              if constexpr (DL) if (do_bias) {
+#pragma unroll
+                for (int q = 0; q < 32 / RG; ++q) bsum += R[u].c[q];
+              }
               __syncthreads();
               if (s == 0 && u == 0 && sub == mbeg) XT_TL(2);
               if (s + u + 4 < nsteps) lfetch(s + u + 4, R[u]);
@@ -930,7 +958,9 @@ constexpr int dgrad_smem_floats() {
 // NST > 0 (round 3): the class reduction has at most NST 32-deep steps and ALL of their operand loads are issued before
 // the first is consumed (NST register stages; needs the 256-VGPR budget of a two-workgroups-per-CU instance).  With
 // two steps in flight the 8-step loop of the Dense layer's input gradient ran at the memory latency, 1.2 us per step.
-template <int BI, int BJ, int WI, int WJ, bool X6 = false, int NST = 0>
+// D1 (the table-free Dense instance: 1x1, stride 1, unpadded): the reduction has ONE tap, so the NST fetches carry no tap
+// decode (a vector integer division each) -- tap = jy = jx = 0 for every k inside the range, the others read as zeros anyway.
+template <int BI, int BJ, int WI, int WJ, bool X6 = false, int NST = 0, bool D1 = false>
 __device__ __forceinline__ void igemm_dgrad_body(const DgradArgs& p, const int bx, const int by, const int bz,
                                                  float* smem) {
   constexpr int TI = BI / (32 * WI), TJ = BJ / (32 * WJ);
@@ -998,9 +1028,9 @@ __device__ __forceinline__ void igemm_dgrad_body(const DgradArgs& p, const int b
     const int kk = k0 + c4 * 4;
     const bool kok = kk < Kc;
     R.ok = 0xffffffffu;
-    const uint32_t tap = fdiv((uint32_t)kk, g.d_n);
+    const uint32_t tap = D1 ? 0u : fdiv((uint32_t)kk, g.d_n);
     const int n = kk - (int)tap * g.N;
-    const int jy = JX > 0 ? (int)tap / JX : 0, jx = (int)tap - jy * JX;
+    const int jy = (!D1 && JX > 0) ? (int)tap / JX : 0, jx = (int)tap - jy * JX;
     const int tapoff = (jy * g.OW + jx) * g.N - n;
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
@@ -1817,8 +1847,9 @@ struct BwdLayerArgs {
 // a kernel is the maximum over all of its paths: the generic form needs 144 VGPR (LDS-tiled dgrad) + 32 AGPR
 // (register-direct dgrad) = two workgroups per CU, this one three.
 template <int WBI, int WBJ, int WWI, int WWJ, bool WPAD, int DBI, int DBJ, int DWI, int DWJ, int D4 = 0, int HALO = 0,
-          bool DX6 = false, int WROWS = 0, int WX6 = 0, bool F21 = false>
+          bool DX6 = false, int WROWS = 0, int WX6 = 0, bool F21 = false, bool DL = false>
 __global__ __launch_bounds__(256, WROWS ? 2 : 3) void igemm_bwd_layer_kernel(const BwdLayerArgs p) {
+  static_assert(!DL || (WROWS == 3 && !WPAD && !F21 && D4 == 0 && HALO == 0), "DL: the Dense instance only (igemm_wgrad_body)");
   constexpr int SMD = HALO == 5 ? 18 * 1024 : HALO == 3 ? 8 * 1024 : HALO == 2 ? 11 * 1024 : HALO == 1 ? 9 * 1024 : dgrad_smem_floats<DBI, DBJ, DX6>();
   constexpr int SMW = (WROWS == 1 || WROWS == 2) ? kWrMaxSmemFloats : wgrad_smem_floats<WBI, WBJ, WPAD, WX6>();
   constexpr int SM0 = SMW > SMD ? SMW : SMD;
@@ -1864,7 +1895,7 @@ __global__ __launch_bounds__(256, WROWS ? 2 : 3) void igemm_bwd_layer_kernel(con
     // (the M tiles of one channel tile stream the same W^T slice: XCD-contiguous order, as the forward)
     if (p.dg_xcd) b = (int)xcd_chunk((uint32_t)b, (uint32_t)p.n_dg);
     const int bx = b % p.dg_gx, r = b / p.dg_gx;
-    igemm_dgrad_body<DBI, DBJ, DWI, DWJ, DX6, (WROWS == 3 ? 8 : 0)>(p.dg, bx, r % p.dg_gy, r / p.dg_gy, smem);
+    igemm_dgrad_body<DBI, DBJ, DWI, DWJ, DX6, (WROWS == 3 ? 8 : 0), DL>(p.dg, bx, r % p.dg_gy, r / p.dg_gy, smem);
     return;
   }
   b -= p.n_dg;
@@ -1878,10 +1909,14 @@ __global__ __launch_bounds__(256, WROWS ? 2 : 3) void igemm_bwd_layer_kernel(con
       return;
     }
     const int bx = b % p.wg_gx, r = b / p.wg_gx;
-    igemm_wgrad_body<WBI, WBJ, WWI, WWJ, false, WPAD, (WROWS == 3), WX6>(p.wg, bx, r % p.wg_gy, r / p.wg_gy, smem);
+    igemm_wgrad_body<WBI, WBJ, WWI, WWJ, false, WPAD, (WROWS == 3), WX6, DL>(p.wg, bx, r % p.wg_gy, r / p.wg_gy, smem);
     return;
   }
   b -= p.n_wg;
+  if constexpr (DL) {      // the launch may have fewer head blocks than head tiles (plan_bwd_layer): block b walks b, b + n_hw, ...
+    for (int it = b; it < p.hw.gx * p.hw.nchunk; it += p.n_hw) heads_wgrad_partial_body(p.hw, it % p.hw.gx, it / p.hw.gx, smem);
+    return;
+  }
   heads_wgrad_partial_body(p.hw, b % p.hw.gx, b / p.hw.gx, smem);
 }
 
@@ -2103,6 +2138,7 @@ int launch_dgrad(const xt_conv_geom* cg, int B, const float* dy, const float* w,
 enum BwdInst {
   kBwdS2Fused, kBwdS2FusedPad, kBwdS2c16, kBwdS2c16Pad, kBwdHalo, kBwdHaloX6, kBwdHaloX6Wx6,
   kBwdClassesPf4, kBwdClassesPf4F21, kBwdClassesWrows2, kBwdClassesWrows1, kBwdClassesX6, kBwdClasses, kBwdDense, kBwdDenseWx6, kBwdPairLLWx6,
+  kBwdDenseLean, kBwdDenseWx6Lean,      // the same two launches without the row table (xt_bwd_dense_lean_set)
   XT_BWD_PAIR4(SS), XT_BWD_PAIR4(SL), XT_BWD_PAIR4(LS), XT_BWD_PAIR4(LL)
 };
 #undef XT_BWD_PAIR4
@@ -2116,6 +2152,10 @@ struct BwdPlan {
   int npre;       // squared-norm partials the weight-gradient blocks leave (0: none)
   int fuse21;     // 1: the input-gradient blocks keep dX and write the producer's weight-gradient slabs (kBwdClassesPf4F21)
 };
+
+// xt_bwd_dense_lean_set (process-wide, not an xt_tuning field: that list is pinned): which form the Dense instance takes
+static std::atomic<int> g_bwd_dense_lean{1};
+int bwd_dense_lean() { return g_bwd_dense_lean.load(std::memory_order_relaxed); }
 
 // LDS-tiled weight gradient: the reduction over M in (at most) `split` slabs, one grid layer each
 static void cut_wgrad(int split, BwdLayerArgs* a) {
@@ -2298,9 +2338,18 @@ static int plan_bwd_layer(const Geom& g, int msplit, bool have_slabs, int slab_c
   // a weight gradient written by ONE slab per tile is final: its blocks also leave their share of the squared global
   // norm, which saves the reduction launch a read of the whole tensor (PpoCnn's Dense layer: 6.4 of its 29 MB)
   if (want_npre && a->wg.msplit == 1) { a->wg.sq_gx = a->wg_gx; p->npre = tiles; }
-  if (dense)      // dense_wgrad_x6: (round 5) the Dense weight gradient on the bf16 matrix cores as well
-    return t.dense_wgrad_x6 ? take(kBwdDenseWx6, XT_BWD_PATH_PF_GENERIC, XT_ARITH_BF16X6)
-                            : take(kBwdDense, XT_BWD_PATH_PF_GENERIC, XT_ARITH_FP32_BF16X6);
+  if (dense) {    // dense_wgrad_x6: (round 5) the Dense weight gradient on the bf16 matrix cores as well
+    // xt_bwd_dense_lean_set: the weight-gradient blocks address row m at m * K * 4 (1x1, stride 1, unpadded: the input IS the
+    // im2col matrix) inside the 2^30-byte bounds of their 32-bit offsets -- same path id, same bits, no row table
+    const bool lean = bwd_dense_lean() != 0 && g.OH == g.H && g.OW == g.W && g.K == g.C && g.HWC == g.OHOW * g.C &&
+                      (long long)g.M * g.K * 4 < (1ll << 30) && (long long)g.M * g.N * 4 < (1ll << 30);
+    // ... and its head weight-gradient tiles (4 us each, 160 of them at B = 320) share the workgroup slots the long blocks
+    // leave of the 512: as blocks of their own the surplus ran in up to four generations and ended the launch
+    const int room = 512 - a->n_dg - a->n_wg;
+    if (lean && room >= 32 && room < n_hw) a->n_hw = room;
+    return t.dense_wgrad_x6 ? take(lean ? kBwdDenseWx6Lean : kBwdDenseWx6, XT_BWD_PATH_PF_GENERIC, XT_ARITH_BF16X6)
+                            : take(lean ? kBwdDenseLean : kBwdDense, XT_BWD_PATH_PF_GENERIC, XT_ARITH_FP32_BF16X6);
+  }
   // the generic 64x64 pair (ImpalaCnnOpt's 11x11 "dense" conv) with the one-LDS-stage bf16x6 weight gradient (three
   // workgroups per CU as before): pong_impala_speedup 214.6 -> 212.3 us per 1000-frame train, breakout_impala unchanged
   if (!wsmall && !dsmall && t.dense_wgrad_x6 && dx6 && !pad) return take(kBwdPairLLWx6, XT_BWD_PATH_PAIR_LL_WX6, XT_ARITH_BF16X6);
@@ -2386,6 +2435,9 @@ int launch_bwd_layer(const BwdLayerCall& c) {
     XT_BWD_PAIR(LS, 64, 64, 2, 2, 128, 32, 4, 1)
     case kBwdPairLLWx6:     XT_BWD_GO(64, 64, 2, 2, false, 64, 64, 2, 2, 0, 0, true, 0, 2); break;
     XT_BWD_PAIR(LL, 64, 64, 2, 2, 64, 64, 2, 2)
+    // (last: the instances above keep their place in the code object)
+    case kBwdDenseWx6Lean:  XT_BWD_GO(64, 64, 2, 2, false, 64, 64, 2, 2, 0, 0, true, 3, 1, false, true); break;
+    case kBwdDenseLean:     XT_BWD_GO(64, 64, 2, 2, false, 64, 64, 2, 2, 0, 0, true, 3, 0, false, true); break;
   }
 #undef XT_BWD_PAIR
 #undef XT_BWD_GO
@@ -2465,6 +2517,11 @@ int xt_layer_bwd(const xt_conv_geom* g, int32_t B, const float* x, const float* 
     XT_LAUNCH_CHECK();
   }
   return 0;
+}
+
+int xt_bwd_dense_lean_set(int32_t on) {
+  XT_REQUIRE(on == 0 || on == 1, "xt_bwd_dense_lean_set: on = %d (must be 0 or 1)", on);
+  return xt::g_bwd_dense_lean.exchange(on);
 }
 
 }  // extern "C"

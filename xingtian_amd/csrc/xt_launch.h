@@ -60,6 +60,8 @@ struct BwdLayerCall {
   const Fuse21Call* f21 = nullptr;     // the producer's weight gradient may ride along (may be null)
 };
 int launch_bwd_layer(const BwdLayerCall& c);
+// xt_bwd_dense_lean_set: 1 (default) = the Dense instance of that launch in its table-free form (same bits), 0 = as before
+int bwd_dense_lean();
 
 // ------------------------------------------------------------------ xt_direct.hip: register-direct family (< 0: not taken)
 int launch_fwd_direct(const xt_conv_geom* cg, const xt_input_xform* xf, int B, const void* in, const int32_t* idx,

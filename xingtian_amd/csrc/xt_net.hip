@@ -830,7 +830,8 @@ static int ppo_step(xt_net* n, const xt_ppo_cfg* c, const void* obs, const int32
 template <typename F>
 static int graph_run(xt_net* net, const char* key_in, hipStream_t st, F enqueue) {
   // every cached graph holds a forward: the fused / two-launch first layers never replay each other's graph
-  const std::string key = std::string(key_in) + (net->fwd_fuse12_flat ? "|F1" : "|F0");
+  // (... nor do the two forms of the Dense backward, xt_bwd_dense_lean_set)
+  const std::string key = std::string(key_in) + (net->fwd_fuse12_flat ? "|F1" : "|F0") + (bwd_dense_lean() ? "" : "|L0");
   xt_net::GraphSlot* slot = nullptr;
   for (auto& g : net->gslots) if (g.exec && g.key == key) slot = &g;
   if (!slot) {

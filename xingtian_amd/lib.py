@@ -206,6 +206,7 @@ SIGNATURES = {
     "xt_net_last_head_path": (c_int32, [_P]),
     "xt_net_set_gauss_fused": (c_int32, [_P, c_int32]),
     "xt_net_set_fwd_fuse12_flat": (c_int32, [_P, c_int32]),
+    "xt_bwd_dense_lean_set": (c_int32, [c_int32]),      # (process-wide; returns the previous value)
     "xt_conv12_valid_fwd": (c_int32, [POINTER(ConvGeom), POINTER(InputXform), POINTER(ConvGeom), c_int32, _P, _P, _P, _P, _P,
                                       _P, _P, _P, _P, c_int32, _P]),
     "xt_net_set_impala_stats": (c_int32, [_P, _P, _P, c_int32]),
@@ -368,6 +369,16 @@ def set_tuning(**knobs):
         setattr(t, k, int(v))
     check(lib.xt_tuning_set(ctypes.byref(t)), "xt_tuning_set")
     return old
+
+
+def set_bwd_dense_lean(on=True):
+    """C ABI ``xt_bwd_dense_lean_set`` (process-wide, default on): the Dense instance of the fused backward launch without
+    its row table -- the same bits either way.  Returns the previous setting as a bool."""
+    lib = load()
+    prev = lib.xt_bwd_dense_lean_set(int(on))
+    if prev not in (0, 1):
+        raise RuntimeError("xt_bwd_dense_lean_set: " + lib.xt_last_error().decode())
+    return bool(prev)
 
 
 def step_report(handle):
