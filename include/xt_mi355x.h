@@ -1284,7 +1284,9 @@ int xt_net_set_dist(xt_net* net, int32_t atoms, double v_min, double v_max);
 /* The two head kernels of a marked net (on by default, re-armed by every xt_net_set_dist): heads_fwd_wide_kernel (one
  * thread per output column instead of one wave reduction per output) for every forward of the net, and in
  * xt_net_dqn_step_dist d(features) summed over the taken action's atoms only (bit-identical to the full sum).  on == 0:
- * the kernels of an unmarked net, for same-run comparisons.  Refused on an unmarked net. */
+ * the kernels of an unmarked net, for same-run comparisons; on == 2: the wide forward with heads_dfeat_kernel behind it, so
+ * that a run can time a mark's d(features) kernel against the generic one under the same forward.  Refused on an unmarked
+ * net. */
 int xt_net_set_dist_wide(xt_net* net, int32_t on);
 /* xt_net_dqn_step_n's chain (ns == NULL: one-step targets; per == NULL: uniform, `slots`) with xt_dqn_loss_dist as the
  * head, same launches in number.  Both nets must carry equal marks; cfg->dueling must be 0; actions <= 64; cfg->q_scratch
@@ -1339,6 +1341,47 @@ int xt_net_dqn_step_quant(xt_net* net, xt_net* target_net, const xt_dqn_cfg* cfg
                           const xt_per_cfg* per, const void* cur_ring, const void* next_ring, int64_t row_bytes,
                           int64_t capacity, int64_t size, const int32_t* slots, int32_t B, const int32_t* action,
                           const double* reward, const uint8_t* done, float* loss_out, float* loss_acc, void* stream);
+
+/* ------------------------------------------------------------------ dueling distributional heads (added under ABI 12; beside
+ * the two heads they extend: tests keep xt_net_graph_cache_info the last xt_net_ prototype of this header)
+ * A dueling network with a C51 or a quantile head (the architecture of Rainbow).  The state-value stream is folded into
+ * the Q head: rows are (A + 1) * N wide, column a * N + i (a < A) is the advantage of atom / quantile i of action a and
+ * group A, columns A * N + i, the state-value stream.  Definitions (host twins dist_dueling_combine /
+ * dist_dueling_combine_grad of xingtian_amd/model/dqn/dqn_cnn.py):
+ *     adv[a, i] = col[a N + i] (a < A);  v[i] = col[A N + i]
+ *     mean_i = (sum over ascending a of adv[a, i]) / (float)A                        float32, sequential
+ *     l[a, i] = v[i] + (adv[a, i] - mean_i)                                           float32
+ * Everything xt_dqn_loss_dist / xt_dqn_loss_quant read as logits[a, :] / quantiles[a, :] -- of the picking, the target and
+ * the online rows -- is l[a, :]; the projection, the losses, the terms and out are theirs.  With d_i = what those entries
+ * leave in dlogits[b, act * N + i] (w_b and / B included):
+ *     dcol[b, a N + i] = d_i * (hot(a == act) - inv_A), inv_A = 1.f / (float)A  (every a < A);  dcol[b, A N + i] = d_i
+ *     dvalue[b] = 0
+ * The kernels write the whole (A + 1) * N row; no atomics, no dependence on thread order.  The argument lists are those of
+ * the entries without _duel; A is the number of actions, logits / t_logits / o_logits / dlogits are [B, (A + 1) * N].
+ * Refused: what those entries refuse, with A outside [1, 63]. */
+int xt_dqn_loss_dist_duel(const float* logits, const float* t_logits, const float* o_logits, int32_t B, int32_t A,
+                          int32_t atoms, double v_min, double v_max, const int32_t* slots, const int32_t* action,
+                          const double* reward, const uint8_t* done, double gamma, float* dlogits, float* dvalue, float* out,
+                          int32_t* astar, float* maxq, float* m, float* acc, const double* weights, const double* disc,
+                          void* stream);
+int xt_dqn_loss_quant_duel(const float* logits, const float* t_logits, const float* o_logits, int32_t B, int32_t A,
+                           int32_t quantiles, double kappa, const int32_t* slots, const int32_t* action, const double* reward,
+                           const uint8_t* done, double gamma, float* dlogits, float* dvalue, float* out, int32_t* astar,
+                           float* maxq, float* acc, const double* weights, const double* disc, void* stream);
+/* Marks a net that carries the mark of xt_net_set_dist / xt_net_set_quant as dueling: the last of its width / N groups is
+ * the state-value stream.  xt_net_dqn_step_dist / _quant then run the _duel head on width / N - 1 actions and take
+ * d(features) from heads_dfeat_duel_kernel (with xt_net_set_dist_wide(net, 0): the generic forward and heads_dfeat_kernel,
+ * for same-run comparisons); the launches are those of the step without the mark in number.  Both nets of a step must
+ * carry the same mark; the dueling flag of xt_dqn_cfg stays refused on a marked net.  Clearing the distributional or
+ * quantile mark clears this one.  Refused: a net without such a mark, fewer than 2 groups, more than 63 actions. */
+int xt_net_set_duel(xt_net* net, int32_t on);
+/* heads_dfeat_duel_kernel stand-alone, for kernel tests and same-run timing: dfeat[b, f] = act'(feat[b, f]) * sum_i d_i *
+ * (wq[f, act N + i] + wq[f, A N + i] - inv_A * sum_a wq[f, a N + i]) with d_i = dlogits[b, A N + i], i.e. the product of a
+ * row the _duel heads left with the folded head's kernel wq [F, (A + 1) * N].  feat / dfeat [B, F]; the taken action is
+ * read through `slots` (may be NULL) and clamped into [0, A).  Refused: a null pointer, A outside [1, 63], N outside
+ * [1, 256]. */
+int xt_heads_dfeat_duel(const float* feat, int32_t B, int32_t F, int32_t A, int32_t N, const float* wq, const float* dlogits,
+                        const int32_t* slots, const int32_t* action, int32_t act_prev, float* dfeat, void* stream);
 
 /* ------------------------------------------------------------------ the step tail stand-alone (appended under ABI 12)
  * The gradient-reduction launch and the optimiser launches every xt_net_*_step ends in, on given buffers, for kernel

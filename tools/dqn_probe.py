@@ -1,7 +1,7 @@
 """Time of one ``DQN.train`` at breakout_dqn's shape, beside a Keras-IMPALA step of the same trunk.
 
     python tools/dqn_probe.py [--windows 5] [--trains 200] [--capacity 4096] [--atoms 51] [--quantiles 51] [--noisy]
-                              [--model DqnCnn] [--out profiles/dqn_step.md]
+                              [--dist-dueling] [--model DqnCnn] [--out profiles/dqn_step.md]
 
 Four things are timed at DqnCnn 84x84x4, A = 4, B = 32, each as a host clock around ``--trains`` calls that ends in a
 device synchronise, after a warm-up, in ``--windows`` windows taken in turn (so that drift of the box hits all alike):
@@ -20,6 +20,10 @@ device synchronise, after a warm-up, in ``--windows`` windows taken in turn (so 
 * with ``--quantiles N`` (0: none) the same arms for the quantile-regression train (``model_config.quantiles``,
   ``xt_net_dqn_step_quant``: the head is again 4 * N wide), so that ``--atoms N --quantiles N`` compares the two
   distributional heads at one width in one run;
+* with ``--dist-dueling`` (and ``--atoms`` / ``--quantiles``) the arms of each head once more for the dueling network
+  (``model_config.dist_dueling``: the head is 5 * N wide, ``xt_net_set_duel``), beside the non-dueling rows of the same
+  run, and a third kernel arm, "generic d(features)": the wide forward with ``heads_dfeat_kernel`` behind it
+  (``set_dist_wide("forward")``), which times ``heads_dfeat_duel_kernel`` against the generic kernel inside the same step;
 * with ``--noisy`` the train of a noisy pair (``model_config.noisy``: ``xt_noisy_compose`` on both nets in front of the step,
   ``xt_noisy_grads`` behind it) without and with ``double_dqn``, as ``DQN.train`` and enqueue only, beside the plain rows
   of the same run, and the three added launches alone (enqueue only);
@@ -54,7 +58,7 @@ def _states(rng, n):
     return rng.integers(0, 256, (n, DIM, DIM, 4), dtype=np.uint8)
 
 
-def build_dqn(double, capacity, per=False, n_step=1, atoms=1, quantiles=1, noisy=False):
+def build_dqn(double, capacity, per=False, n_step=1, atoms=1, quantiles=1, noisy=False, dist_dueling=False):
     from xingtian_amd.algorithm import alg_builder
     info = {"actor": {"model_name": MODEL["name"], "type": "learner",
                       "state_dim": [4] if MODEL["name"] == "DqnMlp" else [DIM, DIM, 4], "action_dim": A_DIM,
@@ -65,6 +69,8 @@ def build_dqn(double, capacity, per=False, n_step=1, atoms=1, quantiles=1, noisy
         info["actor"]["model_config"]["quantiles"] = quantiles
     if noisy:
         info["actor"]["model_config"]["noisy"] = True
+    if dist_dueling:
+        info["actor"]["model_config"]["dist_dueling"] = True
     cfg = {"instance_num": 1, "agent_num": 1, "prepare_times_per_train": 4, "BUFFER_SIZE": capacity, "BATCH_SIZE": B,
            "TARGET_UPDATE_FREQ": 1000, "double_dqn": double, "prioritized_replay": per}
     if n_step != 1:
@@ -87,6 +93,7 @@ def main():
     ap.add_argument("--atoms", type=int, default=0)
     ap.add_argument("--quantiles", type=int, default=0)
     ap.add_argument("--noisy", action="store_true")
+    ap.add_argument("--dist-dueling", action="store_true")
     ap.add_argument("--model", default="DqnCnn", choices=["DqnCnn", "DqnMlp"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -158,12 +165,15 @@ def main():
     if args.model == "DqnMlp":
         cases = cases[:-1]                                  # (the IMPALA row is the CNN trunk's)
     pos = 12                                                # the head arms go behind the twelve train rows
-    for key, count in (("atoms", args.atoms), ("quantiles", args.quantiles)):
+    heads = [(key, count, duel) for key, count in (("atoms", args.atoms), ("quantiles", args.quantiles))
+             for duel in ((False, True) if args.dist_dueling else (False,))]
+    for key, count, duel in heads:
         if count <= 1:
             continue
         # the distributional arms share ONE algorithm per (PER, n_step) -- double_dqn is an argument of the train and the
         # kernel selection a switch of the two nets -- so four more rings, not sixteen
-        dist = {(per, n): build_dqn(False, args.capacity, per, n, **{key: count}) for per in (False, True) for n in (1, 3)}
+        dist = {(per, n): build_dqn(False, args.capacity, per, n, dist_dueling=duel, **{key: count})
+                for per in (False, True) for n in (1, 3)}
         dist_slots = torch.tensor(dist[(False, 1)].buff.sample(B), dtype=torch.int32).cuda()
 
         def dist_case(per, n, double, wide, read_back, dist=dist, dist_slots=dist_slots):
@@ -181,12 +191,13 @@ def main():
             return fn
         extra = []
         for read_back in (True, False):
-            for wide in (True, False):
+            for wide in (True, "forward", False) if duel else (True, False):
                 for per, n, double in ((False, 1, False), (True, 1, False), (False, 3, False), (True, 3, False),
                                        (False, 1, True), (True, 1, True), (False, 3, True), (True, 3, True)):
-                    name = "{}, {} {}{}{}{}{}{}".format(
-                        "DQN.train" if read_back else "dqn step + adam", key, count, ", PER" if per else "",
-                        ", n_step 3" if n == 3 else "", ", double_dqn" if double else "", "" if wide else ", generic head kernels",
+                    name = "{}, {} {}{}{}{}{}{}{}".format(
+                        "DQN.train" if read_back else "dqn step + adam", key, count, ", dist_dueling" if duel else "",
+                        ", PER" if per else "", ", n_step 3" if n == 3 else "", ", double_dqn" if double else "",
+                        {True: "", "forward": ", generic d(features)", False: ", generic head kernels"}[wide],
                         " (loss read back)" if read_back else ", enqueue only")
                     extra.append((name, dist_case(per, n, double, wide, read_back)))
         cases = cases[:pos] + extra + cases[pos:]

@@ -44,6 +44,8 @@ knows about it.  The target sync copies the whole store, means and sigmas.
 
 Every variant reaches its C entry through the model's ``train_replay`` / ``train_replay_per`` and one method of the net,
 ``HipActorCritic.dqn_step``, whose keywords (``follow`` / ``n``, ``per``, ``dist``, ``quant``) choose the entry.
+``model_config.dist_dueling`` with either distributional head makes the network dueling (the value stream folded into the Q
+head, ``xt_net_set_duel``): the same two entries read the mark, and nothing changes here.
 """
 import random
 

@@ -226,12 +226,75 @@ __device__ __forceinline__ float dist_q_wave(const float* __restrict__ l, int N,
   return sz / se;
 }
 
+// ---- the dueling form of the two distributional heads (kDuel; DESIGN.md section 7, "Dueling distributional heads").
+// A row is (A + 1) * N wide: adv[a, i] = row[a N + i] (a < A), v[i] = row[A N + i], and everything the heads read as
+// "logits[a, i]" is l[a, i] = v[i] + (adv[a, i] - mean_i), mean_i = (sum over ascending a of adv[a, i]) / (float)A, as
+// dqn_mean / dqn_q.  A lane forms mean_i of its own columns i = lane + 64 k once per net it reads (A strided loads per i)
+// and combines on the fly: nothing of the A * N row is staged.
+__device__ __forceinline__ void duel_means(const float* __restrict__ row, int A, int N, int lane, float (&mean)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = lane + 64 * k;
+    mean[k] = 0.f;
+    if (i < N) {
+      float s = 0.f;
+      for (int a = 0; a < A; ++a) s += row[(size_t)a * N + i];
+      mean[k] = s / (float)A;
+    }
+  }
+}
+__device__ __forceinline__ float duel_at(const float* __restrict__ row, int A, int N, int a, int i, float mean) {
+  return row[(size_t)A * N + i] + (row[(size_t)a * N + i] - mean);
+}
+// dist_q_wave on the combined logits of action a of a dueling row (mean: the lane's duel_means of that row)
+__device__ __forceinline__ float dist_q_wave_duel(const float* __restrict__ row, int A, int N, int a, const float (&mean)[4],
+                                                  double v_min, double delta, int lane, float* mx_out, float* se_out) {
+  float l[4];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = lane + 64 * k;
+    l[k] = 0.f;
+    if (i < N) { l[k] = duel_at(row, A, N, a, i, mean[k]); mx = fmaxf(mx, l[k]); }
+  }
+  mx = dist_wave_max(mx);
+  float se = 0.f, sz = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = lane + 64 * k;
+    if (i < N) {
+      const float e = expf(l[k] - mx);
+      se += e;
+      sz += (float)dist_atom(v_min, delta, i) * e;
+    }
+  }
+  se = dist_wave_sum(se);
+  sz = dist_wave_sum(sz);
+  *mx_out = mx; *se_out = se;
+  return sz / se;
+}
+// the gradient row of a dueling head from d_i of the lane's columns: dcol[a N + i] = d_i (hot(a == act) - 1 / A) for every
+// a < A and dcol[A N + i] = d_i -- the whole (A + 1) * N row, each entry by the one lane that owns column i
+__device__ __forceinline__ void duel_store_grad(float* __restrict__ dl, int A, int N, int act, int lane, const float (&d)[4]) {
+  const float inv_a = 1.f / (float)A;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = lane + 64 * k;
+    if (i < N) {
+      for (int a = 0; a < A; ++a) dl[(size_t)a * N + i] = d[k] * ((a == act ? 1.f : 0.f) - inv_a);
+      dl[(size_t)A * N + i] = d[k];
+    }
+  }
+}
+
 // One wavefront per sample (grid B, 64 threads), lanes stride the atoms (up to 4 per lane at N = 256).  In order:
 // dist_q of every action of the picking logits (o_logits, else t_logits) and a* = the first maximal one; p_j = softmax of
 // the target logits of a* and b_j = (clamp(dn ? R : R + g z_j) - v_min) / delta into LDS as float64; every lane forms its
 // m_i = (float) sum_j p_j max(0, 1 - |b_j - i|) over ascending j (a gather: no atomics, no dependence on thread order);
 // then the log-softmax of the taken action's online logits, loss_b = -sum_i m_i logq_i, the gradient row
 // w_b (q_i M_b - m_i) / B with exact zeros in every other column, dvalue = 0 and terms[b] = (loss_b, dist_q_target(a*)).
+// kDuel: rows are (A + 1) * N wide and every logit read is the combined one (above); the gradient row is duel_store_grad's.
+template <bool kDuel>
 __global__ __launch_bounds__(64) void dqn_loss_dist_kernel(const float* __restrict__ logits, const float* __restrict__ t_logits,
                                                            const float* __restrict__ o_logits, int B, int A, int N,
                                                            double v_min, double v_max, const int32_t* __restrict__ slots,
@@ -247,39 +310,88 @@ __global__ __launch_bounds__(64) void dqn_loss_dist_kernel(const float* __restri
   const int b = blockIdx.x;
   if (b >= B) return;
   const double delta = (v_max - v_min) / (double)(N - 1);
-  const size_t W = (size_t)A * N;
+  const size_t W = (size_t)(kDuel ? A + 1 : A) * N;
   const long long row = slots ? (long long)slots[b] : (long long)b;
   const float* tl = t_logits + (size_t)b * W;
   const float* pl = o_logits ? o_logits + (size_t)b * W : tl;
+  float tmean[4], lo[4];                           // kDuel: the target row's means; the combined online logits
   float mx, se;
   int astar = 0;
-  float qb = dist_q_wave(pl, N, v_min, delta, lane, &mx, &se);
-  for (int a = 1; a < A; ++a) {
-    const float q = dist_q_wave(pl + (size_t)a * N, N, v_min, delta, lane, &mx, &se);
-    if (q > qb) { qb = q; astar = a; }
+  float qstar;
+  if constexpr (kDuel) {
+    float pmean[4];
+    duel_means(pl, A, N, lane, pmean);
+    float qb = dist_q_wave_duel(pl, A, N, 0, pmean, v_min, delta, lane, &mx, &se);
+    for (int a = 1; a < A; ++a) {
+      const float q = dist_q_wave_duel(pl, A, N, a, pmean, v_min, delta, lane, &mx, &se);
+      if (q > qb) { qb = q; astar = a; }
+    }
+    if (o_logits) {
+      duel_means(tl, A, N, lane, tmean);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) tmean[k] = pmean[k];
+    }
+    qstar = dist_q_wave_duel(tl, A, N, astar, tmean, v_min, delta, lane, &mx, &se);
+  } else {
+    float qb = dist_q_wave(pl, N, v_min, delta, lane, &mx, &se);
+    for (int a = 1; a < A; ++a) {
+      const float q = dist_q_wave(pl + (size_t)a * N, N, v_min, delta, lane, &mx, &se);
+      if (q > qb) { qb = q; astar = a; }
+    }
+    qstar = dist_q_wave(tl + (size_t)astar * N, N, v_min, delta, lane, &mx, &se);
   }
   // (the wave sums leave the same bits in every lane, so a* is uniform)
   const float* ts = tl + (size_t)astar * N;
-  const float qstar = dist_q_wave(ts, N, v_min, delta, lane, &mx, &se);
   const double R = reward[row];
   const double g = disc ? disc[b] : gamma;
   const bool dn = done[row] != 0;
-  for (int j = lane; j < N; j += 64) {
-    const double z = dist_atom(v_min, delta, j);
-    double tz = dn ? R : R + g * z;
-    tz = tz < v_min ? v_min : (tz > v_max ? v_max : tz);
-    s_p[j] = (double)(expf(ts[j] - mx) / se);
-    s_b[j] = (tz - v_min) / delta;
+  if constexpr (kDuel) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int j = lane + 64 * k;
+      if (j < N) {
+        const double z = dist_atom(v_min, delta, j);
+        double tz = dn ? R : R + g * z;
+        tz = tz < v_min ? v_min : (tz > v_max ? v_max : tz);
+        s_p[j] = (double)(expf(duel_at(tl, A, N, astar, j, tmean[k]) - mx) / se);
+        s_b[j] = (tz - v_min) / delta;
+      }
+    }
+  } else {
+    for (int j = lane; j < N; j += 64) {
+      const double z = dist_atom(v_min, delta, j);
+      double tz = dn ? R : R + g * z;
+      tz = tz < v_min ? v_min : (tz > v_max ? v_max : tz);
+      s_p[j] = (double)(expf(ts[j] - mx) / se);
+      s_b[j] = (tz - v_min) / delta;
+    }
   }
   __syncthreads();
   int act = action[row];
   act = act < 0 ? 0 : (act >= A ? A - 1 : act);    // (an action outside [0, A) never indexes outside the row)
   const float* l = logits + (size_t)b * W + (size_t)act * N;
   float lmx = -INFINITY;
-  for (int i = lane; i < N; i += 64) lmx = fmaxf(lmx, l[i]);
-  lmx = dist_wave_max(lmx);
   float lse = 0.f;
-  for (int i = lane; i < N; i += 64) lse += expf(l[i] - lmx);
+  if constexpr (kDuel) {
+    const float* lr = logits + (size_t)b * W;
+    float omean[4];
+    duel_means(lr, A, N, lane, omean);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = lane + 64 * k;
+      lo[k] = 0.f;
+      if (i < N) { lo[k] = duel_at(lr, A, N, act, i, omean[k]); lmx = fmaxf(lmx, lo[k]); }
+    }
+    lmx = dist_wave_max(lmx);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (lane + 64 * k < N) lse += expf(lo[k] - lmx);
+  } else {
+    for (int i = lane; i < N; i += 64) lmx = fmaxf(lmx, l[i]);
+    lmx = dist_wave_max(lmx);
+    for (int i = lane; i < N; i += 64) lse += expf(l[i] - lmx);
+  }
   lse = logf(dist_wave_sum(lse));
   float m[4], lq[4];
   float loss = 0.f, mass = 0.f;
@@ -295,7 +407,8 @@ __global__ __launch_bounds__(64) void dqn_loss_dist_kernel(const float* __restri
         s += s_p[j] * (w > 0.0 ? w : 0.0);
       }
       m[k] = (float)s;
-      lq[k] = (l[i] - lmx) - lse;
+      if constexpr (kDuel) lq[k] = (lo[k] - lmx) - lse;
+      else lq[k] = (l[i] - lmx) - lse;
       loss += m[k] * lq[k];
       mass += m[k];
       if (m_out) m_out[(size_t)b * N + i] = m[k];
@@ -305,15 +418,28 @@ __global__ __launch_bounds__(64) void dqn_loss_dist_kernel(const float* __restri
   mass = dist_wave_sum(mass);
   const float fb = (float)B;
   float* dl = dlogits + (size_t)b * W;
-  const size_t c0 = (size_t)act * N;
-  for (size_t c = lane; c < W; c += 64)
-    if (c < c0 || c >= c0 + N) dl[c] = 0.f;
+  if constexpr (kDuel) {
+    float dd[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int i = lane + 64 * k;
-    if (i < N) {
-      const float d = expf(lq[k]) * mass - m[k];
-      dl[c0 + i] = (weights ? (float)weights[b] * d : d) / fb;
+    for (int k = 0; k < 4; ++k) {
+      dd[k] = 0.f;
+      if (lane + 64 * k < N) {
+        const float d = expf(lq[k]) * mass - m[k];
+        dd[k] = (weights ? (float)weights[b] * d : d) / fb;
+      }
+    }
+    duel_store_grad(dl, A, N, act, lane, dd);
+  } else {
+    const size_t c0 = (size_t)act * N;
+    for (size_t c = lane; c < W; c += 64)
+      if (c < c0 || c >= c0 + N) dl[c] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = lane + 64 * k;
+      if (i < N) {
+        const float d = expf(lq[k]) * mass - m[k];
+        dl[c0 + i] = (weights ? (float)weights[b] * d : d) / fb;
+      }
     }
   }
   if (lane == 0) {
@@ -338,6 +464,23 @@ __device__ __forceinline__ float quant_q_of(const float* __restrict__ th, int N)
 // quantiles of a* go into LDS; every lane forms r_i and g_i of its quantiles of the taken action by the float64 sum over
 // ascending j (LDS broadcasts: no atomics, no dependence on thread order); loss_b = sum_i r_i by a wave reduction; then
 // the gradient row w_b g_i / B with exact zeros in every other column, dvalue = 0 and terms[b] = (loss_b, quant_q_target(a*)).
+// kDuel: rows are (A + 1) * N wide and every quantile read is the combined one (above dqn_loss_dist_kernel).  quant_q stays
+// one thread's float64 sum over ascending i, so the lanes leave the mean_i they formed (N floats per net read, not the
+// A * N row) in LDS, where the thread that sums action a finds them; the gradient row is duel_store_grad's.
+// quant_q of the combined quantiles of action a of a dueling row by one thread (mean: the row's N means)
+__device__ __forceinline__ float quant_q_duel(const float* __restrict__ row, int A, int N, int a, const float* mean) {
+  double s = 0.0;
+  for (int i = 0; i < N; ++i) s += (double)duel_at(row, A, N, a, i, mean[i]);
+  return (float)(s / (double)N);
+}
+__device__ __forceinline__ void duel_means_lds(const float* __restrict__ row, int A, int N, int lane, float* s_mean) {
+  float mean[4];
+  duel_means(row, A, N, lane, mean);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (lane + 64 * k < N) s_mean[lane + 64 * k] = mean[k];
+}
+template <bool kDuel>
 __global__ __launch_bounds__(64) void dqn_loss_quant_kernel(const float* __restrict__ logits, const float* __restrict__ t_logits,
                                                             const float* __restrict__ o_logits, int B, int A, int N,
                                                             float kappa, const int32_t* __restrict__ slots,
@@ -352,12 +495,22 @@ __global__ __launch_bounds__(64) void dqn_loss_quant_kernel(const float* __restr
   const int lane = threadIdx.x;
   const int b = blockIdx.x;
   if (b >= B) return;
-  const size_t W = (size_t)A * N;
+  __shared__ float s_mean[kDuel ? 3 : 1][kDuel ? 256 : 1];   // kDuel: mean_i of the picking, the target and the online row
+  const size_t W = (size_t)(kDuel ? A + 1 : A) * N;
   const long long row = slots ? (long long)slots[b] : (long long)b;
   const float* tl = t_logits + (size_t)b * W;
   const float* pl = o_logits ? o_logits + (size_t)b * W : tl;
+  const float* tmean = s_mean[0];
+  if constexpr (kDuel) {
+    duel_means_lds(pl, A, N, lane, s_mean[0]);
+    if (o_logits) { duel_means_lds(tl, A, N, lane, s_mean[1]); tmean = s_mean[1]; }
+    duel_means_lds(logits + (size_t)b * W, A, N, lane, s_mean[2]);
+    __syncthreads();
+  }
   // (A <= 64: one action per lane; a lane without one holds -inf under an index no action has)
-  float q = lane < A ? quant_q_of(pl + (size_t)lane * N, N) : -INFINITY;
+  float q;
+  if constexpr (kDuel) q = lane < A ? quant_q_duel(pl, A, N, lane, s_mean[0]) : -INFINITY;
+  else q = lane < A ? quant_q_of(pl + (size_t)lane * N, N) : -INFINITY;
   float qb = q;
   int astar = lane;
 #pragma unroll
@@ -369,11 +522,18 @@ __global__ __launch_bounds__(64) void dqn_loss_quant_kernel(const float* __restr
   astar = __shfl(astar, 0, 64);                    // (uniform whatever the quantiles hold)
   astar = astar < A ? astar : A - 1;
   const float* ts = tl + (size_t)astar * N;
-  const float qstar = o_logits ? quant_q_of(ts, N) : __shfl(q, astar, 64);
+  float qstar;
+  if constexpr (kDuel) qstar = o_logits ? quant_q_duel(tl, A, N, astar, tmean) : __shfl(q, astar, 64);
+  else qstar = o_logits ? quant_q_of(ts, N) : __shfl(q, astar, 64);
   const double R = reward[row];
   const double g = disc ? disc[b] : gamma;
   const bool dn = done[row] != 0;
-  for (int j = lane; j < N; j += 64) s_t[j] = dn ? (float)R : (float)(R + g * (double)ts[j]);
+  for (int j = lane; j < N; j += 64) {
+    float tj;
+    if constexpr (kDuel) tj = duel_at(tl, A, N, astar, j, tmean[j]);
+    else tj = ts[j];
+    s_t[j] = dn ? (float)R : (float)(R + g * (double)tj);
+  }
   __syncthreads();
   int act = action[row];
   act = act < 0 ? 0 : (act >= A ? A - 1 : act);    // (an action outside [0, A) never indexes outside the row)
@@ -386,7 +546,9 @@ __global__ __launch_bounds__(64) void dqn_loss_quant_kernel(const float* __restr
     const int i = lane + 64 * k;
     gr[k] = 0.f;
     if (i < N) {
-      const float th = l[i];
+      float th;
+      if constexpr (kDuel) th = duel_at(logits + (size_t)b * W, A, N, act, i, s_mean[2][i]);
+      else th = l[i];
       const double tau = (double)(2 * i + 1) / (2.0 * dN);
       const float w_neg = (float)(1.0 - tau), w_pos = (float)tau;
       double sr = 0.0, sg = 0.0;
@@ -406,13 +568,20 @@ __global__ __launch_bounds__(64) void dqn_loss_quant_kernel(const float* __restr
   loss = dist_wave_sum(loss);
   const float fb = (float)B;
   float* dl = dlogits + (size_t)b * W;
-  const size_t c0 = (size_t)act * N;
-  for (size_t c = lane; c < W; c += 64)
-    if (c < c0 || c >= c0 + N) dl[c] = 0.f;
+  if constexpr (kDuel) {
+    float dd[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int i = lane + 64 * k;
-    if (i < N) dl[c0 + i] = (weights ? (float)weights[b] * gr[k] : gr[k]) / fb;
+    for (int k = 0; k < 4; ++k) dd[k] = lane + 64 * k < N ? (weights ? (float)weights[b] * gr[k] : gr[k]) / fb : 0.f;
+    duel_store_grad(dl, A, N, act, lane, dd);
+  } else {
+    const size_t c0 = (size_t)act * N;
+    for (size_t c = lane; c < W; c += 64)
+      if (c < c0 || c >= c0 + N) dl[c] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = lane + 64 * k;
+      if (i < N) dl[c0 + i] = (weights ? (float)weights[b] * gr[k] : gr[k]) / fb;
+    }
   }
   if (lane == 0) {
     dvalue[b] = 0.f;
@@ -435,6 +604,61 @@ static int replay_gather_check(const char* who, const void* ring, const void* ds
   return 0;
 }
 
+// xt_dqn_loss_dist / xt_dqn_loss_dist_duel: the checks and the two launches (`who` names the entry in refusals).  duel: A
+// actions on rows (A + 1) * atoms wide, so at most 63 of them (the folded head keeps the step's 64-group limit).
+static int dqn_loss_dist_entry(const char* who, bool duel, const float* logits, const float* t_logits, const float* o_logits,
+                               int32_t B, int32_t A, int32_t atoms, double v_min, double v_max, const int32_t* slots,
+                               const int32_t* action, const double* reward, const uint8_t* done, double gamma, float* dlogits,
+                               float* dvalue, float* out, int32_t* astar, float* maxq, float* m, float* acc,
+                               const double* weights, const double* disc, void* stream) {
+  const int amax = duel ? 63 : 64;
+  XT_REQUIRE(logits && t_logits && action && reward && done && dlogits && dvalue && out, "%s: null argument", who);
+  XT_REQUIRE(atoms >= 2 && atoms <= 256, "%s: atoms = %d outside [2, 256]", who, atoms);
+  XT_REQUIRE(B > 0 && A >= 1 && A <= amax, "%s: bad sizes (B=%d A=%d; 1 <= A <= %d)", who, B, A, amax);
+  XT_REQUIRE(std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max,
+             "%s: the support needs finite v_min < v_max (got %g, %g)", who, v_min, v_max);
+  XT_REQUIRE(((uintptr_t)out & 7) == 0, "%s: out must be 8-byte aligned", who);
+  hipStream_t st = as_stream(stream);
+  float2* terms = reinterpret_cast<float2*>(out + 4);       // out: >= 4 + 2*B floats
+  if (duel)
+    hipLaunchKernelGGL(dqn_loss_dist_kernel<true>, dim3(B), dim3(64), 0, st, logits, t_logits, o_logits, B, A, atoms, v_min,
+                       v_max, slots, action, reward, done, gamma, dlogits, dvalue, terms, astar, maxq, m, weights, disc);
+  else
+    hipLaunchKernelGGL(dqn_loss_dist_kernel<false>, dim3(B), dim3(64), 0, st, logits, t_logits, o_logits, B, A, atoms, v_min,
+                       v_max, slots, action, reward, done, gamma, dlogits, dvalue, terms, astar, maxq, m, weights, disc);
+  XT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(dqn_loss_reduce_kernel<true>, dim3(1), dim3(256), 0, st, terms, B, A, out, acc, weights);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+
+// xt_dqn_loss_quant / xt_dqn_loss_quant_duel, likewise
+static int dqn_loss_quant_entry(const char* who, bool duel, const float* logits, const float* t_logits, const float* o_logits,
+                                int32_t B, int32_t A, int32_t quantiles, double kappa, const int32_t* slots,
+                                const int32_t* action, const double* reward, const uint8_t* done, double gamma, float* dlogits,
+                                float* dvalue, float* out, int32_t* astar, float* maxq, float* acc, const double* weights,
+                                const double* disc, void* stream) {
+  const int amax = duel ? 63 : 64;
+  XT_REQUIRE(logits && t_logits && action && reward && done && dlogits && dvalue && out, "%s: null argument", who);
+  XT_REQUIRE(quantiles >= 2 && quantiles <= 256, "%s: quantiles = %d outside [2, 256]", who, quantiles);
+  XT_REQUIRE(B > 0 && A >= 1 && A <= amax, "%s: bad sizes (B=%d A=%d; 1 <= A <= %d)", who, B, A, amax);
+  XT_REQUIRE(std::isfinite(kappa) && (float)kappa > 0.f && std::isfinite((float)kappa),
+             "%s: kappa must be finite and > 0 as a float32 (got %g)", who, kappa);
+  XT_REQUIRE(((uintptr_t)out & 7) == 0, "%s: out must be 8-byte aligned", who);
+  hipStream_t st = as_stream(stream);
+  float2* terms = reinterpret_cast<float2*>(out + 4);       // out: >= 4 + 2*B floats
+  if (duel)
+    hipLaunchKernelGGL(dqn_loss_quant_kernel<true>, dim3(B), dim3(64), 0, st, logits, t_logits, o_logits, B, A, quantiles,
+                       (float)kappa, slots, action, reward, done, gamma, dlogits, dvalue, terms, astar, maxq, weights, disc);
+  else
+    hipLaunchKernelGGL(dqn_loss_quant_kernel<false>, dim3(B), dim3(64), 0, st, logits, t_logits, o_logits, B, A, quantiles,
+                       (float)kappa, slots, action, reward, done, gamma, dlogits, dvalue, terms, astar, maxq, weights, disc);
+  XT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(dqn_loss_reduce_kernel<true>, dim3(1), dim3(256), 0, st, terms, B, A, out, acc, weights);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace xt
 
 extern "C" {
@@ -443,40 +667,33 @@ int xt_dqn_loss_dist(const float* logits, const float* t_logits, const float* o_
                      double v_min, double v_max, const int32_t* slots, const int32_t* action, const double* reward,
                      const uint8_t* done, double gamma, float* dlogits, float* dvalue, float* out, int32_t* astar,
                      float* maxq, float* m, float* acc, const double* weights, const double* disc, void* stream) {
-  XT_REQUIRE(logits && t_logits && action && reward && done && dlogits && dvalue && out, "xt_dqn_loss_dist: null argument");
-  XT_REQUIRE(atoms >= 2 && atoms <= 256, "xt_dqn_loss_dist: atoms = %d outside [2, 256]", atoms);
-  XT_REQUIRE(B > 0 && A >= 1 && A <= 64, "xt_dqn_loss_dist: bad sizes (B=%d A=%d; 1 <= A <= 64)", B, A);
-  XT_REQUIRE(std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max,
-             "xt_dqn_loss_dist: the support needs finite v_min < v_max (got %g, %g)", v_min, v_max);
-  XT_REQUIRE(((uintptr_t)out & 7) == 0, "xt_dqn_loss_dist: out must be 8-byte aligned");
-  hipStream_t st = xt::as_stream(stream);
-  float2* terms = reinterpret_cast<float2*>(out + 4);       // out: >= 4 + 2*B floats
-  hipLaunchKernelGGL(xt::dqn_loss_dist_kernel, dim3(B), dim3(64), 0, st, logits, t_logits, o_logits, B, A, atoms, v_min, v_max,
-                     slots, action, reward, done, gamma, dlogits, dvalue, terms, astar, maxq, m, weights, disc);
-  XT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(xt::dqn_loss_reduce_kernel<true>, dim3(1), dim3(256), 0, st, terms, B, A, out, acc, weights);
-  XT_LAUNCH_CHECK();
-  return 0;
+  return xt::dqn_loss_dist_entry("xt_dqn_loss_dist", false, logits, t_logits, o_logits, B, A, atoms, v_min, v_max, slots, action,
+                                 reward, done, gamma, dlogits, dvalue, out, astar, maxq, m, acc, weights, disc, stream);
+}
+
+int xt_dqn_loss_dist_duel(const float* logits, const float* t_logits, const float* o_logits, int32_t B, int32_t A,
+                          int32_t atoms, double v_min, double v_max, const int32_t* slots, const int32_t* action,
+                          const double* reward, const uint8_t* done, double gamma, float* dlogits, float* dvalue, float* out,
+                          int32_t* astar, float* maxq, float* m, float* acc, const double* weights, const double* disc,
+                          void* stream) {
+  return xt::dqn_loss_dist_entry("xt_dqn_loss_dist_duel", true, logits, t_logits, o_logits, B, A, atoms, v_min, v_max, slots,
+                                 action, reward, done, gamma, dlogits, dvalue, out, astar, maxq, m, acc, weights, disc, stream);
 }
 
 int xt_dqn_loss_quant(const float* logits, const float* t_logits, const float* o_logits, int32_t B, int32_t A,
                       int32_t quantiles, double kappa, const int32_t* slots, const int32_t* action, const double* reward,
                       const uint8_t* done, double gamma, float* dlogits, float* dvalue, float* out, int32_t* astar, float* maxq,
                       float* acc, const double* weights, const double* disc, void* stream) {
-  XT_REQUIRE(logits && t_logits && action && reward && done && dlogits && dvalue && out, "xt_dqn_loss_quant: null argument");
-  XT_REQUIRE(quantiles >= 2 && quantiles <= 256, "xt_dqn_loss_quant: quantiles = %d outside [2, 256]", quantiles);
-  XT_REQUIRE(B > 0 && A >= 1 && A <= 64, "xt_dqn_loss_quant: bad sizes (B=%d A=%d; 1 <= A <= 64)", B, A);
-  XT_REQUIRE(std::isfinite(kappa) && (float)kappa > 0.f && std::isfinite((float)kappa),
-             "xt_dqn_loss_quant: kappa must be finite and > 0 as a float32 (got %g)", kappa);
-  XT_REQUIRE(((uintptr_t)out & 7) == 0, "xt_dqn_loss_quant: out must be 8-byte aligned");
-  hipStream_t st = xt::as_stream(stream);
-  float2* terms = reinterpret_cast<float2*>(out + 4);       // out: >= 4 + 2*B floats
-  hipLaunchKernelGGL(xt::dqn_loss_quant_kernel, dim3(B), dim3(64), 0, st, logits, t_logits, o_logits, B, A, quantiles,
-                     (float)kappa, slots, action, reward, done, gamma, dlogits, dvalue, terms, astar, maxq, weights, disc);
-  XT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(xt::dqn_loss_reduce_kernel<true>, dim3(1), dim3(256), 0, st, terms, B, A, out, acc, weights);
-  XT_LAUNCH_CHECK();
-  return 0;
+  return xt::dqn_loss_quant_entry("xt_dqn_loss_quant", false, logits, t_logits, o_logits, B, A, quantiles, kappa, slots, action,
+                                  reward, done, gamma, dlogits, dvalue, out, astar, maxq, acc, weights, disc, stream);
+}
+
+int xt_dqn_loss_quant_duel(const float* logits, const float* t_logits, const float* o_logits, int32_t B, int32_t A,
+                           int32_t quantiles, double kappa, const int32_t* slots, const int32_t* action, const double* reward,
+                           const uint8_t* done, double gamma, float* dlogits, float* dvalue, float* out, int32_t* astar,
+                           float* maxq, float* acc, const double* weights, const double* disc, void* stream) {
+  return xt::dqn_loss_quant_entry("xt_dqn_loss_quant_duel", true, logits, t_logits, o_logits, B, A, quantiles, kappa, slots,
+                                  action, reward, done, gamma, dlogits, dvalue, out, astar, maxq, acc, weights, disc, stream);
 }
 
 int xt_replay_gather(const void* ring, int64_t row_bytes, int64_t capacity, const int32_t* slots, int32_t B, void* dst,

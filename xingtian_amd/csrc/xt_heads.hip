@@ -420,6 +420,62 @@ __global__ __launch_bounds__(256) void heads_dfeat_dist_kernel(const float* __re
   df_pi[e] = (s + sv) * act_grad(f_pi[e], act_prev);
 }
 
+// heads_dfeat_kernel (shared trunk) behind a dueling distributional head (xt_net_set_duel), whose gradient row is dense but
+// structured: with d_i = dlogits[b, A N + i] (the value group), column a N + i holds d_i (hot(a == act) - 1 / A), so
+//   df[b, f] = sum_i d_i (w[f, act, i] + c[f, i]),   c[f, i] = w[f, A, i] - (1 / A) sum_a w[f, a, i].
+// A workgroup owns kDuelTile features: wave t forms c of feature t once (lanes stride i, coalesced) and leaves it in LDS;
+// then the waves split the samples, and each reads d_i once for the tile's features.  The weights are read once per launch
+// for c and N of them per (sample, feature) behind it, instead of (A + 1) N.  Sums are wave butterflies: a fixed order.
+// W = (A + 1) * N is the row's width; N <= 256.  The taken action is read as the loss kernels read it.
+constexpr int kDuelTile = 4;
+__global__ __launch_bounds__(256) void heads_dfeat_duel_kernel(const float* __restrict__ f_pi, int B, int F, int W, int N,
+                                                               const float* __restrict__ wpi,
+                                                               const float* __restrict__ dlogits,
+                                                               const int32_t* __restrict__ slots,
+                                                               const int32_t* __restrict__ action, int act_prev,
+                                                               float* __restrict__ df_pi) {
+  __shared__ float s_c[kDuelTile][256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int A = W / N - 1;
+  const int f0 = blockIdx.x * kDuelTile;
+  const float inv_a = 1.f / (float)A;
+  if (f0 + wave < F) {
+    const float* w = wpi + (size_t)(f0 + wave) * W;
+    for (int i = lane; i < N; i += 64) {
+      float s = 0.f;
+      for (int a = 0; a < A; ++a) s += w[(size_t)a * N + i];
+      s_c[wave][i] = w[(size_t)A * N + i] - inv_a * s;
+    }
+  }
+  __syncthreads();
+  float c[kDuelTile][4];
+#pragma unroll
+  for (int t = 0; t < kDuelTile; ++t)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[t][k] = (f0 + t < F && lane + 64 * k < N) ? s_c[t][lane + 64 * k] : 0.f;
+  for (int b = wave; b < B; b += 4) {
+    int act = action[slots ? (long long)slots[b] : (long long)b];
+    act = act < 0 ? 0 : (act >= A ? A - 1 : act);
+    const float* dv = dlogits + (size_t)b * W + (size_t)A * N;
+    float d[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = lane + 64 * k < N ? dv[lane + 64 * k] : 0.f;
+#pragma unroll
+    for (int t = 0; t < kDuelTile; ++t) {
+      const int f = f0 + t;
+      if (f >= F) break;
+      const float* w = wpi + (size_t)f * W + (size_t)act * N;
+      float s = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (lane + 64 * k < N) s = fmaf(d[k], w[lane + 64 * k] + c[t][k], s);
+      s = wave_sum(s);
+      const size_t e = (size_t)b * F + f;
+      if (lane == 0) df_pi[e] = s * act_grad(f_pi[e], act_prev);
+    }
+  }
+}
+
 // head weight gradients: block = 64 features x 4 batch groups; outputs in chunks of 8
 __global__ __launch_bounds__(256) void heads_wgrad_kernel(const float* __restrict__ f_pi, const float* __restrict__ f_v,
                                                           int B, int F, int A, const float* __restrict__ dlogits,
@@ -913,6 +969,15 @@ int launch_heads_dfeat_dist(const float* f_pi, int B, int F, int A, int N, const
   XT_REQUIRE(N >= 1 && A % N == 0 && action, "heads_dfeat_dist: bad arguments (A=%d N=%d)", A, N);
   hipLaunchKernelGGL(heads_dfeat_dist_kernel, dim3((B * F + 255) / 256), dim3(256), 0, st, f_pi, B, F, A, N, wpi, wv, dlogits,
                      dvalue, slots, action, act_prev, df_pi);
+  XT_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_heads_dfeat_duel(const float* f_pi, int B, int F, int A, int N, const float* wpi, const float* dlogits,
+                            const int32_t* slots, const int32_t* action, int act_prev, float* df_pi, hipStream_t st) {
+  XT_REQUIRE(N >= 1 && N <= 256 && A % N == 0 && A / N >= 2 && action, "heads_dfeat_duel: bad arguments (A=%d N=%d)", A, N);
+  hipLaunchKernelGGL(heads_dfeat_duel_kernel, dim3((F + kDuelTile - 1) / kDuelTile), dim3(256), 0, st, f_pi, B, F, A, N, wpi,
+                     dlogits, slots, action, act_prev, df_pi);
   XT_LAUNCH_CHECK();
   return 0;
 }
@@ -1894,6 +1959,15 @@ int xt_heads_bwd(const float* f_pi, const float* f_v, int32_t B, int32_t F, int3
                      dwpi, dbpi, dwv, dbv);
   XT_LAUNCH_CHECK();
   return 0;
+}
+
+int xt_heads_dfeat_duel(const float* feat, int32_t B, int32_t F, int32_t A, int32_t N, const float* wq, const float* dlogits,
+                        const int32_t* slots, const int32_t* action, int32_t act_prev, float* dfeat, void* stream) {
+  XT_REQUIRE(feat && wq && dlogits && action && dfeat, "xt_heads_dfeat_duel: null argument");
+  XT_REQUIRE(B > 0 && F > 0 && A >= 1 && A <= 63 && N >= 1 && N <= 256,
+             "xt_heads_dfeat_duel: bad sizes (B=%d F=%d A=%d N=%d; 1 <= A <= 63, 1 <= N <= 256)", B, F, A, N);
+  return xt::launch_heads_dfeat_duel(feat, B, F, (A + 1) * N, N, wq, dlogits, slots, action, act_prev, dfeat,
+                                     xt::as_stream(stream));
 }
 
 int xt_adv_normalize_f64(double* adv, int64_t n, double eps, double* stats, void* stream) {

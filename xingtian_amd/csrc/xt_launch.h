@@ -141,6 +141,9 @@ int launch_heads_fwd_wide(const float* feat, int B, int F, int A, const float* w
 int launch_heads_dfeat_dist(const float* f_pi, int B, int F, int A, int N, const float* wpi, const float* wv,
                             const float* dlogits, const float* dvalue, const int32_t* slots, const int32_t* action,
                             int act_prev, float* df_pi, hipStream_t st);
+// (A: the folded row's width (actions + 1) * N)
+int launch_heads_dfeat_duel(const float* f_pi, int B, int F, int A, int N, const float* wpi, const float* dlogits,
+                            const int32_t* slots, const int32_t* action, int act_prev, float* df_pi, hipStream_t st);
 int launch_heads_wgrad_partial(const float* f_pi, const float* f_v, int B, int F, int A, const float* dlogits,
                                const float* dvalue, float* slab_pi, long long stride_pi, float* slab_v,
                                long long stride_v, int* nchunk_out, hipStream_t st);

@@ -148,7 +148,9 @@ struct xt_net {
   int head_kind = XT_HEAD_SCALAR;
   double dist_vmin = 0.0, dist_vmax = 0.0;
   double quant_kappa = 0.0;
-  int dist_wide = 0;                  // xt_net_set_dist_wide: the wide-head forward and the taken-action d(features)
+  int dist_wide = 0;                  // xt_net_set_dist_wide: 1 the wide-head forward and the mark's own d(features) kernel;
+                                      // 2 the wide forward alone; 0 the kernels of an unmarked net
+  int head_duel = 0;                  // xt_net_set_duel: the head's last group of head_group columns is the state-value stream
   // xt_net_last_step_report: what the most recent forward / backward / tail decided (host words, read by nothing else)
   int last_fuse12 = 0, last_fuse21 = 0, last_tail_mode = 0, last_finish_form = -1;
   // xt_net_set_impala_stats: the caller's running sums and per-trajectory rows [itraj_max][XT_IMPALA_TRAJ_STATS_FLOATS] (both
@@ -240,7 +242,11 @@ static int heads_forward(xt_net* n, int B, hipStream_t st) {
 static int heads_dfeat(xt_net* n, int B, hipStream_t st, const int32_t* dist_slots = nullptr,
                        const int32_t* dist_action = nullptr) {
   const Heads h = heads_of(n);
-  if (dist_action && n->head_group && n->dist_wide && h.fd_pi == h.fd_v)
+  // (a dueling row is dense: its own kernel, or with dist_wide off the generic one below, which is right on any row)
+  if (dist_action && n->head_group && n->head_duel && n->dist_wide == 1 && h.fd_pi == h.fd_v)
+    return launch_heads_dfeat_duel(h.fd_pi, B, h.F, h.A, n->head_group, h.wpi, n->ws + n->off_dlogits, dist_slots,
+                                   dist_action, h.Lp->g.act, n->ws + h.Lp->dact_off, st);
+  if (dist_action && n->head_group && !n->head_duel && n->dist_wide == 1 && h.fd_pi == h.fd_v)
     return launch_heads_dfeat_dist(h.fd_pi, B, h.F, h.A, n->head_group, h.wpi, h.wv, n->ws + n->off_dlogits,
                                    n->ws + n->off_dvalue, dist_slots, dist_action, h.Lp->g.act, n->ws + h.Lp->dact_off, st);
   return launch_heads_dfeat(h.fd_pi, h.fd_v, B, h.F, h.A, h.wpi, h.wv, n->ws + n->off_dlogits, n->ws + n->off_dvalue,
@@ -1908,6 +1914,13 @@ static int dqn_chain(xt_net* n, xt_net* tn, const dqn_args& a) {
     atoms = n->head_group;
     XT_REQUIRE(!c->dueling, "%s: no dueling stream with a quantile head (it would have to be %d wide)", a.who, atoms);
   }
+  // the mark of xt_net_set_duel: the head's last group is the state-value stream, so one group fewer are actions
+  const bool duel = a.head != XT_HEAD_SCALAR && n->head_duel;
+  XT_REQUIRE(a.head == XT_HEAD_SCALAR || n->head_duel == tn->head_duel,
+             "%s: both nets must carry the same dueling mark (xt_net_set_duel: net %d, target_net %d)", a.who, n->head_duel,
+             tn->head_duel);
+  XT_REQUIRE(!duel || n->A / atoms - 1 <= 63, "%s: a dueling head of %d actions exceeds 63 (xt_net_set_duel)", a.who,
+             n->A / atoms - 1);
   XT_REQUIRE(n->A / atoms <= 64, "%s: A = %d exceeds 64", a.who, n->A / atoms);
   XT_REQUIRE(a.B > 0 && a.B <= n->maxB && a.B <= tn->maxB, "%s: batch %d outside (0,%d]", a.who, a.B,
              n->maxB < tn->maxB ? n->maxB : tn->maxB);
@@ -1962,10 +1975,16 @@ static int dqn_chain(xt_net* n, xt_net* tn, const dqn_args& a) {
   const double* l_disc = ns ? ns->disc_n : nullptr;
   const bool grouped = a.head != XT_HEAD_SCALAR;
   if (a.head == XT_HEAD_QUANT) {
-    if (int rc = xt_dqn_loss_quant(n->ws + n->off_logits, t_logits, o_logits, a.B, A / atoms, atoms, n->quant_kappa, l_slots,
-                                   l_action, l_reward, l_done, c->gamma, n->ws + n->off_dlogits, n->ws + n->off_dvalue, lo,
-                                   reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB, a.loss_acc, weights, l_disc,
-                                   a.stream))
+    if (int rc = (duel ? xt_dqn_loss_quant_duel : xt_dqn_loss_quant)(
+            n->ws + n->off_logits, t_logits, o_logits, a.B, A / atoms - (duel ? 1 : 0), atoms, n->quant_kappa, l_slots,
+            l_action, l_reward, l_done, c->gamma, n->ws + n->off_dlogits, n->ws + n->off_dvalue, lo,
+            reinterpret_cast<int32_t*>(rows + n->maxB), rows + 2 * n->maxB, a.loss_acc, weights, l_disc, a.stream))
+      return rc;
+  } else if (a.head == XT_HEAD_C51 && duel) {
+    if (int rc = xt_dqn_loss_dist_duel(n->ws + n->off_logits, t_logits, o_logits, a.B, A / atoms - 1, atoms, n->dist_vmin,
+                                       n->dist_vmax, l_slots, l_action, l_reward, l_done, c->gamma, n->ws + n->off_dlogits,
+                                       n->ws + n->off_dvalue, lo, reinterpret_cast<int32_t*>(rows + n->maxB),
+                                       rows + 2 * n->maxB, nullptr, a.loss_acc, weights, l_disc, a.stream))
       return rc;
   } else if (a.head == XT_HEAD_C51) {
     if (int rc = xt_dqn_loss_dist(n->ws + n->off_logits, t_logits, o_logits, a.B, A / atoms, atoms, n->dist_vmin, n->dist_vmax,
@@ -2050,7 +2069,7 @@ int xt_net_set_quant(xt_net* net, int32_t quantiles, double kappa) {
   XT_REQUIRE(net->head_kind != XT_HEAD_C51,
              "xt_net_set_quant: the net is marked distributional (xt_net_set_dist): a net carries one mark, clear that one first");
   if (quantiles == 1) {
-    net->head_group = 0; net->head_kind = XT_HEAD_SCALAR; net->quant_kappa = 0.0; net->dist_wide = 0;
+    net->head_group = 0; net->head_kind = XT_HEAD_SCALAR; net->quant_kappa = 0.0; net->dist_wide = 0; net->head_duel = 0;
     return 0;
   }
   XT_REQUIRE(quantiles >= 2 && quantiles <= 256, "xt_net_set_quant: quantiles = %d outside [1, 256]", quantiles);
@@ -2069,6 +2088,7 @@ int xt_net_set_dist(xt_net* net, int32_t atoms, double v_min, double v_max) {
              "xt_net_set_dist: the net is marked quantile (xt_net_set_quant): a net carries one mark, clear that one first");
   if (atoms == 1) {
     net->head_group = 0; net->head_kind = XT_HEAD_SCALAR; net->dist_vmin = net->dist_vmax = 0.0; net->dist_wide = 0;
+    net->head_duel = 0;
     return 0;
   }
   XT_REQUIRE(atoms >= 2 && atoms <= 256, "xt_net_set_dist: atoms = %d outside [1, 256]", atoms);
@@ -2080,11 +2100,24 @@ int xt_net_set_dist(xt_net* net, int32_t atoms, double v_min, double v_max) {
   return 0;
 }
 
+int xt_net_set_duel(xt_net* net, int32_t on) {
+  XT_REQUIRE(net, "xt_net_set_duel: null net");
+  XT_REQUIRE(net->head_group, "xt_net_set_duel: the net is not marked distributional (xt_net_set_dist) or quantile "
+                              "(xt_net_set_quant): the scalar head's dueling stream is the dueling flag of xt_dqn_cfg");
+  XT_REQUIRE(!on || net->A / net->head_group >= 2,
+             "xt_net_set_duel: the head is %d wide, one group of %d: a dueling head needs the value group and at least one "
+             "action", net->A, net->head_group);
+  XT_REQUIRE(!on || net->A / net->head_group - 1 <= 63, "xt_net_set_duel: a dueling head of %d actions exceeds 63",
+             net->A / net->head_group - 1);
+  net->head_duel = on ? 1 : 0;
+  return 0;
+}
+
 int xt_net_set_dist_wide(xt_net* net, int32_t on) {
   XT_REQUIRE(net, "xt_net_set_dist_wide: null net");
   XT_REQUIRE(net->head_group,
              "xt_net_set_dist_wide: the net is not marked distributional (xt_net_set_dist) or quantile (xt_net_set_quant)");
-  net->dist_wide = on ? 1 : 0;
+  net->dist_wide = on == 2 ? 2 : (on ? 1 : 0);
   return 0;
 }
 

@@ -306,6 +306,13 @@ SIGNATURES = {
     "xt_net_set_quant": (c_int32, [_P, c_int32, c_double]),
     "xt_net_dqn_step_quant": (c_int32, [_P, _P, POINTER(DqnCfg), POINTER(NstepCfg), POINTER(PerCfg), _P, _P, c_int64, c_int64,
                                         c_int64, _P, c_int32, _P, _P, _P, _P, _P, _P]),
+    # (the dueling distributional entries; tests/test_cpu_noisy.py keeps the two noisy entries last)
+    "xt_dqn_loss_dist_duel": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_double, c_double, _P, _P, _P, _P, c_double, _P,
+                                        _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "xt_dqn_loss_quant_duel": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P, c_double, _P, _P, _P,
+                                         _P, _P, _P, _P, _P, _P]),
+    "xt_net_set_duel": (c_int32, [_P, c_int32]),
+    "xt_heads_dfeat_duel": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, _P]),
     "xt_noisy_compose": (c_int32, [POINTER(NoisyLayer), c_int32, _P, _P, c_int64, _P, _P, ctypes.c_uint64, ctypes.c_uint64,
                                    c_int32, c_int32, _P]),
     "xt_noisy_grads": (c_int32, [POINTER(NoisyLayer), c_int32, _P, _P, _P]),

@@ -27,6 +27,13 @@ variables ``<layer>/kernel`` / ``bias`` hold the means, ``<layer>/sigma_kernel``
 runs on W_eff = mu + sigma * (f_in f_out^T) with vectors drawn from a counter-based generator keyed by (``SEED``, call,
 stream).  ``noisy_philox`` ... ``noisy_sigma_grads`` are the host twins of ``xt_noisy_compose`` / ``xt_noisy_grads``
 ("Noisy layers"), and what the CPU replica composes with.
+
+``model_config.dist_dueling`` (false unless asked for; with ``atoms`` or ``quantiles`` > 1 only) makes the distributional
+or quantile network dueling, the architecture of Rainbow: the Q head is (A + 1) * N wide, group a < A the advantages of
+action a and group A the state-value stream, and everything the two heads read as an action's logits / quantiles is
+l[a, i] = v[i] + (adv[a, i] - mean_a adv[a, i]) (``dist_dueling_combine``, the host twin of what ``xt_dqn_loss_dist_duel`` /
+``xt_dqn_loss_quant_duel`` do on the fly; ``dist_dueling_combine_grad`` is its transpose).  ``predict`` combines first.  The
+key ``dueling`` keeps meaning the 1-wide stream of the scalar head and stays refused with ``atoms`` / ``quantiles``.
 """
 import numpy as np
 
@@ -91,6 +98,38 @@ def categorical_projection(p, reward, disc, done, v_min, v_max):
     return m.astype(np.float32)
 
 
+def dist_dueling_combine(cols, n_actions, n):
+    """The dueling combine of a folded head's output ``cols`` [B, (A + 1) * N] (float32): adv[a, i] = cols[a N + i],
+    v[i] = cols[A N + i], mean_i = (sum over ascending a of adv[a, i]) / (float32)A, l[a, i] = v[i] + (adv[a, i] - mean_i).
+    -> l float32 [B, A, N]"""
+    a, n = int(n_actions), int(n)
+    c = np.asarray(cols, np.float32).reshape(-1, a + 1, n)
+    s = np.zeros((c.shape[0], n), np.float32)
+    for k in range(a):                                  # ascending a: the kernel's order of summation
+        s = s + c[:, k]
+    mean = s / np.float32(a)
+    return c[:, a:a + 1] + (c[:, :a] - mean[:, None, :])
+
+
+def dist_dueling_combine_grad(d, action, n_actions):
+    """The gradient of a folded row from d_i = d loss / d l[act, i] (``d`` float32 [B, N], ``action`` already inside
+    [0, A)): dcol[a N + i] = d_i * (hot(a == act) - inv_A) with inv_A = 1 / (float32)A for every a < A, dcol[A N + i] = d_i.
+    -> float32 [B, (A + 1) * N]"""
+    a = int(n_actions)
+    d = np.asarray(d, np.float32)
+    hot = (np.arange(a)[None, :] == np.asarray(action).reshape(-1, 1)).astype(np.float32)
+    inv_a = np.float32(1.0) / np.float32(a)
+    adv = d[:, None, :] * (hot - inv_a)[:, :, None]
+    return np.concatenate([adv, d[:, None, :]], axis=1).reshape(d.shape[0], -1)
+
+
+def dist_dueling_config(model_config, action_dim):
+    """-> ``dist_dueling`` of a DQN ``model_config`` after its checks (call it behind ``dist_config`` / ``quant_config``,
+    whose refusal of ``dueling`` with ``atoms`` / ``quantiles`` comes first)"""
+    return netspec.check_dist_dueling(model_config.get("dist_dueling", False), netspec.check_atoms(model_config.get("atoms", 1)),
+                                      netspec.check_quantiles(model_config.get("quantiles", 1)), action_dim)
+
+
 def dist_config(model_config, action_dim):
     """-> (atoms, v_min, v_max) of a DQN ``model_config`` after the checks of the distributional keys"""
     atoms = netspec.check_atoms(model_config.get("atoms", 1))
@@ -101,7 +140,8 @@ def dist_config(model_config, action_dim):
                 atoms, v_min, v_max))
         if bool(model_config.get("dueling", False)):
             raise NotImplementedError("dueling with atoms = {}: the dueling stream is 1 wide, a distributional dueling "
-                                      "network needs an atoms-wide one; not provided".format(atoms))
+                                      "network needs an atoms-wide one; not provided (the folded form is the key "
+                                      "dist_dueling)".format(atoms))
         if int(action_dim) > 64:
             raise ValueError("atoms = {}: action_dim = {} exceeds 64 (the device step's limit)".format(atoms, action_dim))
     return atoms, v_min, v_max
@@ -172,7 +212,8 @@ def quant_config(model_config, action_dim):
                              "not both".format(quantiles, model_config["atoms"]))
         if bool(model_config.get("dueling", False)):
             raise NotImplementedError("dueling with quantiles = {}: the dueling stream is 1 wide, a quantile dueling "
-                                      "network needs a quantiles-wide one; not provided".format(quantiles))
+                                      "network needs a quantiles-wide one; not provided (the folded form is the key "
+                                      "dist_dueling)".format(quantiles))
         if not (np.isfinite(np.float32(kappa)) and np.float32(kappa) > 0):
             raise ValueError("quantiles = {}: kappa must be finite and > 0, got kappa = {} (the pure |u| loss, kappa = 0, "
                              "is not provided)".format(quantiles, kappa))
@@ -268,16 +309,16 @@ def dqn_spec(model_info):
     if name == "DqnCnnPong":
         raise NotImplementedError(PONG_MESSAGE)
     noisy, sigma0, _ = noisy_config(cfg)
+    atoms, quantiles = dist_config(cfg, model_info["action_dim"])[0], quant_config(cfg, model_info["action_dim"])[0]
+    duel = dist_dueling_config(cfg, model_info["action_dim"])
     if name == "DqnCnn":
-        return netspec.dqn_cnn(tuple(model_info["state_dim"]), model_info["action_dim"], dueling,
-                               dist_config(cfg, model_info["action_dim"])[0], quant_config(cfg, model_info["action_dim"])[0],
-                               noisy, sigma0)
+        return netspec.dqn_cnn(tuple(model_info["state_dim"]), model_info["action_dim"], dueling, atoms, quantiles, noisy,
+                               sigma0, duel)
     if name == "DqnMlp":
         from xingtian_amd.model.dqn import default_config as d
         return netspec.dqn_mlp(tuple(model_info["state_dim"]), model_info["action_dim"],
                                cfg.get("HIDDEN_SIZE", d.HIDDEN_SIZE), cfg.get("NUM_LAYERS", d.NUM_LAYERS), dueling,
-                               dist_config(cfg, model_info["action_dim"])[0], quant_config(cfg, model_info["action_dim"])[0],
-                               noisy, sigma0)
+                               atoms, quantiles, noisy, sigma0, duel)
     raise KeyError("no DQN model named {}".format(name))
 
 
@@ -292,6 +333,7 @@ class DqnModel(XTModel):
         self.atoms, self.v_min, self.v_max = dist_config(model_config, self.action_dim)
         self.support = dist_support(self.atoms, self.v_min, self.v_max)[0] if self.atoms > 1 else None
         self.quantiles, self.kappa = quant_config(model_config, self.action_dim)
+        self.dist_dueling = dist_dueling_config(model_config, self.action_dim)
         self.noisy, self.noisy_sigma0, self.noisy_predict_mean = noisy_config(model_config)
         self.noisy_predict_calls = 0              # the call word of the noise ``predict`` draws on a learner net
         self.seed = model_config.get("SEED")
@@ -310,6 +352,8 @@ class DqnModel(XTModel):
             self.net.set_dist(self.atoms, self.v_min, self.v_max)
         if self.quantiles > 1 and not getattr(self.net, "inference_only", False):
             self.net.set_quant(self.quantiles, self.kappa)
+        if self.dist_dueling and not getattr(self.net, "inference_only", False):
+            self.net.set_duel(True)
         if self.noisy:
             # the key of every noise draw: SEED, or one drawn here when the configuration gives none
             key = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2 ** 63))
@@ -334,12 +378,15 @@ class DqnModel(XTModel):
 
     def predict(self, state):
         """-> Q [N, A] (numpy float32); with ``atoms`` > 1 the expectation under every action's softmax (``dist_q``), with
-        ``quantiles`` > 1 the mean of every action's quantiles (``quant_q``).  A noisy model draws new noise per call
+        ``quantiles`` > 1 the mean of every action's quantiles (``quant_q``), with ``dist_dueling`` of the combined logits /
+        quantiles (``dist_dueling_combine``).  A noisy model draws new noise per call
         (stream 2; the CPU replica from a counter of its own inside ``forward``) unless ``NOISY_PREDICT_MEAN``."""
         if self.noisy and not getattr(self.net, "inference_only", False):
             self.net.compose(self.noisy_predict_calls, NOISY_STREAM_PREDICT, mean_only=self.noisy_predict_mean)
             self.noisy_predict_calls += 1
         logits, value = self.net.forward(np.asarray(state))
+        if self.dist_dueling:                               # the folded head: combine first, [B, A, N]
+            logits = dist_dueling_combine(as_numpy(logits), self.action_dim, max(self.atoms, self.quantiles))
         if self.atoms > 1:
             return dist_q(as_numpy(logits).reshape(-1, self.action_dim, self.atoms), self.support)
         if self.quantiles > 1:
@@ -400,4 +447,4 @@ class DqnCnn(DqnModel):
 
     def _spec(self):
         return netspec.dqn_cnn(tuple(self.state_dim), self.action_dim, self.dueling, self.atoms, self.quantiles, self.noisy,
-                               self.noisy_sigma0)
+                               self.noisy_sigma0, self.dist_dueling)

@@ -14,4 +14,4 @@ class DqnMlp(DqnModel):
 
     def _spec(self):
         return netspec.dqn_mlp(tuple(self.state_dim), self.action_dim, HIDDEN_SIZE, NUM_LAYERS, self.dueling,
-                               self.atoms, self.quantiles, self.noisy, self.noisy_sigma0)
+                               self.atoms, self.quantiles, self.noisy, self.noisy_sigma0, self.dist_dueling)

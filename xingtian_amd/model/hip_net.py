@@ -893,7 +893,8 @@ class HipActorCritic(object):
         ``nstep_action`` / ``nstep_reward`` / ``nstep_disc`` / ``nstep_done`` [max_batch].
 
         ``dist``: the categorical projection and cross-entropy head ``xt_dqn_loss_dist`` of a distributional pair (both
-        nets carry the mark of ``set_dist``; no dueling); the new priority of a start slot is its loss + eps and the
+        nets carry the mark of ``set_dist``; no ``dueling`` -- a dueling distributional pair carries the mark of ``set_duel``
+        on both nets and the entry reads it); the new priority of a start slot is its loss + eps and the
         tensor returned is [loss, mean per-sample loss, mean bootstrap Q].
 
         ``quant``: the quantile-Huber head ``xt_dqn_loss_quant`` of a quantile pair (both nets carry the mark of
@@ -1002,6 +1003,8 @@ class HipActorCritic(object):
         ``xt_net_set_dist``; ``spec.action_dim`` is actions * atoms); ``atoms`` 1 clears the mark."""
         L.check(self.lib.xt_net_set_dist(self.handle, int(atoms), float(v_min), float(v_max)), "xt_net_set_dist")
         self.dist = (int(atoms), float(v_min), float(v_max)) if int(atoms) > 1 else None
+        if self.dist is None:
+            self.duel = False                           # (clearing the mark clears the dueling one)
 
     def set_quant(self, quantiles, kappa):
         """Mark the net as carrying a quantile (QR-DQN) Q head of ``quantiles`` quantiles with Huber threshold ``kappa`` (C
@@ -1009,6 +1012,15 @@ class HipActorCritic(object):
         carries one mark: ``set_dist`` and this refuse a net the other has marked."""
         L.check(self.lib.xt_net_set_quant(self.handle, int(quantiles), float(kappa)), "xt_net_set_quant")
         self.quant = (int(quantiles), float(kappa)) if int(quantiles) > 1 else None
+        if self.quant is None:
+            self.duel = False                           # (clearing the mark clears the dueling one)
+
+    def set_duel(self, on):
+        """Mark a net that carries the mark of ``set_dist`` / ``set_quant`` as dueling (C ABI ``xt_net_set_duel``): the last
+        group of its head is the state-value stream (``netspec`` with ``dist_dueling``), and ``dqn_step`` with ``dist`` /
+        ``quant`` runs the dueling head.  Clearing the other mark clears this one."""
+        L.check(self.lib.xt_net_set_duel(self.handle, int(bool(on))), "xt_net_set_duel")
+        self.duel = bool(on)
 
     def set_noisy(self, seed, sigma0):
         """Give the noisy layers of the net's spec the 64-bit key ``seed`` of their noise draws; ``sigma0`` is the spec's
@@ -1040,8 +1052,9 @@ class HipActorCritic(object):
 
     def set_dist_wide(self, on):
         """Switch a marked net between the wide-head kernels (the default) and those of an unmarked net (C ABI
-        ``xt_net_set_dist_wide``): for same-run comparisons and tests."""
-        L.check(self.lib.xt_net_set_dist_wide(self.handle, int(bool(on))), "xt_net_set_dist_wide")
+        ``xt_net_set_dist_wide``): for same-run comparisons and tests.  ``on`` = "forward": the wide forward with the generic
+        feature-gradient kernel behind it."""
+        L.check(self.lib.xt_net_set_dist_wide(self.handle, 2 if on == "forward" else int(bool(on))), "xt_net_set_dist_wide")
 
     def _nstep_cfg(self, who, follow, n, cap):
         """-> ``NstepCfg`` after the check of ``follow``; allocates the label scratch ``nstep_*`` [max_batch]"""

@@ -358,13 +358,36 @@ def _add_noisy(spec, sigma0, dueling):
     spec.n_params = sum(int(_prod(s)) for _, s in spec.names.values())
 
 
+MAX_DIST_DUELING_ACTIONS = 63    # the device step holds 64 groups of columns; a dueling head spends one on the value stream
+
+
+def check_dist_dueling(dist_dueling, atoms, quantiles, action_dim):
+    """``dist_dueling`` of a DQN model as a bool after its checks (``dueling`` with ``atoms`` / ``quantiles`` > 1 is the
+    callers' own refusal and comes first), else ValueError"""
+    if not isinstance(dist_dueling, bool):
+        raise ValueError("dist_dueling = {!r} must be a bool".format(dist_dueling))
+    if not dist_dueling:
+        return False
+    if atoms <= 1 and quantiles <= 1:
+        raise ValueError("dist_dueling without atoms or quantiles > 1: the scalar Q head's dueling stream is the key "
+                         "`dueling`; dist_dueling is the dueling form of a distributional (atoms) or quantile head")
+    if int(action_dim) > MAX_DIST_DUELING_ACTIONS:
+        raise ValueError("dist_dueling: action_dim = {} exceeds {} (the device step holds 64 groups of columns and the "
+                         "state-value stream is one of them)".format(action_dim, MAX_DIST_DUELING_ACTIONS))
+    return True
+
+
 def _dqn_spec(layers, feat, action_dim, n_trunk_layers, dueling, xf, state_dim, atoms=1, quantiles=1, noisy=False,
-              noisy_sigma0=0.5):
+              noisy_sigma0=0.5, dist_dueling=False):
     """The Q head is the Keras layer after the trunk (dense_<n>), the dueling 1-wide stream the one after it.  ``atoms``
     > 1: the distributional head -- kernel (F, A * atoms), column a * atoms + i is atom i of action a; the spec's
     ``action_dim`` is then the head's width A * atoms, ``n_actions`` is A and ``atoms`` the count.  ``quantiles`` > 1: the
     quantile head, by the same width rule (column a * quantiles + i is quantile i of action a; ``quantiles`` the count);
-    a head is one or the other.  ``noisy``: see ``_add_noisy``; a spec without it is unchanged."""
+    a head is one or the other.  ``noisy``: see ``_add_noisy``; a spec without it is unchanged.  ``dist_dueling`` (with
+    ``atoms`` or ``quantiles`` > 1): the state-value stream is folded into the Q head as one more group -- kernel
+    (F, (A + 1) * N) under the unchanged name, column a * N + i (a < A) the advantage of atom / quantile i of action a,
+    columns A * N + i the state-value stream; ``action_dim`` is (A + 1) * N, ``n_actions`` stays A, ``dist_dueling`` says
+    so, and the 1-wide block stays laid out and hidden."""
     noisy, noisy_sigma0 = check_noisy(noisy, noisy_sigma0)
     atoms, quantiles = check_atoms(atoms), check_quantiles(quantiles)
     if atoms > 1 and quantiles > 1:
@@ -372,34 +395,38 @@ def _dqn_spec(layers, feat, action_dim, n_trunk_layers, dueling, xf, state_dim, 
                          "not both".format(atoms, quantiles))
     if atoms > 1 and dueling:
         raise NotImplementedError("dueling with atoms = {}: the dueling stream is 1 wide, a distributional dueling network "
-                                  "needs an atoms-wide one; not provided".format(atoms))
+                                  "needs an atoms-wide one; not provided (the folded form is the key "
+                                  "dist_dueling)".format(atoms))
     if quantiles > 1 and dueling:
         raise NotImplementedError("dueling with quantiles = {}: the dueling stream is 1 wide, a quantile dueling network "
-                                  "needs a quantiles-wide one; not provided".format(quantiles))
-    width = int(action_dim) * atoms * quantiles
+                                  "needs a quantiles-wide one; not provided (the folded form is the key "
+                                  "dist_dueling)".format(quantiles))
+    dist_dueling = check_dist_dueling(dist_dueling, atoms, quantiles, action_dim)
+    width = (int(action_dim) + (1 if dist_dueling else 0)) * atoms * quantiles
     spec = NetSpec(layers, 1, feat, width, "dense_%d" % n_trunk_layers, "dense_%d" % (n_trunk_layers + 1),
                    (feat, width), xf, state_dim, hidden_v=not dueling)
-    spec.atoms, spec.quantiles, spec.n_actions = atoms, quantiles, int(action_dim)
+    spec.atoms, spec.quantiles, spec.n_actions, spec.dist_dueling = atoms, quantiles, int(action_dim), dist_dueling
     if noisy:
         _add_noisy(spec, noisy_sigma0, dueling)
     return spec
 
 
-def dqn_cnn(state_dim, action_dim, dueling=False, atoms=1, quantiles=1, noisy=False, noisy_sigma0=0.5):
+def dqn_cnn(state_dim, action_dim, dueling=False, atoms=1, quantiles=1, noisy=False, noisy_sigma0=0.5, dist_dueling=False):
     """Keras ``DqnCnn`` (xt/model/dqn/dqn_cnn.py:45-59): the trunk of ``impala_cnn`` (Conv2D 32@8x8/4, 64@4x4/2, 64@3x3/1
     valid relu on uint8 / 255, Dense 256 relu), a linear Q head Dense(A) and, with ``dueling``, a 1-wide Dense stream:
     Q_a = s + (l_a - mean_a l).  Variable names are Keras' automatic ones of a first-built model: conv2d, conv2d_1,
-    conv2d_2, dense, the Q head dense_1, the 1-wide stream dense_2.  ``atoms`` / ``quantiles`` > 1 and ``noisy``: see
-    ``_dqn_spec``."""
+    conv2d_2, dense, the Q head dense_1, the 1-wide stream dense_2.  ``atoms`` / ``quantiles`` > 1, ``noisy`` and
+    ``dist_dueling``: see ``_dqn_spec``."""
     trunk = impala_cnn(state_dim, action_dim).layers
-    return _dqn_spec(trunk, 256, action_dim, 1, dueling, (1, 0.0, 255.0), state_dim, atoms, quantiles, noisy, noisy_sigma0)
+    return _dqn_spec(trunk, 256, action_dim, 1, dueling, (1, 0.0, 255.0), state_dim, atoms, quantiles, noisy, noisy_sigma0,
+                     dist_dueling)
 
 
 def dqn_mlp(state_dim, action_dim, hidden_size=128, num_layers=1, dueling=False, atoms=1, quantiles=1, noisy=False,
-            noisy_sigma0=0.5):
+            noisy_sigma0=0.5, dist_dueling=False):
     """Keras ``DqnMlp`` (xt/model/dqn/dqn_mlp.py:43-56): ``impala_mlp``'s trunk (dense ... dense_{L-1}), the Q head
-    dense_L and, with ``dueling``, the 1-wide stream dense_{L+1}.  ``atoms`` / ``quantiles`` > 1 and ``noisy``: see
-    ``_dqn_spec``."""
+    dense_L and, with ``dueling``, the 1-wide stream dense_{L+1}.  ``atoms`` / ``quantiles`` > 1, ``noisy`` and
+    ``dist_dueling``: see ``_dqn_spec``."""
     trunk = impala_mlp(state_dim, action_dim, hidden_size, num_layers).layers
     return _dqn_spec(trunk, hidden_size, action_dim, int(num_layers), dueling, (0, 0.0, 1.0), (1, 1, int(state_dim[0])),
-                     atoms, quantiles, noisy, noisy_sigma0)
+                     atoms, quantiles, noisy, noisy_sigma0, dist_dueling)
