@@ -541,6 +541,15 @@ int xt_net_set_gauss_fused(xt_net* net, int32_t on);
  * sign mask and everything downstream are bit for bit what the two launches give.  on == 0: always two launches.  The
  * flag is part of the key of every cached hipGraph of the net. */
 int xt_net_set_fwd_fuse12_flat(xt_net* net, int32_t on);
+/* PpoCnn's first THREE layers in one forward launch (appended under ABI 12; per net, default ON).  on != 0: a trunk that
+ * would take the launch above and whose third layer is the 3x3/1 VALID 32 -> 64 one, with a further layer behind it, runs
+ * conv123_u8_valid_fwd_flat_kernel for all three when neither the second nor the third layer's own forward would be split
+ * over K and the automatic split needs at most one workgroup per CU (201 <= B <= 320 for 84x84 frames); every other
+ * forward is the one of a net that never had the switch.  The three activations, the sign mask and everything downstream
+ * are bit for bit what the separate launches give.  Needs xt_net_set_fwd_fuse12_flat on (its default).  The tail word
+ * XT_STEP_TAIL_FWD_FUSE123 of xt_net_last_step_report is 1 after a forward that took it.  The flag is part of the key
+ * of every cached hipGraph of the net. */
+int xt_net_set_fwd_fuse123_flat(xt_net* net, int32_t on);
 
 /* Gradient exchange hook of xt_net_ppo_train (ABI >= 4): the reference's learner is single-process
  * (its grad_communicate host averaging, xt/framework/trainer.py:89-92, is dead code); data parallelism is this
@@ -903,6 +912,34 @@ int xt_conv12_valid_fwd(const xt_conv_geom* g0, const xt_input_xform* xf, const 
                         const void* in, const int32_t* idx, const float* w0, const float* b0, float* act1,
                         uint32_t* relu_mask, const float* w1, const float* b1, float* act2, int32_t rows_per_block,
                         void* stream);
+/* The same with the 3x3/1 VALID 32 -> 64 layer g2 behind g1, three layers in ONE launch
+ * (conv123_u8_valid_fwd_flat_kernel, see xt_net_set_fwd_fuse123_flat; appended, the ABI version stays): act1 / relu_mask /
+ * act2 receive what xt_conv12_valid_fwd writes and act3 what xt_layer_fwd (ksplit 1) of g2 writes from that act2, bit for
+ * bit.  rows_per_block: rows of g2's output (over all samples) per workgroup; 0 = the automatic split (groups of whole
+ * samples cut into equal runs, one workgroup per CU while the batch allows).  Refused when the layers, the batch or
+ * rows_per_block are outside the kernel's envelope (a workgroup holds 64 positions of g2's output, 128 of g1's and 768 of
+ * g0's, within 160 KB of LDS: at 84x84 frames runs of up to 8 rows, or 9 that touch two samples). */
+int xt_conv123_valid_fwd(const xt_conv_geom* g0, const xt_input_xform* xf, const xt_conv_geom* g1, const xt_conv_geom* g2,
+                         int32_t B, const void* in, const int32_t* idx, const float* w0, const float* b0, float* act1,
+                         uint32_t* relu_mask, const float* w1, const float* b1, float* act2, const float* w2, const float* b2,
+                         float* act3, int32_t rows_per_block, void* stream);
+/* The envelope and the split of xt_conv123_valid_fwd as host words (no device call): out[0 .. XT_CONV123_PLAN_WORDS), then
+ * XT_CONV123_BLOCK_WORDS per workgroup while `cap` words last.  INSIDE = 1 when xt_conv123_valid_fwd would launch (all
+ * other words but LDS_LIMIT are 0 when not); IN_NET = 1 when a network with the switch on takes the launch at this batch;
+ * BLOCKS; GROUP_ROWS / GROUP_BLOCKS = the rows of g2's output are cut into groups of GROUP_ROWS, each into GROUP_BLOCKS
+ * equal runs; LDS_BYTES of the launch and the LDS_LIMIT it is held to; MAX_CONV1_POS / MAX_CONV2_POS = positions of g0's /
+ * g1's output the largest workgroup computes.  Per workgroup: the rows [0], [1]) of g2's output it owns, the rows [2], [3])
+ * of g1's output it computes (both over all samples), its first sample, the positions of g0's output it computes, then
+ * for each of its three sample pieces {rows of g1's output, first row of g0's output (it computes 2 n + 2 from there), 1
+ * when the piece ends its sample}. */
+enum {
+  XT_CONV123_PLAN_INSIDE = 0, XT_CONV123_PLAN_IN_NET = 1, XT_CONV123_PLAN_BLOCKS = 2, XT_CONV123_PLAN_GROUP_ROWS = 3,
+  XT_CONV123_PLAN_GROUP_BLOCKS = 4, XT_CONV123_PLAN_LDS_BYTES = 5, XT_CONV123_PLAN_LDS_LIMIT = 6,
+  XT_CONV123_PLAN_MAX_CONV1_POS = 7, XT_CONV123_PLAN_MAX_CONV2_POS = 8, XT_CONV123_PLAN_WORDS = 9,
+  XT_CONV123_BLOCK_WORDS = 15
+};
+int xt_conv123_valid_plan(const xt_conv_geom* g0, const xt_input_xform* xf, const xt_conv_geom* g1, const xt_conv_geom* g2,
+                          int32_t B, int32_t rows_per_block, int32_t* out, int32_t cap);
 
 /* xt_layer_wgrad the way a network's update runs it (appended; the ABI version stays): the gradient is left in slabs
  * (no reduction inside the launcher) and the slab buffer has `slab_cap` slabs, which is what lets the uint8 first-layer
@@ -1468,7 +1505,10 @@ int xt_norm_finalize_ex(const float* partial, int32_t nblocks, const xt_finish_a
  * Layer: KSPLIT = split-K partial slabs the last forward LEFT in the layer's own region (1: none -- a layer that was not
  * offered the deferral finishes its split itself and reports 1), DEFERRED = 1 when they were left for the fused head; MSPLIT = weight-gradient slabs of the last backward, SLAB_CAP = slabs the region holds;
  * MASK_VALID = 1 when the last forward wrote the relu sign mask; PREACT = 1 when the layer keeps its pre-activation
- * (swish / gelu); NPRE = squared-norm partials the last backward launch pre-reduced; TRUNK. */
+ * (swish / gelu); NPRE = squared-norm partials the last backward launch pre-reduced; TRUNK.
+ * Tail (appended): XT_STEP_TAIL_WORDS words behind the out[WORDS] words above, written when `cap` has room for them
+ * and not counted in WORDS: XT_STEP_TAIL_FWD_FUSE123 = 1 when the last forward ran the one-launch conv1 + conv2 + conv3 forward
+ * (xt_net_set_fwd_fuse123_flat). */
 enum {
   XT_STEP_REPORT_WORDS = 0, XT_STEP_REPORT_LAYERS = 1, XT_STEP_REPORT_TRUNKS = 2, XT_STEP_REPORT_FWD_FUSE12 = 3,
   XT_STEP_REPORT_BWD_FUSE21 = 4, XT_STEP_REPORT_HEAD_PATH = 5, XT_STEP_REPORT_TAIL_OVERLAP = 6,
@@ -1480,6 +1520,7 @@ enum {
   XT_STEP_REPORT_L_MASK_VALID = 4, XT_STEP_REPORT_L_PREACT = 5, XT_STEP_REPORT_L_NPRE = 6, XT_STEP_REPORT_L_TRUNK = 7,
   XT_STEP_REPORT_LAYER_WORDS = 8
 };
+enum { XT_STEP_TAIL_FWD_FUSE123 = 0, XT_STEP_TAIL_WORDS = 1 };
 int xt_net_last_step_report(const xt_net* net, int32_t* out, int32_t cap);
 
 /* What the hipGraph cache of xt_net_ppo_train / xt_net_impala_train(_io) has done on this net so far (appended under ABI

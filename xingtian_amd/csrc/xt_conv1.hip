@@ -12,6 +12,10 @@
 // channels, no padding (TF VALID) -- PpoCnn's 8x8/4 first layer on 84x84x4 frame stacks
 // (xt/model/model_utils.py:126-131).  One workgroup stages ONE frame stack (28 KB) into LDS with coalesced
 // 16-byte loads (the minibatch row gather idx[b] is fused here) and produces all of its OH*OW x 32 outputs.
+#include <array>
+#include <map>
+#include <mutex>
+#include <utility>
 #include "xt_common.h"
 #include "xt_conv1_dev.h"
 #include "xt_launch.h"
@@ -495,7 +499,7 @@ struct C12Args {
   int tab_off;         // LDS byte of the position table [positions] x {global position or -1, plane slot}
 };
 
-constexpr int kC12Pieces = 3, kC12MaxRows = 12, kC12Blocks = 256;
+constexpr int kC12Pieces = 3, kC12MaxRows = 12, kC12Blocks = 256, kC12LdsLimit = 160 * 1024;
 constexpr int kC12TbufBytes = 8 * 32 * 36 * 4, kC12RedBytes = 4 * 128 * 36 * 4, kC12WplBytes = 16 * 3 * 64 * 16;
 
 // the pieces of the row run [row0, row1): n output rows from conv1 row clo on, first local position lbase; own_all: the
@@ -551,14 +555,51 @@ __device__ __forceinline__ void c12_conv1_steps(const uint8_t* limg, const uint4
   }
 }
 
-__global__ __launch_bounds__(512) void conv12_u8_valid_fwd_flat_kernel(const C12Args a) {
+// The third stage (conv123_u8_valid_fwd_flat_kernel): PpoCnn's 3x3/1 VALID 32 -> 64 conv3 behind conv2.  The blocks own
+// runs of whole conv3 rows: (sample, conv3 row) is flattened into T3 = B * OH3 rows, cut into groups of G rows, and block j
+// of the N blocks of a group takes rows [j G / N, (j + 1) G / N) of it (G a multiple of OH3 in the automatic split, so
+// every group starts a sample and all groups have the same runs).
+struct C3Args {
+  const float* w3;     // [9 * 32][64]
+  const float* b3;     // [64]
+  float* y3;           // [B * OH3 * OW3][64]
+  int OH3, OW3, act3;
+  int T3, G, N;
+  int nps3;            // 16-byte slots per (plane, k quarter) run of the act2 planes
+};
+
+constexpr int kC3MaxPos = 64, kC3RedStride = 68, kC3RedBytes = 2 * kC3MaxPos * kC3RedStride * 4;
+
+// the conv3 rows [*r0, *r1) of block blk, and the conv2 rows [*c0, *c1) under them (conv3 row oy reads conv2 rows oy ..
+// oy + 2 of its sample; a run that crosses into the next sample needs that sample from its row 0 on, which follows the
+// last conv2 row of this one in the flat order, so the conv2 rows are one run too)
+__device__ __host__ __forceinline__ void c3_rows(int blk, int T3, int G, int N, int OH3, int OH2, int* r0, int* r1,
+                                                 int* c0, int* c1) {
+  const int grp = blk / N, j = blk - grp * N;
+  int a = grp * G + (j * G) / N, b = grp * G + ((j + 1) * G) / N;
+  a = a < T3 ? a : T3;
+  b = b < T3 ? b : T3;
+  *r0 = a; *r1 = b;
+  const int sa = a / OH3, last = b - 1, sb = last / OH3;
+  *c0 = sa * OH2 + (a - sa * OH3);
+  *c1 = b > a ? sb * OH2 + (last - sb * OH3) + 3 : *c0;
+}
+
+template <bool C3>
+__device__ __forceinline__ void c12_body(const C12Args& a, const C3Args& c) {
   constexpr int NW = 8, NT = 512, NP = kC12Pieces, WQ = 1024 / NT, U = 6, SL = 3;
   extern __shared__ __attribute__((aligned(16))) uint8_t limg[];
   const C1FwdArgs& p = a.c1;
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int HWC = p.H * p.W * 4, Wrow = p.W * 4, OW1 = p.OW, OHOW1 = p.OH * p.OW, HW1 = (OW1 + 1) >> 1;
   const int blk = blockIdx.x;
-  const int row0 = blk * a.q + min(blk, a.r), row1 = min(a.T, row0 + a.q + (blk < a.r ? 1 : 0));
+  int row0, row1, r3a = 0, r3b = 0;           // the block's conv2 rows, and (C3) its conv3 rows
+  if constexpr (C3) {
+    c3_rows(blk, c.T3, c.G, c.N, c.OH3, a.OH2, &r3a, &r3b, &row0, &row1);
+  } else {
+    row0 = blk * a.q + min(blk, a.r);
+    row1 = min(a.T, row0 + a.q + (blk < a.r ? 1 : 0));
+  }
   const int s0 = row0 / a.OH2;
   int pn[NP], clo[NP], lbase[NP], own_all[NP], npos;
   c12_pieces(row0, row1, a.OH2, OW1, pn, clo, lbase, own_all, &npos);
@@ -649,7 +690,9 @@ __global__ __launch_bounds__(512) void conv12_u8_valid_fwd_flat_kernel(const C12
   for (int L = t; L < npos; L += NT) {
     const int i = L >= lbase[2] ? 2 : L >= lbase[1] ? 1 : 0;
     const int l = L - XT_C12_SEL(lbase, i), lr = l / OW1, x = l - lr * OW1;
-    const bool own = lr < 2 * XT_C12_SEL(pn, i) || XT_C12_SEL(own_all, i) != 0;
+    // (C3: a piece of n conv2 rows holds n - 2 conv3 rows, and conv3 row oy owns conv2 row oy and conv1 rows 2 oy, 2 oy + 1;
+    // the last conv3 row of a sample owns the rows past them)
+    const bool own = lr < 2 * (XT_C12_SEL(pn, i) - (C3 ? 2 : 0)) || XT_C12_SEL(own_all, i) != 0;
     const int gpos = (s0 + i) * OHOW1 + (XT_C12_SEL(clo, i) + lr) * OW1 + x;
     ptab[L] = make_int2(own ? gpos : -1, XT_C12_SEL(lbase, i) + lr * OW1 + (x & 1) * HW1 + (x >> 1));
   }
@@ -780,7 +823,28 @@ __global__ __launch_bounds__(512) void conv12_u8_valid_fwd_flat_kernel(const C12
       const int row = ((wave & 1) * 2 + tt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
       red[(grp * 128 + row) * RS + il] = acc2[tt][r];
     }
+  // (C3) conv3's weights of this wave: wave group g3 = wave >> 2 takes the taps [5 g3, 5 g3 + 5) of the nine -- the K
+  // halves of igemm_fwd_kernel<64, 64, 2, 2, false, false, 2, true> at K = 288 --, row tile (wave >> 1) & 1, column tile
+  // wave & 1; a lane's 8 consecutive k of ONE column per chunk, as for conv2 -- in flight while conv2 is combined
+  constexpr int kC3Steps = 5, kC3Taps = 9;
+  const int g3 = wave >> 2, ti3 = (wave >> 1) & 1, tj3 = wave & 1;
+  float w3v[C3 ? kC3Steps : 1][2][8];
+  if constexpr (C3) {
+#pragma unroll
+    for (int s = 0; s < kC3Steps; ++s) {
+      const int tap = min(g3 * kC3Steps + s, kC3Taps - 1);
+#pragma unroll
+      for (int ch = 0; ch < 2; ++ch) {
+        const float* wl = c.w3 + (size_t)(tap * 32 + 16 * ch + 8 * h) * 64 + tj3 * 32 + il;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) w3v[s][ch][j] = wl[j * 64];
+      }
+    }
+  }
   __syncthreads();
+  // (C3) act2 stays in LDS behind the combine buffer as three bf16 planes [plane][16-byte k quarter][conv2 position]
+  uint8_t* planes3 = limg + kC12RedBytes;
+  const int qrun3 = c.nps3 * 16, prun3 = 4 * qrun3;
   for (int e = t; e < 128 * 8; e += NT) {
     const int row = e >> 3, c4 = (e & 7) * 4;
     if (row >= n2) continue;
@@ -791,13 +855,80 @@ __global__ __launch_bounds__(512) void conv12_u8_valid_fwd_flat_kernel(const C12
       s.x += b.x; s.y += b.y; s.z += b.z; s.w += b.w;
     }
     const float4 bb = *reinterpret_cast<const float4*>(a.b2 + c4);
-    store4_wt(a.y2, (size_t)(row0 * a.OW2 + row) * 32 + c4,
-              make_float4(act_apply(s.x + bb.x, a.act2), act_apply(s.y + bb.y, a.act2),
-                          act_apply(s.z + bb.z, a.act2), act_apply(s.w + bb.w, a.act2)));
+    const float4 v = make_float4(act_apply(s.x + bb.x, a.act2), act_apply(s.y + bb.y, a.act2),
+                                 act_apply(s.z + bb.z, a.act2), act_apply(s.w + bb.w, a.act2));
+    if constexpr (C3) {
+      // the block stores the conv2 rows its conv3 rows own: row oy of conv3 row oy, and the rows past the last conv3 row
+      const int f2 = row0 + row / a.OW2, smp = f2 / a.OH2, oy = f2 - smp * a.OH2;
+      const int f3 = smp * c.OH3 + min(oy, c.OH3 - 1);
+      if (f3 >= r3a && f3 < r3b) store4_wt(a.y2, (size_t)(row0 * a.OW2 + row) * 32 + c4, v);
+      split3_store(planes3 + (c4 >> 3) * qrun3 + row * 16 + ((c4 >> 2) & 1) * 8, prun3, v);
+    } else {
+      store4_wt(a.y2, (size_t)(row0 * a.OW2 + row) * 32 + c4, v);
+    }
+  }
+  if constexpr (C3) {
+    __syncthreads();                         // the act2 planes are complete, the combine buffer is dead
+    // ---- phase 4: conv3 from the planes, the sums of igemm_fwd_kernel<64, 64, 2, 2, false, false, 2, true>: per tap two
+    // 16-channel chunks of mfma_bf16x6 into one accumulator per 32x32 tile, the two K halves summed through LDS in order
+    const int n3 = (r3b - r3a) * c.OW3;
+    int aoff3;
+    {
+      const int j = ti3 * 32 + il;
+      const int jc = j < n3 ? j : 0;         // rows past the block's positions read position 0 and are dropped below
+      const int rr = jc / c.OW3, ox = jc - rr * c.OW3;
+      const int f3 = r3a + rr, smp = f3 / c.OH3, oy = f3 - smp * c.OH3;
+      aoff3 = ((smp * a.OH2 + oy - row0) * a.OW2 + ox) * 16 + h * qrun3;
+    }
+    f32x16 acc3;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc3[r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < kC3Steps; ++s) {
+      const int tap = g3 * kC3Steps + s;
+      if (tap < kC3Taps) {                   // (wave-uniform)
+        const int ky = tap / 3, kx = tap - 3 * ky;
+        bf16x8 bw[2][3], av[2][3];
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch)
+#pragma unroll
+          for (int pl = 0; pl < 3; ++pl)
+            av[ch][pl] = *reinterpret_cast<const bf16x8*>(planes3 + pl * prun3 + ch * 2 * qrun3 + aoff3 +
+                                                          (ky * a.OW2 + kx) * 16);
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch)
+          split3_regs(make_float4(w3v[s][ch][0], w3v[s][ch][1], w3v[s][ch][2], w3v[s][ch][3]),
+                      make_float4(w3v[s][ch][4], w3v[s][ch][5], w3v[s][ch][6], w3v[s][ch][7]), bw[ch]);
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch) acc3 = mfma_bf16x6(av[ch], bw[ch], acc3);
+      }
+    }
+    float* red3 = reinterpret_cast<float*>(limg);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = ti3 * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      red3[(g3 * kC3MaxPos + row) * kC3RedStride + tj3 * 32 + il] = acc3[r];
+    }
+    __syncthreads();
+    for (int e = t; e < kC3MaxPos * 16; e += NT) {
+      const int row = e >> 4, c4 = (e & 15) * 4;
+      if (row >= n3) continue;
+      const float4 s0v = *reinterpret_cast<const float4*>(&red3[row * kC3RedStride + c4]);
+      const float4 s1v = *reinterpret_cast<const float4*>(&red3[(kC3MaxPos + row) * kC3RedStride + c4]);
+      const float4 bb = *reinterpret_cast<const float4*>(c.b3 + c4);
+      store4_wt(c.y3, (size_t)(r3a * c.OW3 + row) * 64 + c4,
+                make_float4(act_apply((s0v.x + s1v.x) + bb.x, c.act3), act_apply((s0v.y + s1v.y) + bb.y, c.act3),
+                            act_apply((s0v.z + s1v.z) + bb.z, c.act3), act_apply((s0v.w + s1v.w) + bb.w, c.act3)));
+    }
   }
   XT_TL_DRAIN(5);
 }
 #undef XT_C12_SEL
+
+__global__ __launch_bounds__(512) void conv12_u8_valid_fwd_flat_kernel(const C12Args a) { c12_body<false>(a, C3Args{}); }
+
+struct C123Args { C12Args c12; C3Args c3; };
+__global__ __launch_bounds__(512) void conv123_u8_valid_fwd_flat_kernel(const C123Args a) { c12_body<true>(a.c12, a.c3); }
 
 // The automatic split: the rows evenly over one block per CU; past 12 rows per block, over more blocks than CUs (B = 342 ..
 // 404 for 84x84 frames: 257 .. 303 blocks still beat the two launches by 4 to 7 us, profiles/fwd_fuse12_flat_ab.md).
@@ -880,14 +1011,148 @@ int launch_conv12_valid_fwd(const xt_conv_geom* g, const xt_input_xform* xf, con
   if (body < (size_t)kC12RedBytes) body = kC12RedBytes;
   a.tab_off = (int)body;
   const size_t fl = body + (size_t)maxpos * 8;
-  if (fl > 160 * 1024) return -1;
+  if (fl > (size_t)kC12LdsLimit) return -1;
   static PerDeviceOnce attr_once;
   attr_once.run([] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv12_u8_valid_fwd_flat_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kC12LdsLimit);
     (void)hipGetLastError();
   });
   hipLaunchKernelGGL(conv12_u8_valid_fwd_flat_kernel, dim3(nblk), dim3(512), fl, st, a);
+  XT_LAUNCH_CHECK();
+  if (mask_written && a.c1.mask) *mask_written = 1;
+  return 0;
+}
+
+// ------------------------------------------------------------------ conv1 -> conv2 -> conv3 (conv123_u8_valid_fwd_flat_kernel)
+// What the largest block of the split (G, N) needs; false when some block is outside what the kernel holds: 64 conv3 and
+// 128 conv2 positions (two and four 32-row tiles), three pieces, three conv1 tile slots per wave, one staging pass, the
+// LDS limit.  A split whose groups start a sample has the same runs in every group: the first and the last are measured.
+static bool c123_measure(const xt_conv_geom* g, const xt_conv_geom* g2, const xt_conv_geom* g3, int B, int G, int N,
+                         C123Plan* pl) {
+  const int T3 = B * g3->OH, Wrow = g->W * 4;
+  const int ngrp = (T3 + G - 1) / G, tail = T3 - (ngrp - 1) * G;
+  int last_blocks = 0;
+  for (int j = 0; j < N; ++j) last_blocks += (j * G) / N < tail ? 1 : 0;
+  pl->G = G; pl->N = N; pl->nblk = (ngrp - 1) * N + last_blocks;
+  pl->maxpos = pl->maxn2 = pl->cap = 0;
+  const bool same = G % g3->OH == 0;
+  for (int b = 0; b < pl->nblk; ++b) {
+    if (same && b >= N && b < (ngrp - 1) * N) { b = (ngrp - 1) * N - 1; continue; }
+    int r0, r1, c0, c1;
+    c3_rows(b, T3, G, N, g3->OH, g2->OH, &r0, &r1, &c0, &c1);
+    if (r1 <= r0 || (r1 - r0) * g3->OW > kC3MaxPos || (c1 - c0) * g2->OW > 128) return false;
+    if ((c1 - 1) / g2->OH - c0 / g2->OH >= kC12Pieces) return false;
+    int pn[kC12Pieces], clo[kC12Pieces], lbase[kC12Pieces], own_all[kC12Pieces], npos;
+    c12_pieces(c0, c1, g2->OH, g->OW, pn, clo, lbase, own_all, &npos);
+    int units = 0;
+    for (int i = 0; i < kC12Pieces; ++i)
+      if (pn[i] > 0) {
+        const int blo = g->S * clo[i] * Wrow, bhi = (g->S * (clo[i] + 2 * pn[i] + 1) + g->KH) * Wrow;
+        units += ((bhi + 15) >> 4) - (blo >> 4);
+      }
+    if (units * 16 > pl->cap) pl->cap = units * 16;
+    if (npos > pl->maxpos) pl->maxpos = npos;
+    if ((c1 - c0) * g2->OW > pl->maxn2) pl->maxn2 = (c1 - c0) * g2->OW;
+  }
+  if (pl->maxpos > 3 * 8 * 32 || pl->cap / 16 > 512 * 6) return false;
+  pl->nps = (pl->maxpos + 7) / 8 * 8 + 4;
+  pl->nps3 = (pl->maxn2 + 7) / 8 * 8 + 4;
+  size_t body = (size_t)2 * pl->cap + kC12WplBytes;
+  if (body < (size_t)192 * pl->nps + kC12TbufBytes) body = (size_t)192 * pl->nps + kC12TbufBytes;
+  if (body < (size_t)kC12RedBytes + (size_t)192 * pl->nps3) body = (size_t)kC12RedBytes + (size_t)192 * pl->nps3;
+  static_assert(kC3RedBytes <= kC12RedBytes, "conv123: conv3's combine buffer lies inside conv2's");
+  pl->tab_off = (int)body;
+  pl->lds = (int)(body + (size_t)pl->maxpos * 8);
+  return pl->lds <= kC12LdsLimit;
+}
+
+// The split.  rows_per_block > 0: runs of that many conv3 rows.  0: groups of S samples over N blocks each, the pair whose
+// largest block has the fewest conv1 positions among those with at most one block per CU (B = 320: five samples over four
+// blocks of 8, 9, 9, 9 rows -- a run of 9 rows that starts on the last row of a sample would touch three samples and
+// 135 conv2 positions, and this pattern has none); where there is no such pair, the one with the fewest blocks.
+static bool c123_plan(const xt_conv_geom* g, const xt_conv_geom* g2, const xt_conv_geom* g3, int B, int rows_per_block,
+                      C123Plan* out) {
+  if (rows_per_block > 0) return c123_measure(g, g2, g3, B, rows_per_block, 1, out);
+  static std::mutex mu;
+  static std::map<std::array<int, 6>, std::pair<bool, C123Plan>> memo;
+  const std::array<int, 6> key = {B, g->H, g->W, g->S, g3->OH, g3->OW};
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = memo.find(key);
+  if (it != memo.end()) { *out = it->second.second; return it->second.first; }
+  bool found = false;
+  C123Plan best{};
+  for (int S = 1; S <= 8; ++S)
+    for (int N = 1; N <= S * g3->OH; ++N) {
+      C123Plan c;
+      if (!c123_measure(g, g2, g3, B, S * g3->OH, N, &c)) continue;
+      const bool c_one = c.nblk <= kC12Blocks, b_one = best.nblk <= kC12Blocks;
+      bool better;
+      if (!found) better = true;
+      else if (c_one != b_one) better = c_one;
+      else if (c_one) better = c.maxpos < best.maxpos || (c.maxpos == best.maxpos && c.nblk < best.nblk);
+      else better = c.nblk < best.nblk || (c.nblk == best.nblk && c.maxpos < best.maxpos);
+      if (better) { best = c; found = true; }
+    }
+  memo[key] = std::make_pair(found, best);
+  *out = best;
+  return found;
+}
+
+// Is (conv1 g, conv2 g2, conv3 g3) at batch B what conv123_u8_valid_fwd_flat_kernel computes, bit for bit what the conv12
+// launch followed by conv3's own would?  conv12's conditions (rows_per_block apart), conv3's geometry, conv3's own forward
+// on the two-group bf16x6 64x64 instance, and a split the kernel holds.  in_net: also what makes the network take it --
+// neither conv2's nor conv3's own forward split over K (at least 128 tiles each) and one block per CU at the most.
+bool conv123_valid_envelope(const xt_conv_geom* g, const xt_input_xform* xf, const xt_conv_geom* g2, const xt_conv_geom* g3,
+                            int B, int rows_per_block, bool in_net, C123Plan* plan) {
+#ifdef XT_NO_FWD123_FLAT
+  return false;
+#endif
+  if (rows_per_block < 0 || !conv12_valid_envelope(g, xf, g2, B, 1)) return false;
+  if (tuning().direct_all) return false;                  // (conv3 would run on the register-direct kernel)
+  if (act_needs_preact(g3->act) || g3->C != 32 || g3->N != 64 || g3->KH != 3 || g3->KW != 3 || g3->S != 1 || g3->PT != 0 ||
+      g3->PL != 0)
+    return false;
+  if (g3->H != g2->OH || g3->W != g2->OW || g3->OH != g3->H - 2 || g3->OW != g3->W - 2 || g3->OH < 1 || g3->OW < 1) return false;
+  const long long M3 = (long long)B * g3->OH * g3->OW;
+  if (M3 * 64 * 4 >= (1ll << 31) || (M3 + 63) / 64 > 320) return false;       // store4_wt; conv3 leaves the two-group form
+  if (in_net) {
+    if (rows_per_block != 0) return false;
+    if (((long long)B * g2->OH * g2->OW + 127) / 128 < 128 || (M3 + 63) / 64 < 128) return false;
+  }
+  C123Plan pl;
+  if (!c123_plan(g, g2, g3, B, rows_per_block, &pl)) return false;
+  if (in_net && pl.nblk > kC12Blocks) return false;
+  if (plan) *plan = pl;
+  return true;
+}
+
+// returns 0 launched, 1 error, -1 outside the envelope (the caller then launches conv12 and conv3)
+int launch_conv123_valid_fwd(const xt_conv_geom* g, const xt_input_xform* xf, const xt_conv_geom* g2, const xt_conv_geom* g3,
+                             int B, const void* in, const int32_t* idx, const float* w, const float* bias, float* y,
+                             uint32_t* relu_mask, const float* w2, const float* b2, float* y2, const float* w3,
+                             const float* b3, float* y3, int rows_per_block, bool in_net, hipStream_t st, int* mask_written) {
+  if (mask_written) *mask_written = 0;
+  C123Plan pl;
+  if (!conv123_valid_envelope(g, xf, g2, g3, B, rows_per_block, in_net, &pl)) return -1;
+  C123Args k;
+  C12Args& a = k.c12;
+  a.c1.in = static_cast<const uint8_t*>(in); a.c1.idx = idx; a.c1.w = w; a.c1.bias = bias; a.c1.y = y;
+  a.c1.B = B; a.c1.H = g->H; a.c1.W = g->W; a.c1.OH = g->OH; a.c1.OW = g->OW; a.c1.S = g->S; a.c1.KH = g->KH; a.c1.act = g->act;
+  a.c1.xs = 1.f / xf->std; a.c1.xb = 0.f;
+  a.c1.mask = (g->act == XT_ACT_RELU) ? relu_mask : nullptr;
+  a.w2 = w2; a.b2 = b2; a.y2 = y2; a.OH2 = g2->OH; a.OW2 = g2->OW; a.act2 = g2->act;
+  a.T = B * g2->OH; a.q = 0; a.r = 0;
+  a.c1.img_cap = 2 * pl.cap; a.nps = pl.nps; a.tab_off = pl.tab_off;
+  k.c3.w3 = w3; k.c3.b3 = b3; k.c3.y3 = y3; k.c3.OH3 = g3->OH; k.c3.OW3 = g3->OW; k.c3.act3 = g3->act;
+  k.c3.T3 = B * g3->OH; k.c3.G = pl.G; k.c3.N = pl.N; k.c3.nps3 = pl.nps3;
+  static PerDeviceOnce attr_once;
+  attr_once.run([] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv123_u8_valid_fwd_flat_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kC12LdsLimit);
+    (void)hipGetLastError();
+  });
+  hipLaunchKernelGGL(conv123_u8_valid_fwd_flat_kernel, dim3(pl.nblk), dim3(512), (size_t)pl.lds, st, k);
   XT_LAUNCH_CHECK();
   if (mask_written && a.c1.mask) *mask_written = 1;
   return 0;
@@ -1963,6 +2228,47 @@ int launch_conv1_wgrad_bf16x3(const xt_conv_geom* g, const xt_input_xform* xf, i
 }
 
 }  // namespace xt
+
+int xt_conv123_valid_fwd(const xt_conv_geom* g0, const xt_input_xform* xf, const xt_conv_geom* g1, const xt_conv_geom* g2,
+                         int32_t B, const void* in, const int32_t* idx, const float* w0, const float* b0, float* act1,
+                         uint32_t* relu_mask, const float* w1, const float* b1, float* act2, const float* w2, const float* b2,
+                         float* act3, int32_t rows_per_block, void* stream) {
+  XT_REQUIRE(g0 && g1 && g2 && in && w0 && b0 && act1 && w1 && b1 && act2 && w2 && b2 && act3 && B > 0,
+             "xt_conv123_valid_fwd: null argument / bad batch");
+  const int rc = xt::launch_conv123_valid_fwd(g0, xf, g1, g2, B, in, idx, w0, b0, act1, relu_mask, w1, b1, act2, w2, b2, act3,
+                                              rows_per_block, false, xt::as_stream(stream), nullptr);
+  XT_REQUIRE(rc >= 0, "xt_conv123_valid_fwd: layers, batch %d or rows per block %d outside the fused kernel's envelope", B,
+             rows_per_block);
+  return rc;
+}
+
+int xt_conv123_valid_plan(const xt_conv_geom* g0, const xt_input_xform* xf, const xt_conv_geom* g1, const xt_conv_geom* g2,
+                          int32_t B, int32_t rows_per_block, int32_t* out, int32_t cap) {
+  XT_REQUIRE(g0 && g1 && g2 && out && cap >= XT_CONV123_PLAN_WORDS, "xt_conv123_valid_plan: null argument / too few words");
+  for (int i = 0; i < XT_CONV123_PLAN_WORDS; ++i) out[i] = 0;
+  out[XT_CONV123_PLAN_LDS_LIMIT] = xt::kC12LdsLimit;
+  xt::C123Plan pl;
+  if (B < 1 || !xt::conv123_valid_envelope(g0, xf, g1, g2, B, rows_per_block, false, &pl)) return 0;
+  out[XT_CONV123_PLAN_INSIDE] = 1;
+  out[XT_CONV123_PLAN_IN_NET] = xt::conv123_valid_envelope(g0, xf, g1, g2, B, rows_per_block, true, nullptr) ? 1 : 0;
+  out[XT_CONV123_PLAN_BLOCKS] = pl.nblk;
+  out[XT_CONV123_PLAN_GROUP_ROWS] = pl.G;
+  out[XT_CONV123_PLAN_GROUP_BLOCKS] = pl.N;
+  out[XT_CONV123_PLAN_LDS_BYTES] = pl.lds;
+  out[XT_CONV123_PLAN_MAX_CONV1_POS] = pl.maxpos;
+  out[XT_CONV123_PLAN_MAX_CONV2_POS] = pl.maxn2;
+  const int nb = (cap - XT_CONV123_PLAN_WORDS) / XT_CONV123_BLOCK_WORDS < pl.nblk
+                     ? (cap - XT_CONV123_PLAN_WORDS) / XT_CONV123_BLOCK_WORDS : pl.nblk;
+  for (int b = 0; b < nb; ++b) {
+    int32_t* o = out + XT_CONV123_PLAN_WORDS + b * XT_CONV123_BLOCK_WORDS;
+    int r0, r1, c0, c1, pn[xt::kC12Pieces], clo[xt::kC12Pieces], lbase[xt::kC12Pieces], own_all[xt::kC12Pieces], npos;
+    xt::c3_rows(b, B * g2->OH, pl.G, pl.N, g2->OH, g1->OH, &r0, &r1, &c0, &c1);
+    xt::c12_pieces(c0, c1, g1->OH, g0->OW, pn, clo, lbase, own_all, &npos);
+    o[0] = r0; o[1] = r1; o[2] = c0; o[3] = c1; o[4] = c0 / g1->OH; o[5] = npos;
+    for (int i = 0; i < xt::kC12Pieces; ++i) { o[6 + 3 * i] = pn[i]; o[7 + 3 * i] = clo[i]; o[8 + 3 * i] = own_all[i]; }
+  }
+  return 0;
+}
 
 int xt_conv12_valid_fwd(const xt_conv_geom* g0, const xt_input_xform* xf, const xt_conv_geom* g1, int32_t B, const void* in,
                         const int32_t* idx, const float* w0, const float* b0, float* act1, uint32_t* relu_mask,

@@ -94,6 +94,17 @@ int launch_conv12_valid_fwd(const xt_conv_geom* g, const xt_input_xform* xf, con
                             const void* in, const int32_t* idx, const float* w, const float* bias, float* y,
                             uint32_t* relu_mask, const float* w2, const float* b2, float* y2, int rows_per_block,
                             hipStream_t st, int* mask_written);
+// PpoCnn's conv1 -> conv2 -> conv3 (3x3/1 VALID 32 -> 64 behind the pair above) in one launch, blocks owning runs of whole
+// conv3 rows (conv123_u8_valid_fwd_flat_kernel); every output bit what the conv12 launch followed by conv3's own writes.
+// rows_per_block: 0 = the automatic split.  in_net: the envelope in which the network takes it (neither conv2's nor
+// conv3's own forward split over K, one block per CU at the most).  plan (may be null): the split and its LDS layout.
+struct C123Plan { int G, N, nblk, cap, maxpos, maxn2, nps, nps3, tab_off, lds; };
+bool conv123_valid_envelope(const xt_conv_geom* g, const xt_input_xform* xf, const xt_conv_geom* g2, const xt_conv_geom* g3,
+                            int B, int rows_per_block, bool in_net, C123Plan* plan);
+int launch_conv123_valid_fwd(const xt_conv_geom* g, const xt_input_xform* xf, const xt_conv_geom* g2, const xt_conv_geom* g3,
+                             int B, const void* in, const int32_t* idx, const float* w, const float* bias, float* y,
+                             uint32_t* relu_mask, const float* w2, const float* b2, float* y2, const float* w3,
+                             const float* b3, float* y3, int rows_per_block, bool in_net, hipStream_t st, int* mask_written);
 
 // ------------------------------------------------------------------ xt_heads.hip: heads and losses
 int launch_act_apply(const float* z, float* y, long long count, int act, hipStream_t st);

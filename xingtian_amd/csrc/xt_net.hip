@@ -141,6 +141,7 @@ struct xt_net {
   int last_head_path = 0;
   int gauss_fused = 0;                // xt_net_set_gauss_fused: a DiagGaussian step inside the envelope takes the fused head launch
   int fwd_fuse12_flat = 1;            // xt_net_set_fwd_fuse12_flat: PpoCnn's conv1 -> conv2 forward as one launch inside its envelope
+  int fwd_fuse123_flat = 1;           // xt_net_set_fwd_fuse123_flat: ... and conv3 in the same launch inside its narrower one
   // xt_net_set_dist / xt_net_set_quant: the mark of a distributional Q head (at most one of the two).  head_group: columns
   // per action (atoms of a C51 head, quantiles of a QR-DQN one; 0: a scalar head -- A is actions * head_group wide);
   // head_kind says which; then the C51 support and the quantile head's Huber threshold
@@ -153,6 +154,7 @@ struct xt_net {
   int head_duel = 0;                  // xt_net_set_duel: the head's last group of head_group columns is the state-value stream
   // xt_net_last_step_report: what the most recent forward / backward / tail decided (host words, read by nothing else)
   int last_fuse12 = 0, last_fuse21 = 0, last_tail_mode = 0, last_finish_form = -1;
+  int last_fuse123 = 0;               // the last forward ran conv123_u8_valid_fwd_flat_kernel (the report's tail word)
   // xt_net_set_impala_stats: the caller's running sums and per-trajectory rows [itraj_max][XT_IMPALA_TRAJ_STATS_FLOATS] (both
   // null: off)
   double* istats = nullptr;
@@ -270,7 +272,7 @@ static int net_forward(xt_net* n, const void* obs, const int32_t* idx, int B, bo
   for (int tr = 0; tr < n->n_trunks; ++tr) {
     const void* x = obs;
     const int l0 = n->t_begin[tr];
-    if (tr == 0) n->last_fuse12 = 0;
+    if (tr == 0) n->last_fuse12 = n->last_fuse123 = 0;
     for (int l = l0; l < n->t_end[tr]; ++l) {
       Layer& L = n->layers[l];
       const bool first = (l == n->t_begin[tr]);
@@ -295,6 +297,30 @@ static int net_forward(xt_net* n, const void* obs, const int32_t* idx, int B, bo
           n->last_fuse12 = 1;
           x = n->ws + L2.act_off;
           ++l;
+          continue;
+        }
+      }
+      if (first && n->fwd_fuse123_flat && n->fwd_fuse12_flat && l + 3 < n->t_end[tr] && L.z_off < 0 &&
+          n->layers[l + 1].z_off < 0 && n->layers[l + 2].z_off < 0 && fwd_split(n->layers[l + 1], B) == 1 &&
+          fwd_split(n->layers[l + 2], B) == 1 &&
+          conv123_valid_envelope(&L.g, &n->xf, &n->layers[l + 1].g, &n->layers[l + 2].g, B, 0, true, nullptr)) {
+        // ... and conv3 behind them in the same launch, blocks owning runs of whole conv3 rows: every bit of the three
+        // activations and of the sign mask what the conv12 launch below and conv3's own write.  Only where neither conv2's
+        // nor conv3's own forward would be split over K, and never for a trunk's last layer (its split may be deferred).
+        Layer &L2 = n->layers[l + 1], &L3 = n->layers[l + 2];
+        if (int rcj = join_pending_update(n, st)) return rcj;      // (the launch reads the other layers' weights too)
+        const int rc = launch_conv123_valid_fwd(&L.g, &n->xf, &L2.g, &L3.g, B, x, idx, w_of(n, L), b_of(n, L), n->ws + L.act_off,
+                                                L.mask_off >= 0 ? reinterpret_cast<uint32_t*>(n->ws + L.mask_off) : nullptr,
+                                                w_of(n, L2), b_of(n, L2), n->ws + L2.act_off, w_of(n, L3), b_of(n, L3),
+                                                n->ws + L3.act_off, 0, true, st, &L.mask_valid);
+        if (rc > 0) return rc;
+        if (rc == 0) {
+          L2.last_ksplit = L3.last_ksplit = 1;
+          L2.mask_valid = L3.mask_valid = 0;
+          L2.last_deferred = L3.last_deferred = 0;
+          n->last_fuse123 = 1;
+          x = n->ws + L3.act_off;
+          l += 2;
           continue;
         }
       }
@@ -837,7 +863,7 @@ template <typename F>
 static int graph_run(xt_net* net, const char* key_in, hipStream_t st, F enqueue) {
   // every cached graph holds a forward: the fused / two-launch first layers never replay each other's graph
   // (... nor do the two forms of the Dense backward, xt_bwd_dense_lean_set)
-  const std::string key = std::string(key_in) + (net->fwd_fuse12_flat ? "|F1" : "|F0") + (bwd_dense_lean() ? "" : "|L0");
+  const std::string key = std::string(key_in) + (net->fwd_fuse12_flat ? "|F1" : "|F0") + (net->fwd_fuse123_flat ? "|T1" : "") + (bwd_dense_lean() ? "" : "|L0");
   xt_net::GraphSlot* slot = nullptr;
   for (auto& g : net->gslots) if (g.exec && g.key == key) slot = &g;
   if (!slot) {
@@ -2171,6 +2197,12 @@ int xt_net_set_fwd_fuse12_flat(xt_net* net, int32_t on) {
   return 0;
 }
 
+int xt_net_set_fwd_fuse123_flat(xt_net* net, int32_t on) {
+  XT_REQUIRE(net, "xt_net_set_fwd_fuse123_flat: null net");
+  net->fwd_fuse123_flat = on ? 1 : 0;
+  return 0;
+}
+
 int xt_net_set_impala_stats(xt_net* net, double* stats, float* traj_stats, int32_t max_traj) {
   XT_REQUIRE(net, "xt_net_set_impala_stats: null net");
   if (!stats && !traj_stats) {
@@ -2343,6 +2375,7 @@ int xt_net_last_step_report(const xt_net* n, int32_t* out, int32_t cap) {
     o[XT_STEP_REPORT_L_NPRE] = L.last_npre;
     o[XT_STEP_REPORT_L_TRUNK] = L.trunk;
   }
+  if (cap >= need + XT_STEP_TAIL_WORDS) out[need + XT_STEP_TAIL_FWD_FUSE123] = n->last_fuse123;
   return 0;
 }
 

@@ -209,6 +209,11 @@ SIGNATURES = {
     "xt_bwd_dense_lean_set": (c_int32, [c_int32]),      # (process-wide; returns the previous value)
     "xt_conv12_valid_fwd": (c_int32, [POINTER(ConvGeom), POINTER(InputXform), POINTER(ConvGeom), c_int32, _P, _P, _P, _P, _P,
                                       _P, _P, _P, _P, c_int32, _P]),
+    "xt_net_set_fwd_fuse123_flat": (c_int32, [_P, c_int32]),
+    "xt_conv123_valid_fwd": (c_int32, [POINTER(ConvGeom), POINTER(InputXform), POINTER(ConvGeom), POINTER(ConvGeom), c_int32,
+                                       _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, _P]),
+    "xt_conv123_valid_plan": (c_int32, [POINTER(ConvGeom), POINTER(InputXform), POINTER(ConvGeom), POINTER(ConvGeom), c_int32,
+                                        c_int32, _P, c_int32]),
     "xt_net_set_impala_stats": (c_int32, [_P, _P, _P, c_int32]),
     "xt_impala_loss_stats": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P, _P,
                                        _P, _P, POINTER(c_int32)]),
@@ -324,6 +329,7 @@ GRAPH_CACHE_SLOTS = 8     # graphs one net holds (xt_net.hip: gslots)
 STEP_REPORT_NET = ("WORDS", "LAYERS", "TRUNKS", "FWD_FUSE12", "BWD_FUSE21", "HEAD_PATH", "TAIL_OVERLAP", "FINISH_FORM",
                    "FINISH_BLOCKS", "PARTIAL_FLOATS", "MAX_NORM_PARTIALS", "HEAD_CHUNKS")
 STEP_REPORT_LAYER = ("KSPLIT", "DEFERRED", "MSPLIT", "SLAB_CAP", "MASK_VALID", "PREACT", "NPRE", "TRUNK")
+STEP_REPORT_TAIL = ("FWD_FUSE123",)      # XT_STEP_TAIL_*: behind the layers' words, not counted in WORDS
 MAX_TRUNK_LAYERS = 9      # kMaxTrunkLayers: trunk layers of one net, both trunks counted (xt_net_create refuses more)
 
 
@@ -391,13 +397,14 @@ def set_bwd_dense_lean(on=True):
 def step_report(handle):
     """``xt_net_last_step_report`` of a net handle -> dict of the net's facts (lower-case names of ``STEP_REPORT_NET``) with
     ``layer`` = list of per-layer dicts (``STEP_REPORT_LAYER``).  Host words only: nothing is launched."""
-    cap = len(STEP_REPORT_NET) + len(STEP_REPORT_LAYER) * 64
+    cap = len(STEP_REPORT_NET) + len(STEP_REPORT_LAYER) * 64 + len(STEP_REPORT_TAIL)
     buf = (c_int32 * cap)()
     check(load().xt_net_last_step_report(handle, buf, cap), "xt_net_last_step_report")
     out = {k.lower(): int(buf[i]) for i, k in enumerate(STEP_REPORT_NET)}
     nl, lw = len(STEP_REPORT_NET), len(STEP_REPORT_LAYER)
     out["layer"] = [{k.lower(): int(buf[nl + lw * l + i]) for i, k in enumerate(STEP_REPORT_LAYER)}
                     for l in range(out["layers"])]
+    out.update({k.lower(): int(buf[out["words"] + i]) for i, k in enumerate(STEP_REPORT_TAIL)})      # (behind the WORDS words)
     return out
 
 

@@ -543,6 +543,15 @@ class HipActorCritic(object):
         L.check(self.lib.xt_net_set_fwd_fuse12_flat(self.handle, 1 if on else 0), "xt_net_set_fwd_fuse12_flat")
         self.fwd_fuse12_flat_on = bool(on)
 
+    fwd_fuse123_flat_on = True
+
+    def set_fwd_fuse123_flat(self, on=True):
+        """C ABI ``xt_net_set_fwd_fuse123_flat``: PpoCnn's conv1 -> conv2 -> conv3 forward as ONE launch
+        (``conv123_u8_valid_fwd_flat_kernel``) where the batch is inside that kernel's envelope (201 .. 320 frames of
+        84x84), bit for bit the separate launches' results.  On by default; needs ``set_fwd_fuse12_flat`` on."""
+        L.check(self.lib.xt_net_set_fwd_fuse123_flat(self.handle, 1 if on else 0), "xt_net_set_fwd_fuse123_flat")
+        self.fwd_fuse123_flat_on = bool(on)
+
     # ------------------------------------------------------------------ per-train IMPALA v-trace diagnostics (opt-in)
     impala_stats_on = False
 
