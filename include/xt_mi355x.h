@@ -1588,6 +1588,103 @@ int xt_noisy_grads(const xt_noisy_layer* layers, int32_t n_layers, const float* 
  * graphs are captured outside a net (a net's own cached hipGraphs carry it in their key). */
 int xt_bwd_dense_lean_set(int32_t on);
 
+/* ------------------------------------------------------------------ MuZero: the unrolled model update (appended under ABI 12)
+ * Three layer chains with shared weights in ONE flat parameter buffer (xt/model/muzero/muzero_model.py:103-140):
+ *   rep   obs -> h_0                       n_rep Dense layers on float32 observations (relu, the last one N == hidden)
+ *   dyn   [h_i | onehot(a_i)] -> t_i       n_dyn - 2 trunk layers (the first one has C == hidden + action_dim), then
+ *         h_{i+1} = relu(Dense_h(t_i))     layer n_dyn - 2 (N == hidden)
+ *         r_{i+1} = softmax(Dense_r(t_i))  layer n_dyn - 1 (N == reward_support)
+ *   pred  h_k -> q_k                       n_pred - 2 trunk layers, then
+ *         v_k = softmax(Dense_v(q_k))      layer n_pred - 2 (N == value_support)
+ *         p_k = softmax(Dense_p(q_k))      layer n_pred - 1 (N == action_dim)
+ * Every layer's block is [K, N] kernel + [N] bias at param_off; the rep chain runs on the trunk-layer kernels (C and N
+ * multiples of 4, blocks 16-byte aligned), the Dense layers of dyn and pred on the kernels of xt_muzero.hip (any width).
+ * The hidden states of all unroll + 1 steps are stacked as [(unroll + 1) * B, hidden], step k in rows [k B, (k + 1) B):
+ * the prediction chain's forward, backward and weight gradient run once over the stack, the reward head and every dyn
+ * layer's weight gradient once over the unroll * B rows of the dynamics steps; only the dyn chain itself is sequential.
+ * No atomics; every sum has a fixed order, so a step is bit-identical from run to run.
+ *
+ * Loss (the weight-decay term of the reference is a constant of its graph and is left out):
+ *   ce(p, t) = -(1 / (B N)) sum_b sum_j t_bj log(p_bj + 1e-10)
+ *   L = ce(p_0, pi_0) + ce(v_0, z_0) + sum_{i < U} [ce(r_{i+1}, u_i) + ce(p_{i+1}, pi_{i+1}) + ce(v_{i+1}, z_{i+1})]
+ * Gradient: the terms of unroll step i carry 1 / U; the gradient that dyn step k sends into h_k is halved for k >= 1. */
+typedef struct xt_mz xt_mz;
+
+#define XT_MZ_MAX_UNROLL 16
+#define XT_MZ_MAX_CHAIN 8
+
+typedef struct xt_mz_desc {
+  int32_t n_rep, n_dyn, n_pred;
+  const xt_layer_desc* rep;
+  const xt_layer_desc* dyn;
+  const xt_layer_desc* pred;
+  int32_t hidden, action_dim, value_support, reward_support, unroll;
+  int32_t obs_dim;               /* width of the float32 observation vector the first rep layer reads      */
+  int64_t n_params;              /* floats of the flat buffer (a multiple of 4)                             */
+  double value_min, value_max, reward_min, reward_max;
+} xt_mz_desc;
+
+typedef struct xt_mz_cfg {
+  float lr, beta1, beta2, eps;   /* tf.train.AdamOptimizer(lr): 0.9, 0.999, 1e-8; no clipping               */
+} xt_mz_cfg;
+
+/* Refused with a message: unroll outside [1, XT_MZ_MAX_UNROLL], a support below 2, action_dim below 1, max <= min, a
+ * chain that is too short, too long or whose widths do not meet, a rep layer that is not a Dense layer. */
+int xt_mz_create(const xt_mz_desc* desc, int32_t max_batch, xt_mz** out);
+void xt_mz_destroy(xt_mz* mz);
+int64_t xt_mz_workspace_bytes(const xt_mz* mz);
+/* Buffers stay caller-owned, as with xt_net_bind: params / grads / adam_m / adam_v hold n_params floats (grads zeroed by
+ * the caller: the padding between blocks is never written), adam_state 8 floats (xt_adam_state_init). */
+int xt_mz_bind(xt_mz* mz, float* params, float* grads, float* adam_m, float* adam_v, float* adam_state, void* workspace,
+               int64_t workspace_bytes);
+/* One whole gradient step, enqueued without synchronising: forward, loss, backward; grads is complete behind it.
+ *   obs            float32 [., obs_dim]: the observation store; sample b is row idx[b] (idx may be NULL: row b)
+ *   actions        int32 [B, unroll]; an action outside [0, action_dim) conditions on a zero row, as tf.one_hot does
+ *   target_value   float64 [B, unroll + 1], target_reward the same: scalars, made two-hot on the device
+ *   target_policy  float32 [B, unroll + 1, action_dim]
+ *   loss_out       1 double: L */
+int xt_mz_step(xt_mz* mz, const void* obs, const int32_t* idx, int32_t B, const int32_t* actions,
+               const double* target_value, const double* target_reward, const float* target_policy, const xt_mz_cfg* cfg,
+               double* loss_out, void* stream);
+/* xt_adam_tf_clip over the flat gradient with a clip factor of exactly 1.0f */
+int xt_mz_apply(xt_mz* mz, const xt_mz_cfg* cfg, void* stream);
+/* Forward only.  policy [B, action_dim], value [B, value_support] (softmax outputs), hidden [B, hidden]. */
+int xt_mz_initial(xt_mz* mz, const void* obs, const int32_t* idx, int32_t B, float* policy, float* value, float* hidden,
+                  void* stream);
+/* hidden_in [B, hidden], action int32 [B] -> hidden_out, reward [B, reward_support], policy, value */
+int xt_mz_recurrent(xt_mz* mz, const float* hidden_in, const int32_t* action, int32_t B, float* hidden_out, float* reward,
+                    float* policy, float* value, void* stream);
+
+/* The loss head stand-alone: softmax + target + cross-entropy + d(logits) for nblk blocks of B rows, N wide.
+ *   logits [nblk * B, N]; row r = k * B + b takes its target from column k of sample b:
+ *   target_dense   (may be NULL) float32 [B, S, N]: row (b, k) as given
+ *   target_scalar  (else) float64 [B, S]: the two-hot row of clip(t, tmin, tmax) - tmin, compressed by
+ *                  c = sign(x) (sqrt(|x| + 1) - 1) + 0.001 x in float64: 1 - rest on floor(c), rest on floor(c) + 1, each
+ *                  rounded once; a floor at or beyond N - 1 puts the whole mass on bin N - 1; nothing leaves the row
+ *   p = softmax (float32, maximum subtracted);  w = t / (p + 1e-10);  dz_j = s / (B N) p_j (sum_i w_i p_i - w_j) with
+ *   s = scale0 for block 0 and scale_rest behind it;  rowloss[r] = -(sum_j t_j log(p_j + 1e-10)) / (B N)  (float64)
+ *   probs, dz (each may be NULL) [nblk * B, N]; rowloss float64 [nblk * B]; loss_out (may be NULL) 1 double: the rows'
+ *   sum in a fixed order.  N <= 64: one wavefront per row, else one workgroup per row.  2 <= N <= 65536. */
+int xt_mz_loss(const float* logits, int32_t nblk, int32_t B, int32_t N, int32_t S, const float* target_dense,
+               const double* target_scalar, double tmin, double tmax, float scale0, float scale_rest, float* probs,
+               float* dz, double* rowloss, double* loss_out, void* stream);
+
+/* The conditioned first dynamics layer stand-alone, without materialising [h | onehot(a)]: w [hidden + A, N], bias [N].
+ * Rows are nblk blocks of B: row r = i * B + b is conditioned on actions[b * a_stride + i].
+ *   forward   y = act(((sum_{k ascending} h_k w[k]) + w[hidden + a]) + bias), float32 without contraction */
+int xt_mz_cond_fwd(const float* h, const int32_t* actions, int32_t a_stride, int32_t nblk, int32_t B, int32_t hidden,
+                   int32_t A, int32_t N, const float* w, const float* bias, int32_t act, float* y, void* stream);
+/*   backward  dy [nblk * B, N] is d(pre-activation).
+ *   dwb [(hidden + A + 1) * N]: dW[k] = sum_r h_rk dy_r, dW[hidden + a] = sum_{r: a_r == a} dy_r (zero where nobody took
+ *   a), db = sum_r dy_r; rows summed in ascending r inside slabs of XT_MZ_WGRAD_ROWS rows, the slabs then in ascending
+ *   order (slabs: scratch of ceil(rows / XT_MZ_WGRAD_ROWS) * (hidden + A + 1) * N floats, may be NULL for one slab)
+ *   g [nblk * B, hidden] = relu'(h) * (g_pred + c * sum_{n ascending} dy_n w[k, n])   (the hidden-state join; g_pred may be
+ *   NULL: 0;  wt: scratch of N * hidden floats for the transposed kernel) */
+#define XT_MZ_WGRAD_ROWS 128
+int xt_mz_cond_bwd(const float* h, const int32_t* actions, int32_t a_stride, int32_t nblk, int32_t B, int32_t hidden,
+                   int32_t A, int32_t N, const float* w, const float* dy, const float* g_pred, float c, float* g, float* dwb,
+                   float* slabs, float* wt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,21 @@ class NoisyLayer(Structure):
                 ("index", c_int32), ("reserved", c_int32)]
 
 
+class MzDesc(Structure):
+    """xt_mz_desc of include/xt_mi355x.h"""
+    _fields_ = [("n_rep", c_int32), ("n_dyn", c_int32), ("n_pred", c_int32), ("rep", POINTER(LayerDesc)),
+                ("dyn", POINTER(LayerDesc)), ("pred", POINTER(LayerDesc)), ("hidden", c_int32), ("action_dim", c_int32),
+                ("value_support", c_int32), ("reward_support", c_int32), ("unroll", c_int32), ("obs_dim", c_int32),
+                ("n_params", c_int64),
+                ("value_min", c_double), ("value_max", c_double), ("reward_min", c_double), ("reward_max", c_double)]
+
+
+class MzCfg(Structure):
+    """xt_mz_cfg of include/xt_mi355x.h"""
+    _fields_ = [("lr", c_float), ("beta1", c_float), ("beta2", c_float), ("eps", c_float)]
+
+
+MZ_MAX_UNROLL, MZ_MAX_CHAIN, MZ_WGRAD_ROWS = 16, 8, 128               # XT_MZ_MAX_UNROLL / _MAX_CHAIN / _WGRAD_ROWS
 NOISY_MAX_LAYERS = 8     # XT_NOISY_MAX_LAYERS
 
 
@@ -318,6 +333,20 @@ SIGNATURES = {
                                          _P, _P, _P, _P, _P, _P]),
     "xt_net_set_duel": (c_int32, [_P, c_int32]),
     "xt_heads_dfeat_duel": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, _P]),
+    # (the MuZero entries, xt_muzero.hip)
+    "xt_mz_create": (c_int32, [POINTER(MzDesc), c_int32, POINTER(c_void_p)]),
+    "xt_mz_destroy": (None, [_P]),
+    "xt_mz_workspace_bytes": (c_int64, [_P]),
+    "xt_mz_bind": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64]),
+    "xt_mz_step": (c_int32, [_P, _P, _P, c_int32, _P, _P, _P, _P, POINTER(MzCfg), _P, _P]),
+    "xt_mz_apply": (c_int32, [_P, POINTER(MzCfg), _P]),
+    "xt_mz_initial": (c_int32, [_P, _P, _P, c_int32, _P, _P, _P, _P]),
+    "xt_mz_recurrent": (c_int32, [_P, _P, _P, c_int32, _P, _P, _P, _P, _P]),
+    "xt_mz_loss": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, _P, _P, c_double, c_double, c_float, c_float, _P, _P, _P,
+                             _P, _P]),
+    "xt_mz_cond_fwd": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, c_int32, _P, _P]),
+    "xt_mz_cond_bwd": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_float, _P, _P, _P,
+                                 _P, _P]),
     "xt_noisy_compose": (c_int32, [POINTER(NoisyLayer), c_int32, _P, _P, c_int64, _P, _P, ctypes.c_uint64, ctypes.c_uint64,
                                    c_int32, c_int32, _P]),
     "xt_noisy_grads": (c_int32, [POINTER(NoisyLayer), c_int32, _P, _P, _P]),

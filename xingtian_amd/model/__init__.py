@@ -12,3 +12,4 @@ def model_builder(model_info):
 from xingtian_amd.model.ppo import ppo_cnn, ppo_mlp  # noqa: E402,F401
 from xingtian_amd.model.impala import impala_cnn, impala_cnn_opt  # noqa: E402,F401
 from xingtian_amd.model.dqn import dqn_cnn, dqn_mlp  # noqa: E402,F401
+from xingtian_amd.model.muzero import muzero_model, muzero_mlp, muzero_cnn  # noqa: E402,F401
