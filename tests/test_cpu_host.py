@@ -1081,6 +1081,66 @@ def test_ring_set_reaps_pinned_rings_whose_slots_are_all_held():
         rs.close()
 
 
+def test_rings_with_a_page_locked_mirror_deliver_and_publish_the_same_bytes():
+    """pin() on a runtime that registers no existing memory gives the ring a page-locked MIRROR of its segment (here: a plain
+    array, fake events, no GPU).  ShmRing: the sink's views of a received message lie in the mirror's slot, hold what was sent
+    and stay intact until the slot is released, through several laps of a two-slot ring.  WeightsRing: what a copy left in the
+    mirror's slot is what a reader fetches after the commit -- and nothing of it before."""
+    from types import SimpleNamespace
+    from xingtian_amd import transport
+
+    class Done(object):
+        def query(self):
+            return True
+
+        def synchronize(self):
+            pass
+
+    ring = transport.ShmRing(slots=2, slot_bytes=1 << 16)
+    ring._mirror, ring.pinned = np.zeros(ring.shm.size, np.uint8), True
+    try:
+        lo = ring._mirror.ctypes.data
+        kept = []
+
+        def sink(d, ctr_info=None):
+            assert ctr_info["_pinned_views"] and lo <= d["x"].ctypes.data < lo + ring._mirror.nbytes
+            assert d["x"].ctypes.data - lo >= ring._base + (ctr_info["seq"] % 2) * ring.slot_bytes      # its own slot
+            kept.append((ctr_info["seq"], d["x"]))
+            ctr_info["_slot_guard"].hold(Done())
+
+        for i in range(5):
+            assert ring.send_bytes(transport.encode({"seq": i}, {"x": np.arange(i, i + 1001, dtype=np.int32)}), block=False)
+            assert ring.recv_into(sink, block=False)["seq"] == i
+            for seq, x in kept[-2:]:                       # this message's slot and the other one's: both still intact
+                assert np.array_equal(x, np.arange(seq, seq + 1001, dtype=np.int32))
+        assert ring.reap() == 0
+    finally:
+        kept = None
+        ring.pinned = False
+        ring.close()
+
+    spec = SimpleNamespace(names={"w": (0, (3, 5)), "b": (15, (5,))}, store_shape={})
+    wring = transport.WeightsRing(slot_bytes=1 << 12, slots=3)
+    wring._mirror, wring.pinned = np.zeros(wring.shm.size, np.uint8), True
+    reader = transport.WeightsRing(name=wring.name, slot_bytes=1 << 12, slots=3, create=False)
+    try:
+        for step in range(4):                              # (more publishes than slots)
+            flat = np.arange(20, dtype=np.float32) + 100 * step
+            k, i, base = wring._reserve_flat(spec, flat.nbytes, {"train_count": step})
+            o = wring._payload_offset(i) + base
+            wring._mirror[o:o + flat.nbytes] = flat.view(np.uint8)          # "the device's copy has landed"
+            wring.publish_enqueued((k, i, base + flat.nbytes, None, None, Done()))
+            assert reader.fetch() is None and reader.latest() == step
+            assert wring.commit_flat_publish() == k == step + 1
+            seq, ctr, got = reader.fetch()
+            assert seq == k and ctr["train_count"] == step
+            assert np.array_equal(got["w"], flat[:15].reshape(3, 5)) and np.array_equal(got["b"], flat[15:])
+    finally:
+        reader.close()
+        wring.pinned = False
+        wring.close()
+
+
 def test_image_observations_with_three_channels_pad_to_four_exactly():
     """examples/ant_ppo.yaml / dog_ppo.yaml: PpoCnn on [84, 84, 3] uint8 (the reference's get_cnn_backbone takes any
     channel count, xt/model/model_utils.py:49-80).  The first layer is stored as a [8, 8, 4, 32] block whose fourth

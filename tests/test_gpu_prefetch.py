@@ -216,7 +216,8 @@ def test_the_copy_kernels_sequence_number_is_only_seen_behind_the_whole_paramete
 def test_sdma_copies_through_the_hsa_runtime_of_the_process():
     """csrc/xt_sdma.hip through the C ABI: ticketed page-locked-host -> device copies (xt_dma_h2d_async / xt_dma_wait_upto:
     tickets count up, ``upto`` covers every earlier copy, the query form) out of a torch pinned tensor and out of a
-    hipHostRegister'ed /dev/shm ring, and the synchronous device -> host copy (xt_sdma_copy_d2h) back into both; bytes exact."""
+    page-locked weights ring (the hipHostRegister'ed /dev/shm segment, or the ring's page-locked mirror where the runtime
+    registers none), and the synchronous device -> host copy (xt_sdma_copy_d2h) back into both; bytes exact."""
     import ctypes
     from xingtian_amd import lib as L, transport
     lib = L.load()
@@ -224,7 +225,7 @@ def test_sdma_copies_through_the_hsa_runtime_of_the_process():
     rng = np.random.default_rng(2)
     ring = transport.WeightsRing(slot_bytes=8 << 20, slots=2)
     assert ring.pin()
-    shm = np.frombuffer(ring.shm.buf, dtype=np.float32, count=n, offset=8192 + 328)
+    shm = np.frombuffer(ring.page_locked(), dtype=np.float32, count=n, offset=8192 + 328)
     shm_addr = ring._pin_addr + 8192 + 328
     pinned = torch.empty(n, dtype=torch.float32, pin_memory=True)
     try:

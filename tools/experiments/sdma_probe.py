@@ -20,7 +20,7 @@ ring = transport.WeightsRing(slot_bytes=8 << 20, slots=4)
 assert ring.pin()
 pinned = torch.zeros(n, dtype=torch.float32, pin_memory=True)
 dst_shm = ring._pin_addr + 8192 + 328
-view = np.frombuffer(ring.shm.buf, dtype=np.float32, count=n, offset=8192 + 328)
+view = np.frombuffer(ring.page_locked(), dtype=np.float32, count=n, offset=8192 + 328)
 for name, dst, chk in (("pinned", pinned.data_ptr(), pinned.numpy()), ("shm", dst_shm, view)):
     t0 = time.perf_counter()
     for _ in range(5):

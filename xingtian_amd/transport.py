@@ -21,7 +21,8 @@ rollout batches to the learner (``cmd: train``) and weight dicts back to the exp
   ``put_raw_buffer`` / ``get_buffers`` pair plus its control queue, without a server process.  ``send`` / ``recv``
   keep the reference channel's ``(ctr_info, data)`` contract.  ``pin()`` (learner side) page-locks the ring with
   ``hipHostRegister``: the ingest then DMA-copies the uint8 frames to HBM straight out of the slot -- wire -> HBM with
-  NO host copy on the learner side.
+  NO host copy on the learner side.  A runtime that cannot register existing memory gets a mirror of the ring that was
+  allocated page-locked (``_page_lock``): one host copy per message, everything else unchanged.
 
 * ``Prefetcher`` -- learner side, asynchronous algorithms (IMPALA): a thread that owns the consumer end of a ring / ring set
   and hands every message to the algorithm's ingest AS IT ARRIVES, so the H2D of train k+1's messages runs under the GPU's
@@ -30,7 +31,7 @@ rollout batches to the learner (``cmd: train``) and weight dicts back to the exp
   to the explorers) by a helper thread when it lands; the learner thread does not wait (as the reference's learner hands the
   weights object to its send queue, xt/framework/learner.py:361-374).
 
-Plumbing only: no arithmetic; the only GPU-runtime call is the optional ``hipHostRegister`` of ``pin()``.
+Plumbing only: no arithmetic; the only GPU-runtime call is the optional page-locking of ``pin()``.
 """
 import struct
 import threading
@@ -166,6 +167,37 @@ class SlotGuard(object):
         self.event = event
 
 
+def _page_lock(shm):
+    """Make ``shm`` (a ``SharedMemory`` segment) reachable for the GPU's copy engines.  -> (address of the page-locked
+    range, uint8 array over a page-locked MIRROR of the segment or None, the HIP runtime or None), or None (no GPU runtime).
+
+    First choice: ``hipHostRegister`` of the segment's own pages -- copies then run straight out of / into shared memory.
+    Where the runtime cannot page-lock memory a process already has (it refuses with an error that also stays behind for the
+    next launch to report: cleared here), the ring gets a block of the segment's size that is ALLOCATED page-locked (torch's
+    pinned allocator, ``hipHostMalloc``): offset for offset the segment's layout, the device copies to / from it and the ring
+    moves the payload between it and the segment with one host copy (``ShmRing.recv_into``, ``WeightsRing.commit_flat_publish``)."""
+    import ctypes
+    try:
+        hip = ctypes.CDLL("libamdhip64.so")
+    except OSError:
+        return None
+    probe = np.frombuffer(shm.buf, dtype=np.uint8)
+    addr = int(probe.ctypes.data)
+    del probe
+    hip.hipHostRegister.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint]
+    hip.hipHostRegister.restype = ctypes.c_int
+    if hip.hipHostRegister(ctypes.c_void_p(addr), ctypes.c_size_t(shm.size), 0) == 0:
+        return addr, None, hip
+    hip.hipGetLastError.restype = ctypes.c_int
+    hip.hipGetLastError()
+    import torch
+    try:
+        block = torch.empty(shm.size, dtype=torch.uint8, pin_memory=True)
+    except RuntimeError:
+        return None
+    return int(block.data_ptr()), block.numpy(), None
+
+
 class ShmRing(object):
     """Single-producer / single-consumer ring of ``slots`` x ``slot_bytes`` in POSIX shared memory.
 
@@ -187,29 +219,24 @@ class ShmRing(object):
         self._len = np.ndarray((self.slots,), dtype=np.uint64, buffer=self.shm.buf, offset=_ALIGN)
         self._base = _ALIGN + 8 * self.slots
         self.pinned = False
+        self._mirror = None        # pin(): the page-locked copy of the slots where the segment itself cannot be registered
         self._held = []            # consumer side: guards of delivered messages whose slot is not released yet
         self._taken = 0            # ... and their number (tail has not advanced past them)
 
     def pin(self):
         """Learner side, optional: page-lock the ring with the HIP runtime (``hipHostRegister``) so that the arrays
         of a received message can be DMA-copied to HBM straight out of the slot -- no staging copy at all
-        (``recv_into`` then tells the sink that its views are pinned).  Needs a GPU process; returns True on success."""
-        import ctypes
+        (``recv_into`` then tells the sink that its views are pinned).  Where the runtime cannot register the segment the
+        ring keeps a page-locked mirror of its slots (``_page_lock``): ``recv_into`` moves a message into the mirror's slot
+        with one host copy and the sink's views point there.  Needs a GPU process; returns True on success."""
         if self.pinned:
             return True
-        try:
-            hip = ctypes.CDLL("libamdhip64.so")
-            self._hip = hip
-            probe = np.frombuffer(self.shm.buf, dtype=np.uint8)
-            self._pin_addr = int(probe.ctypes.data)
-            del probe
-            hip.hipHostRegister.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint]
-            hip.hipHostRegister.restype = ctypes.c_int
-            rc = hip.hipHostRegister(ctypes.c_void_p(self._pin_addr), ctypes.c_size_t(self.shm.size), 0)
-        except OSError:
+        locked = _page_lock(self.shm)
+        if locked is None:
             return False
-        self.pinned = (rc == 0)
-        return self.pinned
+        self._pin_addr, self._mirror, self._hip = locked
+        self.pinned = True
+        return True
 
     # ---- producer side
     def send(self, ctr_info, data, block=True, timeout=None, pack_lists=False):
@@ -287,6 +314,14 @@ class ShmRing(object):
                 if g.event is not None:
                     g.event.synchronize()
                 self._reap()
+            if self._mirror is not None:
+                # the message moves into the SAME slot of the page-locked mirror: that slot is free, the segment's slot is
+                # released -- and so refilled -- only once the copy out of the mirror's has landed
+                off = self._base + ((int(self._ctl[1]) + self._taken) % self.slots) * self.slot_bytes
+                page_locked = self._mirror[off:off + len(view)]
+                page_locked[:] = view
+                view = memoryview(page_locked)
+                del page_locked
             ctr, data = decode(view)
             guard = SlotGuard()
             sink(data, ctr_info=dict(ctr, _pinned_views=True, _slot_guard=guard))   # the sink may DMA straight out of the slot
@@ -330,8 +365,10 @@ class ShmRing(object):
             self._reap(wait=True)
         self._ctl = self._len = None
         if self.pinned:
-            self._hip.hipHostUnregister.argtypes = [__import__("ctypes").c_void_p]
-            self._hip.hipHostUnregister(__import__("ctypes").c_void_p(self._pin_addr))
+            if getattr(self, "_hip", None) is not None:
+                self._hip.hipHostUnregister.argtypes = [__import__("ctypes").c_void_p]
+                self._hip.hipHostUnregister(__import__("ctypes").c_void_p(self._pin_addr))
+            self._mirror = None
             self.pinned = False
         try:
             self.shm.close()
@@ -452,7 +489,8 @@ class WeightsRing(object):
                      for i in range(self.slots)]
         self._seen = 0
         self.pinned = False
-        self._pending = []          # begun, uncommitted packed publishes, oldest first: (seq, slot, bytes, event)
+        self._mirror = None         # pin(): the page-locked copy of the slots where the segment itself cannot be registered
+        self._pending = []        # begun, uncommitted packed publishes, oldest first: (seq, slot, bytes, event)
         self._wlock = threading.Condition(threading.RLock())     # writer state (_pending, headers, latest)
         self.async_commit = False   # start_committer(): begun publishes are committed by a helper thread as their copies land
         self._committer = None
@@ -486,23 +524,21 @@ class WeightsRing(object):
 
     def pin(self):
         """Learner side, optional: page-lock the ring (``hipHostRegister``) so that ``publish_flat_from_device`` can DMA
-        the parameter block from HBM straight into the slot.  Needs a GPU process; returns True on success."""
-        import ctypes
+        the parameter block from HBM straight into the slot.  Where the runtime cannot register the segment the copy lands in
+        a page-locked mirror of the slots (``_page_lock``) and ``commit_flat_publish`` moves it into the segment with one host
+        copy before the readers see the publish.  Needs a GPU process; returns True on success."""
         if getattr(self, "pinned", False):
             return True
-        try:
-            hip = ctypes.CDLL("libamdhip64.so")
-            self._hip = hip
-            probe = np.frombuffer(self.shm.buf, dtype=np.uint8)
-            self._pin_addr = int(probe.ctypes.data)
-            del probe
-            hip.hipHostRegister.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint]
-            hip.hipHostRegister.restype = ctypes.c_int
-            rc = hip.hipHostRegister(ctypes.c_void_p(self._pin_addr), ctypes.c_size_t(self.shm.size), 0)
-        except OSError:
+        locked = _page_lock(self.shm)
+        if locked is None:
             return False
-        self.pinned = (rc == 0)
-        return self.pinned
+        self._pin_addr, self._mirror, self._hip = locked
+        self.pinned = True
+        return True
+
+    def page_locked(self):
+        """-> uint8 array over the page-locked range that ``_pin_addr`` names (the segment itself, or its mirror)"""
+        return self._mirror if self._mirror is not None else np.frombuffer(self.shm.buf, dtype=np.uint8)
 
     def _reserve_flat(self, spec, nbytes, ctr_info):
         """Claim the next slot for a packed publish of ``nbytes`` bytes of ``spec``'s flat parameter buffer and write the
@@ -664,6 +700,14 @@ class WeightsRing(object):
         with self._wlock:
             if self._pending and self._pending[0][0] == k:
                 self._pending.pop(0)
+                if self._mirror is not None:
+                    # the copy landed in the mirror's slot: its array section (behind the header _reserve_flat wrote into the
+                    # segment) goes into the segment now, while the slot is still invalid
+                    view = self._payload(i)
+                    base = _pad(8 + struct.unpack_from("<I", view, 4)[0])
+                    o = self._payload_offset(i)
+                    view[base:total] = self._mirror[o + base:o + total]
+                    del view
                 self._hdr[i][1] = total
                 self._hdr[i][0] = k
                 self._latest[0] = k
@@ -786,9 +830,11 @@ class WeightsRing(object):
         self._latest = None
         self._hdr = None
         if getattr(self, "pinned", False):
-            import ctypes
-            self._hip.hipHostUnregister.argtypes = [ctypes.c_void_p]
-            self._hip.hipHostUnregister(ctypes.c_void_p(self._pin_addr))
+            if getattr(self, "_hip", None) is not None:
+                import ctypes
+                self._hip.hipHostUnregister.argtypes = [ctypes.c_void_p]
+                self._hip.hipHostUnregister(ctypes.c_void_p(self._pin_addr))
+            self._mirror = None
             self.pinned = False
         try:
             self.shm.close()
