@@ -1685,6 +1685,75 @@ int xt_mz_cond_bwd(const float* h, const int32_t* actions, int32_t a_stride, int
                    int32_t A, int32_t N, const float* w, const float* dy, const float* g_pred, float c, float* g, float* dwb,
                    float* slabs, float* wt, void* stream);
 
+/* ---- QMIX: GRU agents and the monotonic mixer (xt_qmix.hip; reference: xt/model/qmix/qmix_tf.py).
+ * A parameter set is 22 tensors in one flat float32 buffer, every tensor on a 16-byte boundary, the agent's 8 first:
+ *    0 dense/kernel [obs_dim, H]     1 dense/bias [H]              2 gates/kernel [2H, 2H] (input rows first, r columns first)
+ *    3 gates/bias [2H]               4 candidate/kernel [2H, H]    5 candidate/bias [H]
+ *    6 dense_1/kernel [H, A]         7 dense_1/bias [A]
+ *    8.. the mixer: hyper_w1/dense [state_dim, hyper_embed], hyper_w1/dense_1 [hyper_embed, E n], hyper_b1/dense [state_dim, E],
+ *        hyper_w_final/dense [state_dim, hyper_embed], hyper_w_final/dense_1 [hyper_embed, E], val_for_bias/dense
+ *        [state_dim, E], val_for_bias/dense_1 [E, 1]; kernel then bias each
+ * Sequences are the S = B * n_agents (episode, agent) pairs, s = b * n_agents + a; the recurrent tensors are time-major
+ * [T1, S, .] with T1 = seq_len + 1.  No atomics; every sum has a fixed order. */
+typedef struct xt_qmix xt_qmix;
+
+#define XT_QMIX_TENSORS 22
+#define XT_QMIX_STATE_FLOATS 32      /* [0] updates applied, [8 + i] the norm of tensor i's gradient at the last update   */
+
+typedef struct xt_qmix_desc {
+  int32_t n_agents, obs_dim, hidden, n_actions, state_dim, embed, hyper_embed, seq_len, double_q;
+} xt_qmix_desc;
+
+typedef struct xt_qmix_cfg {
+  float lr, decay, eps, grad_norm_clip, gamma;   /* RMSPropOptimizer(lr, 0.95, epsilon 1.5e-7, centered); clip 10; 0.99  */
+} xt_qmix_cfg;
+
+/* offsets[0 .. 21]: the tensors' offsets in a parameter set (floats), offsets[22]: floats of the whole set; offsets[8] is
+ * the agent's prefix.  Host arithmetic only. */
+int xt_qmix_layout(const xt_qmix_desc* desc, int64_t* offsets);
+/* Refused with a message, before any device call: hidden other than 32 or 64; n_agents above 32, n_actions or embed above
+ * 64; a stacked tensor beyond 2^31 elements. */
+int xt_qmix_create(const xt_qmix_desc* desc, int32_t max_batch, xt_qmix** out);
+void xt_qmix_destroy(xt_qmix* h);
+int64_t xt_qmix_workspace_bytes(const xt_qmix* h);
+/* Caller-owned buffers: params_eval / params_target / grads / mg / ms hold offsets[22] floats (ms starts at 1, mg at 0,
+ * grads zeroed: the padding is never written), state XT_QMIX_STATE_FLOATS floats (zeroed). */
+int xt_qmix_bind(xt_qmix* h, float* params_eval, float* params_target, float* grads, float* mg, float* ms, float* state,
+                 void* workspace, int64_t workspace_bytes);
+/* Loss and the eval set's 22 gradients of one batch of B episodes, enqueued without synchronising.  The layouts are the
+ * reference's placeholders: obs [B, T1, n, obs_dim]; lens int32 [B n] (may be NULL: all T1); avail [B, T1, n, A]; actions
+ * int32 [B, seq_len, n]; state_cur / state_next [B, seq_len, state_dim]; rewards / terminated / mask [B, seq_len];
+ * loss_out 1 double = sum((mask (q_tot - y))^2) / sum(mask). */
+int xt_qmix_step(xt_qmix* h, const float* obs, const int32_t* lens, const float* avail, const int32_t* actions,
+                 const float* state_cur, const float* state_next, const float* rewards, const float* terminated,
+                 const float* mask, int32_t B, const xt_qmix_cfg* cfg, double* loss_out, void* stream);
+/* Centred RMSProp on the eval set; every tensor's gradient is first scaled by clip / max(its own norm, clip). */
+int xt_qmix_apply(xt_qmix* h, const xt_qmix_cfg* cfg, void* stream);
+/* params_target <- params_eval, device to device */
+int xt_qmix_sync_target(xt_qmix* h, void* stream);
+/* The agent alone, T <= T1 steps from hidden_in ([B n, H], NULL: zero): agent_params is the agent's prefix of a parameter
+ * set (offsets[8] floats); obs [B, T, n, obs_dim] -> q [B, T, n, A], hidden_out [B n, H] (may be NULL). */
+int xt_qmix_agent_forward(xt_qmix* h, const float* agent_params, const float* obs, int32_t B, int32_t T,
+                          const float* hidden_in, const int32_t* lens, float* q, float* hidden_out, void* stream);
+
+/* The kernels stand-alone.  xg [T1, S, 3H] holds the input halves with their biases (x Wg[:H] + bg | x Wc[:H] + bc); wg / wc
+ * are the whole kernels, of which the recurrent rows [H, 2H) are read.  saved [T1, S, 4H] = r | u | c | h (the carried state
+ * past the length); out [T1, S, H] is h below the length and zero past it; hT [S, H] the final state.  h0, lens, saved, hT
+ * may be NULL. */
+int xt_qmix_gru_fwd(const float* wg, const float* wc, const float* xg, const float* h0, const int32_t* lens, int32_t T1,
+                    int32_t S, int32_t H, float* saved, float* out, float* hT, void* stream);
+/* dout [T1, S, H] = d(out), dhT [S, H] = d(hT) (may be NULL) -> dg3 [T1, S, 3H] = d(pre-activations) dr | du | dc (which is
+ * d(xg)), dh0 [S, H] (may be NULL) */
+int xt_qmix_gru_bwd(const float* wg, const float* wc, const float* saved, const float* h0, const float* dout, const float* dhT,
+                    const int32_t* lens, int32_t T1, int32_t S, int32_t H, float* dg3, float* dh0, void* stream);
+/* The fused head over the B * T rows.  q_eval / q_tgt [T + 1, S, A] time-major; hyp_* [B T, n E + 2 E + 1] = the raw
+ * hypernet outputs w1 | b1 | w_final | v; -> dq [T + 1, S, A], dhyp (the eval row's gradient), qtot [B T, 2] = (q_tot, y)
+ * (may be NULL), rowloss float64 [B T], masksum 1 double, loss_out 1 double (may be NULL). */
+int xt_qmix_mix(const float* q_eval, const float* q_tgt, const float* avail, const int32_t* actions, const float* hyp_eval,
+                const float* hyp_tgt, const float* rewards, const float* terminated, const float* mask, int32_t B, int32_t T,
+                int32_t n, int32_t A, int32_t E, float gamma, int32_t double_q, float* dq, float* dhyp, float* qtot,
+                double* rowloss, double* masksum, double* loss_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

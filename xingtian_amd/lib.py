@@ -129,6 +129,18 @@ class MzCfg(Structure):
     _fields_ = [("lr", c_float), ("beta1", c_float), ("beta2", c_float), ("eps", c_float)]
 
 
+class QmixDesc(Structure):
+    """xt_qmix_desc of include/xt_mi355x.h"""
+    _fields_ = [(n, c_int32) for n in ("n_agents", "obs_dim", "hidden", "n_actions", "state_dim", "embed", "hyper_embed",
+                                       "seq_len", "double_q")]
+
+
+class QmixCfg(Structure):
+    """xt_qmix_cfg of include/xt_mi355x.h"""
+    _fields_ = [(n, c_float) for n in ("lr", "decay", "eps", "grad_norm_clip", "gamma")]
+
+
+QMIX_TENSORS, QMIX_STATE_FLOATS = 22, 32                             # XT_QMIX_TENSORS / XT_QMIX_STATE_FLOATS
 MZ_MAX_UNROLL, MZ_MAX_CHAIN, MZ_WGRAD_ROWS = 16, 8, 128               # XT_MZ_MAX_UNROLL / _MAX_CHAIN / _WGRAD_ROWS
 NOISY_MAX_LAYERS = 8     # XT_NOISY_MAX_LAYERS
 
@@ -347,6 +359,20 @@ SIGNATURES = {
     "xt_mz_cond_fwd": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, c_int32, _P, _P]),
     "xt_mz_cond_bwd": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_float, _P, _P, _P,
                                  _P, _P]),
+    # (the QMIX entries, xt_qmix.hip)
+    "xt_qmix_layout": (c_int32, [POINTER(QmixDesc), POINTER(c_int64)]),
+    "xt_qmix_create": (c_int32, [POINTER(QmixDesc), c_int32, POINTER(c_void_p)]),
+    "xt_qmix_destroy": (None, [_P]),
+    "xt_qmix_workspace_bytes": (c_int64, [_P]),
+    "xt_qmix_bind": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64]),
+    "xt_qmix_step": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, POINTER(QmixCfg), _P, _P]),
+    "xt_qmix_apply": (c_int32, [_P, POINTER(QmixCfg), _P]),
+    "xt_qmix_sync_target": (c_int32, [_P, _P]),
+    "xt_qmix_agent_forward": (c_int32, [_P, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P]),
+    "xt_qmix_gru_fwd": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
+    "xt_qmix_gru_bwd": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P]),
+    "xt_qmix_mix": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32,
+                              _P, _P, _P, _P, _P, _P, _P]),
     "xt_noisy_compose": (c_int32, [POINTER(NoisyLayer), c_int32, _P, _P, c_int64, _P, _P, ctypes.c_uint64, ctypes.c_uint64,
                                    c_int32, c_int32, _P]),
     "xt_noisy_grads": (c_int32, [POINTER(NoisyLayer), c_int32, _P, _P, _P]),
