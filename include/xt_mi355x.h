@@ -1754,6 +1754,67 @@ int xt_qmix_mix(const float* q_eval, const float* q_tgt, const float* avail, con
                 int32_t n, int32_t A, int32_t E, float gamma, int32_t double_q, float* dq, float* dhyp, float* qtot,
                 double* rowloss, double* masksum, double* loss_out, void* stream);
 
+/* ---- SCC: GRU agents, the multi-channel critic and counterfactual credits (xt_scc.hip; reference:
+ * xt/model/scc/scc_tf.py).  A parameter set is one flat float32 buffer, every tensor on a 16-byte boundary: the agent's 8
+ * tensors as in QMIX (obs_dim = obs_shape), then per agent group g: L1_g [o + A, U], b1_g [U], L2_g [U, U], b2_g [U], then the
+ * final Dense: kernel [n U, 1] (concat) or [U, 1] (add), bias [1].  o = obs_dim - n_actions - n_agents is the raw observation
+ * width; R = B * seq_len rows; items are (row, agent) pairs, agent-major: item = agent * R + row.  The critic, the target critic
+ * and the credits all read row min(t + 1, seq_len - 1) of episode b (the reference's aliased placeholders).  No atomics, no
+ * random numbers; every sum has a fixed order. */
+typedef struct xt_scc xt_scc;
+
+#define XT_SCC_MAX_GROUPS 32
+#define XT_SCC_MAX_TENSORS 138       /* 8 + 4 * XT_SCC_MAX_GROUPS + 2                                                    */
+#define XT_SCC_STATE_FLOATS 160      /* [0] updates applied, [8 + i] the norm of tensor i's gradient at the last update   */
+#define XT_SCC_MERGE_CONCAT 0
+#define XT_SCC_MERGE_ADD 1
+
+typedef struct xt_scc_desc {
+  int32_t n_agents, obs_dim, hidden, n_actions, units, seq_len, merge, multi_channel, n_groups;
+  int32_t groups[XT_SCC_MAX_GROUPS];  /* agents per group, in agent order; they sum to n_agents                            */
+} xt_scc_desc;
+
+typedef struct xt_scc_cfg {
+  float c_lr, a_lr, mixer_clip, actor_clip, gamma;      /* 0.0005, 0.0005, 10, 10, 0.99                                  */
+  float beta1, beta2, adam_eps, rms_decay, rms_eps;     /* TF1 defaults: 0.9, 0.999, 1e-8; 0.9, 1e-10                    */
+} xt_scc_cfg;
+
+/* offsets[0 .. nt - 1]: the tensors' offsets (floats), offsets[nt]: floats of the whole set, nt = 8 + 4 n_groups + 2 (written
+ * to n_tensors, may be NULL); offsets has XT_SCC_MAX_TENSORS + 1 slots.  Host arithmetic only. */
+int xt_scc_layout(const xt_scc_desc* desc, int64_t* offsets, int32_t* n_tensors);
+/* Refused with a message, before any device call: multi_channel 0; merge other than concat / add; units other than 32, 64,
+ * 128; o + n_actions above 1024; hidden other than 32 or 64; n_agents above 32, n_actions above 64; groups that do not sum to
+ * n_agents; a stacked tensor beyond 2^31 elements. */
+int xt_scc_create(const xt_scc_desc* desc, int32_t max_batch, xt_scc** out);
+void xt_scc_destroy(xt_scc* h);
+int64_t xt_scc_workspace_bytes(const xt_scc* h);
+/* Caller-owned buffers of offsets[nt] floats: params_eval, params_target (its critic part is read), grads (zeroed), slot1
+ * (Adam's m over the critic part; zeroed), slot2 (RMSProp's ms over the agent part: ones; Adam's v over the critic part:
+ * zeros); state XT_SCC_STATE_FLOATS floats (zeroed). */
+int xt_scc_bind(xt_scc* h, float* params_eval, float* params_target, float* grads, float* slot1, float* slot2, float* state,
+                void* workspace, int64_t workspace_bytes);
+/* Credits, both losses and all gradients of one batch of B episodes, enqueued without synchronising.  agent_obs [B, T1, n,
+ * obs_dim] (the agent's input), obs [B, T1, n, o] (the critic's), lens int32 [B n] (may be NULL), actions int32 [B, seq_len,
+ * n], rewards / terminated / mask [B, seq_len]; loss_out 2 doubles = actor_loss, mixer_loss. */
+int xt_scc_step(xt_scc* h, const float* agent_obs, const float* obs, const int32_t* lens, const int32_t* actions,
+                const float* rewards, const float* terminated, const float* mask, int32_t B, const xt_scc_cfg* cfg,
+                double* loss_out, void* stream);
+/* TF1 Adam on the critic, TF1 RMSProp on the agent; every tensor's gradient is first scaled by clip / max(its norm, clip)
+ * with mixer_clip / actor_clip, both only when actor_clip > 0 (the reference's gate). */
+int xt_scc_apply(xt_scc* h, const xt_scc_cfg* cfg, void* stream);
+/* the critic part of params_target <- params_eval (all the reference's assign_targets copies) */
+int xt_scc_sync_target(xt_scc* h, void* stream);
+/* The agent alone, as xt_qmix_agent_forward. */
+int xt_scc_agent_forward(xt_scc* h, const float* agent_params, const float* obs, int32_t B, int32_t T, const float* hidden_in,
+                         const int32_t* lens, float* q, float* hidden_out, void* stream);
+/* The critic stand-alone on a bound handle.  params_target may be NULL.  raw == 0: obs [B, T1, n, o] and actions [B, seq_len, n]
+ * with the row shift; raw != 0: obs is a [B, seq_len, n, o + A] array read as it is (get_mixer_output), actions unused; it
+ * yields v alone (scalars, credits and dv are refused: there is no action part to zero).
+ * -> scalars [3, n R] = s_eval_full | s_eval_alt | s_target_full (2 blocks without a target), credits [R, n], v [R] (the eval
+ * critic's value); each may be NULL.  With dv [R] (raw == 0): the critic's gradients into the critic part of the flat `grads`. */
+int xt_scc_critic(xt_scc* h, const float* params_eval, const float* params_target, const float* obs, const int32_t* actions,
+                  int32_t B, int32_t raw, float* scalars, float* credits, float* v, const float* dv, float* grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

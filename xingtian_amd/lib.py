@@ -140,6 +140,19 @@ class QmixCfg(Structure):
     _fields_ = [(n, c_float) for n in ("lr", "decay", "eps", "grad_norm_clip", "gamma")]
 
 
+class SccDesc(Structure):
+    """xt_scc_desc of include/xt_mi355x.h"""
+    _fields_ = [(n, c_int32) for n in ("n_agents", "obs_dim", "hidden", "n_actions", "units", "seq_len", "merge", "multi_channel",
+                                       "n_groups")] + [("groups", c_int32 * 32)]
+
+
+class SccCfg(Structure):
+    """xt_scc_cfg of include/xt_mi355x.h"""
+    _fields_ = [(n, c_float) for n in ("c_lr", "a_lr", "mixer_clip", "actor_clip", "gamma", "beta1", "beta2", "adam_eps",
+                                       "rms_decay", "rms_eps")]
+
+
+SCC_MAX_GROUPS, SCC_MAX_TENSORS, SCC_STATE_FLOATS = 32, 138, 160     # XT_SCC_MAX_GROUPS / _MAX_TENSORS / _STATE_FLOATS
 QMIX_TENSORS, QMIX_STATE_FLOATS = 22, 32                             # XT_QMIX_TENSORS / XT_QMIX_STATE_FLOATS
 MZ_MAX_UNROLL, MZ_MAX_CHAIN, MZ_WGRAD_ROWS = 16, 8, 128               # XT_MZ_MAX_UNROLL / _MAX_CHAIN / _WGRAD_ROWS
 NOISY_MAX_LAYERS = 8     # XT_NOISY_MAX_LAYERS
@@ -373,6 +386,17 @@ SIGNATURES = {
     "xt_qmix_gru_bwd": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P]),
     "xt_qmix_mix": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32,
                               _P, _P, _P, _P, _P, _P, _P]),
+    # (the SCC entries, xt_scc.hip)
+    "xt_scc_layout": (c_int32, [POINTER(SccDesc), POINTER(c_int64), POINTER(c_int32)]),
+    "xt_scc_create": (c_int32, [POINTER(SccDesc), c_int32, POINTER(c_void_p)]),
+    "xt_scc_destroy": (None, [_P]),
+    "xt_scc_workspace_bytes": (c_int64, [_P]),
+    "xt_scc_bind": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64]),
+    "xt_scc_step": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, POINTER(SccCfg), _P, _P]),
+    "xt_scc_apply": (c_int32, [_P, POINTER(SccCfg), _P]),
+    "xt_scc_sync_target": (c_int32, [_P, _P]),
+    "xt_scc_agent_forward": (c_int32, [_P, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P]),
+    "xt_scc_critic": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
     "xt_noisy_compose": (c_int32, [POINTER(NoisyLayer), c_int32, _P, _P, c_int64, _P, _P, ctypes.c_uint64, ctypes.c_uint64,
                                    c_int32, c_int32, _P]),
     "xt_noisy_grads": (c_int32, [POINTER(NoisyLayer), c_int32, _P, _P, _P]),

@@ -14,3 +14,4 @@ from xingtian_amd.model.impala import impala_cnn, impala_cnn_opt  # noqa: E402,F
 from xingtian_amd.model.dqn import dqn_cnn, dqn_mlp  # noqa: E402,F401
 from xingtian_amd.model.muzero import muzero_model, muzero_mlp, muzero_cnn  # noqa: E402,F401
 from xingtian_amd.model.qmix import qmix_model  # noqa: E402,F401
+from xingtian_amd.model.scc import scc_model  # noqa: E402,F401
