@@ -385,6 +385,16 @@ struct DpStep {                     // what the optimiser kernels do for a data-
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+static inline int64_t al4(int64_t x) { return (x + 3) & ~(int64_t)3; }      // float counts in steps of 16 bytes
+
+// a learner handle (xt_mz, xt_qmix, xt_scc) is bound, `params` being its parameter pointer, and 1 <= B <= its max_batch
+template <typename Handle>
+static int check_bound(const Handle* z, float* Handle::*params, int B, const char* who) {
+  XT_REQUIRE(z && z->*params && z->ws, "%s: the handle is not bound", who);
+  XT_REQUIRE(B >= 1 && B <= z->max_batch, "%s: B = %d outside [1, %d]", who, B, z->max_batch);
+  return 0;
+}
+
 // One-time set-up PER DEVICE (function attributes such as the dynamic-LDS limit belong to the device's copy of the
 // code object): a process may drive several GPUs, one learner thread each (PBT-style multi-learner set-ups).  The body
 // must be idempotent: two threads on the same device may both run it.

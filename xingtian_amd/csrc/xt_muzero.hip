@@ -2,10 +2,11 @@
 //
 // The representation chain (Dense layers on float32 observations) runs on the trunk-layer kernels of xt_igemm.hip
 // (launch_fwd, xt_layer_bwd, xt_layer_wgrad_slabs).  Everything behind it is Dense layers of any width (supports of 3, 7, 26, 305 columns, hidden
-// states of 4) over the STACKED rows of all unroll steps, on the kernels of this file:
-//   mz_gemm_kernel      y = epilogue(x . w): forward (conditioning row + bias + relu) or input gradient (on the transposed
-//                       kernel: join term + scale + relu mask)
-//   mz_wgrad_kernel     dW / db over row slabs of XT_MZ_WGRAD_ROWS rows, with the gathered rows of the conditioned layer
+// states of 4) over the STACKED rows of all unroll steps, on the plain Dense kernels of xt_dense_dev.h, shared with QMIX and SCC,
+// and the loss head of this file:
+//   dense_gemm_kernel   y = epilogue(x . w): forward (conditioning row + bias + relu) or input gradient (on the transposed
+//                       kernel: scale + join term + relu mask)
+//   dense_wgrad_kernel  dW / db over row slabs of XT_MZ_WGRAD_ROWS rows, with the gathered rows of the conditioned layer
 //   mz_loss_kernel      softmax + two-hot / dense target + cross-entropy + d(logits)
 // All of them float32 without contraction (the build's -ffp-contract=off), sums in ascending order: the NumPy twins of the
 // tests reproduce them bit for bit.
@@ -13,75 +14,10 @@
 #include <new>
 
 #include "xt_common.h"
+#include "xt_dense_dev.h"
 #include "xt_launch.h"
 
 namespace xt {
-
-// ------------------------------------------------------------------ y[m, n] = epilogue(sum_k x[m, k] w[k, n])
-// One thread owns 4 consecutive rows of one column (the w element is loaded once for the four); consecutive threads own
-// consecutive columns, so w loads coalesce and x loads are a few broadcast addresses per wavefront.
-struct MzGemm {
-  const float* x; int ldx;        // [M, ldx], K columns read
-  const float* w;                 // [K (+ A), N]
-  int M, K, N;
-  // forward epilogue
-  const float* bias;              // [N] or null
-  const int32_t* actions;         // null, or the conditioning: row r = i * B + b adds w[K + actions[b * a_stride + i]]
-  int a_stride, B, A;
-  int relu;
-  // input-gradient epilogue (MODE 1): y = mask(maskx) * (add + c * acc)
-  const float* add;               // [M, N] or null
-  float c;
-  const float* maskx;             // [M, N] or null: y = 0 where maskx <= 0
-  float* y;                       // [M, N]
-};
-
-template <int MODE>
-__global__ __launch_bounds__(256) void mz_gemm_kernel(const MzGemm a) {
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long total = (long long)((a.M + 3) >> 2) * a.N;
-  if (gid >= total) return;
-  const int n = (int)(gid % a.N);
-  const int m0 = (int)(gid / a.N) * 4;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  const float* xr[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) xr[r] = a.x + (long long)(m0 + r < a.M ? m0 + r : a.M - 1) * a.ldx;
-  for (int k = 0; k < a.K; ++k) {
-    const float wv = a.w[(long long)k * a.N + n];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = acc[r] + xr[r][k] * wv;
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int m = m0 + r;
-    if (m >= a.M) break;
-    float v = acc[r];
-    if (MODE == 0) {
-      if (a.actions) {
-        const int act = a.actions[(long long)(m % a.B) * a.a_stride + m / a.B];
-        if (act >= 0 && act < a.A) v = v + a.w[(long long)(a.K + act) * a.N + n];
-      }
-      if (a.bias) v = v + a.bias[n];
-      if (a.relu) v = v > 0.f ? v : 0.f;
-    } else {
-      v = a.c * v;
-      if (a.add) v = a.add[(long long)m * a.N + n] + v;
-      if (a.maskx && !(a.maskx[(long long)m * a.N + n] > 0.f)) v = 0.f;
-    }
-    a.y[(long long)m * a.N + n] = v;
-  }
-}
-
-template <int MODE>
-static int launch_gemm(const MzGemm& a, hipStream_t st) {
-  XT_REQUIRE(a.M > 0 && a.N > 0 && a.K >= 0 && a.y && (a.K == 0 || (a.x && a.w)), "mz gemm: bad arguments");
-  const long long total = (long long)((a.M + 3) >> 2) * a.N;
-  XT_REQUIRE((total + 255) / 256 < (1ll << 31), "mz gemm: too many outputs");
-  hipLaunchKernelGGL(mz_gemm_kernel<MODE>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
-  XT_LAUNCH_CHECK();
-  return 0;
-}
 
 // wt[n, k] = w[k, n] for k < K (the first K rows of a [rows, N] kernel): the input gradient then runs as a forward
 __global__ __launch_bounds__(256) void mz_transpose_kernel(const float* __restrict__ w, int K, int N, float* __restrict__ wt) {
@@ -97,79 +33,7 @@ static int launch_transpose(const float* w, int K, int N, float* wt, hipStream_t
   return 0;
 }
 
-// ------------------------------------------------------------------ weight + bias gradient over row slabs
-// out[s][kk, n] for kk in [0, K + A]: kk < K: sum_r x[r, kk] dy[r, n]; K <= kk < K + A: sum over the rows whose action is
-// kk - K of dy[r, n] (zero when nobody took it); kk == K + A: sum_r dy[r, n].  Rows [s * chunk, (s + 1) * chunk) ascending.
-struct MzWgrad {
-  const float* x; int ldx;
-  const float* dy;
-  const int32_t* actions; int a_stride, B, A;
-  int M, K, N, nslab;
-  float* out;                     // [nslab, (K + A + 1) * N]
-};
-
-__global__ __launch_bounds__(256) void mz_wgrad_kernel(const MzWgrad a) {
-  const long long count = (long long)(a.K + a.A + 1) * a.N;
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= count * a.nslab) return;
-  const int s = (int)(gid / count);
-  const int e = (int)(gid % count);
-  const int kk = e / a.N, n = e % a.N;
-  const int r0 = s * XT_MZ_WGRAD_ROWS;
-  const int r1 = r0 + XT_MZ_WGRAD_ROWS < a.M ? r0 + XT_MZ_WGRAD_ROWS : a.M;
-  float acc = 0.f;
-  if (kk < a.K) {
-    int r = r0;
-    for (; r + 4 <= r1; r += 4) {      // four rows' loads in flight, added in ascending order
-      float xv[4], dv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        xv[u] = a.x[(long long)(r + u) * a.ldx + kk];
-        dv[u] = a.dy[(long long)(r + u) * a.N + n];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc = acc + xv[u] * dv[u];
-    }
-    for (; r < r1; ++r) acc = acc + a.x[(long long)r * a.ldx + kk] * a.dy[(long long)r * a.N + n];
-  } else if (kk < a.K + a.A) {
-    const int want = kk - a.K;
-    for (int r = r0; r < r1; ++r)
-      if (a.actions[(long long)(r % a.B) * a.a_stride + r / a.B] == want) acc = acc + a.dy[(long long)r * a.N + n];
-  } else {
-    for (int r = r0; r < r1; ++r) acc = acc + a.dy[(long long)r * a.N + n];
-  }
-  a.out[gid] = acc;
-}
-
-// dwb[e] = sum over ascending s of slabs[s][e]
-__global__ __launch_bounds__(256) void mz_slab_sum_kernel(const float* __restrict__ slabs, long long count, int nslab,
-                                                          float* __restrict__ dwb) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= count) return;
-  float acc = 0.f;
-  for (int s = 0; s < nslab; ++s) acc = acc + slabs[(long long)s * count + e];
-  dwb[e] = acc;
-}
-
-static inline int mz_nslab(int M) { return (M + XT_MZ_WGRAD_ROWS - 1) / XT_MZ_WGRAD_ROWS; }
-
-// a: out is ignored; dwb receives the gradient, `slabs` holds mz_nslab(M) slabs when that is more than one
-static int launch_mz_wgrad(MzWgrad a, float* dwb, float* slabs, hipStream_t st) {
-  XT_REQUIRE(a.x && a.dy && dwb && a.M > 0 && a.K > 0 && a.N > 0 && a.A >= 0 && (a.A == 0 || (a.actions && a.B > 0)),
-             "mz wgrad: bad arguments");
-  a.nslab = mz_nslab(a.M);
-  XT_REQUIRE(a.nslab == 1 || slabs, "mz wgrad: %d rows need a slab buffer", a.M);
-  const long long count = (long long)(a.K + a.A + 1) * a.N;
-  XT_REQUIRE((count * a.nslab + 255) / 256 < (1ll << 31), "mz wgrad: too large");
-  a.out = a.nslab == 1 ? dwb : slabs;
-  hipLaunchKernelGGL(mz_wgrad_kernel, dim3((unsigned)((count * a.nslab + 255) / 256)), dim3(256), 0, st, a);
-  XT_LAUNCH_CHECK();
-  if (a.nslab > 1) {
-    hipLaunchKernelGGL(mz_slab_sum_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, slabs, count, a.nslab, dwb);
-    XT_LAUNCH_CHECK();
-  }
-  return 0;
-}
+static inline int mz_nslab(int M) { return dense_nslab(M, XT_MZ_WGRAD_ROWS); }
 
 // ------------------------------------------------------------------ the loss head
 struct MzLoss {
@@ -268,20 +132,6 @@ __global__ __launch_bounds__(256) void mz_loss_kernel(const MzLoss a) {
   if (t == 0) a.rowloss[r] = -sl / bn;
 }
 
-// out[0] = the sum of n doubles: thread t takes t, t + 256, ... ascending, then a fixed tree
-__global__ __launch_bounds__(256) void mz_loss_sum_kernel(const double* __restrict__ rowloss, long long n, double* __restrict__ out) {
-  __shared__ double sh[256];
-  double acc = 0.0;
-  for (long long i = threadIdx.x; i < n; i += 256) acc += rowloss[i];
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = sh[0];
-}
-
 static int launch_mz_loss(const MzLoss& a, hipStream_t st) {
   XT_REQUIRE(a.logits && a.nblk > 0 && a.B > 0 && a.N >= 2 && a.N <= 65536, "xt_mz_loss: nblk %d, B %d, N %d out of range",
              a.nblk, a.B, a.N);
@@ -328,8 +178,6 @@ static int mz_dense_ok(const xt_layer_desc& l, const char* who, int i) {
   XT_REQUIRE(l.param_off >= 0, "xt_mz_create: %s layer %d: negative offset", who, i);
   return 0;
 }
-
-static inline int64_t al4(int64_t x) { return (x + 3) & ~(int64_t)3; }
 
 static int rep_msplit(const xt_conv_geom& g, int B, int cap) {
   const long long M = (long long)B * g.OH * g.OW;
@@ -406,11 +254,11 @@ static float* gof(const xt_mz* z, const xt_layer_desc& l) { return z->grads + l.
 // y = act(x . w + b) of one Dense layer over M rows; actions != null: the conditioned layer (w has A more rows)
 static int mz_fwd(const xt_mz* z, const xt_layer_desc& l, const float* x, int M, float* y, const int32_t* actions, int a_stride,
                   int B, hipStream_t st) {
-  MzGemm a{};
+  DenseGemm a{};
   const int A = actions ? z->d.action_dim : 0;
-  a.x = x; a.K = l.g.C - A; a.ldx = a.K; a.w = wof(z, l); a.M = M; a.N = l.g.N; a.bias = bof(z, l);
-  a.actions = actions; a.a_stride = a_stride; a.B = B > 0 ? B : 1; a.A = A; a.relu = l.g.act == XT_ACT_RELU; a.y = y;
-  return launch_gemm<0>(a, st);
+  a.x = x; a.K = l.g.C - A; a.ldx = a.K; a.w = wof(z, l); a.ldw = l.g.N; a.M = M; a.N = l.g.N; a.bias = bof(z, l);
+  a.actions = actions; a.a_stride = a_stride; a.B = B > 0 ? B : 1; a.A = A; a.relu = l.g.act == XT_ACT_RELU; a.y = y; a.ldy = l.g.N;
+  return launch_dense_gemm(a, st);
 }
 
 // the transposed kernels the step's input gradients read: [N, Kuse] per layer, Kuse = hidden for the conditioned layer
@@ -424,27 +272,31 @@ static int mz_transpose_all(const xt_mz* z, hipStream_t st) {
   return 0;
 }
 
-// dx [M, Kuse] = mask(maskx) * (add + c * dy . w[:Kuse]^T), wt = the layer's transposed kernel [N, Kuse]
+// dx [M, Kuse] = mask(maskx) * (add + c * dy . wt), wt [N, Kuse] = the transposed kernel; N == 0: mask(maskx) * add
+static int mz_dgrad_rows(const float* dy, int N, const float* wt, int Kuse, int M, const float* add, float c, const float* maskx,
+                         float* dx, hipStream_t st) {
+  DenseGemm a{};
+  a.x = dy; a.ldx = N; a.K = N; a.w = wt; a.ldw = Kuse; a.M = M; a.N = Kuse; a.add = add; a.c = c; a.maskx = maskx; a.ldm = Kuse; a.y = dx;
+  a.ldy = Kuse;
+  return launch_dense_gemm(a, st);
+}
 static int mz_dgrad(const xt_mz* z, const xt_layer_desc& l, const float* wt, int Kuse, const float* dy, int M, const float* add,
                     float c, const float* maskx, float* dx, hipStream_t st) {
-  MzGemm a{};
-  a.x = dy; a.ldx = l.g.N; a.K = l.g.N; a.w = wt; a.M = M; a.N = Kuse; a.add = add; a.c = c; a.maskx = maskx; a.y = dx;
-  return launch_gemm<1>(a, st);
+  return mz_dgrad_rows(dy, l.g.N, wt, Kuse, M, add, c, maskx, dx, st);
 }
 
+// dwb = [dW (K + A rows) | db] of a Dense layer over M rows, in slabs of XT_MZ_WGRAD_ROWS rows; one slab goes straight to dwb
+static int mz_wgrad_rows(const float* x, int K, const float* dy, int N, int M, const int32_t* actions, int a_stride, int B, int A,
+                         float* dwb, float* slabs, hipStream_t st) {
+  XT_REQUIRE(M > 0, "mz wgrad: bad arguments");
+  DenseWgrad a{};
+  a.x = x; a.K = K; a.ldx = K; a.dy = dy; a.ldy = N; a.actions = actions; a.a_stride = a_stride; a.B = B > 0 ? B : 1; a.A = A; a.M = M; a.N = N;
+  return launch_dense_wgrad(a, dwb, dwb + (int64_t)(K + A) * N, slabs, XT_MZ_WGRAD_ROWS, true, st);
+}
 static int mz_wgrad(const xt_mz* z, const xt_layer_desc& l, const float* x, const float* dy, int M, const int32_t* actions,
                     int a_stride, int B, hipStream_t st) {
-  MzWgrad a{};
   const int A = actions ? z->d.action_dim : 0;
-  a.x = x; a.K = l.g.C - A; a.ldx = a.K; a.dy = dy; a.actions = actions; a.a_stride = a_stride; a.B = B > 0 ? B : 1; a.A = A;
-  a.M = M; a.N = l.g.N;
-  return launch_mz_wgrad(a, gof(z, l), z->ws + z->o_slabs, st);
-}
-
-static int mz_check_bound(const xt_mz* z, int B, const char* who) {
-  XT_REQUIRE(z && z->params && z->ws, "%s: the handle is not bound", who);
-  XT_REQUIRE(B >= 1 && B <= z->max_batch, "%s: B = %d outside [1, %d]", who, B, z->max_batch);
-  return 0;
+  return mz_wgrad_rows(x, l.g.C - A, dy, l.g.N, M, actions, a_stride, B, A, gof(z, l), z->ws + z->o_slabs, st);
 }
 
 // float32 observations [., obs_dim] (sample b = row idx[b], or row b) -> hstack rows [0, B)
@@ -593,7 +445,7 @@ int xt_mz_bind(xt_mz* mz, float* params, float* grads, float* adam_m, float* ada
 int xt_mz_step(xt_mz* mz, const void* obs, const int32_t* idx, int32_t B, const int32_t* actions, const double* target_value,
                const double* target_reward, const float* target_policy, const xt_mz_cfg* cfg, double* loss_out, void* stream) {
   using namespace xt;
-  if (int rc = mz_check_bound(mz, B, "xt_mz_step")) return rc;
+  if (int rc = check_bound(mz, &xt_mz::params, B, "xt_mz_step")) return rc;
   XT_REQUIRE(obs && actions && target_value && target_reward && target_policy && cfg && loss_out, "xt_mz_step: null argument");
   const xt_mz* z = mz;
   const xt_mz_desc& d = z->d;
@@ -628,8 +480,7 @@ int xt_mz_step(xt_mz* mz, const void* obs, const int32_t* idx, int32_t B, const 
     a.logits = ws + z->o_zr; a.nblk = U; a.N = d.reward_support; a.target_scalar = target_reward;
     a.tmin = d.reward_min; a.tmax = d.reward_max; a.scale0 = inv_u; a.dz = ws + z->o_dr; a.rowloss = rowloss + 2 * MS;
     if (int rc = launch_mz_loss(a, st)) return rc;
-    hipLaunchKernelGGL(mz_loss_sum_kernel, dim3(1), dim3(256), 0, st, rowloss, (long long)(2 * MS + MU), loss_out);
-    XT_LAUNCH_CHECK();
+    if (int rc = launch_dense_sum((const double*)rowloss, (long long)(2 * MS + MU), nullptr, loss_out, st)) return rc;
   }
 
   // ---- the prediction chain's backward, once over the stack
@@ -659,10 +510,8 @@ int xt_mz_step(xt_mz* mz, const void* obs, const int32_t* idx, int32_t B, const 
 
   // ---- the dynamics chain backwards: the only sequential part
   {   // step U has no consumer but the prediction net: d(pre) = relu'(h_U) * g_pred
-    MzGemm a{};
-    a.M = B; a.N = H; a.K = 0; a.add = gp + (int64_t)U * B * H; a.c = 0.f; a.maskx = hs + (int64_t)U * B * H;
-    a.y = dh + (int64_t)U * B * H;
-    if (int rc = launch_gemm<1>(a, st)) return rc;
+    const int64_t rU = (int64_t)U * B * H;
+    if (int rc = mz_dgrad_rows(nullptr, 0, nullptr, H, B, gp + rU, 0.f, hs + rU, dh + rU, st)) return rc;
   }
   for (int i = U - 1; i >= 0; --i) {
     const int64_t r0 = (int64_t)i * B;
@@ -718,7 +567,7 @@ int xt_mz_apply(xt_mz* mz, const xt_mz_cfg* cfg, void* stream) {
 int xt_mz_initial(xt_mz* mz, const void* obs, const int32_t* idx, int32_t B, float* policy, float* value, float* hidden,
                   void* stream) {
   using namespace xt;
-  if (int rc = mz_check_bound(mz, B, "xt_mz_initial")) return rc;
+  if (int rc = check_bound(mz, &xt_mz::params, B, "xt_mz_initial")) return rc;
   XT_REQUIRE(obs && policy && value && hidden, "xt_mz_initial: null argument");
   const hipStream_t st = as_stream(stream);
   float* hs = mz->ws + mz->o_h;
@@ -733,7 +582,7 @@ int xt_mz_initial(xt_mz* mz, const void* obs, const int32_t* idx, int32_t B, flo
 int xt_mz_recurrent(xt_mz* mz, const float* hidden_in, const int32_t* action, int32_t B, float* hidden_out, float* reward,
                     float* policy, float* value, void* stream) {
   using namespace xt;
-  if (int rc = mz_check_bound(mz, B, "xt_mz_recurrent")) return rc;
+  if (int rc = check_bound(mz, &xt_mz::params, B, "xt_mz_recurrent")) return rc;
   XT_REQUIRE(hidden_in && action && hidden_out && reward && policy && value, "xt_mz_recurrent: null argument");
   const hipStream_t st = as_stream(stream);
   float* hs = mz->ws + mz->o_h;
@@ -757,10 +606,7 @@ int xt_mz_loss(const float* logits, int32_t nblk, int32_t B, int32_t N, int32_t 
   a.tmin = tmin; a.tmax = tmax; a.scale0 = scale0; a.scale_rest = scale_rest; a.probs = probs; a.dz = dz; a.rowloss = rowloss;
   const hipStream_t st = as_stream(stream);
   if (int rc = launch_mz_loss(a, st)) return rc;
-  if (loss_out) {
-    hipLaunchKernelGGL(mz_loss_sum_kernel, dim3(1), dim3(256), 0, st, rowloss, (long long)nblk * B, loss_out);
-    XT_LAUNCH_CHECK();
-  }
+  if (loss_out) return launch_dense_sum((const double*)rowloss, (long long)nblk * B, nullptr, loss_out, st);
   return 0;
 }
 
@@ -770,10 +616,10 @@ int xt_mz_cond_fwd(const float* h, const int32_t* actions, int32_t a_stride, int
   XT_REQUIRE(h && actions && w && bias && y && nblk >= 1 && B >= 1 && hidden >= 1 && A >= 1 && N >= 1 && a_stride >= nblk &&
              (long long)nblk * B * (N > hidden ? N : hidden) < (1ll << 31), "xt_mz_cond_fwd: bad arguments");
   XT_REQUIRE(act == XT_ACT_RELU || act == XT_ACT_NONE, "xt_mz_cond_fwd: activation %d (relu or none)", act);
-  MzGemm a{};
-  a.x = h; a.ldx = hidden; a.K = hidden; a.w = w; a.M = nblk * B; a.N = N; a.bias = bias; a.actions = actions; a.a_stride = a_stride;
-  a.B = B; a.A = A; a.relu = act == XT_ACT_RELU; a.y = y;
-  return launch_gemm<0>(a, as_stream(stream));
+  DenseGemm a{};
+  a.x = h; a.ldx = hidden; a.K = hidden; a.w = w; a.ldw = N; a.M = nblk * B; a.N = N; a.bias = bias; a.actions = actions; a.a_stride = a_stride;
+  a.B = B; a.A = A; a.relu = act == XT_ACT_RELU; a.y = y; a.ldy = N;
+  return launch_dense_gemm(a, as_stream(stream));
 }
 
 int xt_mz_cond_bwd(const float* h, const int32_t* actions, int32_t a_stride, int32_t nblk, int32_t B, int32_t hidden, int32_t A,
@@ -784,14 +630,9 @@ int xt_mz_cond_bwd(const float* h, const int32_t* actions, int32_t a_stride, int
              a_stride >= nblk && (long long)nblk * B * (N > hidden ? N : hidden) < (1ll << 31), "xt_mz_cond_bwd: bad arguments");
   const hipStream_t st = as_stream(stream);
   const int M = nblk * B;
-  MzWgrad wg{};
-  wg.x = h; wg.ldx = hidden; wg.K = hidden; wg.dy = dy; wg.actions = actions; wg.a_stride = a_stride; wg.B = B; wg.A = A; wg.M = M;
-  wg.N = N;
-  if (int rc = launch_mz_wgrad(wg, dwb, slabs, st)) return rc;
+  if (int rc = mz_wgrad_rows(h, hidden, dy, N, M, actions, a_stride, B, A, dwb, slabs, st)) return rc;
   if (int rc = launch_transpose(w, hidden, N, wt, st)) return rc;
-  MzGemm a{};
-  a.x = dy; a.ldx = N; a.K = N; a.w = wt; a.M = M; a.N = hidden; a.add = g_pred; a.c = c; a.maskx = h; a.y = g;
-  return launch_gemm<1>(a, st);
+  return mz_dgrad_rows(dy, N, wt, hidden, M, g_pred, c, h, g, st);
 }
 
 }  // extern "C"

@@ -7,7 +7,8 @@
 //                         one wavefront per (episode, step) row
 //   qmix_norm_kernel / qmix_rmsprop_kernel   centred RMSProp with tf.clip_by_norm per tensor
 // Everything that is not sequential (dense, the input half of the GRU, dense_1, the hypernet layers; forward, input
-// gradient, weight gradient) runs on the two plain kernels qm_gemm_kernel / qm_wgrad_kernel over the stacked rows, any width.
+// gradient, weight gradient) runs on the two plain kernels dense_gemm_kernel / dense_wgrad_kernel of xt_dense_dev.h over the
+// stacked rows, any width; the agent's forward and backward are agent_fwd / agent_bwd of xt_qmix_dev.h, shared with SCC.
 // All of it float32 without contraction, no atomics, every sum in a fixed order: a train is bit-identical from run to run.
 #include <cmath>
 #include <new>
@@ -135,14 +136,10 @@ static int launch_mix(const QmMix& a, double* loss_out, hipStream_t st) {
              a.dq && a.dhyp && a.rowloss, "xt_qmix_mix: null argument");
   const long long rows = (long long)a.B * a.T;
   double* msum = const_cast<double*>(a.masksum);
-  hipLaunchKernelGGL(qm_sum_kernel<float>, dim3(1), dim3(256), 0, st, a.mask, rows, (const double*)nullptr, msum);
-  XT_LAUNCH_CHECK();
+  if (int rc = launch_dense_sum(a.mask, rows, nullptr, msum, st)) return rc;
   hipLaunchKernelGGL(qmix_mix_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a);
   XT_LAUNCH_CHECK();
-  if (loss_out) {
-    hipLaunchKernelGGL(qm_sum_kernel<double>, dim3(1), dim3(256), 0, st, (const double*)a.rowloss, rows, a.masksum, loss_out);
-    XT_LAUNCH_CHECK();
-  }
+  if (loss_out) return launch_dense_sum((const double*)a.rowloss, rows, a.masksum, loss_out, st);
   return 0;
 }
 
@@ -187,9 +184,8 @@ struct xt_qmix {
 
 namespace xt {
 
-enum { QW1, QB1, QWG, QBG, QWC, QBC, QW2, QB2, HW1K0, HW1B0, HW1K1, HW1B1, HB1K, HB1B, HWFK0, HWFB0, HWFK1, HWFB1, HVK0, HVB0, HVK1, HVB1 };
-
-static inline int64_t qm_al4(int64_t x) { return (x + 3) & ~(int64_t)3; }
+// (the agent's eight tensors AW1 .. AB2 come first)
+enum { HW1K0 = kQmAgentTensors, HW1B0, HW1K1, HW1B1, HB1K, HB1B, HWFK0, HWFB0, HWFK1, HWFB1, HVK0, HVB0, HVK1, HVB1 };
 
 static int qm_check_desc(const xt_qmix_desc& d, const char* who) {
   XT_REQUIRE(d.hidden == 32 || d.hidden == 64, "%s: rnn_hidden_dim = %d (the recurrent kernels take 32 or 64)", who, d.hidden);
@@ -211,7 +207,7 @@ static void qm_layout(const xt_qmix_desc& d, int64_t* off, int* cnt) {
   for (int i = 0; i < kQmTensors; ++i) {
     off[i] = o;
     if (cnt) cnt[i] = c[i];
-    o += qm_al4(c[i]);
+    o += al4(c[i]);
   }
   off[kQmTensors] = o;
 }
@@ -221,7 +217,7 @@ static void qm_plan(xt_qmix* z) {
   const int64_t B = z->max_batch, T = d.seq_len, T1 = T + 1, n = d.n_agents, S = B * n, M = T1 * S, R = B * T;
   const int64_t H = d.hidden, A = d.n_actions, E = d.embed, HE = d.hyper_embed, P = n * E + 2 * E + 1, D = d.obs_dim, sd = d.state_dim;
   int64_t off = 0;
-  auto take = [&](int64_t k) { const int64_t o = off; off += qm_al4(k); return o; };
+  auto take = [&](int64_t k) { const int64_t o = off; off += al4(k); return o; };
   for (int s = 0; s < 2; ++s) {
     z->o_x1[s] = take(M * H); z->o_xg[s] = take(M * 3 * H); z->o_out[s] = take(M * H); z->o_q[s] = take(M * A);
     z->o_ahw1[s] = take(R * HE); z->o_ahwf[s] = take(R * HE); z->o_av[s] = take(R * E); z->o_hyp[s] = take(R * P);
@@ -239,48 +235,23 @@ static void qm_plan(xt_qmix* z) {
   z->ws_floats = off;
 }
 
-struct QmSets { const float* p[2]; };
-
-// the agent's forward of `nset` parameter sets over B episodes of T1 steps: q [T1, S, A] time-major per set (or, `q_bt`, one set
-// into a [B, T1, n, A] array)
-static int qm_agent_fwd(const xt_qmix* z, const QmSets& ps, int nset, const float* obs, int B, int T1, const float* h0, const int32_t* lens,
-                        bool save, float* q_bt, float* hT, hipStream_t st) {
-  const xt_qmix_desc& d = z->d;
-  const int H = d.hidden, A = d.n_actions, n = d.n_agents, S = B * n, M = T1 * S;
+// the agent's view of the handle: its tensors and its part of the workspace
+static RnnAgent qm_agent(const xt_qmix* z) {
+  RnnAgent g{};
+  g.obs_dim = z->d.obs_dim; g.H = z->d.hidden; g.A = z->d.n_actions; g.n = z->d.n_agents;
+  for (int i = 0; i < kQmAgentTensors; ++i) g.off[i] = z->off[i];
   float* ws = z->ws;
-  QmGruFwd gf{};
-  for (int s = 0; s < nset; ++s) {
-    const float* p = ps.p[s];
-    QmGemm a{};
-    a.x = obs; a.ldx = d.obs_dim; a.K = d.obs_dim; a.w = p + z->off[QW1]; a.ldw = H; a.M = M; a.N = H; a.bias = p + z->off[QB1];
-    a.relu = 1; a.y = ws + z->o_x1[s]; a.ldy = H; a.imap = 1; a.S = S; a.n = n; a.T = T1;
-    if (int rc = launch_qm_gemm(a, st)) return rc;
-    QmGemm g{};
-    g.x = ws + z->o_x1[s]; g.ldx = H; g.K = H; g.w = p + z->off[QWG]; g.ldw = 2 * H; g.M = M; g.N = 2 * H; g.bias = p + z->off[QBG];
-    g.y = ws + z->o_xg[s]; g.ldy = 3 * H;
-    if (int rc = launch_qm_gemm(g, st)) return rc;
-    g.w = p + z->off[QWC]; g.ldw = H; g.N = H; g.bias = p + z->off[QBC]; g.y = ws + z->o_xg[s] + 2 * H;
-    if (int rc = launch_qm_gemm(g, st)) return rc;
-    gf.wg[s] = p + z->off[QWG]; gf.wc[s] = p + z->off[QWC]; gf.xg[s] = ws + z->o_xg[s]; gf.h0[s] = h0;
-    gf.saved[s] = save && s == 0 ? ws + z->o_saved : nullptr; gf.out[s] = ws + z->o_out[s]; gf.hT[s] = hT;
-  }
-  gf.lens = lens; gf.T1 = T1; gf.S = S;
-  if (int rc = launch_gru_fwd(gf, H, nset, st)) return rc;
-  for (int s = 0; s < nset; ++s) {
-    const float* p = ps.p[s];
-    QmGemm a{};
-    a.x = ws + z->o_out[s]; a.ldx = H; a.K = H; a.w = p + z->off[QW2]; a.ldw = A; a.M = M; a.N = A; a.bias = p + z->off[QB2];
-    a.y = q_bt ? q_bt : ws + z->o_q[s]; a.ldy = A; a.omap = q_bt ? 1 : 0; a.S = S; a.n = n; a.T = T1;
-    if (int rc = launch_qm_gemm(a, st)) return rc;
-  }
-  return 0;
+  for (int s = 0; s < 2; ++s) { g.x1[s] = ws + z->o_x1[s]; g.xg[s] = ws + z->o_xg[s]; g.out[s] = ws + z->o_out[s]; g.q[s] = ws + z->o_q[s]; }
+  g.saved = ws + z->o_saved; g.dq = ws + z->o_dq; g.dout = ws + z->o_dout; g.dg3 = ws + z->o_dg3; g.dx1 = ws + z->o_dx1;
+  g.slabs = ws + z->o_slabs;
+  return g;
 }
 
 // y [R, N] at column `c0` of a [R, ldy] array = act(x . w + b) of Dense tensor pair (k, k + 1)
 static int qm_dense(const xt_qmix* z, const float* p, int k, const float* x, int K, int R, int N, int relu, float* y, int ldy, hipStream_t st) {
-  QmGemm a{};
+  DenseGemm a{};
   a.x = x; a.ldx = K; a.K = K; a.w = p + z->off[k]; a.ldw = N; a.M = R; a.N = N; a.bias = p + z->off[k + 1]; a.relu = relu; a.y = y; a.ldy = ldy;
-  return launch_qm_gemm(a, st);
+  return launch_dense_gemm(a, st);
 }
 
 static int qm_hyper_fwd(const xt_qmix* z, const float* p, int s, const float* state, int R, hipStream_t st) {
@@ -299,22 +270,16 @@ static int qm_hyper_fwd(const xt_qmix* z, const float* p, int s, const float* st
 
 // gradient of Dense pair (k, k + 1): dW = x^T dy, db = sum dy
 static int qm_dense_wgrad(const xt_qmix* z, int k, const float* x, int K, const float* dy, int ldy, int R, int N, hipStream_t st) {
-  QmWgrad a{};
+  DenseWgrad a{};
   a.x = x; a.ldx = K; a.dy = dy; a.ldy = ldy; a.M = R; a.K = K; a.N = N;
-  return launch_qm_wgrad(a, z->grads + z->off[k], z->grads + z->off[k + 1], z->ws + z->o_slabs, st);
+  return launch_dense_wgrad(a, z->grads + z->off[k], z->grads + z->off[k + 1], z->ws + z->o_slabs, kQmWgradRows, false, st);
 }
 
 // dx [R, K] = relu'(xact) * (dy . w^T) of Dense kernel k ([K, N])
 static int qm_dense_dgrad(const xt_qmix* z, int k, const float* dy, int ldy, int R, int K, int N, const float* xact, float* dx, hipStream_t st) {
-  QmGemm a{};
+  DenseGemm a{};
   a.x = dy; a.ldx = ldy; a.K = N; a.w = z->pe + z->off[k]; a.ldw = N; a.wt = 1; a.M = R; a.N = K; a.maskx = xact; a.ldm = K; a.y = dx; a.ldy = K;
-  return launch_qm_gemm(a, st);
-}
-
-static int qm_bound(const xt_qmix* z, int B, const char* who) {
-  XT_REQUIRE(z && z->pe && z->ws, "%s: the handle is not bound", who);
-  XT_REQUIRE(B >= 1 && B <= z->max_batch, "%s: B = %d outside [1, %d]", who, B, z->max_batch);
-  return 0;
+  return launch_dense_gemm(a, st);
 }
 
 }  // namespace xt
@@ -374,20 +339,20 @@ int xt_qmix_step(xt_qmix* h, const float* obs, const int32_t* lens, const float*
                  const float* state_next, const float* rewards, const float* terminated, const float* mask, int32_t B,
                  const xt_qmix_cfg* cfg, double* loss_out, void* stream) {
   using namespace xt;
-  if (int rc = qm_bound(h, B, "xt_qmix_step")) return rc;
+  if (int rc = check_bound(h, &xt_qmix::pe, B, "xt_qmix_step")) return rc;
   XT_REQUIRE(obs && avail && actions && state_cur && state_next && rewards && terminated && mask && cfg && loss_out,
              "xt_qmix_step: null argument");
   const xt_qmix* z = h;
   const xt_qmix_desc& d = z->d;
   const hipStream_t st = as_stream(stream);
-  const int H = d.hidden, A = d.n_actions, n = d.n_agents, E = d.embed, HE = d.hyper_embed, sd = d.state_dim, T = d.seq_len, T1 = T + 1;
-  const int S = B * n, M = T1 * S, R = B * T, P = n * E + 2 * E + 1;
+  const int A = d.n_actions, n = d.n_agents, E = d.embed, HE = d.hyper_embed, sd = d.state_dim, T = d.seq_len, T1 = T + 1;
+  const int R = B * T, P = n * E + 2 * E + 1;
   float* ws = z->ws;
-  float* slabs = ws + z->o_slabs;
+  const RnnAgent ag = qm_agent(z);
 
   // ---- forward: both agents (one recurrent launch), both hypernets
-  QmSets ps{{z->pe, z->pt}};
-  if (int rc = qm_agent_fwd(z, ps, 2, obs, B, T1, nullptr, lens, true, nullptr, nullptr, st)) return rc;
+  const float* const ps[2] = {z->pe, z->pt};
+  if (int rc = agent_fwd(ag, ps, 2, obs, B, T1, nullptr, lens, true, nullptr, nullptr, st)) return rc;
   if (int rc = qm_hyper_fwd(z, z->pe, 0, state_cur, R, st)) return rc;
   if (int rc = qm_hyper_fwd(z, z->pt, 1, state_next, R, st)) return rc;
 
@@ -413,42 +378,8 @@ int xt_qmix_step(xt_qmix* h, const float* obs, const int32_t* lens, const float*
   if (int rc = qm_dense_dgrad(z, HVK1, dhyp + n * E + 2 * E, P, R, E, 1, ws + z->o_av[0], ws + z->o_dav, st)) return rc;
   if (int rc = qm_dense_wgrad(z, HVK0, state_cur, sd, ws + z->o_dav, E, R, E, st)) return rc;
 
-  // ---- the eval agent's backward: dense_1, BPTT, then everything over the stacked rows
-  const float* dq = ws + z->o_dq;
-  if (int rc = qm_dense_wgrad(z, QW2, ws + z->o_out[0], H, dq, A, M, A, st)) return rc;
-  if (int rc = qm_dense_dgrad(z, QW2, dq, A, M, H, A, nullptr, ws + z->o_dout, st)) return rc;
-  QmGruBwd gb{};
-  gb.wg = z->pe + z->off[QWG]; gb.wc = z->pe + z->off[QWC]; gb.saved = ws + z->o_saved; gb.dout = ws + z->o_dout; gb.lens = lens;
-  gb.dg3 = ws + z->o_dg3; gb.T1 = T1; gb.S = S;
-  if (int rc = launch_gru_bwd(gb, H, st)) return rc;
-  const float* dg3 = ws + z->o_dg3;
-  const float* x1 = ws + z->o_x1[0];
-  const float* saved = ws + z->o_saved;
-  {
-    QmWgrad a{};      // gates kernel, input rows (and the bias); then the recurrent rows: h_{t-1} is the saved state one step up
-    a.x = x1; a.ldx = H; a.dy = dg3; a.ldy = 3 * H; a.M = M; a.K = H; a.N = 2 * H;
-    if (int rc = launch_qm_wgrad(a, z->grads + z->off[QWG], z->grads + z->off[QBG], slabs, st)) return rc;
-    a.x = saved + 3 * H; a.ldx = 4 * H; a.dy = dg3 + (long long)S * 3 * H; a.M = M - S;
-    if (int rc = launch_qm_wgrad(a, z->grads + z->off[QWG] + 2 * H * H, nullptr, slabs, st)) return rc;
-    QmWgrad c{};      // candidate kernel: input rows (and the bias), then r o h_{t-1}
-    c.x = x1; c.ldx = H; c.dy = dg3 + 2 * H; c.ldy = 3 * H; c.M = M; c.K = H; c.N = H;
-    if (int rc = launch_qm_wgrad(c, z->grads + z->off[QWC], z->grads + z->off[QBC], slabs, st)) return rc;
-    c.x = saved + 3 * H; c.ldx = 4 * H; c.xmul = saved + (long long)S * 4 * H; c.ldxm = 4 * H; c.dy = dg3 + (long long)S * 3 * H + 2 * H;
-    c.M = M - S;
-    if (int rc = launch_qm_wgrad(c, z->grads + z->off[QWC] + H * H, nullptr, slabs, st)) return rc;
-  }
-  {
-    QmGemm a{};       // d x1 = relu'(x1) * ([dr | du] . Wg[:H]^T + dc . Wc[:H]^T)
-    a.x = dg3; a.ldx = 3 * H; a.K = 2 * H; a.w = z->pe + z->off[QWG]; a.ldw = 2 * H; a.wt = 1; a.M = M; a.N = H; a.y = ws + z->o_dx1; a.ldy = H;
-    if (int rc = launch_qm_gemm(a, st)) return rc;
-    a.x = dg3 + 2 * H; a.K = H; a.w = z->pe + z->off[QWC]; a.ldw = H; a.add = ws + z->o_dx1; a.maskx = x1; a.ldm = H;
-    if (int rc = launch_qm_gemm(a, st)) return rc;
-    QmWgrad wg{};
-    wg.x = obs; wg.ldx = d.obs_dim; wg.dy = ws + z->o_dx1; wg.ldy = H; wg.M = M; wg.K = d.obs_dim; wg.N = H; wg.imap = 1; wg.S = S; wg.n = n;
-    wg.T = T1;
-    if (int rc = launch_qm_wgrad(wg, z->grads + z->off[QW1], z->grads + z->off[QB1], slabs, st)) return rc;
-  }
-  return 0;
+  // ---- the eval agent's backward
+  return agent_bwd(ag, z->pe, z->grads, obs, lens, B, T1, st);
 }
 
 int xt_qmix_apply(xt_qmix* h, const xt_qmix_cfg* cfg, void* stream) {
@@ -481,11 +412,10 @@ int xt_qmix_sync_target(xt_qmix* h, void* stream) {
 int xt_qmix_agent_forward(xt_qmix* h, const float* agent_params, const float* obs, int32_t B, int32_t T, const float* hidden_in,
                           const int32_t* lens, float* q, float* hidden_out, void* stream) {
   using namespace xt;
-  if (int rc = qm_bound(h, B, "xt_qmix_agent_forward")) return rc;
+  if (int rc = check_bound(h, &xt_qmix::pe, B, "xt_qmix_agent_forward")) return rc;
   XT_REQUIRE(agent_params && obs && q, "xt_qmix_agent_forward: null argument");
   XT_REQUIRE(T >= 1 && T <= h->d.seq_len + 1, "xt_qmix_agent_forward: T = %d outside [1, %d]", T, h->d.seq_len + 1);
-  QmSets ps{{agent_params, nullptr}};
-  return qm_agent_fwd(h, ps, 1, obs, B, T, hidden_in, lens, false, q, hidden_out, as_stream(stream));
+  return agent_fwd(qm_agent(h), &agent_params, 1, obs, B, T, hidden_in, lens, false, q, hidden_out, as_stream(stream));
 }
 
 int xt_qmix_gru_fwd(const float* wg, const float* wc, const float* xg, const float* h0, const int32_t* lens, int32_t T1, int32_t S,

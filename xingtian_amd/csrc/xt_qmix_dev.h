@@ -1,10 +1,12 @@
 // Device code shared by the QMIX and SCC learners (xt_qmix.hip, xt_scc.hip): the two persistent GRU kernels and their
-// launchers, the plain Dense / weight-gradient kernels over stacked rows, the ordered float64 sum and the per-tensor norm.
+// launchers, the Dense -> GRU -> Dense agent built from them and the plain Dense kernels of xt_dense_dev.h (agent_fwd,
+// agent_bwd), and the per-tensor norm.
 // Every translation unit that includes this file gets its own copy (internal linkage).
 #pragma once
 #include <cmath>
 
 #include "xt_common.h"
+#include "xt_dense_dev.h"
 
 namespace xt {
 namespace {
@@ -14,154 +16,7 @@ constexpr int kQmWgradRows = 512;       // rows of one weight-gradient slab
 constexpr int kQmTensors = XT_QMIX_TENSORS;
 constexpr int kQmAgentTensors = 8;
 
-// time-major row r = t * S + b * n + a  ->  row (b * T + t) * n + a of a [B, T, n, .] array
-__device__ __forceinline__ long long qm_bt_row(long long r, int S, int n, int T) {
-  const int t = (int)(r / S), s = (int)(r % S);
-  return ((long long)(s / n) * T + t) * n + s % n;
-}
-
-// ------------------------------------------------------------------ y = epilogue(x . w)
-struct QmGemm {
-  const float* x; int ldx;
-  const float* w; int ldw; int wt;       // element (k, n) of the kernel at w[k * ldw + n], or (wt) at w[n * ldw + k]
-  int M, K, N;
-  const float* bias; int relu;
-  const float* add;                      // [M, ldy] or null: y = add + acc (may be y itself)
-  const float* maskx; int ldm;           // null, or y = 0 where maskx[m, n] <= 0
-  float* y; int ldy;
-  int imap, omap, S, n, T;               // imap / omap: x / y rows are [B, T, n, .] rows, m is time-major
-};
-
-__global__ __launch_bounds__(256) void qm_gemm_kernel(const QmGemm a) {
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long total = (long long)((a.M + 3) >> 2) * a.N;
-  if (gid >= total) return;
-  const int n = (int)(gid % a.N);
-  const int m0 = (int)(gid / a.N) * 4;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  const float* xr[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const long long m = m0 + r < a.M ? m0 + r : a.M - 1;
-    xr[r] = a.x + (a.imap ? qm_bt_row(m, a.S, a.n, a.T) : m) * a.ldx;
-  }
-  const long long wk = a.wt ? 1 : a.ldw, wn = a.wt ? a.ldw : 1;
-  for (int k = 0; k < a.K; ++k) {
-    const float wv = a.w[k * wk + n * wn];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = acc[r] + xr[r][k] * wv;
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int m = m0 + r;
-    if (m >= a.M) break;
-    float v = acc[r];
-    const long long yr = a.omap ? qm_bt_row(m, a.S, a.n, a.T) : m;
-    if (a.bias) v = v + a.bias[n];
-    if (a.add) v = a.add[yr * a.ldy + n] + v;
-    if (a.relu) v = v > 0.f ? v : 0.f;
-    if (a.maskx && !(a.maskx[(long long)m * a.ldm + n] > 0.f)) v = 0.f;
-    a.y[yr * a.ldy + n] = v;
-  }
-}
-
-static int launch_qm_gemm(const QmGemm& a, hipStream_t st) {
-  XT_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0 && a.x && a.w && a.y, "qmix gemm: bad arguments");
-  const long long total = (long long)((a.M + 3) >> 2) * a.N;
-  XT_REQUIRE((total + 255) / 256 < (1ll << 31), "qmix gemm: too many outputs");
-  hipLaunchKernelGGL(qm_gemm_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
-  XT_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------ dW = x^T . dy (+ db) over row slabs, then the slabs
-struct QmWgrad {
-  const float* x; int ldx;
-  const float* xmul; int ldxm;           // null, or the x element is x * xmul (r o h of the candidate kernel)
-  const float* dy; int ldy;
-  int M, K, N, nslab, bias;
-  int imap, S, n, T;
-  float* out;                            // [nslab, (K + bias) * N]
-};
-
-__global__ __launch_bounds__(256) void qm_wgrad_kernel(const QmWgrad a) {
-  const long long count = (long long)(a.K + a.bias) * a.N;
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= count * a.nslab) return;
-  const int s = (int)(gid / count);
-  const int e = (int)(gid % count);
-  const int kk = e / a.N, n = e % a.N;
-  const int r0 = s * kQmWgradRows;
-  const int r1 = r0 + kQmWgradRows < a.M ? r0 + kQmWgradRows : a.M;
-  float acc = 0.f;
-  if (kk < a.K) {
-    for (int r = r0; r < r1; ++r) {
-      const long long xr = a.imap ? qm_bt_row(r, a.S, a.n, a.T) : r;
-      float xv = a.x[xr * a.ldx + kk];
-      if (a.xmul) xv = xv * a.xmul[(long long)r * a.ldxm + kk];
-      acc = acc + xv * a.dy[(long long)r * a.ldy + n];
-    }
-  } else {
-    for (int r = r0; r < r1; ++r) acc = acc + a.dy[(long long)r * a.ldy + n];
-  }
-  a.out[gid] = acc;
-}
-
-// dw[e] (e < nw) / db[e - nw] = sum over ascending s of slabs[s][e]
-__global__ __launch_bounds__(256) void qm_slab_sum_kernel(const float* __restrict__ slabs, long long count, long long nw, int nslab,
-                                                          float* __restrict__ dw, float* __restrict__ db) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= count) return;
-  float acc = 0.f;
-  for (int s = 0; s < nslab; ++s) acc = acc + slabs[(long long)s * count + e];
-  if (e < nw) dw[e] = acc;
-  else db[e - nw] = acc;
-}
-
-__global__ __launch_bounds__(256) void qm_fill_kernel(float* __restrict__ p, long long n, float v) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (e < n) p[e] = v;
-}
-
-static inline int qm_nslab(long long M) { return (int)((M + kQmWgradRows - 1) / kQmWgradRows); }
-
-// dw [K, N] and (db != null) db [N]; `slabs` holds qm_nslab(M) * (K + 1) * N floats.  M == 0: dw (and db) = 0.
-static int launch_qm_wgrad(QmWgrad a, float* dw, float* db, float* slabs, hipStream_t st) {
-  XT_REQUIRE(dw && slabs && a.K > 0 && a.N > 0 && a.M >= 0, "qmix wgrad: bad arguments");
-  a.bias = db ? 1 : 0;
-  const long long count = (long long)(a.K + a.bias) * a.N, nw = (long long)a.K * a.N;
-  if (a.M == 0) {
-    hipLaunchKernelGGL(qm_fill_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, dw, nw, 0.f);
-    if (db) hipLaunchKernelGGL(qm_fill_kernel, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, st, db, (long long)a.N, 0.f);
-    XT_LAUNCH_CHECK();
-    return 0;
-  }
-  XT_REQUIRE(a.x && a.dy, "qmix wgrad: bad arguments");
-  a.nslab = qm_nslab(a.M);
-  a.out = slabs;
-  XT_REQUIRE((count * a.nslab + 255) / 256 < (1ll << 31), "qmix wgrad: too large");
-  hipLaunchKernelGGL(qm_wgrad_kernel, dim3((unsigned)((count * a.nslab + 255) / 256)), dim3(256), 0, st, a);
-  XT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(qm_slab_sum_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, slabs, count, nw, a.nslab, dw, db);
-  XT_LAUNCH_CHECK();
-  return 0;
-}
-
-// out[0] = (sum of n values, thread t takes t, t + 256, ... ascending, then a fixed tree) / (div ? div[0] : 1)
-template <typename T>
-__global__ __launch_bounds__(256) void qm_sum_kernel(const T* __restrict__ src, long long n, const double* __restrict__ div,
-                                                     double* __restrict__ out) {
-  __shared__ double sh[256];
-  double acc = 0.0;
-  for (long long i = threadIdx.x; i < n; i += 256) acc += (double)src[i];
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = div ? sh[0] / div[0] : sh[0];
-}
+static inline int qm_nslab(long long M) { return dense_nslab(M, kQmWgradRows); }
 
 // ------------------------------------------------------------------ the persistent GRU forward
 // Tile = 16 sequences x all T1 steps; H / 16 wavefronts, wavefront w owns the hidden columns [16 w, 16 w + 16) of r, u and c.
@@ -379,6 +234,89 @@ static int launch_gru_bwd(const QmGruBwd& a, int H, hipStream_t st) {
   return 0;
 }
 
+// ------------------------------------------------------------------ the recurrent agent: dense (relu) -> GRU -> dense_1
+enum { AW1, AB1, AWG, ABG, AWC, ABC, AW2, AB2 };      // its eight tensors, the first eight of a parameter set
+
+struct RnnAgent {
+  int obs_dim, H, A, n;
+  int64_t off[kQmAgentTensors];          // flat offsets of the tensors in a parameter set (and in the gradient)
+  float *x1[2], *xg[2], *out[2], *q[2];  // per parameter set of one forward: [M, H], [M, 3H], [M, H], [M, A], M = T1 S time-major
+  float *saved;                          // [M, 4H] of set 0
+  float *dq, *dout, *dg3, *dx1, *slabs;  // the backward's: [M, A], [M, H], [M, 3H], [M, H], qm_nslab(M) weight-gradient slabs
+};
+
+// the forward of `nset` parameter sets (one recurrent launch) over B episodes of T1 steps: q [T1, S, A] time-major per set (or,
+// `q_bt`, one set into a [B, T1, n, A] array)
+static int agent_fwd(const RnnAgent& g, const float* const* ps, int nset, const float* obs, int B, int T1, const float* h0,
+                     const int32_t* lens, bool save, float* q_bt, float* hT, hipStream_t st) {
+  const int H = g.H, A = g.A, S = B * g.n, M = T1 * S;
+  QmGruFwd gf{};
+  for (int s = 0; s < nset; ++s) {
+    const float* p = ps[s];
+    DenseGemm a{};
+    a.x = obs; a.ldx = g.obs_dim; a.K = g.obs_dim; a.w = p + g.off[AW1]; a.ldw = H; a.M = M; a.N = H; a.bias = p + g.off[AB1];
+    a.relu = 1; a.y = g.x1[s]; a.ldy = H; a.imap = 1; a.S = S; a.n = g.n; a.T = T1;
+    if (int rc = launch_dense_gemm(a, st)) return rc;
+    DenseGemm x{};
+    x.x = g.x1[s]; x.ldx = H; x.K = H; x.w = p + g.off[AWG]; x.ldw = 2 * H; x.M = M; x.N = 2 * H; x.bias = p + g.off[ABG];
+    x.y = g.xg[s]; x.ldy = 3 * H;
+    if (int rc = launch_dense_gemm(x, st)) return rc;
+    x.w = p + g.off[AWC]; x.ldw = H; x.N = H; x.bias = p + g.off[ABC]; x.y = g.xg[s] + 2 * H;
+    if (int rc = launch_dense_gemm(x, st)) return rc;
+    gf.wg[s] = p + g.off[AWG]; gf.wc[s] = p + g.off[AWC]; gf.xg[s] = g.xg[s]; gf.h0[s] = h0;
+    gf.saved[s] = save && s == 0 ? g.saved : nullptr; gf.out[s] = g.out[s]; gf.hT[s] = hT;
+  }
+  gf.lens = lens; gf.T1 = T1; gf.S = S;
+  if (int rc = launch_gru_fwd(gf, H, nset, st)) return rc;
+  for (int s = 0; s < nset; ++s) {
+    const float* p = ps[s];
+    DenseGemm a{};
+    a.x = g.out[s]; a.ldx = H; a.K = H; a.w = p + g.off[AW2]; a.ldw = A; a.M = M; a.N = A; a.bias = p + g.off[AB2];
+    a.y = q_bt ? q_bt : g.q[s]; a.ldy = A; a.omap = q_bt ? 1 : 0; a.S = S; a.n = g.n; a.T = T1;
+    if (int rc = launch_dense_gemm(a, st)) return rc;
+  }
+  return 0;
+}
+
+// the backward of parameter set `p` (set 0 of a saving forward) from dq [T1, S, A] into `gr`: dense_1, BPTT, then everything over
+// the stacked rows
+static int agent_bwd(const RnnAgent& g, const float* p, float* gr, const float* obs, const int32_t* lens, int B, int T1, hipStream_t st) {
+  const int H = g.H, A = g.A, S = B * g.n, M = T1 * S;
+  const float *x1 = g.x1[0], *saved = g.saved, *dg3 = g.dg3;
+  auto wgrad = [&](const DenseWgrad& a, int k, int row0, bool bias) {
+    return launch_dense_wgrad(a, gr + g.off[k] + row0 * a.N, bias ? gr + g.off[k + 1] : nullptr, g.slabs, kQmWgradRows, false, st);
+  };
+  DenseWgrad w2{};
+  w2.x = g.out[0]; w2.ldx = H; w2.dy = g.dq; w2.ldy = A; w2.M = M; w2.K = H; w2.N = A;
+  if (int rc = wgrad(w2, AW2, 0, true)) return rc;
+  DenseGemm dx{};     // d out = dq . W2^T
+  dx.x = g.dq; dx.ldx = A; dx.K = A; dx.w = p + g.off[AW2]; dx.ldw = A; dx.wt = 1; dx.M = M; dx.N = H; dx.y = g.dout; dx.ldy = H;
+  if (int rc = launch_dense_gemm(dx, st)) return rc;
+  QmGruBwd gb{};
+  gb.wg = p + g.off[AWG]; gb.wc = p + g.off[AWC]; gb.saved = saved; gb.dout = g.dout; gb.lens = lens; gb.dg3 = g.dg3; gb.T1 = T1; gb.S = S;
+  if (int rc = launch_gru_bwd(gb, H, st)) return rc;
+  DenseWgrad a{};     // gates kernel, input rows (and the bias); then the recurrent rows: h_{t-1} is the saved state one step up
+  a.x = x1; a.ldx = H; a.dy = dg3; a.ldy = 3 * H; a.M = M; a.K = H; a.N = 2 * H;
+  if (int rc = wgrad(a, AWG, 0, true)) return rc;
+  a.x = saved + 3 * H; a.ldx = 4 * H; a.dy = dg3 + (long long)S * 3 * H; a.M = M - S;
+  if (int rc = wgrad(a, AWG, H, false)) return rc;
+  DenseWgrad c{};     // candidate kernel: input rows (and the bias), then r o h_{t-1}
+  c.x = x1; c.ldx = H; c.dy = dg3 + 2 * H; c.ldy = 3 * H; c.M = M; c.K = H; c.N = H;
+  if (int rc = wgrad(c, AWC, 0, true)) return rc;
+  c.x = saved + 3 * H; c.ldx = 4 * H; c.xmul = saved + (long long)S * 4 * H; c.ldxm = 4 * H; c.dy = dg3 + (long long)S * 3 * H + 2 * H;
+  c.M = M - S;
+  if (int rc = wgrad(c, AWC, H, false)) return rc;
+  DenseGemm e{};      // d x1 = relu'(x1) * ([dr | du] . Wg[:H]^T + dc . Wc[:H]^T)
+  e.x = dg3; e.ldx = 3 * H; e.K = 2 * H; e.w = p + g.off[AWG]; e.ldw = 2 * H; e.wt = 1; e.M = M; e.N = H; e.y = g.dx1; e.ldy = H;
+  if (int rc = launch_dense_gemm(e, st)) return rc;
+  e.x = dg3 + 2 * H; e.K = H; e.w = p + g.off[AWC]; e.ldw = H; e.add = g.dx1; e.maskx = x1; e.ldm = H;
+  if (int rc = launch_dense_gemm(e, st)) return rc;
+  DenseWgrad w1{};
+  w1.x = obs; w1.ldx = g.obs_dim; w1.dy = g.dx1; w1.ldy = H; w1.M = M; w1.K = g.obs_dim; w1.N = H; w1.imap = 1; w1.S = S; w1.n = g.n;
+  w1.T = T1;
+  return wgrad(w1, AW1, 0, true);
+}
+
 // ------------------------------------------------------------------ centred RMSProp, tf.clip_by_norm per tensor
 struct QmSegs {
   int n;
@@ -387,18 +325,12 @@ struct QmSegs {
 
 // norm2[i] = sum of squares of tensor i: thread t takes t, t + 256, ... ascending in float64, then a fixed tree
 __global__ __launch_bounds__(256) void qmix_norm_kernel(const float* __restrict__ g, const QmSegs s, double* __restrict__ norm2) {
-  __shared__ double sh[256];
   const float* p = g + s.off[blockIdx.x];
   const int cnt = s.cnt[blockIdx.x];
   double acc = 0.0;
   for (int i = threadIdx.x; i < cnt; i += 256) acc += (double)p[i] * (double)p[i];
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) norm2[blockIdx.x] = sh[0];
+  const double sum = dense_tree_sum(acc);
+  if (threadIdx.x == 0) norm2[blockIdx.x] = sum;
 }
 
 }  // namespace

@@ -1,5 +1,6 @@
 // SCC: the multi-channel critic, the counterfactual credits and the two optimisers (xt_scc_* of include/xt_mi355x.h, DESIGN
-// section 10).  The GRU agent is QMIX's: its kernels and the plain Dense kernels come from xt_qmix_dev.h.
+// section 10).  The GRU agent is QMIX's: agent_fwd / agent_bwd and the recurrent kernels come from xt_qmix_dev.h, the plain Dense
+// kernels (dense_gemm_kernel, dense_wgrad_kernel, the slab sum, the ordered sum) from xt_dense_dev.h.
 //
 //   scc_critic_fwd_kernel   one pass over the (row, agent) items, agent-major: a workgroup stages its group's L2 in LDS once and
 //                           walks 16-item tiles; one first-layer product (fp32 MFMA 16x16x4, the one-hot column added as a weight
@@ -25,9 +26,6 @@ namespace xt {
 constexpr int kSccKC = 64;               // first-layer K chunk staged in LDS
 constexpr int kSccMaxAgents = 32;
 constexpr int kSccAgentTensors = 8;
-enum { SW1, SB1, SWG, SBG, SWC, SBC, SW2, SB2 };
-
-static inline int64_t scc_al4(int64_t x) { return (x + 3) & ~(int64_t)3; }
 __device__ __forceinline__ int scc_dal4(int x) { return (x + 3) & ~3; }
 
 // where agent i's critic weights are in a parameter set, and how an item finds its source row
@@ -281,7 +279,7 @@ static int launch_scc_bwd(const SccCriticBwd& a, int U, hipStream_t st) {
   return launch_scc_bwd_u<32>(a, st);
 }
 
-// ------------------------------------------------------------------ weight gradients, slab-ordered as qm_wgrad_kernel
+// ------------------------------------------------------------------ weight gradients, slab-ordered as dense_wgrad_kernel
 // dL1 [o + A, U] | db1 [U] of one group: the rows are the group's items (agent-major), the x element is the observation below o,
 // the one-hot of the action from o to o + A (made here, never stored), 1 for the bias
 struct SccWgrad1 {
@@ -458,7 +456,7 @@ static int scc_layout(const xt_scc_desc& d, int64_t* off, int* cnt) {
   for (int i = 0; i < nt; ++i) {
     off[i] = o;
     if (cnt) cnt[i] = c[i];
-    o += scc_al4(c[i]);
+    o += al4(c[i]);
   }
   off[nt] = o;
   return nt;
@@ -469,7 +467,7 @@ static void scc_plan(xt_scc* z) {
   const int64_t B = z->max_batch, T = d.seq_len, T1 = T + 1, n = d.n_agents, S = B * n, M = T1 * S, R = B * T, NR = n * R;
   const int64_t H = d.hidden, A = d.n_actions, U = d.units, D = d.obs_dim, KA = D - n;
   int64_t off = 0;
-  auto take = [&](int64_t k) { const int64_t o = off; off += scc_al4(k); return o; };
+  auto take = [&](int64_t k) { const int64_t o = off; off += al4(k); return o; };
   z->o_x1 = take(M * H); z->o_xg = take(M * 3 * H); z->o_out = take(M * H); z->o_q = take(M * A); z->o_saved = take(M * 4 * H);
   z->o_dq = take(M * A); z->o_dout = take(M * H); z->o_dg3 = take(M * 3 * H); z->o_dx1 = take(M * H);
   z->o_sc = take(3 * NR); z->o_h1 = take(NR * U); z->o_h2 = take(NR * U); z->o_dh1 = take(NR * U); z->o_dh2 = take(NR * U);
@@ -484,76 +482,16 @@ static void scc_plan(xt_scc* z) {
   z->ws_floats = off;
 }
 
-static int scc_bound(const xt_scc* z, int B, const char* who) {
-  XT_REQUIRE(z && z->pe && z->ws, "%s: the handle is not bound", who);
-  XT_REQUIRE(B >= 1 && B <= z->max_batch, "%s: B = %d outside [1, %d]", who, B, z->max_batch);
-  return 0;
-}
-
-// the agent of parameter prefix `p` over B episodes of T1 steps: q [T1, S, A] time-major in the workspace, or [B, T1, n, A] in q_bt
-static int scc_agent_fwd(const xt_scc* z, const float* p, const float* obs, int B, int T1, const float* h0, const int32_t* lens, bool save,
-                         float* q_bt, float* hT, hipStream_t st) {
-  const xt_scc_desc& d = z->d;
-  const int H = d.hidden, A = d.n_actions, n = d.n_agents, S = B * n, M = T1 * S;
+// the agent's view of the handle: its tensors and its part of the workspace (one parameter set per forward)
+static RnnAgent scc_agent(const xt_scc* z) {
+  RnnAgent g{};
+  g.obs_dim = z->d.obs_dim; g.H = z->d.hidden; g.A = z->d.n_actions; g.n = z->d.n_agents;
+  for (int i = 0; i < kSccAgentTensors; ++i) g.off[i] = z->off[i];
   float* ws = z->ws;
-  QmGemm a{};
-  a.x = obs; a.ldx = d.obs_dim; a.K = d.obs_dim; a.w = p + z->off[SW1]; a.ldw = H; a.M = M; a.N = H; a.bias = p + z->off[SB1];
-  a.relu = 1; a.y = ws + z->o_x1; a.ldy = H; a.imap = 1; a.S = S; a.n = n; a.T = T1;
-  if (int rc = launch_qm_gemm(a, st)) return rc;
-  QmGemm g{};
-  g.x = ws + z->o_x1; g.ldx = H; g.K = H; g.w = p + z->off[SWG]; g.ldw = 2 * H; g.M = M; g.N = 2 * H; g.bias = p + z->off[SBG];
-  g.y = ws + z->o_xg; g.ldy = 3 * H;
-  if (int rc = launch_qm_gemm(g, st)) return rc;
-  g.w = p + z->off[SWC]; g.ldw = H; g.N = H; g.bias = p + z->off[SBC]; g.y = ws + z->o_xg + 2 * H;
-  if (int rc = launch_qm_gemm(g, st)) return rc;
-  QmGruFwd gf{};
-  gf.wg[0] = p + z->off[SWG]; gf.wc[0] = p + z->off[SWC]; gf.xg[0] = ws + z->o_xg; gf.h0[0] = h0;
-  gf.saved[0] = save ? ws + z->o_saved : nullptr; gf.out[0] = ws + z->o_out; gf.hT[0] = hT; gf.lens = lens; gf.T1 = T1; gf.S = S;
-  if (int rc = launch_gru_fwd(gf, H, 1, st)) return rc;
-  QmGemm q{};
-  q.x = ws + z->o_out; q.ldx = H; q.K = H; q.w = p + z->off[SW2]; q.ldw = A; q.M = M; q.N = A; q.bias = p + z->off[SB2];
-  q.y = q_bt ? q_bt : ws + z->o_q; q.ldy = A; q.omap = q_bt ? 1 : 0; q.S = S; q.n = n; q.T = T1;
-  return launch_qm_gemm(q, st);
-}
-
-// the eval agent's backward from dq [T1, S, A]: dense_1, BPTT, then everything over the stacked rows
-static int scc_agent_bwd(const xt_scc* z, const float* obs, const int32_t* lens, int B, hipStream_t st) {
-  const xt_scc_desc& d = z->d;
-  const int H = d.hidden, A = d.n_actions, n = d.n_agents, T1 = d.seq_len + 1, S = B * n, M = T1 * S;
-  float* ws = z->ws;
-  float* slabs = ws + z->o_slabs;
-  float* gr = z->grads;
-  const float *dq = ws + z->o_dq, *dg3 = ws + z->o_dg3, *x1 = ws + z->o_x1, *saved = ws + z->o_saved;
-  QmWgrad w2{};
-  w2.x = ws + z->o_out; w2.ldx = H; w2.dy = dq; w2.ldy = A; w2.M = M; w2.K = H; w2.N = A;
-  if (int rc = launch_qm_wgrad(w2, gr + z->off[SW2], gr + z->off[SB2], slabs, st)) return rc;
-  QmGemm dx{};
-  dx.x = dq; dx.ldx = A; dx.K = A; dx.w = z->pe + z->off[SW2]; dx.ldw = A; dx.wt = 1; dx.M = M; dx.N = H; dx.y = ws + z->o_dout; dx.ldy = H;
-  if (int rc = launch_qm_gemm(dx, st)) return rc;
-  QmGruBwd gb{};
-  gb.wg = z->pe + z->off[SWG]; gb.wc = z->pe + z->off[SWC]; gb.saved = saved; gb.dout = ws + z->o_dout; gb.lens = lens;
-  gb.dg3 = ws + z->o_dg3; gb.T1 = T1; gb.S = S;
-  if (int rc = launch_gru_bwd(gb, H, st)) return rc;
-  QmWgrad a{};        // gates kernel, input rows (and the bias); then the recurrent rows: h_{t-1} is the saved state one step up
-  a.x = x1; a.ldx = H; a.dy = dg3; a.ldy = 3 * H; a.M = M; a.K = H; a.N = 2 * H;
-  if (int rc = launch_qm_wgrad(a, gr + z->off[SWG], gr + z->off[SBG], slabs, st)) return rc;
-  a.x = saved + 3 * H; a.ldx = 4 * H; a.dy = dg3 + (long long)S * 3 * H; a.M = M - S;
-  if (int rc = launch_qm_wgrad(a, gr + z->off[SWG] + 2 * H * H, nullptr, slabs, st)) return rc;
-  QmWgrad c{};        // candidate kernel: input rows (and the bias), then r o h_{t-1}
-  c.x = x1; c.ldx = H; c.dy = dg3 + 2 * H; c.ldy = 3 * H; c.M = M; c.K = H; c.N = H;
-  if (int rc = launch_qm_wgrad(c, gr + z->off[SWC], gr + z->off[SBC], slabs, st)) return rc;
-  c.x = saved + 3 * H; c.ldx = 4 * H; c.xmul = saved + (long long)S * 4 * H; c.ldxm = 4 * H; c.dy = dg3 + (long long)S * 3 * H + 2 * H;
-  c.M = M - S;
-  if (int rc = launch_qm_wgrad(c, gr + z->off[SWC] + H * H, nullptr, slabs, st)) return rc;
-  QmGemm e{};         // d x1 = relu'(x1) * ([dr | du] . Wg[:H]^T + dc . Wc[:H]^T)
-  e.x = dg3; e.ldx = 3 * H; e.K = 2 * H; e.w = z->pe + z->off[SWG]; e.ldw = 2 * H; e.wt = 1; e.M = M; e.N = H; e.y = ws + z->o_dx1; e.ldy = H;
-  if (int rc = launch_qm_gemm(e, st)) return rc;
-  e.x = dg3 + 2 * H; e.K = H; e.w = z->pe + z->off[SWC]; e.ldw = H; e.add = ws + z->o_dx1; e.maskx = x1; e.ldm = H;
-  if (int rc = launch_qm_gemm(e, st)) return rc;
-  QmWgrad w1{};
-  w1.x = obs; w1.ldx = d.obs_dim; w1.dy = ws + z->o_dx1; w1.ldy = H; w1.M = M; w1.K = d.obs_dim; w1.N = H; w1.imap = 1; w1.S = S; w1.n = n;
-  w1.T = T1;
-  return launch_qm_wgrad(w1, gr + z->off[SW1], gr + z->off[SB1], slabs, st);
+  g.x1[0] = ws + z->o_x1; g.xg[0] = ws + z->o_xg; g.out[0] = ws + z->o_out; g.q[0] = ws + z->o_q;
+  g.saved = ws + z->o_saved; g.dq = ws + z->o_dq; g.dout = ws + z->o_dout; g.dg3 = ws + z->o_dg3; g.dx1 = ws + z->o_dx1;
+  g.slabs = ws + z->o_slabs;
+  return g;
 }
 
 static SccSrc scc_src(const xt_scc* z, const float* x, const int32_t* actions, int B, bool raw) {
@@ -583,17 +521,15 @@ static int scc_critic_bwd(const xt_scc* z, const float* p_eval, const SccSrc& sr
   for (int g = 0; g < d.n_groups; ++g) {
     const int i0 = z->gstart[g], M = d.groups[g] * R, t0 = kSccAgentTensors + 4 * g;
     const long long row0 = (long long)i0 * R * U;
-    QmWgrad w2{};
+    DenseWgrad w2{};
     w2.x = ws + z->o_h1 + row0; w2.ldx = U; w2.dy = ws + z->o_dh2 + row0; w2.ldy = U; w2.M = M; w2.K = U; w2.N = U;
-    if (int rc = launch_qm_wgrad(w2, grads + z->off[t0 + 2], grads + z->off[t0 + 3], slabs, st)) return rc;
+    if (int rc = launch_dense_wgrad(w2, grads + z->off[t0 + 2], grads + z->off[t0 + 3], slabs, kQmWgradRows, false, st)) return rc;
     SccWgrad1 w1{};
     w1.src = src; w1.dy = ws + z->o_dh1 + row0; w1.U = U; w1.n = n; w1.i0 = i0; w1.M = M; w1.nslab = qm_nslab(M); w1.out = slabs;
     const long long count = (long long)(src.K + src.A + 1) * U, nw = (long long)(src.K + src.A) * U;
     hipLaunchKernelGGL(scc_wgrad1_kernel, dim3((unsigned)((count * w1.nslab + 255) / 256)), dim3(256), 0, st, w1);
     XT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(qm_slab_sum_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, slabs, count, nw, w1.nslab,
-                       grads + z->off[t0], grads + z->off[t0 + 1]);
-    XT_LAUNCH_CHECK();
+    if (int rc = launch_slab_sum(slabs, count, nw, w1.nslab, grads + z->off[t0], grads + z->off[t0 + 1], st)) return rc;
   }
   SccVgrad v{};
   v.h2 = ws + z->o_h2; v.dv = dv; v.U = U; v.R = R; v.n = n; v.per_agent = d.merge == XT_SCC_MERGE_CONCAT;
@@ -602,10 +538,7 @@ static int scc_critic_bwd(const xt_scc* z, const float* p_eval, const SccSrc& sr
   hipLaunchKernelGGL(scc_vgrad_kernel, dim3((unsigned)(((nW + 1) * v.nslab + 255) / 256)), dim3(256), 0, st, v);
   XT_LAUNCH_CHECK();
   const int tv = kSccAgentTensors + 4 * d.n_groups;
-  hipLaunchKernelGGL(qm_slab_sum_kernel, dim3((unsigned)((nW + 1 + 255) / 256)), dim3(256), 0, st, slabs, nW + 1, nW, v.nslab,
-                     grads + z->off[tv], grads + z->off[tv + 1]);
-  XT_LAUNCH_CHECK();
-  return 0;
+  return launch_slab_sum(slabs, nW + 1, nW, v.nslab, grads + z->off[tv], grads + z->off[tv + 1], st);
 }
 
 }  // namespace xt
@@ -670,7 +603,7 @@ int xt_scc_bind(xt_scc* h, float* params_eval, float* params_target, float* grad
 int xt_scc_step(xt_scc* h, const float* agent_obs, const float* obs, const int32_t* lens, const int32_t* actions, const float* rewards,
                 const float* terminated, const float* mask, int32_t B, const xt_scc_cfg* cfg, double* loss_out, void* stream) {
   using namespace xt;
-  if (int rc = scc_bound(h, B, "xt_scc_step")) return rc;
+  if (int rc = check_bound(h, &xt_scc::pe, B, "xt_scc_step")) return rc;
   XT_REQUIRE(agent_obs && obs && actions && rewards && terminated && mask && cfg && loss_out, "xt_scc_step: null argument");
   const xt_scc* z = h;
   const xt_scc_desc& d = z->d;
@@ -683,29 +616,26 @@ int xt_scc_step(xt_scc* h, const float* agent_obs, const float* obs, const int32
   // ---- the critic: one pass, the TD error, the credits (from the eval critic before its update), the backward
   const SccSrc src = scc_src(z, obs, actions, B, false);
   if (int rc = scc_critic_fwd(z, z->pe, z->pt, src, true, st)) return rc;
-  hipLaunchKernelGGL(qm_sum_kernel<float>, dim3(1), dim3(256), 0, st, mask, (long long)R, (const double*)nullptr, scal);
-  XT_LAUNCH_CHECK();
+  if (int rc = launch_dense_sum(mask, (long long)R, nullptr, scal, st)) return rc;
   SccTd td{};
   td.sc = ws + z->o_sc; td.bv_e = z->pe + z->off[tv + 1]; td.bv_t = z->pt + z->off[tv + 1]; td.rewards = rewards; td.terminated = terminated;
   td.mask = mask; td.masksum = scal; td.gamma = cfg->gamma; td.R = R; td.n = n; td.credits = ws + z->o_credits; td.dv = ws + z->o_dv;
   td.rowloss = rowloss; td.alivesum = scal + 1;
   hipLaunchKernelGGL(scc_td_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, td);
   XT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(qm_sum_kernel<double>, dim3(1), dim3(256), 0, st, (const double*)rowloss, (long long)R, (const double*)scal, loss_out + 1);
-  XT_LAUNCH_CHECK();
+  if (int rc = launch_dense_sum((const double*)rowloss, (long long)R, scal, loss_out + 1, st)) return rc;
   if (int rc = scc_critic_bwd(z, z->pe, src, ws + z->o_dv, z->grads, st)) return rc;
 
   // ---- the actor: the agent's forward, the head against the credits, the agent's backward
-  if (int rc = scc_agent_fwd(z, z->pe, agent_obs, B, T + 1, nullptr, lens, true, nullptr, nullptr, st)) return rc;
+  const RnnAgent ag = scc_agent(z);
+  if (int rc = agent_fwd(ag, &z->pe, 1, agent_obs, B, T + 1, nullptr, lens, true, nullptr, nullptr, st)) return rc;
   SccActor ac{};
   ac.q = ws + z->o_q; ac.actions = actions; ac.credits = ws + z->o_credits; ac.mask = mask; ac.alivesum = scal + 1; ac.B = B; ac.T = T;
   ac.n = n; ac.A = d.n_actions; ac.dq = ws + z->o_dq; ac.rowloss = rowloss + R;
   hipLaunchKernelGGL(scc_actor_head_kernel, dim3((unsigned)((NR + 255) / 256)), dim3(256), 0, st, ac);
   XT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(qm_sum_kernel<double>, dim3(1), dim3(256), 0, st, (const double*)(rowloss + R), (long long)NR, (const double*)(scal + 1),
-                     loss_out);
-  XT_LAUNCH_CHECK();
-  return scc_agent_bwd(z, agent_obs, lens, B, st);
+  if (int rc = launch_dense_sum((const double*)(rowloss + R), (long long)NR, scal + 1, loss_out, st)) return rc;
+  return agent_bwd(ag, z->pe, z->grads, agent_obs, lens, B, T + 1, st);
 }
 
 int xt_scc_apply(xt_scc* h, const xt_scc_cfg* cfg, void* stream) {
@@ -751,16 +681,16 @@ int xt_scc_sync_target(xt_scc* h, void* stream) {
 int xt_scc_agent_forward(xt_scc* h, const float* agent_params, const float* obs, int32_t B, int32_t T, const float* hidden_in,
                          const int32_t* lens, float* q, float* hidden_out, void* stream) {
   using namespace xt;
-  if (int rc = scc_bound(h, B, "xt_scc_agent_forward")) return rc;
+  if (int rc = check_bound(h, &xt_scc::pe, B, "xt_scc_agent_forward")) return rc;
   XT_REQUIRE(agent_params && obs && q, "xt_scc_agent_forward: null argument");
   XT_REQUIRE(T >= 1 && T <= h->d.seq_len + 1, "xt_scc_agent_forward: T = %d outside [1, %d]", T, h->d.seq_len + 1);
-  return scc_agent_fwd(h, agent_params, obs, B, T, hidden_in, lens, false, q, hidden_out, as_stream(stream));
+  return agent_fwd(scc_agent(h), &agent_params, 1, obs, B, T, hidden_in, lens, false, q, hidden_out, as_stream(stream));
 }
 
 int xt_scc_critic(xt_scc* h, const float* params_eval, const float* params_target, const float* obs, const int32_t* actions, int32_t B,
                   int32_t raw, float* scalars, float* credits, float* v, const float* dv, float* grads, void* stream) {
   using namespace xt;
-  if (int rc = scc_bound(h, B, "xt_scc_critic")) return rc;
+  if (int rc = check_bound(h, &xt_scc::pe, B, "xt_scc_critic")) return rc;
   XT_REQUIRE(params_eval && obs && (raw || actions), "xt_scc_critic: null argument");
   XT_REQUIRE(!dv == !grads && !(raw && dv), "xt_scc_critic: gradients take dv and grads, and the placeholder layout of obs");
   XT_REQUIRE(!(raw && (scalars || credits)), "xt_scc_critic: a raw critic state has no actions to zero: it yields v alone");
