@@ -1629,7 +1629,8 @@ typedef struct xt_mz_cfg {
 } xt_mz_cfg;
 
 /* Refused with a message: unroll outside [1, XT_MZ_MAX_UNROLL], a support below 2, action_dim below 1, max <= min, a
- * chain that is too short, too long or whose widths do not meet, a rep layer that is not a Dense layer. */
+ * chain that is too short, too long or whose widths do not meet, a rep layer that is not a Dense layer (conv chains:
+ * xt_mz_create_conv of xt_mz_conv.h, which also declares the switch of the fused dynamics unroll). */
 int xt_mz_create(const xt_mz_desc* desc, int32_t max_batch, xt_mz** out);
 void xt_mz_destroy(xt_mz* mz);
 int64_t xt_mz_workspace_bytes(const xt_mz* mz);

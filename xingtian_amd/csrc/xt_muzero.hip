@@ -1,13 +1,15 @@
 // MuZero: the K-step unrolled model update (xt_mz_* of include/xt_mi355x.h).
 //
-// The representation chain (Dense layers on float32 observations) runs on the trunk-layer kernels of xt_igemm.hip
-// (launch_fwd, xt_layer_bwd, xt_layer_wgrad_slabs).  Everything behind it is Dense layers of any width (supports of 3, 7, 26, 305 columns, hidden
-// states of 4) over the STACKED rows of all unroll steps, on the plain Dense kernels of xt_dense_dev.h, shared with QMIX and SCC,
+// The representation chain (Dense layers on float32 observations, or behind xt_mz_create_conv VALID conv layers first, on uint8 or
+// float32 frames) runs on the trunk-layer kernels of xt_igemm.hip (launch_fwd, xt_layer_bwd, xt_layer_wgrad_slabs).
+// Everything behind it is Dense layers of any width (supports of 3, 7, 26, 305 columns, hidden states of 4) over the STACKED rows of all unroll steps, on the plain Dense kernels of xt_dense_dev.h, shared with QMIX and SCC,
 // and the loss head of this file:
 //   dense_gemm_kernel   y = epilogue(x . w): forward (conditioning row + bias + relu) or input gradient (on the transposed
 //                       kernel: scale + join term + relu mask)
 //   dense_wgrad_kernel  dW / db over row slabs of XT_MZ_WGRAD_ROWS rows, with the gathered rows of the conditioned layer
 //   mz_loss_kernel      softmax + two-hot / dense target + cross-entropy + d(logits)
+// The dynamics chain alone may run fused instead, the whole unroll in two persistent MFMA kernels (xt_mz_dyn_dev.h,
+// xt_mz_set_dyn_fused; off by default).
 // All of them float32 without contraction (the build's -ffp-contract=off), sums in ascending order: the NumPy twins of the
 // tests reproduce them bit for bit.
 #include <cmath>
@@ -16,6 +18,8 @@
 #include "xt_common.h"
 #include "xt_dense_dev.h"
 #include "xt_launch.h"
+#include "xt_mz_conv.h"
+#include "xt_mz_dyn_dev.h"
 
 namespace xt {
 
@@ -154,6 +158,8 @@ struct xt_mz {
   xt_layer_desc rep[XT_MZ_MAX_CHAIN], dyn[XT_MZ_MAX_CHAIN], pred[XT_MZ_MAX_CHAIN];
   int max_batch;
   int nt, nq;                       // trunk layers of dyn / pred
+  xt_input_xform xf;                // what the first rep layer reads: {0, 0, 1} behind xt_mz_create
+  int dyn_rows;                     // 0: the per-layer dynamics chain; 16 / 32: the fused unroll, batch rows per workgroup
   float *params, *grads, *m, *v, *state;
   float* ws;
   int64_t ws_floats;
@@ -248,7 +254,9 @@ static int mz_plan(xt_mz* z) {
 }
 
 static const float* wof(const xt_mz* z, const xt_layer_desc& l) { return z->params + l.param_off; }
-static const float* bof(const xt_mz* z, const xt_layer_desc& l) { return z->params + l.param_off + (int64_t)l.g.C * l.g.N; }
+static const float* bof(const xt_mz* z, const xt_layer_desc& l) {
+  return z->params + l.param_off + (int64_t)l.g.KH * l.g.KW * l.g.C * l.g.N;      // (a conv layer's kernel is [KH KW C, N])
+}
 static float* gof(const xt_mz* z, const xt_layer_desc& l) { return z->grads + l.param_off; }
 
 // y = act(x . w + b) of one Dense layer over M rows; actions != null: the conditioned layer (w has A more rows)
@@ -299,9 +307,9 @@ static int mz_wgrad(const xt_mz* z, const xt_layer_desc& l, const float* x, cons
   return mz_wgrad_rows(x, l.g.C - A, dy, l.g.N, M, actions, a_stride, B, A, gof(z, l), z->ws + z->o_slabs, st);
 }
 
-// float32 observations [., obs_dim] (sample b = row idx[b], or row b) -> hstack rows [0, B)
+// observations as the handle's transform reads them (sample b = row idx[b], or row b) -> hstack rows [0, B)
 static int mz_rep_fwd(const xt_mz* z, const void* obs, const int32_t* idx, int B, hipStream_t st) {
-  const xt_input_xform xf = {0, 0.f, 1.f};
+  const xt_input_xform xf = z->xf;
   const void* x = obs;
   for (int l = 0; l < z->d.n_rep; ++l) {
     const xt_layer_desc& L = z->rep[l];
@@ -344,12 +352,72 @@ static int mz_softmax(const float* logits, int rows, int N, float* probs, hipStr
   return launch_mz_loss(a, st);
 }
 
-}  // namespace xt
+// the dynamics chain backwards, one launch per layer and step: d(pre) of every trunk activation and the joined d(pre) of the
+// hidden stack, from the prediction gradient o_gpred and the reward head's o_tr
+static int mz_dyn_bwd(const xt_mz* z, int B, hipStream_t st) {
+  const int U = z->d.unroll, H = z->d.hidden, nt = z->nt;
+  float* ws = z->ws;
+  float *hs = ws + z->o_h, *dh = ws + z->o_dh, *gp = ws + z->o_gpred;
+  const xt_layer_desc& Lh = z->dyn[nt];
+  {   // step U has no consumer but the prediction net: d(pre) = relu'(h_U) * g_pred
+    const int64_t rU = (int64_t)U * B * H;
+    if (int rc = mz_dgrad_rows(nullptr, 0, nullptr, H, B, gp + rU, 0.f, hs + rU, dh + rU, st)) return rc;
+  }
+  for (int i = U - 1; i >= 0; --i) {
+    const int64_t r0 = (int64_t)i * B;
+    const int Nt = z->dyn[nt - 1].g.N;
+    // t_i: the reward head's gradient + Dense_h's, through the trunk's relu
+    if (int rc = mz_dgrad(z, Lh, ws + z->o_wt_dyn[nt], Lh.g.C, dh + (r0 + B) * H, B, ws + z->o_tr + r0 * Nt, 1.f, ws + z->o_t[nt - 1] + r0 * Nt,
+                          ws + z->o_dt[nt - 1] + r0 * Nt, st))
+      return rc;
+    for (int l = nt - 1; l >= 1; --l) {
+      const int Np = z->dyn[l - 1].g.N, Nl = z->dyn[l].g.N;
+      if (int rc = mz_dgrad(z, z->dyn[l], ws + z->o_wt_dyn[l], z->dyn[l].g.C, ws + z->o_dt[l] + r0 * Nl, B, nullptr, 1.f, ws + z->o_t[l - 1] + r0 * Np,
+                            ws + z->o_dt[l - 1] + r0 * Np, st))
+        return rc;
+    }
+    // the hidden-state join: g(h_i) = g_pred(h_i) + c * dh, c = 0.5 behind scale_gradient (i >= 1), 1 for h_0
+    if (int rc = mz_dgrad(z, z->dyn[0], ws + z->o_wt_dyn[0], H, ws + z->o_dt[0] + r0 * z->dyn[0].g.N, B, gp + r0 * H, i >= 1 ? 0.5f : 1.f, hs + r0 * H,
+                          dh + r0 * H, st))
+      return rc;
+  }
+  return 0;
+}
 
-extern "C" {
+// the dynamics chain as the fused kernels walk it: forward (BWD = false) or backward, for a batch of B rows
+template <bool BWD>
+static MzDynChain mz_dyn_chain(const xt_mz* z, int B, const int32_t* actions) {
+  const xt_mz_desc& d = z->d;
+  const int nt = z->nt, H = d.hidden;
+  float* ws = z->ws;
+  MzDynChain a{};
+  a.nl = nt + 1; a.U = d.unroll; a.B = B; a.H = H; a.A = d.action_dim; a.a_stride = d.unroll; a.actions = actions;
+  if (!BWD) {
+    for (int p = 0; p <= nt; ++p) {
+      const xt_layer_desc& L = z->dyn[p];
+      a.w[p] = wof(z, L); a.bias[p] = bof(z, L); a.K[p] = p == 0 ? H : L.g.C; a.N[p] = L.g.N;
+      a.out[p] = p < nt ? ws + z->o_t[p] : ws + z->o_h + (int64_t)B * H;
+    }
+    a.x0 = ws + z->o_h;
+  } else {
+    // p = 0: Dense_h; then the trunk layers nt - 1 .. 1; last the conditioned layer's join into the hidden stack
+    for (int p = 0; p <= nt; ++p) {
+      const int l = p == 0 ? nt : nt - p;
+      a.w[p] = ws + z->o_wt_dyn[l];
+      a.K[p] = z->dyn[l].g.N;
+      a.N[p] = l == 0 ? H : z->dyn[l].g.C;
+      a.add[p] = p == 0 ? ws + z->o_tr : (l == 0 ? ws + z->o_gpred : nullptr);
+      a.mask[p] = l == 0 ? ws + z->o_h : ws + z->o_t[(p == 0 ? nt : l) - 1];
+      a.out[p] = l == 0 ? ws + z->o_dh : ws + z->o_dt[(p == 0 ? nt : l) - 1];
+    }
+    const int64_t rU = (int64_t)d.unroll * B * H;
+    a.x0 = ws + z->o_h + rU; a.g0 = ws + z->o_gpred + rU; a.d0 = ws + z->o_dh + rU;
+  }
+  return a;
+}
 
-int xt_mz_create(const xt_mz_desc* desc, int32_t max_batch, xt_mz** out) {
-  using namespace xt;
+// xt_mz_create (xf == null: Dense representation chains on float32 vectors) and xt_mz_create_conv
+static int mz_create(const xt_mz_desc* desc, const xt_input_xform* xf, int32_t max_batch, xt_mz** out) {
   XT_REQUIRE(desc && out, "xt_mz_create: null argument");
   *out = nullptr;
   const xt_mz_desc& d = *desc;
@@ -369,12 +437,27 @@ int xt_mz_create(const xt_mz_desc* desc, int32_t max_batch, xt_mz** out) {
   XT_REQUIRE(d.n_params > 0 && d.n_params % 4 == 0, "xt_mz_create: n_params = %lld is not a positive multiple of 4",
              (long long)d.n_params);
   XT_REQUIRE(d.obs_dim >= 1, "xt_mz_create: obs_dim = %d below 1", d.obs_dim);
-  // the rep chain: Dense layers whose widths meet
+  // the rep chain: Dense layers whose widths meet; behind xt_mz_create_conv, VALID conv layers first, each reading the
+  // image its producer writes (a Dense layer reads it flattened)
+  XT_REQUIRE(!xf || ((xf->is_u8 == 0 || xf->is_u8 == 1) && xf->std > 0.f), "xt_mz_create_conv: input transform {%d, %g, %g}: "
+             "is_u8 is 0 or 1 and std positive", xf->is_u8, xf->mean, xf->std);
   int h = 1, w = 1, c = d.obs_dim;
   for (int l = 0; l < d.n_rep; ++l) {
     const xt_conv_geom& g = d.rep[l].g;
-    XT_REQUIRE(g.H == 1 && g.W == 1 && g.KH == 1 && g.KW == 1 && g.S == 1 && g.OH == 1 && g.OW == 1 && g.PT == 0 && g.PL == 0,
+    const bool dense = g.H == 1 && g.W == 1 && g.KH == 1 && g.KW == 1 && g.S == 1 && g.OH == 1 && g.OW == 1 && g.PT == 0 && g.PL == 0;
+    XT_REQUIRE(dense || xf,
                "xt_mz_create: rep layer %d is not a Dense layer: the representation chain takes Dense layers only (MuzeroMlp)", l);
+    if (!dense) {
+      XT_REQUIRE(g.H >= 1 && g.W >= 1 && g.C >= 1 && g.KH >= 1 && g.KW >= 1 && g.S >= 1 && g.OH >= 1 && g.OW >= 1 && g.N >= 1 &&
+                 g.PT == 0 && g.PL == 0 && (long long)(g.OH - 1) * g.S + g.KH <= g.H && (long long)(g.OW - 1) * g.S + g.KW <= g.W,
+                 "xt_mz_create_conv: rep layer %d (input %dx%dx%d, kernel %dx%d stride %d, output %dx%d) is not a VALID convolution",
+                 l, g.H, g.W, g.C, g.KH, g.KW, g.S, g.OH, g.OW);
+      // (the first layer's image shape is the caller's: obs_dim is its element count)
+      XT_REQUIRE(l == 0 || (g.H == h && g.W == w && g.C == c), "xt_mz_create_conv: rep layer %d reads %dx%dx%d, its producer "
+                 "writes %dx%dx%d", l, g.H, g.W, g.C, h, w, c);
+      XT_REQUIRE((long long)max_batch * g.H * g.W * g.C < (1ll << 31) && (long long)max_batch * g.OH * g.OW * g.N < (1ll << 31),
+                 "xt_mz_create_conv: rep layer %d: max_batch * its image exceeds 2^31 elements", l);
+    }
     XT_REQUIRE((long long)g.H * g.W * g.C == (long long)h * w * c, "xt_mz_create: rep layer %d reads %dx%dx%d, its producer "
                "writes %dx%dx%d", l, g.H, g.W, g.C, h, w, c);
     XT_REQUIRE(g.C % 4 == 0 && g.N % 4 == 0 && d.rep[l].param_off % 4 == 0, "xt_mz_create: rep layer %d: C = %d, N = %d and its "
@@ -421,8 +504,36 @@ int xt_mz_create(const xt_mz_desc* desc, int32_t max_batch, xt_mz** out) {
   for (int l = 0; l < d.n_pred; ++l) z->pred[l] = d.pred[l];
   z->d.rep = z->rep; z->d.dyn = z->dyn; z->d.pred = z->pred;
   z->max_batch = max_batch; z->nt = nt; z->nq = nq;
+  z->xf = xf ? *xf : xt_input_xform{0, 0.f, 1.f};
+  z->dyn_rows = 0;
   if (int rc = mz_plan(z)) { delete z; return rc; }
   *out = z;
+  return 0;
+}
+
+}  // namespace xt
+
+extern "C" {
+
+int xt_mz_create(const xt_mz_desc* desc, int32_t max_batch, xt_mz** out) { return xt::mz_create(desc, nullptr, max_batch, out); }
+
+int xt_mz_create_conv(const xt_mz_desc* desc, const xt_input_xform* xf, int32_t max_batch, xt_mz** out) {
+  XT_REQUIRE(xf, "xt_mz_create_conv: null input transform");
+  if (out) *out = nullptr;
+  return xt::mz_create(desc, xf, max_batch, out);
+}
+
+int xt_mz_set_dyn_fused(xt_mz* mz, int32_t on) {
+  using namespace xt;
+  XT_REQUIRE(mz, "xt_mz_set_dyn_fused: null handle");
+  XT_REQUIRE(on == 0 || on == 1 || on == 16 || on == 32, "xt_mz_set_dyn_fused: on = %d (0, 1, or 16 / 32 rows per workgroup)", on);
+  if (on) {
+    int bad = mz->d.hidden % 16 || mz->d.hidden > kMzDynMaxWidth ? mz->d.hidden : 0;
+    for (int l = 0; !bad && l < mz->nt; ++l) bad = mz->dyn[l].g.N % 16 || mz->dyn[l].g.N > kMzDynMaxWidth ? mz->dyn[l].g.N : 0;
+    XT_REQUIRE(!bad, "xt_mz_set_dyn_fused: a dynamics width of %d: the fused unroll takes a hidden width and trunk widths that "
+               "are multiples of 16, up to %d", bad, kMzDynMaxWidth);
+  }
+  mz->dyn_rows = on == 1 ? kMzDynRowsDefault : on;
   return 0;
 }
 
@@ -459,8 +570,12 @@ int xt_mz_step(xt_mz* mz, const void* obs, const int32_t* idx, int32_t B, const 
 
   // ---- forward
   if (int rc = mz_rep_fwd(z, obs, idx, B, st)) return rc;
-  for (int i = 0; i < U; ++i)
-    if (int rc = mz_dyn_fwd(z, hs + (int64_t)i * B * H, actions, U, i, B, (int64_t)i * B, hs + (int64_t)(i + 1) * B * H, st)) return rc;
+  if (z->dyn_rows) {      // the whole unroll in one launch (xt_mz_dyn_dev.h)
+    if (int rc = launch_mz_dyn<false>(mz_dyn_chain<false>(z, B, actions), z->dyn_rows, st)) return rc;
+  } else {
+    for (int i = 0; i < U; ++i)
+      if (int rc = mz_dyn_fwd(z, hs + (int64_t)i * B * H, actions, U, i, B, (int64_t)i * B, hs + (int64_t)(i + 1) * B * H, st)) return rc;
+  }
   const float* tl = ws + z->o_t[nt - 1];                      // the trunk's output of all steps, [U B, Nt]
   if (int rc = mz_fwd(z, z->dyn[nt + 1], tl, MU, ws + z->o_zr, nullptr, 0, 0, st)) return rc;
   if (int rc = mz_pred_fwd(z, hs, MS, st)) return rc;
@@ -509,27 +624,10 @@ int xt_mz_step(xt_mz* mz, const void* obs, const int32_t* idx, int32_t B, const 
   if (int rc = mz_wgrad(z, Lr, tl, ws + z->o_dr, MU, nullptr, 0, 0, st)) return rc;
 
   // ---- the dynamics chain backwards: the only sequential part
-  {   // step U has no consumer but the prediction net: d(pre) = relu'(h_U) * g_pred
-    const int64_t rU = (int64_t)U * B * H;
-    if (int rc = mz_dgrad_rows(nullptr, 0, nullptr, H, B, gp + rU, 0.f, hs + rU, dh + rU, st)) return rc;
-  }
-  for (int i = U - 1; i >= 0; --i) {
-    const int64_t r0 = (int64_t)i * B;
-    const int Nt = z->dyn[nt - 1].g.N;
-    // t_i: the reward head's gradient + Dense_h's, through the trunk's relu
-    if (int rc = mz_dgrad(z, Lh, ws + z->o_wt_dyn[nt], Lh.g.C, dh + (r0 + B) * H, B, ws + z->o_tr + r0 * Nt, 1.f, ws + z->o_t[nt - 1] + r0 * Nt,
-                          ws + z->o_dt[nt - 1] + r0 * Nt, st))
-      return rc;
-    for (int l = nt - 1; l >= 1; --l) {
-      const int Np = z->dyn[l - 1].g.N, Nl = z->dyn[l].g.N;
-      if (int rc = mz_dgrad(z, z->dyn[l], ws + z->o_wt_dyn[l], z->dyn[l].g.C, ws + z->o_dt[l] + r0 * Nl, B, nullptr, 1.f, ws + z->o_t[l - 1] + r0 * Np,
-                            ws + z->o_dt[l - 1] + r0 * Np, st))
-        return rc;
-    }
-    // the hidden-state join: g(h_i) = g_pred(h_i) + c * dh, c = 0.5 behind scale_gradient (i >= 1), 1 for h_0
-    if (int rc = mz_dgrad(z, z->dyn[0], ws + z->o_wt_dyn[0], H, ws + z->o_dt[0] + r0 * z->dyn[0].g.N, B, gp + r0 * H, i >= 1 ? 0.5f : 1.f, hs + r0 * H,
-                          dh + r0 * H, st))
-      return rc;
+  if (z->dyn_rows) {
+    if (int rc = launch_mz_dyn<true>(mz_dyn_chain<true>(z, B, actions), z->dyn_rows, st)) return rc;
+  } else if (int rc = mz_dyn_bwd(z, B, st)) {
+    return rc;
   }
 
   // ---- the dynamics layers' weight gradients, once over the stacked rows the backward chain has filled
@@ -548,7 +646,7 @@ int xt_mz_step(xt_mz* mz, const void* obs, const int32_t* idx, int32_t B, const 
                                 ws + z->o_rep_dpre[l - 1], gof(z, L), slabs, ms, ms, stream, nullptr))
         return rc;
     } else {
-      const xt_input_xform xf0 = {0, 0.f, 1.f};
+      const xt_input_xform xf0 = z->xf;
       if (int rc = xt_layer_wgrad_slabs(&L.g, &xf0, B, obs, idx, ws + z->o_rep_dpre[0], gof(z, L), slabs, ms, ms, stream, nullptr))
         return rc;
     }

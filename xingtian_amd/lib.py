@@ -401,6 +401,11 @@ SIGNATURES = {
                                    c_int32, c_int32, _P]),
     "xt_noisy_grads": (c_int32, [POINTER(NoisyLayer), c_int32, _P, _P, _P]),
 }
+# every symbol include/xt_mz_conv.h declares (the MuzeroCnn entries; the xt_mz_ rows above are pinned to xt_mi355x.h's section)
+MZ_CONV_SIGNATURES = {
+    "xt_mz_create_conv": (c_int32, [POINTER(MzDesc), POINTER(InputXform), c_int32, POINTER(c_void_p)]),
+    "xt_mz_set_dyn_fused": (c_int32, [_P, c_int32]),
+}
 # XT_GRAPH_CACHE_<name> of include/xt_mi355x.h: word of every counter of xt_net_graph_cache_info
 GRAPH_CACHE_WORDS = ("CAPTURES", "LAUNCHES", "EVICTIONS", "LIVE_SLOTS")
 GRAPH_CACHE_SLOTS = 8     # graphs one net holds (xt_net.hip: gslots)
@@ -430,7 +435,7 @@ def load():
             "xingtian_amd: HIP library {} is missing -- run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C xingtian_amd/csrc`). There is no CPU fallback.".format(LIB_PATH))
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(MZ_CONV_SIGNATURES.items()):
         fn = getattr(lib, name)   # AttributeError if the ABI symbol is missing
         fn.restype = res
         fn.argtypes = args

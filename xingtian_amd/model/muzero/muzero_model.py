@@ -21,7 +21,9 @@ The update is one C call (``xt_mz_step``, then ``xt_mz_apply``); U is ``td_step`
 Scalar targets become two-hot rows on the device exactly as ``conver_value`` makes them on the host (float64, one
 rounding); where the reference would raise -- the compressed value an exact integer at the top of the range -- the whole
 mass goes on the last bin.  Weights are keyed by Keras' automatic layer names in the reference's list order
-(representation, dynamics, prediction); ``set_weights`` takes that dict or a list in that order.  Explorer processes get
+(representation, dynamics, prediction); ``set_weights`` takes that dict or a list in that order.  A learner-side ``MuzeroCnn`` takes the
+device update with ``model_config: {DEVICE_UPDATE: true}`` (``xt_mz_create_conv``; ``DYN_FUSED`` switches the dynamics
+unroll between the per-layer chain and two persistent kernels).  Explorer processes get
 the inference-only NumPy replica ``CpuMuzero`` (``initial_inference`` / ``recurrent_inference`` / ``value_inference``).
 """
 import ctypes
@@ -208,6 +210,16 @@ def obs_as_network_input(spec, obs, obs_type):
     return np.ascontiguousarray(x)
 
 
+def obs_as_device_input(spec, obs, obs_type):
+    """the observation array as ``HipMuzero`` is fed it: a conv chain (``MuzeroCnn``) reads uint8 frames as they are (the
+    first layer's kernels divide by 255) and float32 / int8 observations as float32 ``x / 255``, one float32 division on the
+    host, the reference's own arithmetic; a Dense chain reads ``obs_as_network_input``"""
+    x = obs_as_network_input(spec, obs, obs_type)
+    if len(spec.state_dim) == 3 and spec.obs_kind != "uint8":
+        x = x.astype(np.float32) / np.float32(255.0)
+    return np.ascontiguousarray(x)
+
+
 def weights_as_dict(spec, weights):
     """a name-keyed dict as it is, or a list in the reference's order (rep, dyn, pred; kernel then bias) -> dict"""
     if hasattr(weights, "keys"):
@@ -311,12 +323,15 @@ class HipMuzero(object):
     inference_only = False
     OPT_M, OPT_V, OPT_B1, OPT_B2, OPT_STEP = "/Adam", "/Adam_1", "beta1_power", "beta2_power", "adam_step"
 
-    def __init__(self, spec, max_batch=32, device="cuda:0", seed=None, lr=1e-3):
+    def __init__(self, spec, max_batch=32, device="cuda:0", seed=None, lr=1e-3, dyn_fused=False):
+        """``dyn_fused``: the dynamics unroll in two persistent kernels (``xt_mz_set_dyn_fused``); True or the rows per
+        workgroup (16 / 32)"""
         import torch
         from xingtian_amd import lib as L
         L.require_gpu()
         self.torch, self.L, self.lib = torch, L, L.load()
         self.spec, self.device = spec, torch.device(device)
+        self.conv, self.dyn_fused = len(spec.state_dim) == 3, int(dyn_fused)
         n = spec.n_flat
         flat = np.zeros(n, np.float32)
         for name, val in initial_weights(spec, seed).items():
@@ -357,11 +372,21 @@ class HipMuzero(object):
         d.rep, d.dyn, d.pred = self._chains
         d.hidden, d.action_dim, d.unroll = spec.hidden, spec.action_dim, spec.unroll
         d.value_support, d.reward_support = spec.value_support, spec.reward_support
-        d.obs_dim = spec.rep[0].C
+        d.obs_dim = spec.rep[0].H * spec.rep[0].W * spec.rep[0].C
         d.n_params = spec.n_flat
         d.value_min, d.value_max, d.reward_min, d.reward_max = spec.value_min, spec.value_max, spec.reward_min, spec.reward_max
         handle = ctypes.c_void_p()
-        L.check(self.lib.xt_mz_create(ctypes.byref(d), int(batch), ctypes.byref(handle)), "xt_mz_create")
+        if self.conv:       # uint8 frames through the first layer's x / 255; everything else arrives as float32
+            xf = L.InputXform(1, 0.0, 255.0) if spec.obs_kind == "uint8" else L.InputXform(0, 0.0, 1.0)
+            L.check(self.lib.xt_mz_create_conv(ctypes.byref(d), ctypes.byref(xf), int(batch), ctypes.byref(handle)),
+                    "xt_mz_create_conv")
+        else:
+            L.check(self.lib.xt_mz_create(ctypes.byref(d), int(batch), ctypes.byref(handle)), "xt_mz_create")
+        if self.dyn_fused:
+            rc = self.lib.xt_mz_set_dyn_fused(handle, self.dyn_fused)
+            if rc:
+                self.lib.xt_mz_destroy(handle)
+                L.check(rc, "xt_mz_set_dyn_fused")
         nbytes = int(self.lib.xt_mz_workspace_bytes(handle))
         self.workspace = torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
         L.check(self.lib.xt_mz_bind(handle, L.ptr(self.params), L.ptr(self.grads), L.ptr(self.adam_m), L.ptr(self.adam_v),
@@ -381,17 +406,21 @@ class HipMuzero(object):
         return self.torch.from_numpy(np.ascontiguousarray(array)).to(self.device)
 
     def _obs(self, obs):
-        """the observations as the device reads them: contiguous float32 [rows, obs_dim]; anything else is refused here,
-        before a kernel reads past a buffer of another element size"""
+        """the observations as the device reads them: contiguous float32 [rows, obs_dim], or for a conv chain [rows, H, W, C]
+        in the element type of its first layer (uint8, or float32 already divided by 255: ``obs_as_device_input``); anything
+        else is refused here, before a kernel reads past a buffer of another element size"""
         torch = self.torch
+        u8 = self.conv and self.spec.obs_kind == "uint8"
+        kind, np_type, dev_type = ("uint8", np.uint8, torch.uint8) if u8 else ("float32", np.float32, torch.float32)
         if not torch.is_tensor(obs):
             obs = np.asarray(obs)
-            if obs.dtype != np.float32:
-                raise TypeError("observations must be float32 (got {})".format(obs.dtype))
+            if obs.dtype != np_type:
+                raise TypeError("observations must be {} (got {})".format(kind, obs.dtype))
             obs = self._dev(obs)
-        if obs.dtype != torch.float32 or obs.dim() != 2 or int(obs.shape[1]) != self.spec.rep[0].C or not obs.is_contiguous():
-            raise TypeError("observations must be a contiguous float32 [rows, {}] array (got {} {})".format(
-                self.spec.rep[0].C, obs.dtype, tuple(obs.shape)))
+        shape = tuple(self.spec.state_dim) if self.conv else (self.spec.rep[0].C,)
+        if obs.dtype != dev_type or tuple(obs.shape[1:]) != shape or obs.dim() != len(shape) + 1 or not obs.is_contiguous():
+            raise TypeError("observations must be a contiguous {} [rows, {}] array (got {} {})".format(
+                kind, ", ".join(str(n) for n in shape), obs.dtype, tuple(obs.shape)))
         return obs
 
     # ---- the update
@@ -543,13 +572,16 @@ class MuzeroModel(XTModel):
         if wants_cpu_replica(model_info):
             self.net = CpuMuzero(self.spec, seed=seed)
         else:
-            if len(self.spec.state_dim) == 3:
+            conv = len(self.spec.state_dim) == 3
+            if conv and not cfg.get("DEVICE_UPDATE", False):
                 raise NotImplementedError(
                     "{}: the device update takes Dense representation chains on float32 vectors only (MuzeroMlp); this "
                     "model builds as the inference-only replica (model_config DEVICE: 'cpu', or any process that is not "
-                    "the learner)".format(type(self).__name__))
+                    "the learner).  model_config DEVICE_UPDATE: true opts a learner into the device update of the conv "
+                    "chain.".format(type(self).__name__))
+            # DYN_FUSED: the dynamics unroll in two persistent kernels; on for an opted-in MuzeroCnn, off for MuzeroMlp
             self.net = HipMuzero(self.spec, max_batch=int(cfg.get("MAX_BATCH", 32)), device=learner_device(model_info),
-                                 seed=seed, lr=self.lr)
+                                 seed=seed, lr=self.lr, dyn_fused=bool(cfg.get("DYN_FUSED", conv)))
         return self.net
 
     # ---- the reference's host helpers as methods
@@ -560,7 +592,9 @@ class MuzeroModel(XTModel):
         return value_transform(value_support, support_size, min, max)
 
     def _input(self, obs):
-        return obs_as_network_input(self.spec, obs, self.obs_type)
+        if self.net.inference_only:
+            return obs_as_network_input(self.spec, obs, self.obs_type)
+        return obs_as_device_input(self.spec, obs, self.obs_type)
 
     # ---- update
     def train(self, state, label):
